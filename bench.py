@@ -2,6 +2,7 @@
 """NOMAD scoring throughput on MI355X: clips/s embedded + N x M NOMAD distances.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python bench.py --gpus N --steps K --warmup W        # N > 1 from a plain shell: spawns the N ranks itself (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -125,6 +126,25 @@ def cpu_baseline(sd, n_samples, budget_s=20.0, max_clips=256):
             "sample": f"{n} clips of {n_samples} samples, batch-1 loop (as nomad.py:171-183) + float64 cdist "
                       f"{n - half}x{half}, {dt:.1f} s wall; host has {ncpu} logical CPUs, thread count calibrated "
                       f"over 8/16/32/64"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: array} as out_dir/<name>.npy (float32 / float64).  When they hold more than `limit` bytes together,
+    each array keeps a fixed, seeded sample of its rows (in order), so that two runs stay comparable row by row."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        for k, a in arrays.items():
+            keep = max(1, int(a.shape[0] * limit / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            arrays[k] = a[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 PRECISION_NOTE = {"f32": "fp32", "bf16": "bf16 storage / fp32 accumulate",
@@ -372,9 +392,16 @@ def main():
     ap.add_argument("--single-stream", action="store_true",
                     help="no two-stream batch split: kernels run alone, as in the pass the roofline is timed in - the command "
                          "the rocprofv3 kernel summaries under profiles/ are taken with")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0's NOMAD scores, distance matrix and "
+                         "all-gathered reference embeddings) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if "RANK" not in os.environ and (args.gpus > 1 or args.spawn):
-        raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))   # before anything touches the GPU in this process
+        # the ranks run from ROOT: DIR as seen from here (a repeated option's last value wins)
+        dump = ["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else []
+        raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:] + dump))   # before anything touches the GPU in this process
 
     import torch
     import torch.distributed as dist
@@ -453,6 +480,9 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     my_elapsed = elapsed
+    if args.dump_outputs and rank == 0:   # outside the timed window, before any later pass reuses the engine
+        dump_outputs(args.dump_outputs, {"scores": mean.cpu().numpy(), "distances": d.cpu().numpy(),
+                                         "ref_embeddings": ref_all_seen.cpu().numpy()})
     prof = eng.profile_read() if profile and not split_prof else None
     if profile and not split_prof:
         eng.profile_enable(False)

@@ -25,6 +25,9 @@ Fixtures written (data only):
                                    (HF layers + torch L1 + torch autograd)
   tests/golden/ref_networks.npz    (``python oracle/make_golden.py refnet``) reference TripletModel / Origw2v outputs on the tiny
                                    batch (both weight sets) and on the six example clips
+  tests/golden/ref_networks_oracle.npz (``python oracle/make_golden.py refnet_oracle``) the same two classes with their
+                                   ``ssl_model`` answered by the oracle's backbone: outputs on two short clips and the
+                                   backbone features they were given
   tests/golden/ref_nomad_classes.npz (``python oracle/make_golden.py refnomad``) outputs of the reference's OWN ``LossNetLayers``,
                                    ``NomadLoss``, ``Nomad.forward`` / ``predict`` / ``get_embeddings(_csv)`` (nomad.py:82-189,
                                    233-282), compiled from the file's ClassDef nodes without importing the module: 13 layer
@@ -111,11 +114,16 @@ class _FairseqCallAdapter(torch.nn.Module):
 def reference_models(hf, sd):
     """(TripletModel, Origw2v) of /root/reference/src/models/networks.py:4-34, imported from the reference tree (build
     container only), around ``hf``; the seeded head goes into ``embedding_layer.1`` as nomad.py:63-65 loads it."""
+    return reference_models_around(_FairseqCallAdapter(hf), sd)
+
+
+def reference_models_around(ssl, sd):
+    """(TripletModel, Origw2v) of the reference tree around any module that answers ``ssl(wav, mask=False,
+    features_only=True)['x']``, seeded head loaded."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("reference_networks", os.path.join(REF, "src", "models", "networks.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    ssl = _FairseqCallAdapter(hf)
     tm = mod.TripletModel(ssl, 768, 256).eval()
     with torch.no_grad():
         tm.embedding_layer[1].weight.copy_(sd["embedding_layer.1.weight"])
@@ -232,6 +240,28 @@ def main_refnet():
     np.savez(os.path.join(GOLD, "ref_networks.npz"), **out)
     old = np.load(os.path.join(GOLD, "hf_tiny.npz"))
     print("ref TripletModel vs hf_tiny.npz emb: max|diff|", float(np.abs(out["emb_seed0"] - old["emb"]).max()))
+
+
+def main_refnet_oracle():
+    """tests/golden/ref_networks_oracle.npz: the reference's own TripletModel / Origw2v (networks.py) with their ``ssl_model``
+    answered by the ORACLE's backbone, and the backbone features they were given - what the classes add on top of the
+    backbone, pinned without the reference tree."""
+    from oracle import nomad_oracle as O
+    torch.set_num_threads(8)
+    sd = seeded_state_dict(0)
+    wav = (0.1 * torch.randn(2, 1, 5000, generator=torch.Generator().manual_seed(5))).clamp(-1, 1)
+    with torch.no_grad():
+        feats = O.backbone(sd, wav.squeeze(1))[0]
+
+    class OracleSSL(torch.nn.Module):
+        def forward(self, wav, mask=False, features_only=True):
+            return {"x": O.backbone(sd, wav)[0]}
+    tm, ow = reference_models_around(OracleSSL(), sd)
+    with torch.no_grad():
+        out = {"wav": wav.numpy(), "features": feats.numpy(), "emb": tm(wav).numpy(), "pooled": ow(wav).numpy()}
+    np.savez(os.path.join(GOLD, "ref_networks_oracle.npz"), **out)
+    print("TripletModel over the oracle backbone vs O.head: max|diff|",
+          float(np.abs(out["emb"] - O.head(feats, sd["embedding_layer.1.weight"], sd["embedding_layer.1.bias"]).numpy()).max()))
 
 
 class _GradMultiply(torch.autograd.Function):
@@ -525,5 +555,7 @@ if __name__ == "__main__":
         main_fgm()
     elif len(sys.argv) > 1 and sys.argv[1] == "refnet":
         main_refnet()
+    elif len(sys.argv) > 1 and sys.argv[1] == "refnet_oracle":
+        main_refnet_oracle()
     else:
         main()

@@ -5,11 +5,21 @@ import os
 import socket
 
 import numpy as np
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from nomad_amd.dist import ShardedScorer, all_gather_rows, partition
+
+
+@pytest.fixture(autouse=True)
+def no_gpu(monkeypatch):
+    """The stand-ins compute on the CPU, so this process and the ranks it spawns see no GPU, on any machine: with one visible,
+    the file pipeline of nomad.py would record device events for the stand-in engine's CPU tensors."""
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "")
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "")
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
 
 
 def _free_port():

@@ -40,6 +40,24 @@ def test_bench_line_contract():
     assert also["unit"] == "clips/s" and also["value"] > 0 and also["max_abs_score_diff_vs_f32"] < 1e-4
 
 
+def test_bench_dump_outputs_repeat_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's scores, distance matrix and reference embeddings, the same from two runs
+    with the same arguments (seeded inputs), and consistent with each other."""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--batch", "16", "--refs", "4", "--no-cpu-baseline", "--no-also", "--no-profile"]
+    for run in ("a", "b"):
+        out = _run(args + ["--dump-outputs", str(tmp_path / run)])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+    got = {run: {k: np.load(tmp_path / run / f"{k}.npy") for k in ("scores", "distances", "ref_embeddings")} for run in "ab"}
+    a = got["a"]
+    assert a["scores"].shape == (12,) and a["distances"].shape == (12, 4) and a["ref_embeddings"].shape == (4, 256)
+    assert a["scores"].dtype == a["distances"].dtype == np.float64 and a["ref_embeddings"].dtype == np.float32
+    assert np.abs(a["distances"].mean(1) - a["scores"]).max() < 1e-12
+    assert np.abs(np.linalg.norm(a["ref_embeddings"], axis=1) - 1).max() < 1e-5
+    for k in a:
+        assert np.array_equal(a[k], got["b"][k]), k
+
+
 def test_bench_under_the_distributed_launcher():
     """The way the driver starts it for N > 1, with N = 1 (one GPU on the box)."""
     out = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "8", "--refs", "2", "--no-cpu-baseline", "--no-also"],
