@@ -76,6 +76,7 @@ struct Tuning {
     double f32_mixed_min = 0.05, f32_mixed_max = 0.70;   // NOMAD_F32_MIXED_MIN / _MAX: fill of the last round that takes the split
     bool f32_mixed_prefer = false; // NOMAD_F32_MIXED_PREFER
     bool f32_quant_tile = true;    // NOMAD_F32_QUANT_TILE: tile choice by the largest tile count any CU gets
+    bool f32_conv_wino = true;     // NOMAD_F32_CONV_WINO: conv1 .. conv4 of every fp32-product forward in polyphase Winograd form (conv_s2_f32.hip.h; 0: the implicit GEMM)
     double f32_quant_penalty = 0.0;  // NOMAD_F32_QUANT_PENALTY (percent): 0 = 8 % with two concurrent parts, 3 % alone
     bool f32_longk_33 = false;     // NOMAD_F32_LONGK_33
     int f32_mid_tile = 31;         // NOMAD_F32_MID_TILE
@@ -133,6 +134,7 @@ static void tuning_from_env(Tuning& t) {
     t.f32_mixed_max = getd("NOMAD_F32_MIXED_MAX", t.f32_mixed_max);
     t.f32_mixed_prefer = getb("NOMAD_F32_MIXED_PREFER", t.f32_mixed_prefer);
     t.f32_quant_tile = getb("NOMAD_F32_QUANT_TILE", t.f32_quant_tile);
+    t.f32_conv_wino = getb("NOMAD_F32_CONV_WINO", t.f32_conv_wino);
     t.f32_quant_penalty = getd("NOMAD_F32_QUANT_PENALTY", t.f32_quant_penalty);
     t.f32_longk_33 = getb("NOMAD_F32_LONGK_33", t.f32_longk_33);
     t.f32_mid_tile = geti("NOMAD_F32_MID_TILE", t.f32_mid_tile);
@@ -364,6 +366,11 @@ NOMAD_INTERNAL int gemm_f32_dispatch(nomad_ctx* c, GemmParams p, int groups, int
 NOMAD_INTERNAL hipError_t gemm_f32_n48_split(const GemmParams& q, int groups, hipStream_t s, int S);   // the grouped pos-conv, K in S slices over blockIdx.z
 NOMAD_INTERNAL int pick_tile(const nomad_ctx* c, int M, int N, int K);
 NOMAD_INTERNAL int mixed_split_rows(const nomad_ctx* c, int M, int N);
+// conv1 .. conv4 (k = 3, stride 2) in polyphase Winograd form, fp32 products: X [rows][512] -> Y (and Upre), W = conv_w[i].
+// Uniform batch: B clips of Lin input / L output frames (ipref == nullptr); ragged: B clips with pair / output / input row prefix
+// sums pp / opref / ipref (device), `pairs` = pp[B].
+NOMAD_INTERNAL int run_conv_s2_f32(nomad_ctx* c, const float* X, const float* W, float* Y, float* Upre, int B, int Lin, int L,
+                                   const int* pp, const int* opref, const int* ipref, int pairs, hipStream_t s);
 // nomad_gemm_bf16.hip
 NOMAD_INTERNAL int run_gemm_bf16(nomad_ctx* c, GemmParams p, int groups, hipStream_t s, int tile = -1);
 #ifdef NOMAD_DIAG

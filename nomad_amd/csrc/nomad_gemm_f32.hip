@@ -1,6 +1,7 @@
 // libnomad_hip.so, translation unit 2 of 3: every fp32 GEMM instantiation (gemm_f32.hip.h) and the code that picks one.
 // (Split out of nomad_hip.hip in round 6 so that the three units compile side by side: see nomad_ctx.hip.h.)
 #include "nomad_ctx.hip.h"
+#include "conv_s2_f32.hip.h"
 
 int gemm_f32_dispatch(nomad_ctx* c, GemmParams p, int groups, int tile, hipStream_t s, int occ) {
     if (tile == 29 && occ == 0) occ = 4;  // measured: 4 workgroups/CU is the best residency for the 128x64x32 kernel
@@ -371,3 +372,76 @@ int nomad_diag_gemm(nomad_ctx* c, const float* A, const float* W, const float* b
 }
 
 }  // extern "C"
+
+int run_conv_s2_f32(nomad_ctx* c, const float* X, const float* W, float* Y, float* Upre, int B, int Lin, int L, const int* pp,
+                    const int* opref, const int* ipref, int pairs, hipStream_t s) {
+    ConvS2Params p{};
+    p.X = X;
+    p.W = W;
+    p.Y = Y;
+    p.Upre = Upre;
+    p.pairs = pairs;
+    p.tiles_m = (pairs + ConvS2Cfg::BMP - 1) / ConvS2Cfg::BMP;
+    p.nclips = B;
+    if (ipref) {
+        p.pp = pp;
+        p.opref = opref;
+        p.ipref = ipref;
+    } else {
+        p.L = L;
+        p.Lin = Lin;
+        p.ppc = (L + 1) / 2;
+        if (Lin < 2 * L + 1 || pairs != B * p.ppc) return fail(NOMAD_ERR_INVALID, "conv_s2: %d clips of %d -> %d frames, %d pairs", B, Lin, L, pairs);
+        p.ppc_magic = 0;
+        p.ppc_shift = 0;
+        if (B > 1 && p.ppc > 1) fast_div_magic((unsigned)p.ppc, &p.ppc_magic, &p.ppc_shift);   // (one pair per clip: c = s, no magic)
+    }
+    // executed FLOPs: 5 products per output pair (2560 of K), odd rows of odd-length clips included - a matrix-pipe fraction
+    const double flops = 2.0 * (double)pairs * 512 * 2560;
+    Scope sc(c, s, NOMAD_K_GEMM, flops, NOMAD_K_GEMM_BIG);
+    static LdsAttrOnce attr_u, attr_r;
+    hipError_t e;
+    if (ipref) {
+        if ((e = attr_r.ensure(reinterpret_cast<const void*>(conv_s2_f32_kernel<true>), ConvS2Cfg::LDS_BYTES)) != hipSuccess)
+            return fail(NOMAD_ERR_HIP, "conv_s2 attribute: %s", hipGetErrorString(e));
+        hipLaunchKernelGGL(conv_s2_f32_kernel<true>, dim3(p.tiles_m * 4), dim3(ConvS2Cfg::NT), ConvS2Cfg::LDS_BYTES, s, p);
+    } else {
+        if ((e = attr_u.ensure(reinterpret_cast<const void*>(conv_s2_f32_kernel<false>), ConvS2Cfg::LDS_BYTES)) != hipSuccess)
+            return fail(NOMAD_ERR_HIP, "conv_s2 attribute: %s", hipGetErrorString(e));
+        hipLaunchKernelGGL(conv_s2_f32_kernel<false>, dim3(p.tiles_m * 4), dim3(ConvS2Cfg::NT), ConvS2Cfg::LDS_BYTES, s, p);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return fail(NOMAD_ERR_HIP, "conv_s2 launch: %s", hipGetErrorString(e));
+    return 0;
+}
+
+#ifdef NOMAD_DIAG
+extern "C" {
+// Test hook (libnomad_diag.so only): one conv1 .. conv4-shaped layer on the Winograd kernel.  X: the clips' input frames packed back
+// to back ([sum lin][512]), W: [512][1536] as conv_w, Y / U (U nullable): [sum L][512], L = (lin - 3) / 2 + 1 per clip.
+// ragged = 0: the uniform launch (every lin equal), 1: the ragged one.  Synchronous.
+int nomad_diag_conv_s2(nomad_ctx* c, const float* X, const float* W, float* Y, float* U, int B, const int* lin_host, int ragged,
+                       void* stream) {
+    if (!c || !X || !W || !Y || !lin_host || B <= 0) return fail(NOMAD_ERR_INVALID, "nomad_diag_conv_s2: bad argument");
+    std::vector<int> meta(3 * (size_t)(B + 1), 0);   // pair / output / input prefix sums
+    for (int b = 0; b < B; ++b) {
+        const int lin = lin_host[b], L = lin >= 3 ? (lin - 3) / 2 + 1 : 0;
+        if (L <= 0 || (!ragged && lin != lin_host[0])) return fail(NOMAD_ERR_INVALID, "nomad_diag_conv_s2: clip %d of %d frames", b, lin);
+        meta[b + 1] = meta[b] + (L + 1) / 2;
+        meta[(B + 1) + b + 1] = meta[(B + 1) + b] + L;
+        meta[2 * (B + 1) + b + 1] = meta[2 * (B + 1) + b] + lin;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int* d = nullptr;
+    HIP_TRY(hipMalloc(&d, sizeof(int) * meta.size()));
+    int rc = 0;
+    if (hipMemcpy(d, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_diag_conv_s2: copy");
+    const int lin0 = lin_host[0], L0 = (lin0 - 3) / 2 + 1;
+    if (rc == 0)
+        rc = ragged ? run_conv_s2_f32(c, X, W, Y, U, B, 0, 0, d, d + (B + 1), d + 2 * (B + 1), meta[B], s)
+                    : run_conv_s2_f32(c, X, W, Y, U, B, lin0, L0, nullptr, nullptr, nullptr, meta[B], s);
+    if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_diag_conv_s2: kernel");
+    (void)hipFree(d);
+    return rc;
+}
+}
+#endif

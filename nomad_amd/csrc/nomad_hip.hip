@@ -392,6 +392,11 @@ int run_gemm(nomad_ctx* c, GemmParams p, int groups, int tile, hipStream_t s, in
 
 namespace {
 
+// conv layer i of an fp32-product forward runs in polyphase Winograd form (conv_s2_f32.hip.h): the k = 3 / stride 2 layers,
+// fp32 products only (the bf16x3 products on fp32 buffers keep the implicit GEMM), NOMAD_F32_CONV_WINO (default on).  Every
+// fp32 forward asks here, so embed, embed_train, layer outputs and the ragged forward switch together.
+bool conv_wino(const nomad_ctx* c, int i) { return c->tune.f32_conv_wino && !c->gemm_x3 && kConvK[i] == 3 && kConvS[i] == 2; }
+
 
 int run_layernorm(nomad_ctx* c, const float* in, const float* g, const float* b, float* out, float* out2, int M, int N,
                   hipStream_t s) {
@@ -751,6 +756,12 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
     // ---- conv1..6: implicit GEMM over time-major activations --------------------------------
     for (int i = 1; i < 7; ++i) {
         const int k = kConvK[i];
+        if (conv_wino(c, i)) {   // conv1 .. conv4: 5 products per output pair instead of 6 (conv_s2_f32.hip.h)
+            if ((rc = run_conv_s2_f32(c, F(lay.conv[i - 1]), c->conv_w[i], F(lay.conv[i]), sv ? sv->u[i] : nullptr, B, sh.L[i - 1], sh.L[i],
+                                      nullptr, nullptr, nullptr, B * ((sh.L[i] + 1) / 2), s)))
+                return rc;
+            continue;
+        }
         GemmParams p{};
         p.A = F(lay.conv[i - 1]);
         p.amap = RowMap{0, (long long)sh.L[i - 1] * 512, sh.L[i], kConvS[i] * 512};
@@ -924,16 +935,18 @@ struct RaggedShapes {
     long long rows[7] = {};   // total frames per conv level
     long long P = 0;          // total padded pos-conv frames, sum (T_c + 128)
     long long blocks = 0;     // total pos-conv frame blocks, sum ceil(T_c / kPosBlk) (bf16x3 path)
-    std::vector<int> meta;    // [lens(B) | pref_0 (B+1) | ... | pref_6 (B+1) | ppref (B+1) | bpref (B+1)]
+    long long pairs[5] = {};  // total output pairs of conv1 .. conv4 (Winograd form), sum ceil(L_i / 2)
+    std::vector<int> meta;    // [lens(B) | pref_0 (B+1) | ... | pref_6 (B+1) | ppref (B+1) | bpref (B+1) | pairpref_1 .. pairpref_4 (B+1)]
     size_t off_lens() const { return 0; }
     size_t off_pref(int i) const { return (size_t)B + (size_t)i * (B + 1); }
     size_t off_ppref() const { return (size_t)B + (size_t)7 * (B + 1); }
     size_t off_bpref() const { return (size_t)B + (size_t)8 * (B + 1); }
+    size_t off_pairpref(int i) const { return (size_t)B + (size_t)(8 + i) * (B + 1); }   // i = 1 .. 4
 };
 
 static bool make_ragged(int B, const int* lens, RaggedShapes* r) {
     r->B = B;
-    r->meta.assign((size_t)B + 9 * (size_t)(B + 1), 0);
+    r->meta.assign((size_t)B + 13 * (size_t)(B + 1), 0);
     for (int c = 0; c < B; ++c) {
         Shapes sh;
         if (!make_shapes(1, lens[c], &sh)) return false;
@@ -941,6 +954,10 @@ static bool make_ragged(int B, const int* lens, RaggedShapes* r) {
         for (int i = 0; i < 7; ++i) {
             r->meta[r->off_pref(i) + c + 1] = r->meta[r->off_pref(i) + c] + sh.L[i];
             r->rows[i] += sh.L[i];
+        }
+        for (int i = 1; i <= 4; ++i) {
+            r->meta[r->off_pairpref(i) + c + 1] = r->meta[r->off_pairpref(i) + c] + (sh.L[i] + 1) / 2;
+            r->pairs[i] += (sh.L[i] + 1) / 2;
         }
         r->meta[r->off_ppref() + c + 1] = r->meta[r->off_ppref() + c] + sh.T + 128;
         r->P += sh.T + 128;
@@ -1024,6 +1041,12 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
                            s, wav, stride, 0, c->conv0_w, scale, shift, cb[0], lens, pref(0));
     }
     for (int i = 1; i < 7; ++i) {
+        if (conv_wino(c, i)) {
+            if ((rc = run_conv_s2_f32(c, cb[(i - 1) % 2], c->conv_w[i], cb[i % 2], nullptr, B, 0, 0, meta + rs.off_pairpref(i), pref(i),
+                                      pref(i - 1), (int)rs.pairs[i], s)))
+                return rc;
+            continue;
+        }
         GemmParams p{};
         p.A = cb[(i - 1) % 2];
         p.amap = RowMap{0, 0, 0, kConvS[i] * 512, pref(i), pref(i - 1), B, 512};
