@@ -2185,6 +2185,29 @@ int nomad_diag_set_snapshot(nomad_ctx* c, int slot, int stage, void* dst_dev, si
     c->snap_cap[slot] = cap;
     return 0;
 }
+/* Poison test (tests/test_gpu_poison.py): fill, on `stream`, every context-owned device buffer whose content is not meant to
+ * outlive a call with `byte`, so that a later call shows any element it reads before writing.  Filled (each one is written in
+ * full by the call that reads it, before it reads it):
+ *   splitk_part     split-K partial slices of the loss forward / backward (nomad_enable_backward)
+ *   pair_scratch    every nomad_pairwise block, bound to a stream or not: per-(ref tile, deg row) row sums
+ *   tap_partial     weight-norm backward and refresh_weights: per-block tap sums (nomad_train_enable)
+ *   tap_dot         weight-norm backward: the per-tap dot products folded from tap_partial
+ * Left alone (state): the weights and every derived copy of them (conv_bw_*, *_wT, pos_w / pos_wb, bf16 / split copies ...),
+ * theta, adam_m, adam_v, grad (written by nomad_train_write), and pos_nrm2: ||v_t||^2 of the pos-conv weight norm, derived from
+ * theta by refresh_weights together with pos_w and read by every later backward, as pos_w is by every forward. */
+int nomad_diag_poison_scratch(nomad_ctx* c, int byte, nomad_stream_t stream) {
+    if (!c || byte < 0 || byte > 255) return fail(NOMAD_ERR_INVALID, "nomad_diag_poison_scratch: bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->splitk_part) HIP_TRY(hipMemsetAsync(c->splitk_part, byte, kSplitKPartFloats * sizeof(float), s));
+    {
+        std::lock_guard<std::mutex> lock(c->pair_mu);
+        for (const auto& e : c->pair_scratch) HIP_TRY(hipMemsetAsync(e.second, byte, sizeof(double) * kPairScratchDoubles, s));
+    }
+    if (c->tap_partial) HIP_TRY(hipMemsetAsync(c->tap_partial, byte, (size_t)576 * 128 * sizeof(double), s));
+    if (c->tap_dot) HIP_TRY(hipMemsetAsync(c->tap_dot, byte, 128 * sizeof(double), s));
+    return 0;
+}
 /* The bf16 forward's front end alone: waveform statistics -> GroupNorm scale / shift -> conv0 + GroupNorm + GELU as bf16
  * out_dev [B][L0][512]; scratch_dev: 8 * 65 * B * (1 + chunks) + 2 * 4 * 512 * B bytes (race hunting: the victim kernel).
  * variant: conv0_gn_gelu_kernel's VAR (0 = the forward's kernel, bit 0 no LDS, bit 1 scalar tap loop). */

@@ -793,3 +793,11 @@ class Engine:
         _lib.check(self.lib.nomad_diag_workspace_region(self.ctx, B, n_samples, name.encode(), C.byref(off), C.byref(nb)),
                    "nomad_diag_workspace_region")
         return self._ws[off.value:off.value + nb.value].view(torch.float32)
+
+    def diag_poison_scratch(self, byte: int = 0xFF):
+        """Fill the context's own per-call scratch (split-K partials, pairwise blocks, weight-norm backward temporaries) with
+        `byte` on the current stream (libnomad_diag.so only; nomad_diag_poison_scratch lists the buffers)."""
+        fn = self.lib.nomad_diag_poison_scratch
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.check(fn(self.ctx, int(byte), self._stream()), "nomad_diag_poison_scratch")
