@@ -185,8 +185,8 @@ __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict_
                                                         const float* __restrict__ bias, const float* __restrict__ de,
                                                         float* __restrict__ gx, float* __restrict__ pooled_out = nullptr,
                                                         float* __restrict__ dz_out = nullptr) {
-    __shared__ float pooled[768], mask[768], z[256], dz[256], red[4], red2[4];
-    __shared__ __attribute__((aligned(16))) float psum[4][768];
+    __shared__ float mask[768], z[256], dz[256], red[4], red2[4];
+    __shared__ __attribute__((aligned(16))) float pooled[768], psum[4][768];   // (both are read as float4)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* xb = x + (long long)b * T * 768;
     if (wave < 4) {   // time sum: wave w takes frames w, w+4, ... (16-byte loads), the four partial sums are combined in fixed order
