@@ -106,13 +106,215 @@ Layout make_layout(const Shapes& s, bool keep) {
     l.qkv = take(act * 3);
     l.ctxb = take(act);
     l.h = take(act * 4);
-    // partial products of the split-K GEMMs of a small layer-output forward (forward_impl): part of the CALL's workspace, so that
+    // partial products of the split-K GEMMs of a small layer-output forward (forward_run): part of the CALL's workspace, so that
     // whether such a forward splits depends on its shape alone - not on which streams other calls are running on
     // Sized from the shape: S x M x N floats for the largest problem splitk_applies / posconv_splitk_applies let through at this M
     // (S x N <= 6144: fc1 2 x 3072, qkv 2 x 2304, fc2 / pos-conv 4 x 768), never more than the fixed cap those checks use.
     l.splitk = s.M < kSplitKLayersMaxM ? take(std::min(kSplitKPartFloats, (size_t)6144 * (size_t)s.M) * sizeof(float)) : 0;
     l.total = off;
     return l;
+}
+
+// ---- ragged batches: clips of different lengths packed back to back ----------------------------------------
+// The reference embeds files one at a time (nomad.py:171-183) because every file has its own length; zero-padding
+// a batch would change GroupNorm statistics and the time mean.  Here clips of ANY lengths share one launch
+// sequence with no padding: every per-frame tensor is packed [sum_c L_i(c)][channels], the transformer GEMMs and
+// LayerNorms see plain packed rows, and only the kernels that care about clip boundaries (front end, conv row maps,
+// pos-conv buffer, attention, head) read per-clip prefix sums.  Each row goes through exactly the arithmetic it
+// would see at batch 1, so results are bit-identical to per-clip calls.
+struct RaggedShapes {
+    int B = 0, max_l0 = 0, max_t = 0, min_t = 1 << 30;
+    long long rows[7] = {};   // total frames per conv level
+    long long P = 0;          // total padded pos-conv frames, sum (T_c + 128)
+    long long blocks = 0;     // total pos-conv frame blocks, sum ceil(T_c / kPosBlk) (bf16x3 path)
+    long long pairs[5] = {};  // total output pairs of conv1 .. conv4 (Winograd form), sum ceil(L_i / 2)
+    std::vector<int> meta;    // [lens(B) | pref_0 (B+1) | ... | pref_6 (B+1) | ppref (B+1) | bpref (B+1) | pairpref_1 .. pairpref_4 (B+1)]
+    size_t off_lens() const { return 0; }
+    size_t off_pref(int i) const { return (size_t)B + (size_t)i * (B + 1); }
+    size_t off_ppref() const { return (size_t)B + (size_t)7 * (B + 1); }
+    size_t off_bpref() const { return (size_t)B + (size_t)8 * (B + 1); }
+    size_t off_pairpref(int i) const { return (size_t)B + (size_t)(8 + i) * (B + 1); }   // i = 1 .. 4
+};
+
+bool make_ragged(int B, const int* lens, RaggedShapes* r) {
+    r->B = B;
+    r->meta.assign((size_t)B + 13 * (size_t)(B + 1), 0);
+    for (int c = 0; c < B; ++c) {
+        Shapes sh;
+        if (!make_shapes(1, lens[c], &sh)) return false;
+        r->meta[c] = lens[c];
+        for (int i = 0; i < 7; ++i) {
+            r->meta[r->off_pref(i) + c + 1] = r->meta[r->off_pref(i) + c] + sh.L[i];
+            r->rows[i] += sh.L[i];
+        }
+        for (int i = 1; i <= 4; ++i) {
+            r->meta[r->off_pairpref(i) + c + 1] = r->meta[r->off_pairpref(i) + c] + (sh.L[i] + 1) / 2;
+            r->pairs[i] += (sh.L[i] + 1) / 2;
+        }
+        r->meta[r->off_ppref() + c + 1] = r->meta[r->off_ppref() + c] + sh.T + 128;
+        r->P += sh.T + 128;
+        const int nb = (sh.T + kPosBlk - 1) / kPosBlk;
+        r->meta[r->off_bpref() + c + 1] = r->meta[r->off_bpref() + c] + nb;
+        r->blocks += nb;
+        r->max_l0 = sh.L[0] > r->max_l0 ? sh.L[0] : r->max_l0;
+        r->max_t = sh.T > r->max_t ? sh.T : r->max_t;
+        r->min_t = sh.T < r->min_t ? sh.T : r->min_t;
+    }
+    return r->rows[0] < (1LL << 31) / 512 * 256;  // row counts stay well inside int
+}
+
+// The batch geometry every forward sequence reads its row maps, clip lengths and prefix sums from, so that one sequence per
+// precision serves equal-length batches (geom_uniform) and ragged ones (geom_ragged).
+struct BatchGeom {
+    int B = 0;
+    long long rows[7] = {};        // total frames per conv level; rows[6] = M
+    long long pad_rows = 0;        // rows of one group of the padded pos-conv buffer
+    long long grp_stride = 0;      // elements of one group of that buffer
+    int max_l0 = 0, min_t = 0, max_t = 0;
+    int wav_ld = 0;                // samples between clips of the wav buffer
+    int L[7] = {}, T = 0;          // frames per clip and conv level, T = L[6]: equal-length batches; 0 when ragged (the kernels
+                                   // read lens / prefixes instead)
+    size_t meta_ints = 0;          // ragged: ints of the device metadata (RaggedShapes::meta); 0 for an equal-length batch
+    const int* lens = kNoInts;     // ragged: device pointers into that metadata; kNoInts for an equal-length batch
+    const int* pref[7] = {};       // frame prefix sums per conv level (pref[6]: the encoder's frames)
+    const int* ppref = kNoInts;    // padded pos-conv frame prefix sums
+    RowMap conv_amap[7] = {};      // im2col rows of conv layer i over the output of layer i - 1
+    long long pairs[5] = {};       // output pairs of conv1 .. conv4 in polyphase Winograd form (fp32)
+    const int* pairpref[5] = {};   // ragged: their prefix sums
+    RowMap pad_map{};              // post_extract_proj output rows in the group-major, padded pos-conv buffer
+    RowMap pos_amap{};             // fp32 / bf16 pos-conv rows: row (clip, t) starts at padded frame t, taps are contiguous
+    // bf16x3 pos-conv as a GEMM over blocks of kPosBlk frames: input rows, output rows (in y), residual rows
+    long long pos_blocks = 0;
+    RowMap blk_amap{}, blk_cmap{}, blk_rmap{};
+    double attn_flops = 0.0;
+    bool ragged() const { return meta_ints != 0; }
+};
+
+// allocates nothing: the equal-length forwards build one per call
+BatchGeom geom_uniform(const Shapes& sh) {
+    BatchGeom g;
+    g.B = sh.B;
+    for (int i = 0; i < 7; ++i) {
+        g.rows[i] = (long long)sh.B * sh.L[i];
+        g.L[i] = sh.L[i];
+    }
+    g.pad_rows = (long long)sh.B * (sh.T + 128);
+    g.grp_stride = g.pad_rows * 48;
+    g.max_l0 = sh.L[0];
+    g.min_t = g.max_t = g.T = sh.T;
+    g.wav_ld = sh.N;
+    const long long pad_ld = (long long)(sh.T + 128) * 48;
+    for (int i = 1; i < 7; ++i) g.conv_amap[i] = RowMap{0, (long long)sh.L[i - 1] * 512, sh.L[i], kConvS[i] * 512};
+    for (int i = 1; i <= 4; ++i) g.pairs[i] = (long long)sh.B * ((sh.L[i] + 1) / 2);
+    g.pad_map = RowMap{64LL * 48, pad_ld, sh.T, 48};
+    g.pos_amap = RowMap{0, pad_ld, sh.T, 48};
+    const int nb = (sh.T + kPosBlk - 1) / kPosBlk;
+    g.pos_blocks = (long long)sh.B * nb;
+    g.blk_amap = RowMap{0, pad_ld, nb, kPosBlk * 48};
+    g.blk_rmap = RowMap{64LL * 48, pad_ld, nb, kPosBlk * 48};
+    g.blk_cmap = RowMap{0, (long long)sh.T * 768, nb, kPosBlk * 768};
+    g.attn_flops = 4.0 * sh.B * 12.0 * (double)sh.T * sh.T * 64;
+    return g;
+}
+
+// meta: the device copy of rs.meta, which the row maps point into (nullptr: sizing only)
+BatchGeom geom_ragged(const RaggedShapes& rs, int stride, const int* meta) {
+    BatchGeom g;
+    g.B = rs.B;
+    for (int i = 0; i < 7; ++i) g.rows[i] = rs.rows[i];
+    g.pad_rows = rs.P;
+    g.grp_stride = rs.P * 48;
+    g.max_l0 = rs.max_l0;
+    g.min_t = rs.min_t;
+    g.max_t = rs.max_t;
+    g.wav_ld = stride;
+    g.meta_ints = rs.meta.size();
+    auto at = [&](size_t off) { return meta ? meta + off : nullptr; };
+    g.lens = at(rs.off_lens());
+    for (int i = 0; i < 7; ++i) g.pref[i] = at(rs.off_pref(i));
+    g.ppref = at(rs.off_ppref());
+    for (int i = 1; i < 7; ++i) g.conv_amap[i] = RowMap{0, 0, 0, kConvS[i] * 512, g.pref[i], g.pref[i - 1], rs.B, 512};
+    for (int i = 1; i <= 4; ++i) {
+        g.pairs[i] = rs.pairs[i];
+        g.pairpref[i] = at(rs.off_pairpref(i));
+    }
+    g.pad_map = RowMap{64LL * 48, 0, 0, 48, g.pref[6], g.ppref, rs.B, 48};
+    g.pos_amap = RowMap{0, 0, 0, 48, g.pref[6], g.ppref, rs.B, 48};
+    const int* bpref = at(rs.off_bpref());
+    g.pos_blocks = rs.blocks;
+    g.blk_amap = RowMap{0, 0, 0, kPosBlk * 48, bpref, g.ppref, rs.B, 48};
+    g.blk_rmap = RowMap{64LL * 48, 0, 0, kPosBlk * 48, bpref, g.ppref, rs.B, 48};
+    g.blk_cmap = RowMap{0, 0, 0, kPosBlk * 768, bpref, g.pref[6], rs.B, 768};
+    for (int i = 0; i < rs.B; ++i) {
+        const double t = rs.meta[rs.off_pref(6) + i + 1] - rs.meta[rs.off_pref(6) + i];
+        g.attn_flops += 4.0 * 12.0 * t * t * 64;
+    }
+    return g;
+}
+
+// Workspace of every forward except the fp32 equal-length one (Layout): the ragged metadata, the front end's statistics, two
+// ping-pong conv buffers and the activations, elem_bytes per element (bf16: 2; fp32 or two bf16 planes: 4).
+struct ActLayout {
+    size_t meta, stats, scale, shift, conva, convb, xpad, x, x2, y, qkv, ctxb, h, total;
+    long long capa, capb;  // elements per plane of the two conv ping-pong buffers
+    long long xpad_plane;  // elements per plane of the padded pos-conv buffer, + xpad_slack zeroed elements (bf16x3)
+};
+
+ActLayout make_act_layout(const BatchGeom& g, size_t elem_bytes, size_t xpad_slack) {
+    ActLayout l{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        size_t o = off;
+        off += align_up(bytes);
+        return o;
+    };
+    const size_t e = elem_bytes, M = (size_t)g.rows[6];
+    l.capa = 512LL * g.rows[0];
+    l.capb = 512LL * g.rows[1];
+    l.meta = take(sizeof(int) * g.meta_ints);
+    l.stats = take(sizeof(double) * stats_doubles(g.B, g.max_l0));
+    l.scale = take(sizeof(float) * 512 * g.B);
+    l.shift = take(sizeof(float) * 512 * g.B);
+    l.conva = take(e * l.capa);
+    l.convb = take(e * l.capb);
+    l.xpad_plane = 768LL * g.pad_rows + (long long)xpad_slack;
+    l.xpad = take(e * (size_t)l.xpad_plane);
+    l.x = take(e * 768 * M);
+    l.x2 = take(e * 768 * M);
+    l.y = take(e * 768 * M);
+    l.qkv = take(e * 2304 * M);
+    l.ctxb = take(e * 768 * M);
+    l.h = take(e * 3072 * M);
+    l.total = off;
+    return l;
+}
+
+struct RaggedBatch {
+    RaggedShapes rs;
+    BatchGeom g;
+    ActLayout lay;
+};
+
+// What every ragged entry point does first: the argument checks (ok: the caller's own), the metadata and the workspace layout.
+// c == nullptr: nomad_workspace_bytes_ragged*, sizing only.  Else a forward: the stride and workspace checks, then the
+// metadata's copy into the workspace, queued on s ahead of every kernel of the call, and the geometry over that copy.
+// Errors name the entry point `who`.
+int ragged_prologue(const char* who, nomad_ctx* c, bool ok, int B, int stride, const int* lens_host, size_t elem_bytes,
+                    size_t xpad_slack, RaggedBatch* r, void* workspace = nullptr, size_t workspace_bytes = 0, hipStream_t s = nullptr) {
+    if (!ok || !lens_host || B <= 0 || !make_ragged(B, lens_host, &r->rs)) return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d)", who, B);
+    r->g = geom_ragged(r->rs, stride, nullptr);
+    r->lay = make_act_layout(r->g, elem_bytes, xpad_slack);
+    if (!c) return 0;
+    for (int i = 0; i < B; ++i)
+        if (lens_host[i] > stride) return fail(NOMAD_ERR_INVALID, "%s: clip %d longer than the row stride", who, i);
+    if (workspace_bytes < r->lay.total)
+        return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, r->lay.total);
+    int* meta = reinterpret_cast<int*>(static_cast<char*>(workspace) + r->lay.meta);
+    std::vector<int>& staged = c->ragged_meta_ring[c->ragged_seq++ & 3];  // must outlive the asynchronous copy
+    staged = r->rs.meta;
+    HIP_TRY(hipMemcpyAsync(meta, staged.data(), sizeof(int) * staged.size(), hipMemcpyHostToDevice, s));
+    r->g = geom_ragged(r->rs, stride, meta);
+    return 0;
 }
 
 // What a training-mode forward keeps for the backward pass (all fp32, carved from the caller's `saved` block).
@@ -393,8 +595,8 @@ int run_gemm(nomad_ctx* c, GemmParams p, int groups, int tile, hipStream_t s, in
 namespace {
 
 // conv layer i of an fp32-product forward runs in polyphase Winograd form (conv_s2_f32.hip.h): the k = 3 / stride 2 layers,
-// fp32 products only (the bf16x3 products on fp32 buffers keep the implicit GEMM), NOMAD_F32_CONV_WINO (default on).  Every
-// fp32 forward asks here, so embed, embed_train, layer outputs and the ragged forward switch together.
+// fp32 products only (the bf16x3 products on fp32 buffers keep the implicit GEMM), NOMAD_F32_CONV_WINO (default on).  The one
+// fp32 forward sequence (forward_run) asks here, so embed, embed_train, layer outputs and the ragged forward switch together.
 bool conv_wino(const nomad_ctx* c, int i) { return c->tune.f32_conv_wino && !c->gemm_x3 && kConvK[i] == 3 && kConvS[i] == 2; }
 
 
@@ -432,8 +634,22 @@ DropCfg make_drop(const nomad_ctx* c, float p) {
 }
 
 
-int run_attention(nomad_ctx* c, const float* qkv, float* out, float* lse, int B, int T, hipStream_t s,
-                  const DropCfg* dc = nullptr, uint32_t site = 0, int bh0 = 0) {
+// fp32 attention.  An equal-length batch: clips [c0, c0 + nc) (nc = 0: all of them), with dropout when dc has a threshold.
+// A ragged one: every clip.
+int run_attention(nomad_ctx* c, const BatchGeom& g, const float* qkv, float* out, float* lse, hipStream_t s,
+                  const DropCfg* dc = nullptr, uint32_t site = 0, int c0 = 0, int nc = 0) {
+    if (g.ragged()) {
+        Scope sc(c, s, NOMAD_K_ATTN, g.attn_flops);
+        // clips of kAttnV2MinT frames or more: attention_f32_v2_kernel; shorter ones: attention_f32_kernel (each skips the
+        // other's clips) - exactly the kernel the clip would get in a batch of its own
+        if (g.max_t >= kAttnV2MinT) HIP_TRY(launch_attention_f32_v2(qkv, out, lse, g.B, g.max_t, g.pref[6], s, kAttnV2MinT));
+        if (g.min_t < kAttnV2MinT)
+            hipLaunchKernelGGL(attention_f32_kernel<float>, dim3((std::min(g.max_t, kAttnV2MinT - 1) + 63) / 64, g.B * 12), dim3(256), 0,
+                               s, qkv, out, lse, 0, g.pref[6], DropCfg{}, 0u, 0, 0LL, kAttnV2MinT);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    const int B = nc ? nc : g.B, T = g.T, bh0 = c0 * 12;
     const double flops = 4.0 * B * 12.0 * (double)T * T * 64;
     Scope sc(c, s, NOMAD_K_ATTN, flops);
     const dim3 grid((T + 63) / 64, B * 12);
@@ -694,21 +910,22 @@ int nomad_diag_workspace_region(const nomad_ctx* c, int B, int n_samples, const 
 
 }  // extern "C"
 
-// The forward pass.  sv == nullptr: scoring mode (intermediates alias inside the workspace).  sv != nullptr:
-// training mode - every tensor the backward needs is written to its slot in `sv` instead.
-static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
-                        float* emb, float* layers_out, void* workspace, size_t workspace_bytes, nomad_stream_t stream,
-                        const Saved* sv) {
-    Shapes sh;
-    if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed: bad argument (B=%d, n_samples=%d)", B, n_samples);
-    const Layout lay = make_layout(sh, c->keep);
-    if (workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed: workspace %zu < required %zu", workspace_bytes, lay.total);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    const int T = sh.T, M = sh.M;
+// The fp32 forward's buffers: the conv output of every level (aliasing ping-pong buffers unless the equal-length layout keeps
+// them), the LayerNorm(512) output and the activations.
+struct F32Bufs {
+    double* stats;
+    float *scale, *shift, *conv[7], *featln, *xpad, *x, *x2, *y, *qkv, *ctxb, *h;
+};
+
+// The fp32 forward, over an equal-length or a ragged batch.  sv == nullptr: scoring mode (intermediates alias inside the
+// workspace).  sv != nullptr: training mode - every tensor the backward needs is written to its slot in `sv` instead.
+// splitk_block: the workspace's split-K block of an equal-length layer-output forward, or nullptr.  The training inputs (sv,
+// its dropout and LayerDrop, layers_out, split-K) are for equal-length batches only.
+static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const F32Bufs& bf, const float* head_w,
+                       const float* head_b, float* emb, float* layers_out, float* splitk_block, hipStream_t s, const Saved* sv) {
+    if (g.ragged() && (sv || layers_out || splitk_block))
+        return fail(NOMAD_ERR_INVALID, "fp32 forward: training inputs, layer outputs and split-K need an equal-length batch");
+    const int B = g.B, T = g.T, M = (int)g.rows[6];
     // the loss forward of Nomad.forward() (saving activations, not fine-tuning): small-M GEMMs may split K.  Round 4: so may the
     // other branch of that loss - a forward that returns the 12 layer outputs (LossNetLayers: `clean`, or `estimate` under
     // no_grad) on fewer than 4096 frames.  The split is a function of the GEMM shape only (fixed slices, ordered fold): the
@@ -716,7 +933,7 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
     // (TripletModel / predict) never splits, whatever the batch.  The partial sums live in the call's own workspace (round 5; they
     // were two context-wide blocks handed to launch streams by hipEventQuery: whether a third stream's forward split depended on
     // timing).  Tuning::splitk_layers = 0 switches the case off (A/B, diag library).
-    float* const loss_block = (sv == nullptr && layers_out != nullptr && lay.splitk != 0 && c->tune.splitk_layers) ? F(lay.splitk) : nullptr;
+    float* const loss_block = (sv == nullptr && layers_out != nullptr && splitk_block != nullptr && c->tune.splitk_layers) ? splitk_block : nullptr;
     const SplitKScope splitk(c, (sv != nullptr || loss_block != nullptr) && !c->train_ready);
     float* const prev_cur = c->splitk_cur;
     c->splitk_cur = sv != nullptr ? c->splitk_part : loss_block;
@@ -737,41 +954,39 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
     const long long act = (long long)M * 768;
 
     // ---- front end: conv0 + GroupNorm + GELU ------------------------------------------------
-    double* stats = reinterpret_cast<double*>(ws + lay.stats);
-    float* gn_scale = sv ? sv->gn_scale : F(lay.scale);
-    float* gn_shift = sv ? sv->gn_shift : F(lay.shift);
+    float* gn_scale = sv ? sv->gn_scale : bf.scale;
+    float* gn_shift = sv ? sv->gn_shift : bf.shift;
     {
         Scope sc(c, s, NOMAD_K_FRONT, 0.0);
-        launch_wav_stats(wav, n_samples, sh.L[0], sh.L[0], B, stats, kNoInts, s);
-        hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(512), 0, s, stats, c->conv0_w, c->gn_w, c->gn_b, sh.L[0],
-                           gn_scale, gn_shift, sv ? sv->gn_mean : nullptr, sv ? sv->gn_rstd : nullptr, kNoInts);
+        launch_wav_stats(wav, g.wav_ld, g.L[0], g.max_l0, B, bf.stats, g.lens, s);
+        hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(512), 0, s, bf.stats, c->conv0_w, c->gn_w, c->gn_b, g.L[0],
+                           gn_scale, gn_shift, sv ? sv->gn_mean : nullptr, sv ? sv->gn_rstd : nullptr, g.lens);
     }
     {
-        Scope sc(c, s, NOMAD_K_FRONT, 2.0 * B * (double)sh.L[0] * 512 * 10);
-        hipLaunchKernelGGL(conv0_gn_gelu_kernel<float>, dim3((sh.L[0] + kConv0Frames - 1) / kConv0Frames, B), dim3(256), 0, s,
-                           wav, n_samples, sh.L[0], c->conv0_w, gn_scale, gn_shift, F(lay.conv[0]), kNoInts, kNoInts);
+        Scope sc(c, s, NOMAD_K_FRONT, 2.0 * (double)g.rows[0] * 512 * 10);
+        hipLaunchKernelGGL(conv0_gn_gelu_kernel<float>, dim3((g.max_l0 + kConv0Frames - 1) / kConv0Frames, B), dim3(256), 0, s,
+                           wav, g.wav_ld, g.L[0], c->conv0_w, gn_scale, gn_shift, bf.conv[0], g.lens, g.pref[0]);
     }
     HIP_TRY(hipGetLastError());
 
     // ---- conv1..6: implicit GEMM over time-major activations --------------------------------
     for (int i = 1; i < 7; ++i) {
-        const int k = kConvK[i];
         if (conv_wino(c, i)) {   // conv1 .. conv4: 5 products per output pair instead of 6 (conv_s2_f32.hip.h)
-            if ((rc = run_conv_s2_f32(c, F(lay.conv[i - 1]), c->conv_w[i], F(lay.conv[i]), sv ? sv->u[i] : nullptr, B, sh.L[i - 1], sh.L[i],
-                                      nullptr, nullptr, nullptr, B * ((sh.L[i] + 1) / 2), s)))
+            if ((rc = run_conv_s2_f32(c, bf.conv[i - 1], c->conv_w[i], bf.conv[i], sv ? sv->u[i] : nullptr, B, g.L[i - 1], g.L[i],
+                                      g.pairpref[i], g.pref[i], g.pref[i - 1], (int)g.pairs[i], s)))
                 return rc;
             continue;
         }
         GemmParams p{};
-        p.A = F(lay.conv[i - 1]);
-        p.amap = RowMap{0, (long long)sh.L[i - 1] * 512, sh.L[i], kConvS[i] * 512};
-        p.K = k * 512;
+        p.A = bf.conv[i - 1];
+        p.amap = g.conv_amap[i];
+        p.K = kConvK[i] * 512;
         p.kchunk = p.K;
         p.W = c->conv_w[i];
         p.ldw = p.K;
-        p.C = (sv && i == 6) ? sv->c6 : F(lay.conv[i]);
+        p.C = (sv && i == 6) ? sv->c6 : bf.conv[i];
         p.Upre = sv ? sv->u[i] : nullptr;
-        p.M = B * sh.L[i];
+        p.M = (int)g.rows[i];
         p.N = 512;
         p.n_valid = 512;
         p.cmap = plain_map(p.M, 512);
@@ -781,33 +996,31 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
     }
 
     // ---- LayerNorm(512) + post_extract_proj into the padded pos-conv buffer ------------------
-    if ((rc = run_layernorm(c, sv ? sv->c6 : F(lay.conv[6]), c->fln_w, c->fln_b, F(lay.featln), nullptr, M, 512, s)))
+    if ((rc = run_layernorm(c, sv ? sv->c6 : bf.conv[6], c->fln_w, c->fln_b, bf.featln, nullptr, M, 512, s)))
         return rc;
-    // group-major pos-conv buffer xg[16][B][T+128][48]; x (post_extract_proj output) sits at frames 64..64+T
-    float* xpad = F(lay.xpad);
-    const long long grp_stride = (long long)B * (T + 128) * 48;
-    const RowMap pad_map{64LL * 48, (long long)(T + 128) * 48, T, 48};
+    // group-major pos-conv buffer xg[16][clip][T+128][48]; x (post_extract_proj output) sits at frames 64..64+T
+    float* xpad = bf.xpad;
     {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        hipLaunchKernelGGL(zero_pad_rows_kernel<float>, dim3(16 * B), dim3(256), 0, s, xpad, T, kNoInts, kNoInts, B);
+        hipLaunchKernelGGL(zero_pad_rows_kernel<float>, dim3(16 * B), dim3(256), 0, s, xpad, T, g.pref[6], g.ppref, B);
     }
     {
-        GemmParams p = dense(F(lay.featln), 512, c->proj_w, c->proj_b, nullptr, xpad, M, 768, 512, 0);
-        p.cmap = pad_map;
+        GemmParams p = dense(bf.featln, 512, c->proj_w, c->proj_b, nullptr, xpad, M, 768, 512, 0);
+        p.cmap = g.pad_map;
         p.c_colblk = 48;
-        p.c_colblk_stride = grp_stride;
+        p.c_colblk_stride = g.grp_stride;
         if ((rc = run_gemm(c, p, 1, pick_tile(c, M, 768, 512), s))) return rc;
     }
     if (d_in.threshold) {  // dropout_input: on the features that feed both the pos-conv and its residual
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        hipLaunchKernelGGL(dropout_groups_kernel, dim3(M), dim3(192), 0, s, xpad, T, grp_stride, d_in, kSiteInput);
+        hipLaunchKernelGGL(dropout_groups_kernel, dim3(M), dim3(192), 0, s, xpad, T, g.grp_stride, d_in, kSiteInput);
     }
     // ---- pos-conv: 16 groups x (M x 48 x 6144), x + gelu(conv + bias) -------------------------
     {
         GemmParams p{};
         p.A = xpad;
-        p.amap = RowMap{0, (long long)(T + 128) * 48, T, 48};  // row (clip, t) starts at frame t: taps are contiguous
-        p.a_goff = grp_stride;
+        p.amap = g.pos_amap;
+        p.a_goff = g.grp_stride;
         p.K = 6144;
         p.kchunk = 6144;
         p.W = c->pos_w;
@@ -815,22 +1028,22 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
         p.w_goff = 64LL * 6144;
         p.bias = c->pos_b;
         p.bias_goff = 48;
-        p.C = sv ? sv->y0 : F(lay.y);
+        p.C = sv ? sv->y0 : bf.y;
         p.Upre = sv ? sv->upc : nullptr;
         p.cmap = plain_map(M, 768);
         p.c_goff = 48;
         p.R = xpad;
-        p.rmap = pad_map;
-        p.r_goff = grp_stride;
+        p.rmap = g.pad_map;
+        p.r_goff = g.grp_stride;
         p.M = M;
         p.N = 64;
         p.n_valid = 48;
         p.gelu = 1;
         if ((rc = run_gemm(c, p, 16, 48, s))) return rc;  // one instantiation for every batch size: same summation order
     }
-    float* x = F(lay.x);
-    float* x2 = F(lay.x2);
-    float* y = F(lay.y);
+    float* x = bf.x;
+    float* x2 = bf.x2;
+    float* y = bf.y;
     if ((rc = run_layernorm(c, sv ? sv->y0 : y, c->eln_w, c->eln_b, x, nullptr, M, 768, s))) return rc;
     if (d_res.threshold && (rc = run_dropout(c, x, nullptr, x, act, d_res, kSiteEncoder, s))) return rc;
 
@@ -840,13 +1053,13 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
     auto run_layer = [&](int l, int c0, int nc) -> int {
         const LayerDev& d = c->layers[l];
         const long long r0 = (long long)c0 * T;
-        const int Ms = nc * T;
+        const int Ms = nc == B ? M : nc * T;   // (branches: equal-length batches only)
         const long long acts = (long long)Ms * 768;
         float* xs = x + r0 * 768;
         float* x2s = x2 + r0 * 768;
-        float* hs = F(lay.h) + r0 * 3072;
-        float* qkv = (sv ? sv->L[l].qkv : F(lay.qkv)) + r0 * 2304;
-        float* ctxb = (sv ? sv->L[l].ctx : F(lay.ctxb)) + r0 * 768;
+        float* hs = bf.h + r0 * 3072;
+        float* qkv = (sv ? sv->L[l].qkv : bf.qkv) + r0 * 2304;
+        float* ctxb = (sv ? sv->L[l].ctx : bf.ctxb) + r0 * 768;
         float* y1 = (sv ? sv->L[l].y1 : y) + r0 * 768;
         float* y2 = (sv ? sv->L[l].y2 : y) + r0 * 768;
         float* lse = sv ? sv->L[l].lse + (long long)c0 * 12 * T : nullptr;
@@ -855,7 +1068,7 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
         int rc;
         if ((rc = run_gemm(c, dense(xs, 768, d.qkv_w, d.qkv_b, nullptr, qkv, Ms, 2304, 768, 0), 1, pick_tile(c, Ms, 2304, 768), s)))
             return rc;
-        if ((rc = run_attention(c, qkv, ctxb, lse, nc, T, s, &d_att, site_attn(l), c0 * 12))) return rc;
+        if ((rc = run_attention(c, g, qkv, ctxb, lse, s, &d_att, site_attn(l), c0, nc))) return rc;
         // residual dropout: y = x + dropout(W a + b) needs the branch on its own, so the residual add moves out
         // of the GEMM epilogue into the dropout kernel
         // (the LayerNorm behind a residual GEMM: inside the GEMM's split-K epilogue where it has one - configs[3] - else on its own)
@@ -920,218 +1133,43 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
 
     // ---- head -----------------------------------------------------------------------------------
     // the FFN hidden buffer is dead by now: scratch for the time sums
-    return run_head<float>(c, x, B, T, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb, kNoInts, F(lay.h), s);
+    return run_head<float>(c, x, B, g.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb, g.pref[6], bf.h, s);
 }
 
-// ---- ragged batches: clips of different lengths packed back to back ----------------------------------------
-// The reference embeds files one at a time (nomad.py:171-183) because every file has its own length; zero-padding
-// a batch would change GroupNorm statistics and the time mean.  Here clips of ANY lengths share one launch
-// sequence with no padding: every per-frame tensor is packed [sum_c L_i(c)][channels], the transformer GEMMs and
-// LayerNorms see plain packed rows, and only the kernels that care about clip boundaries (front end, conv row maps,
-// pos-conv buffer, attention, head) read per-clip prefix sums.  Each row goes through exactly the arithmetic it
-// would see at batch 1, so results are bit-identical to per-clip calls.
-struct RaggedShapes {
-    int B = 0, max_l0 = 0, max_t = 0, min_t = 1 << 30;
-    long long rows[7] = {};   // total frames per conv level
-    long long P = 0;          // total padded pos-conv frames, sum (T_c + 128)
-    long long blocks = 0;     // total pos-conv frame blocks, sum ceil(T_c / kPosBlk) (bf16x3 path)
-    long long pairs[5] = {};  // total output pairs of conv1 .. conv4 (Winograd form), sum ceil(L_i / 2)
-    std::vector<int> meta;    // [lens(B) | pref_0 (B+1) | ... | pref_6 (B+1) | ppref (B+1) | bpref (B+1) | pairpref_1 .. pairpref_4 (B+1)]
-    size_t off_lens() const { return 0; }
-    size_t off_pref(int i) const { return (size_t)B + (size_t)i * (B + 1); }
-    size_t off_ppref() const { return (size_t)B + (size_t)7 * (B + 1); }
-    size_t off_bpref() const { return (size_t)B + (size_t)8 * (B + 1); }
-    size_t off_pairpref(int i) const { return (size_t)B + (size_t)(8 + i) * (B + 1); }   // i = 1 .. 4
-};
-
-static bool make_ragged(int B, const int* lens, RaggedShapes* r) {
-    r->B = B;
-    r->meta.assign((size_t)B + 13 * (size_t)(B + 1), 0);
-    for (int c = 0; c < B; ++c) {
-        Shapes sh;
-        if (!make_shapes(1, lens[c], &sh)) return false;
-        r->meta[c] = lens[c];
-        for (int i = 0; i < 7; ++i) {
-            r->meta[r->off_pref(i) + c + 1] = r->meta[r->off_pref(i) + c] + sh.L[i];
-            r->rows[i] += sh.L[i];
-        }
-        for (int i = 1; i <= 4; ++i) {
-            r->meta[r->off_pairpref(i) + c + 1] = r->meta[r->off_pairpref(i) + c] + (sh.L[i] + 1) / 2;
-            r->pairs[i] += (sh.L[i] + 1) / 2;
-        }
-        r->meta[r->off_ppref() + c + 1] = r->meta[r->off_ppref() + c] + sh.T + 128;
-        r->P += sh.T + 128;
-        const int nb = (sh.T + kPosBlk - 1) / kPosBlk;
-        r->meta[r->off_bpref() + c + 1] = r->meta[r->off_bpref() + c] + nb;
-        r->blocks += nb;
-        r->max_l0 = sh.L[0] > r->max_l0 ? sh.L[0] : r->max_l0;
-        r->max_t = sh.T > r->max_t ? sh.T : r->max_t;
-        r->min_t = sh.T < r->min_t ? sh.T : r->min_t;
-    }
-    return r->rows[0] < (1LL << 31) / 512 * 256;  // row counts stay well inside int
-}
-
-struct RaggedLayout {
-    size_t meta, stats, scale, shift, conva, convb, xpad, x, x2, y, qkv, ctxb, h, total;
-};
-
-static RaggedLayout make_ragged_layout(const RaggedShapes& r) {
-    RaggedLayout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += align_up(bytes);
-        return o;
-    };
-    const size_t M = (size_t)r.rows[6];
-    l.meta = take(sizeof(int) * r.meta.size());
-    l.stats = take(sizeof(double) * stats_doubles(r.B, r.max_l0));
-    l.scale = take(sizeof(float) * 512 * r.B);
-    l.shift = take(sizeof(float) * 512 * r.B);
-    l.conva = take(sizeof(float) * 512 * (size_t)r.rows[0]);
-    l.convb = take(sizeof(float) * 512 * (size_t)r.rows[1]);
-    l.xpad = take(sizeof(float) * 768 * (size_t)r.P);
-    l.x = take(sizeof(float) * 768 * M);
-    l.x2 = take(sizeof(float) * 768 * M);
-    l.y = take(sizeof(float) * 768 * M);
-    l.qkv = take(sizeof(float) * 2304 * M);
-    l.ctxb = take(sizeof(float) * 768 * M);
-    l.h = take(sizeof(float) * 3072 * M);
-    l.total = off;
-    return l;
+// nomad_embed / nomad_embed_train: an equal-length batch in the Layout of make_layout
+static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
+                        float* emb, float* layers_out, void* workspace, size_t workspace_bytes, nomad_stream_t stream,
+                        const Saved* sv) {
+    Shapes sh;
+    if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
+        return fail(NOMAD_ERR_INVALID, "nomad_embed: bad argument (B=%d, n_samples=%d)", B, n_samples);
+    const Layout lay = make_layout(sh, c->keep);
+    if (workspace_bytes < lay.total)
+        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed: workspace %zu < required %zu", workspace_bytes, lay.total);
+    char* ws = static_cast<char*>(workspace);
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.featln), F(lay.xpad), F(lay.x),
+               F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
+    for (int i = 0; i < 7; ++i) bf.conv[i] = F(lay.conv[i]);
+    return forward_run(c, wav, geom_uniform(sh), bf, head_w, head_b, emb, layers_out, lay.splitk != 0 ? F(lay.splitk) : nullptr,
+                       static_cast<hipStream_t>(stream), sv);
 }
 
 static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, const float* head_w,
                           const float* head_b, float* emb, void* workspace, size_t workspace_bytes,
                           nomad_stream_t stream) {
-    RaggedShapes rs;
-    if (!c || !wav || !lens_host || !emb || !workspace || B <= 0 || !make_ragged(B, lens_host, &rs))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged: bad argument (B=%d)", B);
-    for (int i = 0; i < B; ++i)
-        if (lens_host[i] > stride) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged: clip %d longer than the row stride", i);
-    const RaggedLayout lay = make_ragged_layout(rs);
-    if (workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_ragged: workspace %zu < required %zu", workspace_bytes, lay.total);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    RaggedBatch r;
+    if (int rc = ragged_prologue("nomad_embed_ragged", c, c && wav && emb && workspace, B, stride, lens_host, sizeof(float), 0, &r,
+                                 workspace, workspace_bytes, s))
+        return rc;
     char* ws = static_cast<char*>(workspace);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    int* meta = reinterpret_cast<int*>(ws + lay.meta);
-    std::vector<int>& staged = c->ragged_meta_ring[c->ragged_seq++ & 3];  // must outlive the asynchronous copy
-    staged = rs.meta;
-    HIP_TRY(hipMemcpyAsync(meta, staged.data(), sizeof(int) * rs.meta.size(), hipMemcpyHostToDevice, s));
-    const int* lens = meta + rs.off_lens();
-    auto pref = [&](int i) { return static_cast<const int*>(meta + rs.off_pref(i)); };
-    const int* tpref = pref(6);
-    const int* ppref = meta + rs.off_ppref();
-    const int M = (int)rs.rows[6];
-    int rc;
-
-    double* stats = reinterpret_cast<double*>(ws + lay.stats);
-    float *scale = F(lay.scale), *shift = F(lay.shift);
-    float* cb[2] = {F(lay.conva), F(lay.convb)};
-    {
-        Scope sc(c, s, NOMAD_K_FRONT, 0.0);
-        launch_wav_stats(wav, stride, 0, rs.max_l0, B, stats, lens, s);
-        hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(512), 0, s, stats, c->conv0_w, c->gn_w, c->gn_b, 0, scale, shift,
-                           static_cast<float*>(nullptr), static_cast<float*>(nullptr), lens);
-    }
-    {
-        Scope sc(c, s, NOMAD_K_FRONT, 2.0 * (double)rs.rows[0] * 512 * 10);
-        hipLaunchKernelGGL(conv0_gn_gelu_kernel<float>, dim3((rs.max_l0 + kConv0Frames - 1) / kConv0Frames, B), dim3(256), 0,
-                           s, wav, stride, 0, c->conv0_w, scale, shift, cb[0], lens, pref(0));
-    }
-    for (int i = 1; i < 7; ++i) {
-        if (conv_wino(c, i)) {
-            if ((rc = run_conv_s2_f32(c, cb[(i - 1) % 2], c->conv_w[i], cb[i % 2], nullptr, B, 0, 0, meta + rs.off_pairpref(i), pref(i),
-                                      pref(i - 1), (int)rs.pairs[i], s)))
-                return rc;
-            continue;
-        }
-        GemmParams p{};
-        p.A = cb[(i - 1) % 2];
-        p.amap = RowMap{0, 0, 0, kConvS[i] * 512, pref(i), pref(i - 1), B, 512};
-        p.K = kConvK[i] * 512;
-        p.kchunk = p.K;
-        p.W = c->conv_w[i];
-        p.ldw = p.K;
-        p.C = cb[i % 2];
-        p.M = (int)rs.rows[i];
-        p.N = 512;
-        p.n_valid = 512;
-        p.cmap = plain_map(p.M, 512);
-        p.rmap = p.cmap;
-        p.gelu = 1;
-        if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, 512, p.K), s))) return rc;
-    }
-    float* featln = cb[1];
-    if ((rc = run_layernorm(c, cb[0], c->fln_w, c->fln_b, featln, nullptr, M, 512, s))) return rc;
-    float* xpad = F(lay.xpad);
-    const long long grp_stride = rs.P * 48;
-    const RowMap pad_map{64LL * 48, 0, 0, 48, tpref, ppref, B, 48};
-    {
-        Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        hipLaunchKernelGGL(zero_pad_rows_kernel<float>, dim3(16 * B), dim3(256), 0, s, xpad, 0, tpref, ppref, B);
-    }
-    {
-        GemmParams p = dense(featln, 512, c->proj_w, c->proj_b, nullptr, xpad, M, 768, 512, 0);
-        p.cmap = pad_map;
-        p.c_colblk = 48;
-        p.c_colblk_stride = grp_stride;
-        if ((rc = run_gemm(c, p, 1, pick_tile(c, M, 768, 512), s))) return rc;
-    }
-    float *x = F(lay.x), *x2 = F(lay.x2), *y = F(lay.y), *qkv = F(lay.qkv), *ctxb = F(lay.ctxb), *hbuf = F(lay.h);
-    {
-        GemmParams p{};
-        p.A = xpad;
-        p.amap = RowMap{0, 0, 0, 48, tpref, ppref, B, 48};
-        p.a_goff = grp_stride;
-        p.K = 6144;
-        p.kchunk = 6144;
-        p.W = c->pos_w;
-        p.ldw = 6144;
-        p.w_goff = 64LL * 6144;
-        p.bias = c->pos_b;
-        p.bias_goff = 48;
-        p.C = y;
-        p.cmap = plain_map(M, 768);
-        p.c_goff = 48;
-        p.R = xpad;
-        p.rmap = pad_map;
-        p.r_goff = grp_stride;
-        p.M = M;
-        p.N = 64;
-        p.n_valid = 48;
-        p.gelu = 1;
-        if ((rc = run_gemm(c, p, 16, 48, s))) return rc;  // one instantiation for every batch size: same summation order
-    }
-    if ((rc = run_layernorm(c, y, c->eln_w, c->eln_b, x, nullptr, M, 768, s))) return rc;
-    double attn_flops = 0.0;
-    for (int i = 0; i < B; ++i) {
-        const double t = rs.meta[rs.off_pref(6) + i + 1] - rs.meta[rs.off_pref(6) + i];
-        attn_flops += 4.0 * 12.0 * t * t * 64;
-    }
-    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
-        const LayerDev& d = c->layers[l];
-        if ((rc = run_gemm(c, dense(x, 768, d.qkv_w, d.qkv_b, nullptr, qkv, M, 2304, 768, 0), 1, pick_tile(c, M, 2304, 768), s)))
-            return rc;
-        {
-            Scope sc(c, s, NOMAD_K_ATTN, attn_flops);
-            // clips of kAttnV2MinT frames or more: attention_f32_v2_kernel; shorter ones: attention_f32_kernel (each skips the
-            // other's clips) - exactly the kernel the clip would get in a batch of its own
-            if (rs.max_t >= kAttnV2MinT) HIP_TRY(launch_attention_f32_v2(qkv, ctxb, nullptr, B, rs.max_t, tpref, s, kAttnV2MinT));
-            if (rs.min_t < kAttnV2MinT)
-                hipLaunchKernelGGL(attention_f32_kernel<float>, dim3((std::min(rs.max_t, kAttnV2MinT - 1) + 63) / 64, B * 12), dim3(256), 0,
-                                   s, qkv, ctxb, static_cast<float*>(nullptr), 0, tpref, DropCfg{}, 0u, 0, 0LL, kAttnV2MinT);
-        }
-        if ((rc = run_gemm(c, dense(ctxb, 768, d.o_w, d.o_b, x, y, M, 768, 768, 0), 1, pick_tile(c, M, 768, 768), s))) return rc;
-        if ((rc = run_layernorm(c, y, d.ln1_w, d.ln1_b, x2, nullptr, M, 768, s))) return rc;
-        if ((rc = run_gemm(c, dense(x2, 768, d.fc1_w, d.fc1_b, nullptr, hbuf, M, 3072, 768, 1), 1, pick_tile(c, M, 3072, 768), s)))
-            return rc;
-        if ((rc = run_gemm(c, dense(hbuf, 3072, d.fc2_w, d.fc2_b, x2, y, M, 768, 3072, 0), 1, pick_tile(c, M, 768, 3072), s)))
-            return rc;
-        if ((rc = run_layernorm(c, y, d.ln2_w, d.ln2_b, x, nullptr, M, 768, s))) return rc;
-    }
-    return run_head<float>(c, x, B, rs.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb, tpref, hbuf, s);
+    const ActLayout& lay = r.lay;
+    F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.convb), F(lay.xpad), F(lay.x),
+               F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
+    for (int i = 0; i < 7; ++i) bf.conv[i] = F(i % 2 ? lay.convb : lay.conva);   // conv6 lands in conva, LN(512) writes to convb
+    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, nullptr, nullptr, s, nullptr);
 }
 
 // One backward GEMM: C[M][N] = A[M][K] * Wt[N][K]^T (Wt = transposed forward weight), optional GELU' and residual.
@@ -1265,7 +1303,9 @@ struct CkSum {
     int snap[4];
     void* sdst[4];
     size_t scap[4];
-    CkSum(nomad_ctx* c_, hipStream_t s_) : c(c_), s(s_), tab(c_->cksum), stages(c_->cksum_stages), segs(c_->cksum_segs) {
+    // on = false (a ragged forward): records nothing, and leaves an armed table / snapshot to the next equal-length call
+    CkSum(nomad_ctx* c_, hipStream_t s_, bool on) : c(c_), s(s_), tab(on ? c_->cksum : nullptr), stages(c_->cksum_stages), segs(c_->cksum_segs) {
+        if (!on) return;
         for (int k = 0; k < 4; ++k) {
             snap[k] = c->snap_stage[k];
             sdst[k] = c->snap_dst[k];
@@ -1293,7 +1333,7 @@ struct CkSum {
 };
 #else
 struct CkSum {
-    CkSum(nomad_ctx*, hipStream_t) {}
+    CkSum(nomad_ctx*, hipStream_t, bool) {}
     void operator()(const void*, int, size_t) {}
 };
 #endif
@@ -1308,88 +1348,52 @@ static void launch_ln_bf16(const bf16_t* in, const float* g, const float* b, bf1
                            static_cast<float*>(nullptr), M);
 }
 
-struct Bf16Layout {
-    size_t stats, scale, shift, conva, convb, xpad, x, x2, y, qkv, ctxb, h, total;
-};
-
-static Bf16Layout make_bf16_layout(const Shapes& s) {
-    Bf16Layout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += align_up(bytes);
-        return o;
-    };
-    const size_t e = sizeof(bf16_t), M = s.M;
-    l.stats = take(sizeof(double) * stats_doubles(s.B, s.L[0]));
-    l.scale = take(sizeof(float) * 512 * s.B);
-    l.shift = take(sizeof(float) * 512 * s.B);
-    l.conva = take(e * 512 * (size_t)s.B * s.L[0]);
-    l.convb = take(e * 512 * (size_t)s.B * s.L[1]);
-    l.xpad = take(e * 768 * (size_t)s.B * (s.T + 128));
-    l.x = take(e * 768 * M);
-    l.x2 = take(e * 768 * M);
-    l.y = take(e * 768 * M);
-    l.qkv = take(e * 2304 * M);
-    l.ctxb = take(e * 768 * M);
-    l.h = take(e * 3072 * M);
-    l.total = off;
-    return l;
-}
-
-// Scoring forward with bf16 activations / weights and fp32 accumulation, statistics and softmax.
-static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, float* emb, void* workspace,
-                        size_t workspace_bytes, nomad_stream_t stream) {
-    Shapes sh;
-    if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16: bad argument (B=%d, n_samples=%d)", B, n_samples);
-    if (!c->bf16_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16: call nomad_enable_bf16 first");
-    const Bf16Layout lay = make_bf16_layout(sh);
-    if (workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_bf16: workspace %zu < required %zu", workspace_bytes, lay.total);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
+// Scoring forward with bf16 activations / weights and fp32 accumulation, statistics and softmax, over an equal-length or a
+// ragged batch (mixed-length long-form files, config C5 through predict: every clip sees the arithmetic of its own
+// single-clip call).  The diag library's checksum / snapshot stages are recorded on equal-length calls only.
+static int forward_bf16_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const ActLayout& lay, float* emb, char* ws,
+                            hipStream_t s) {
     auto H = [&](size_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
     auto asf = [](const bf16_t* p_) { return reinterpret_cast<const float*>(p_); };  // GemmParams carries typeless pointers
     auto asfm = [](bf16_t* p_) { return reinterpret_cast<float*>(p_); };
-    const int T = sh.T, M = sh.M;
+    const int B = g.B, T = g.T, M = (int)g.rows[6];
     int rc;
     double* stats = reinterpret_cast<double*>(ws + lay.stats);
     float* scale = reinterpret_cast<float*>(ws + lay.scale);
     float* shift = reinterpret_cast<float*>(ws + lay.shift);
     bf16_t* cb[2] = {H(lay.conva), H(lay.convb)};
-    CkSum CK(c, s);  // no-op in the product library
+    CkSum CK(c, s, !g.ragged());  // no-op in the product library
     {
         Scope sc(c, s, NOMAD_K_FRONT, 0.0);
-        launch_wav_stats(wav, n_samples, sh.L[0], sh.L[0], B, stats, kNoInts, s);
-        hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(512), 0, s, stats, c->conv0_w, c->gn_w, c->gn_b, sh.L[0], scale,
-                           shift, static_cast<float*>(nullptr), static_cast<float*>(nullptr), kNoInts);
+        launch_wav_stats(wav, g.wav_ld, g.L[0], g.max_l0, B, stats, g.lens, s);
+        hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(512), 0, s, stats, c->conv0_w, c->gn_w, c->gn_b, g.L[0], scale,
+                           shift, static_cast<float*>(nullptr), static_cast<float*>(nullptr), g.lens);
     }
     CK(stats, B, sizeof(double) * kStatsPerClip);
     CK(scale, B, sizeof(float) * 512);
     CK(shift, B, sizeof(float) * 512);
     {
-        Scope sc(c, s, NOMAD_K_FRONT, 2.0 * B * (double)sh.L[0] * 512 * 10);
-        launch_conv0_bf16(c, wav, n_samples, sh.L[0], sh.L[0], B, scale, shift, cb[0], kNoInts, kNoInts, s);
+        Scope sc(c, s, NOMAD_K_FRONT, 2.0 * (double)g.rows[0] * 512 * 10);
+        launch_conv0_bf16(c, wav, g.wav_ld, g.L[0], g.max_l0, B, scale, shift, cb[0], g.lens, g.pref[0], s);
     }
-    CK(cb[0], B, sizeof(bf16_t) * 512 * (size_t)sh.L[0]);
+    CK(cb[0], B, sizeof(bf16_t) * 512 * (size_t)g.L[0]);
     for (int i = 1; i < 7; ++i) {
         GemmParams p{};
         p.A = asf(cb[(i - 1) % 2]);
-        p.amap = RowMap{0, (long long)sh.L[i - 1] * 512, sh.L[i], kConvS[i] * 512};
+        p.amap = g.conv_amap[i];
         p.K = kConvK[i] * 512;
         p.kchunk = p.K;
         p.W = asf(c->conv_w16[i]);
         p.ldw = p.K;
         p.C = asfm(cb[i % 2]);
-        p.M = B * sh.L[i];
+        p.M = (int)g.rows[i];
         p.N = 512;
         p.n_valid = 512;
         p.cmap = plain_map(p.M, 512);
         p.rmap = p.cmap;
         p.gelu = 1;
         if ((rc = run_gemm_bf16(c, p, 1, s))) return rc;
-        CK(cb[i % 2], B, sizeof(bf16_t) * 512 * (size_t)sh.L[i]);
+        CK(cb[i % 2], B, sizeof(bf16_t) * 512 * (size_t)g.L[i]);
     }
     bf16_t* conv6 = cb[0];
     bf16_t* featln = cb[1];
@@ -1399,28 +1403,26 @@ static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, fl
     }
     CK(featln, B, sizeof(bf16_t) * 512 * (size_t)T);
     bf16_t* xpad = H(lay.xpad);
-    const long long grp_stride = (long long)B * (T + 128) * 48;
-    const RowMap pad_map{64LL * 48, (long long)(T + 128) * 48, T, 48};
     {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        hipLaunchKernelGGL(zero_pad_rows_kernel<bf16_t>, dim3(16 * B), dim3(256), 0, s, xpad, T, kNoInts, kNoInts, B);
+        hipLaunchKernelGGL(zero_pad_rows_kernel<bf16_t>, dim3(16 * B), dim3(256), 0, s, xpad, T, g.pref[6], g.ppref, B);
     }
     {
         GemmParams p = dense(asf(featln), 512, asf(c->proj_w16), c->proj_b, nullptr, asfm(xpad), M, 768, 512, 0);
-        p.cmap = pad_map;
+        p.cmap = g.pad_map;
         p.c_colblk = 48;
-        p.c_colblk_stride = grp_stride;
+        p.c_colblk_stride = g.grp_stride;
         if ((rc = run_gemm_bf16(c, p, 1, s))) return rc;
     }
     CK(xpad, 16 * B, sizeof(bf16_t) * 48 * (size_t)(T + 128));
     bf16_t *x = H(lay.x), *x2 = H(lay.x2), *y = H(lay.y), *qkv = H(lay.qkv), *ctxb = H(lay.ctxb), *hb = H(lay.h);
     if (c->tune.bf16_posconv_slab) {
-        if ((rc = run_posconv_bf16_slab(c, xpad, y, T, B, M, nullptr, nullptr, s))) return rc;
+        if ((rc = run_posconv_bf16_slab(c, xpad, y, g.max_t, B, M, g.pref[6], g.ppref, s))) return rc;
     } else {
         GemmParams p{};
         p.A = asf(xpad);
-        p.amap = RowMap{0, (long long)(T + 128) * 48, T, 48};
-        p.a_goff = grp_stride;
+        p.amap = g.pos_amap;
+        p.a_goff = g.grp_stride;
         p.K = 6144;
         p.kchunk = 6144;
         p.W = asf(c->pos_w16);
@@ -1432,8 +1434,8 @@ static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, fl
         p.cmap = plain_map(M, 768);
         p.c_goff = 48;
         p.R = asf(xpad);
-        p.rmap = pad_map;
-        p.r_goff = grp_stride;
+        p.rmap = g.pad_map;
+        p.r_goff = g.grp_stride;
         p.M = M;
         p.N = 64;
         p.n_valid = 48;
@@ -1453,8 +1455,8 @@ static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, fl
             return rc;
         CK(qkv, B, clip768 * 3);
         {
-            Scope sc(c, s, NOMAD_K_ATTN, 4.0 * B * 12.0 * (double)T * T * 64);
-            HIP_TRY(run_attention_bf16(c, qkv, ctxb, B, T, nullptr, true, s));
+            Scope sc(c, s, NOMAD_K_ATTN, g.attn_flops);
+            HIP_TRY(run_attention_bf16(c, qkv, ctxb, B, g.max_t, g.pref[6], true, s));
         }
         CK(ctxb, B, clip768);
         if ((rc = run_gemm_bf16(c, dense(asf(ctxb), 768, asf(c->o_w16[l]), d.o_b, asf(x), asfm(y), M, 768, 768, 0), 1, s)))
@@ -1477,9 +1479,33 @@ static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, fl
         }
         CK(x, B, clip768);
     }
-    rc = run_head<bf16_t>(c, x, B, T, c->emb_w, c->emb_b, emb, kNoInts, reinterpret_cast<float*>(hb), s);
+    rc = run_head<bf16_t>(c, x, B, g.max_t, c->emb_w, c->emb_b, emb, g.pref[6], reinterpret_cast<float*>(hb), s);
     CK(emb, B, sizeof(float) * 256);
     return rc;
+}
+
+static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, float* emb, void* workspace,
+                        size_t workspace_bytes, nomad_stream_t stream) {
+    Shapes sh;
+    if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
+        return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16: bad argument (B=%d, n_samples=%d)", B, n_samples);
+    if (!c->bf16_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16: call nomad_enable_bf16 first");
+    const BatchGeom g = geom_uniform(sh);
+    const ActLayout lay = make_act_layout(g, sizeof(bf16_t), 0);
+    if (workspace_bytes < lay.total)
+        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_bf16: workspace %zu < required %zu", workspace_bytes, lay.total);
+    return forward_bf16_run(c, wav, g, lay, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+static int forward_ragged_bf16(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, float* emb,
+                               void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    if (c && !c->bf16_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16: call nomad_enable_bf16 first");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RaggedBatch r;
+    if (int rc = ragged_prologue("nomad_embed_ragged_bf16", c, c && wav && emb && workspace, B, stride, lens_host, sizeof(bf16_t), 0,
+                                 &r, workspace, workspace_bytes, s))
+        return rc;
+    return forward_bf16_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s);
 }
 
 
@@ -1512,106 +1538,9 @@ static int run_attention_x3(nomad_ctx* c, const bf16s_t* qkv, long long in_plane
     return 0;
 }
 
-// One implementation serves equal-length batches and ragged ones: X3Geom carries the row maps of either.
-struct X3Geom {
-    int B = 0;
-    long long rows[7] = {};      // total frames per conv level; rows[6] = M
-    long long pad_rows = 0;      // rows of one group of the padded pos-conv buffer
-    int max_l0 = 0, max_t = 0;
-    int wav_ld = 0;              // samples between clips of the wav buffer
-    int L0 = 0, T = 0;           // equal-length batches; 0 when ragged (the kernels read lens / prefixes instead)
-    RowMap conv_amap[7];         // im2col rows of conv layer i over the output of layer i - 1
-    RowMap pad_map;              // post_extract_proj output rows in the group-major, padded pos-conv buffer
-    // pos-conv as a GEMM over blocks of kPosBlk frames: input rows, output rows (in y), residual rows
-    long long pos_blocks = 0;
-    RowMap pos_amap, pos_cmap, pos_rmap;
-    double attn_flops = 0.0;
-    const RaggedShapes* ragged = nullptr;
-};
-
-struct X3Layout {
-    size_t meta, stats, scale, shift, conva, convb, xpad, x, x2, y, qkv, ctxb, h, total;
-    long long capa, capb;  // elements per plane of the two conv ping-pong buffers
-    long long xpad_plane;  // elements per plane of the padded pos-conv buffer (+ kXpadSlack zeroed elements: the last
-                           // frame block of a clip reads up to kPosBlk - 1 frames past the clip's padding)
-};
+// bf16x3: the padded pos-conv buffer has kXpadSlack zeroed elements behind each plane - the last frame block of a clip reads up
+// to kPosBlk - 1 frames past the clip's padding
 constexpr int kXpadSlack = 256;
-
-static X3Layout make_x3_layout(const X3Geom& g) {
-    X3Layout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += align_up(bytes);
-        return o;
-    };
-    const size_t e = 4, M = (size_t)g.rows[6];  // fp32, or two bf16 planes
-    l.capa = 512LL * g.rows[0];
-    l.capb = 512LL * g.rows[1];
-    l.meta = take(g.ragged ? sizeof(int) * g.ragged->meta.size() : 0);
-    l.stats = take(sizeof(double) * stats_doubles(g.B, g.max_l0));
-    l.scale = take(sizeof(float) * 512 * g.B);
-    l.shift = take(sizeof(float) * 512 * g.B);
-    l.conva = take(e * l.capa);
-    l.convb = take(e * l.capb);
-    l.xpad_plane = 768LL * g.pad_rows + kXpadSlack;
-    l.xpad = take(e * (size_t)l.xpad_plane);
-    l.x = take(e * 768 * M);
-    l.x2 = take(e * 768 * M);
-    l.y = take(e * 768 * M);
-    l.qkv = take(e * 2304 * M);
-    l.ctxb = take(e * 768 * M);
-    l.h = take(e * 3072 * M);
-    l.total = off;
-    return l;
-}
-
-static X3Geom x3_geom_fixed(const Shapes& sh) {
-    X3Geom g;
-    g.B = sh.B;
-    for (int i = 0; i < 7; ++i) g.rows[i] = (long long)sh.B * sh.L[i];
-    g.pad_rows = (long long)sh.B * (sh.T + 128);
-    g.max_l0 = sh.L[0];
-    g.max_t = sh.T;
-    g.wav_ld = sh.N;
-    g.L0 = sh.L[0];
-    g.T = sh.T;
-    for (int i = 1; i < 7; ++i) g.conv_amap[i] = RowMap{0, (long long)sh.L[i - 1] * 512, sh.L[i], kConvS[i] * 512};
-    g.pad_map = RowMap{64LL * 48, (long long)(sh.T + 128) * 48, sh.T, 48};
-    const int nb = (sh.T + kPosBlk - 1) / kPosBlk;
-    g.pos_blocks = (long long)sh.B * nb;
-    g.pos_amap = RowMap{0, (long long)(sh.T + 128) * 48, nb, kPosBlk * 48};
-    g.pos_rmap = RowMap{64LL * 48, (long long)(sh.T + 128) * 48, nb, kPosBlk * 48};
-    g.pos_cmap = RowMap{0, (long long)sh.T * 768, nb, kPosBlk * 768};
-    g.attn_flops = 4.0 * sh.B * 12.0 * (double)sh.T * sh.T * 64;
-    return g;
-}
-
-// meta: the device copy of rs.meta (prefix tables); the row maps point into it
-static X3Geom x3_geom_ragged(const RaggedShapes& rs, int stride, const int* meta) {
-    X3Geom g;
-    g.B = rs.B;
-    for (int i = 0; i < 7; ++i) g.rows[i] = rs.rows[i];
-    g.pad_rows = rs.P;
-    g.max_l0 = rs.max_l0;
-    g.max_t = rs.max_t;
-    g.wav_ld = stride;
-    g.ragged = &rs;
-    auto pref = [&](int i) { return meta ? meta + rs.off_pref(i) : nullptr; };
-    const int* ppref = meta ? meta + rs.off_ppref() : nullptr;
-    for (int i = 1; i < 7; ++i) g.conv_amap[i] = RowMap{0, 0, 0, kConvS[i] * 512, pref(i), pref(i - 1), rs.B, 512};
-    const int* bpref = meta ? meta + rs.off_bpref() : nullptr;
-    g.pad_map = RowMap{64LL * 48, 0, 0, 48, pref(6), ppref, rs.B, 48};
-    g.pos_blocks = rs.blocks;
-    g.pos_amap = RowMap{0, 0, 0, kPosBlk * 48, bpref, ppref, rs.B, 48};
-    g.pos_rmap = RowMap{64LL * 48, 0, 0, kPosBlk * 48, bpref, ppref, rs.B, 48};
-    g.pos_cmap = RowMap{0, 0, 0, kPosBlk * 768, bpref, pref(6), rs.B, 768};
-    for (int i = 0; i < rs.B; ++i) {
-        const double t = rs.meta[rs.off_pref(6) + i + 1] - rs.meta[rs.off_pref(6) + i];
-        g.attn_flops += 4.0 * 12.0 * t * t * 64;
-    }
-    return g;
-}
 
 static GemmParams dense_x3(const bf16s_t* A, long long a_plane, int lda, const bf16s_t* W, const float* bias,
                            const bf16s_t* R, long long r_plane, void* C, long long c_plane, int M, int N, int K, int gelu) {
@@ -1624,22 +1553,18 @@ static GemmParams dense_x3(const bf16s_t* A, long long a_plane, int lda, const b
     return p;
 }
 
-// meta (ragged only): device prefix tables, already on their way (same stream)
 // The GEMM instantiation of the path (run_gemm_bf16 tile ids): the kernel that stages every plane once
 // (gemm_bf16x3.hip.h), 2-3 % ahead of the K-concatenated form (20 / 21) in profiles/r01_gemm_bf16x3_shapes.json.
 // One instantiation for every shape and batch size: a clip's bits do not depend on the batch it is in.
 constexpr int kX3Split = 27, kX3F32 = 28;
 
-static int forward_x3_run(nomad_ctx* c, const float* wav, const X3Geom& g, const X3Layout& lay, const int* meta, float* emb,
+static int forward_x3_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const ActLayout& lay, float* emb,
                           char* ws, hipStream_t s, const float* head_w = nullptr, const float* head_b = nullptr,
                           float* layers_out = nullptr) {
     auto S = [&](size_t off) { return reinterpret_cast<bf16s_t*>(ws + off); };
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const int B = g.B, M = (int)g.rows[6];
-    const int* lens = g.ragged ? meta + g.ragged->off_lens() : kNoInts;
-    const int* pref0 = g.ragged ? meta + g.ragged->off_pref(0) : kNoInts;
-    const int* tpref = g.ragged ? meta + g.ragged->off_pref(6) : kNoInts;
-    const int* ppref = g.ragged ? meta + g.ragged->off_ppref() : kNoInts;
+    const int *lens = g.lens, *tpref = g.pref[6];
     const long long pl768 = 768LL * M, pl3072 = 3072LL * M;
     int rc;
     double* stats = reinterpret_cast<double*>(ws + lay.stats);
@@ -1649,14 +1574,14 @@ static int forward_x3_run(nomad_ctx* c, const float* wav, const X3Geom& g, const
     const long long cap[2] = {lay.capa, lay.capb};
     {
         Scope sc(c, s, NOMAD_K_FRONT, 0.0);
-        launch_wav_stats(wav, g.wav_ld, g.L0, g.max_l0, B, stats, lens, s);
-        hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(512), 0, s, stats, c->conv0_w, c->gn_w, c->gn_b, g.L0, scale,
+        launch_wav_stats(wav, g.wav_ld, g.L[0], g.max_l0, B, stats, lens, s);
+        hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(512), 0, s, stats, c->conv0_w, c->gn_w, c->gn_b, g.L[0], scale,
                            shift, static_cast<float*>(nullptr), static_cast<float*>(nullptr), lens);
     }
     {
         Scope sc(c, s, NOMAD_K_FRONT, 2.0 * (double)g.rows[0] * 512 * 10);
         hipLaunchKernelGGL(conv0_gn_gelu_kernel<bf16s_t>, dim3((g.max_l0 + kConv0Frames - 1) / kConv0Frames, B), dim3(256), 0,
-                           s, wav, g.wav_ld, g.L0, c->conv0_w, scale, shift, cb[0], lens, pref0, cap[0]);
+                           s, wav, g.wav_ld, g.L[0], c->conv0_w, scale, shift, cb[0], lens, g.pref[0], cap[0]);
     }
     for (int i = 1; i < 7; ++i) {
         GemmParams p{};
@@ -1686,12 +1611,11 @@ static int forward_x3_run(nomad_ctx* c, const float* wav, const X3Geom& g, const
                            c->fln_b, featln, static_cast<float*>(nullptr), M, cap[0], cap[1]);
     }
     bf16s_t* xpad = S(lay.xpad);
-    const long long grp_stride = g.pad_rows * 48;
     {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
         for (int pl = 0; pl < 2; ++pl) {  // the padding frames (and the slack behind them) are zero in both planes
             bf16_t* plane = reinterpret_cast<bf16_t*>(xpad) + pl * lay.xpad_plane;
-            hipLaunchKernelGGL(zero_pad_rows_kernel<bf16_t>, dim3(16 * B), dim3(256), 0, s, plane, g.T, tpref, ppref, B);
+            hipLaunchKernelGGL(zero_pad_rows_kernel<bf16_t>, dim3(16 * B), dim3(256), 0, s, plane, g.T, tpref, g.ppref, B);
             HIP_TRY(hipMemsetAsync(plane + 768LL * g.pad_rows, 0, kXpadSlack * sizeof(bf16_t), s));
         }
     }
@@ -1699,7 +1623,7 @@ static int forward_x3_run(nomad_ctx* c, const float* wav, const X3Geom& g, const
         GemmParams p = dense_x3(featln, cap[1], 512, c->proj_wx, c->proj_b, nullptr, 0, xpad, lay.xpad_plane, M, 768, 512, 0);
         p.cmap = g.pad_map;
         p.c_colblk = 48;
-        p.c_colblk_stride = grp_stride;
+        p.c_colblk_stride = g.grp_stride;
         if ((rc = run_gemm_bf16(c, p, 1, s, kX3Split))) return rc;
     }
     bf16s_t *x = S(lay.x), *x2 = S(lay.x2), *ctxb = S(lay.ctxb), *hb = S(lay.h);
@@ -1712,8 +1636,8 @@ static int forward_x3_run(nomad_ctx* c, const float* wav, const X3Geom& g, const
         GemmParams p{};
         p.A = reinterpret_cast<const float*>(xpad);
         p.a_plane = lay.xpad_plane;
-        p.amap = g.pos_amap;
-        p.a_goff = grp_stride;
+        p.amap = g.blk_amap;
+        p.a_goff = g.grp_stride;
         p.K = kPosKt;
         p.kchunk = kPosKt;
         p.W = reinterpret_cast<const float*>(c->pos_wx);
@@ -1723,7 +1647,7 @@ static int forward_x3_run(nomad_ctx* c, const float* wav, const X3Geom& g, const
         p.bias = c->pos_bx;
         p.bias_goff = 256;
         p.C = y;
-        p.cmap = g.pos_cmap;
+        p.cmap = g.blk_cmap;
         p.c_goff = 48;
         p.c_colblk = 48;
         p.c_colblk_stride = 768;   // column block j = the next frame's row of y
@@ -1731,8 +1655,8 @@ static int forward_x3_run(nomad_ctx* c, const float* wav, const X3Geom& g, const
         p.c_clip_frames = g.T;
         p.R = reinterpret_cast<const float*>(xpad);   // residual: frame 64 + 5 i + j of the same buffer = rmap(row) + j * 48 + co
         p.r_plane = lay.xpad_plane;
-        p.rmap = g.pos_rmap;
-        p.r_goff = grp_stride;
+        p.rmap = g.blk_rmap;
+        p.r_goff = g.grp_stride;
         p.M = (int)g.pos_blocks;
         p.N = 256;
         p.n_valid = kPosBlk * 48;
@@ -1773,199 +1697,23 @@ static int forward_x3(nomad_ctx* c, const float* wav, int B, int n_samples, floa
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh) || (!head_w != !head_b))
         return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16x3: bad argument (B=%d, n_samples=%d)", B, n_samples);
     if (!c->x3_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16x3: call nomad_enable_bf16x3 first");
-    const X3Geom g = x3_geom_fixed(sh);
-    const X3Layout lay = make_x3_layout(g);
+    const BatchGeom g = geom_uniform(sh);
+    const ActLayout lay = make_act_layout(g, 4, kXpadSlack);
     if (workspace_bytes < lay.total)
         return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_bf16x3: workspace %zu < required %zu", workspace_bytes, lay.total);
-    return forward_x3_run(c, wav, g, lay, nullptr, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), head_w, head_b,
+    return forward_x3_run(c, wav, g, lay, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), head_w, head_b,
                           layers_out);
 }
 
 static int forward_ragged_x3(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, float* emb,
                              void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
-    RaggedShapes rs;
-    if (!c || !wav || !lens_host || !emb || !workspace || B <= 0 || !make_ragged(B, lens_host, &rs))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16x3: bad argument (B=%d)", B);
-    if (!c->x3_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16x3: call nomad_enable_bf16x3 first");
-    for (int i = 0; i < B; ++i)
-        if (lens_host[i] > stride) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16x3: clip %d longer than the row stride", i);
-    const X3Layout lay = make_x3_layout(x3_geom_ragged(rs, stride, nullptr));
-    if (workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_ragged_bf16x3: workspace %zu < required %zu", workspace_bytes, lay.total);
+    if (c && !c->x3_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16x3: call nomad_enable_bf16x3 first");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    int* meta = reinterpret_cast<int*>(ws + lay.meta);
-    std::vector<int>& staged = c->ragged_meta_ring[c->ragged_seq++ & 3];  // must outlive the asynchronous copy
-    staged = rs.meta;
-    HIP_TRY(hipMemcpyAsync(meta, staged.data(), sizeof(int) * rs.meta.size(), hipMemcpyHostToDevice, s));
-    const X3Geom g = x3_geom_ragged(rs, stride, meta);
-    return forward_x3_run(c, wav, g, lay, meta, emb, ws, s);
-}
-
-// Ragged bf16 forward: forward_ragged with the bf16 kernels of forward_bf16 (mixed-length long-form files, config C5
-// through predict).  Every clip sees the arithmetic of its own single-clip bf16 call.
-static size_t ragged_bf16_layout(const RaggedShapes& r, RaggedLayout* l) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += align_up(bytes);
-        return o;
-    };
-    const size_t e = sizeof(bf16_t), M = (size_t)r.rows[6];
-    l->meta = take(sizeof(int) * r.meta.size());
-    l->stats = take(sizeof(double) * stats_doubles(r.B, r.max_l0));
-    l->scale = take(sizeof(float) * 512 * r.B);
-    l->shift = take(sizeof(float) * 512 * r.B);
-    l->conva = take(e * 512 * (size_t)r.rows[0]);
-    l->convb = take(e * 512 * (size_t)r.rows[1]);
-    l->xpad = take(e * 768 * (size_t)r.P);
-    l->x = take(e * 768 * M);
-    l->x2 = take(e * 768 * M);
-    l->y = take(e * 768 * M);
-    l->qkv = take(e * 2304 * M);
-    l->ctxb = take(e * 768 * M);
-    l->h = take(e * 3072 * M);
-    l->total = off;
-    return off;
-}
-
-static int forward_ragged_bf16(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, float* emb,
-                               void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
-    RaggedShapes rs;
-    if (!c || !wav || !lens_host || !emb || !workspace || B <= 0 || !make_ragged(B, lens_host, &rs))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16: bad argument (B=%d)", B);
-    if (!c->bf16_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16: call nomad_enable_bf16 first");
-    for (int i = 0; i < B; ++i)
-        if (lens_host[i] > stride) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16: clip %d longer than the row stride", i);
-    RaggedLayout lay{};
-    ragged_bf16_layout(rs, &lay);
-    if (workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_ragged_bf16: workspace %zu < required %zu", workspace_bytes, lay.total);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto H = [&](size_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
-    auto asf = [](const bf16_t* p_) { return reinterpret_cast<const float*>(p_); };
-    auto asfm = [](bf16_t* p_) { return reinterpret_cast<float*>(p_); };
-    int* meta = reinterpret_cast<int*>(ws + lay.meta);
-    std::vector<int>& staged = c->ragged_meta_ring[c->ragged_seq++ & 3];  // must outlive the asynchronous copy
-    staged = rs.meta;
-    HIP_TRY(hipMemcpyAsync(meta, staged.data(), sizeof(int) * rs.meta.size(), hipMemcpyHostToDevice, s));
-    const int* lens = meta + rs.off_lens();
-    auto pref = [&](int i) { return static_cast<const int*>(meta + rs.off_pref(i)); };
-    const int* tpref = pref(6);
-    const int* ppref = meta + rs.off_ppref();
-    const int M = (int)rs.rows[6];
-    int rc;
-    double* stats = reinterpret_cast<double*>(ws + lay.stats);
-    float* scale = reinterpret_cast<float*>(ws + lay.scale);
-    float* shift = reinterpret_cast<float*>(ws + lay.shift);
-    bf16_t* cb[2] = {H(lay.conva), H(lay.convb)};
-    {
-        Scope sc(c, s, NOMAD_K_FRONT, 0.0);
-        launch_wav_stats(wav, stride, 0, rs.max_l0, B, stats, lens, s);
-        hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(512), 0, s, stats, c->conv0_w, c->gn_w, c->gn_b, 0, scale, shift,
-                           static_cast<float*>(nullptr), static_cast<float*>(nullptr), lens);
-    }
-    {
-        Scope sc(c, s, NOMAD_K_FRONT, 2.0 * (double)rs.rows[0] * 512 * 10);
-        launch_conv0_bf16(c, wav, stride, 0, rs.max_l0, B, scale, shift, cb[0], lens, pref(0), s);
-    }
-    for (int i = 1; i < 7; ++i) {
-        GemmParams p{};
-        p.A = asf(cb[(i - 1) % 2]);
-        p.amap = RowMap{0, 0, 0, kConvS[i] * 512, pref(i), pref(i - 1), B, 512};
-        p.K = kConvK[i] * 512;
-        p.kchunk = p.K;
-        p.W = asf(c->conv_w16[i]);
-        p.ldw = p.K;
-        p.C = asfm(cb[i % 2]);
-        p.M = (int)rs.rows[i];
-        p.N = 512;
-        p.n_valid = 512;
-        p.cmap = plain_map(p.M, 512);
-        p.rmap = p.cmap;
-        p.gelu = 1;
-        if ((rc = run_gemm_bf16(c, p, 1, s))) return rc;
-    }
-    bf16_t* featln = cb[1];
-    {
-        Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        launch_ln_bf16<2>(cb[0], c->fln_w, c->fln_b, featln, M, s, c->tune.bf16_ln_rows);
-    }
-    bf16_t* xpad = H(lay.xpad);
-    const long long grp_stride = rs.P * 48;
-    const RowMap pad_map{64LL * 48, 0, 0, 48, tpref, ppref, B, 48};
-    {
-        Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        hipLaunchKernelGGL(zero_pad_rows_kernel<bf16_t>, dim3(16 * B), dim3(256), 0, s, xpad, 0, tpref, ppref, B);
-    }
-    {
-        GemmParams p = dense(asf(featln), 512, asf(c->proj_w16), c->proj_b, nullptr, asfm(xpad), M, 768, 512, 0);
-        p.cmap = pad_map;
-        p.c_colblk = 48;
-        p.c_colblk_stride = grp_stride;
-        if ((rc = run_gemm_bf16(c, p, 1, s))) return rc;
-    }
-    bf16_t *x = H(lay.x), *x2 = H(lay.x2), *y = H(lay.y), *qkv = H(lay.qkv), *ctxb = H(lay.ctxb), *hb = H(lay.h);
-    if (c->tune.bf16_posconv_slab) {
-        if ((rc = run_posconv_bf16_slab(c, xpad, y, rs.max_t, B, M, tpref, ppref, s))) return rc;
-    } else {
-        GemmParams p{};
-        p.A = asf(xpad);
-        p.amap = RowMap{0, 0, 0, 48, tpref, ppref, B, 48};
-        p.a_goff = grp_stride;
-        p.K = 6144;
-        p.kchunk = 6144;
-        p.W = asf(c->pos_w16);
-        p.ldw = 6144;
-        p.w_goff = 64LL * 6144;
-        p.bias = c->pos_b;
-        p.bias_goff = 48;
-        p.C = asfm(y);
-        p.cmap = plain_map(M, 768);
-        p.c_goff = 48;
-        p.R = asf(xpad);
-        p.rmap = pad_map;
-        p.r_goff = grp_stride;
-        p.M = M;
-        p.N = 64;
-        p.n_valid = 48;
-        p.gelu = 1;
-        if ((rc = run_gemm_bf16(c, p, 16, s))) return rc;
-    }
-    {
-        Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        launch_ln_bf16<3>(y, c->eln_w, c->eln_b, x, M, s, c->tune.bf16_ln_rows);
-    }
-    double attn_flops = 0.0;
-    for (int i = 0; i < B; ++i) {
-        const double t = rs.meta[rs.off_pref(6) + i + 1] - rs.meta[rs.off_pref(6) + i];
-        attn_flops += 4.0 * 12.0 * t * t * 64;
-    }
-    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
-        const LayerDev& d = c->layers[l];
-        if ((rc = run_gemm_bf16(c, dense(asf(x), 768, asf(c->qkv_w16[l]), c->qkv_b16[l], nullptr, asfm(qkv), M, 2304, 768, 0), 1, s)))
-            return rc;
-        {
-            Scope sc(c, s, NOMAD_K_ATTN, attn_flops);
-            HIP_TRY(run_attention_bf16(c, qkv, ctxb, B, rs.max_t, tpref, true, s));
-        }
-        if ((rc = run_gemm_bf16(c, dense(asf(ctxb), 768, asf(c->o_w16[l]), d.o_b, asf(x), asfm(y), M, 768, 768, 0), 1, s)))
-            return rc;
-        {
-            Scope sc(c, s, NOMAD_K_ROW, 0.0);
-            launch_ln_bf16<3>(y, d.ln1_w, d.ln1_b, x2, M, s, c->tune.bf16_ln_rows);
-        }
-        if ((rc = run_gemm_bf16(c, dense(asf(x2), 768, asf(c->fc1_w16[l]), d.fc1_b, nullptr, asfm(hb), M, 3072, 768, 1), 1, s)))
-            return rc;
-        if ((rc = run_gemm_bf16(c, dense(asf(hb), 3072, asf(c->fc2_w16[l]), d.fc2_b, asf(x2), asfm(y), M, 768, 3072, 0), 1, s)))
-            return rc;
-        {
-            Scope sc(c, s, NOMAD_K_ROW, 0.0);
-            launch_ln_bf16<3>(y, d.ln2_w, d.ln2_b, x, M, s, c->tune.bf16_ln_rows);
-        }
-    }
-    return run_head<bf16_t>(c, x, B, rs.max_t, c->emb_w, c->emb_b, emb, tpref, reinterpret_cast<float*>(hb), s);
+    RaggedBatch r;
+    if (int rc = ragged_prologue("nomad_embed_ragged_bf16x3", c, c && wav && emb && workspace, B, stride, lens_host, 4, kXpadSlack,
+                                 &r, workspace, workspace_bytes, s))
+        return rc;
+    return forward_x3_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s);
 }
 
 extern "C" {
@@ -2032,7 +1780,7 @@ int nomad_workspace_bytes_bf16(const nomad_ctx* c, int B, int n_samples, size_t*
     Shapes sh;
     if (!c || !bytes || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "nomad_workspace_bytes_bf16: bad shape B=%d N=%d", B, n_samples);
-    *bytes = make_bf16_layout(sh).total;
+    *bytes = make_act_layout(geom_uniform(sh), sizeof(bf16_t), 0).total;
     return 0;
 }
 
@@ -2092,15 +1840,14 @@ int nomad_workspace_bytes_bf16x3(const nomad_ctx* c, int B, int n_samples, size_
     Shapes sh;
     if (!c || !bytes || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "nomad_workspace_bytes_bf16x3: bad shape B=%d N=%d", B, n_samples);
-    *bytes = make_x3_layout(x3_geom_fixed(sh)).total;
+    *bytes = make_act_layout(geom_uniform(sh), 4, kXpadSlack).total;
     return 0;
 }
 
 int nomad_workspace_bytes_ragged_bf16x3(const nomad_ctx* c, int B, const int* lengths_host, size_t* bytes) {
-    RaggedShapes rs;
-    if (!c || !bytes || !lengths_host || B <= 0 || !make_ragged(B, lengths_host, &rs))
-        return fail(NOMAD_ERR_INVALID, "nomad_workspace_bytes_ragged_bf16x3: bad argument");
-    *bytes = make_x3_layout(x3_geom_ragged(rs, 0, nullptr)).total;
+    RaggedBatch r;
+    if (int rc = ragged_prologue("nomad_workspace_bytes_ragged_bf16x3", nullptr, c && bytes, B, 0, lengths_host, 4, kXpadSlack, &r)) return rc;
+    *bytes = r.lay.total;
     return 0;
 }
 
@@ -2153,11 +1900,10 @@ int nomad_diag_gemm_bf16x3(nomad_ctx* c, const void* A, const void* W, const flo
 }
 
 int nomad_workspace_bytes_ragged_bf16(const nomad_ctx* c, int B, const int* lengths_host, size_t* bytes) {
-    RaggedShapes rs;
-    if (!c || !bytes || !lengths_host || B <= 0 || !make_ragged(B, lengths_host, &rs))
-        return fail(NOMAD_ERR_INVALID, "nomad_workspace_bytes_ragged_bf16: bad argument");
-    RaggedLayout lay{};
-    *bytes = ragged_bf16_layout(rs, &lay);
+    RaggedBatch r;
+    if (int rc = ragged_prologue("nomad_workspace_bytes_ragged_bf16", nullptr, c && bytes, B, 0, lengths_host, sizeof(bf16_t), 0, &r))
+        return rc;
+    *bytes = r.lay.total;
     return 0;
 }
 
@@ -2327,10 +2073,9 @@ int nomad_embed(nomad_ctx* c, const float* wav, int B, int n_samples, const floa
 }
 
 int nomad_workspace_bytes_ragged(const nomad_ctx* c, int B, const int* lengths_host, size_t* bytes) {
-    RaggedShapes rs;
-    if (!c || !bytes || !lengths_host || B <= 0 || !make_ragged(B, lengths_host, &rs))
-        return fail(NOMAD_ERR_INVALID, "nomad_workspace_bytes_ragged: bad argument");
-    *bytes = make_ragged_layout(rs).total;
+    RaggedBatch r;
+    if (int rc = ragged_prologue("nomad_workspace_bytes_ragged", nullptr, c && bytes, B, 0, lengths_host, sizeof(float), 0, &r)) return rc;
+    *bytes = r.lay.total;
     return 0;
 }
 
@@ -2508,7 +2253,7 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
     // the regularisation of the forward this backward belongs to (the caller re-sets it: nomad_train_set_stochastic)
     const DropCfg d_in = make_drop(c, train ? c->p_input : 0.f), d_res = make_drop(c, train ? c->p_drop : 0.f),
                   d_att = make_drop(c, train ? c->p_attn : 0.f);
-    int nbr = 1;  // LayerDrop masks: one for the call, or one per branch of a merged batch (see forward_impl)
+    int nbr = 1;  // LayerDrop masks: one for the call, or one per branch of a merged batch (see forward_run)
     unsigned bmask[4] = {train ? c->layer_mask : 0xFFFu, 0xFFFu, 0xFFFu, 0xFFFu};
     if (train && c->branches > 1) {
         if (B % c->branches) return fail(NOMAD_ERR_INVALID, "nomad_train_backward: B=%d is not %d equal branches", B, c->branches);
@@ -3423,7 +3168,10 @@ int nomad_diag_attention_bwd(nomad_ctx* c, const float* qkv, const float* dctx, 
     if (!c || !qkv || !dctx || !ctx_out || !lse || !dqkv || B <= 0 || T <= 0)
         return fail(NOMAD_ERR_INVALID, "nomad_diag_attention_bwd: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = run_attention(c, qkv, ctx_out, lse, B, T, s);
+    BatchGeom g;
+    g.B = B;
+    g.T = T;
+    int rc = run_attention(c, g, qkv, ctx_out, lse, s);
     if (rc) return rc;
     float* D = nullptr;  // diagnostics only: the product path carves this from the caller's workspace
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&D), sizeof(float) * 12 * (size_t)B * T));
@@ -3444,7 +3192,10 @@ int nomad_diag_attention_bf16(nomad_ctx* c, const void* qkv, void* out, int B, i
 
 int nomad_diag_attention(nomad_ctx* c, const float* qkv, float* out, int B, int T, nomad_stream_t stream) {
     if (!c || !qkv || !out || B <= 0 || T <= 0) return fail(NOMAD_ERR_INVALID, "nomad_diag_attention: bad argument");
-    return run_attention(c, qkv, out, nullptr, B, T, static_cast<hipStream_t>(stream));
+    BatchGeom g;
+    g.B = B;
+    g.T = T;
+    return run_attention(c, g, qkv, out, nullptr, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
