@@ -187,6 +187,7 @@ struct nomad_ctx {
     // (the no-gradient branches of Nomad.forward() - layer outputs wanted, nothing saved - take their partial-sum block from the
     // call's own workspace: Layout::splitk)
     float* splitk_cur = nullptr;                            // the block of the call being enqueued
+    size_t splitk_cur_floats = 0;                           // its capacity: no split whose S x M x N partials exceed it
     bool splitk_ok = false;
     // A LayerNorm(768) the caller will apply to the output of the NEXT dense GEMM (run_layer: out_proj -> LN, fc2 -> LN): when that GEMM
     // splits K, its epilogue normalises the rows itself (splitk_epilogue_ln_kernel) and sets `done`; otherwise the caller launches the

@@ -74,6 +74,14 @@ void launch_wav_stats(const float* wav, int ld, int L0, int max_l0, int B, doubl
     hipLaunchKernelGGL(wav_stats_fold_kernel, dim3(B), dim3(128), 0, s, part, nchunk, L0, stats, lens);
 }
 
+// floats in the split-K block of a small layer-output forward (Layout::splitk), 0 where that forward does not split: S x M x N
+// for the largest transformer problem splitk_applies / posconv_splitk_applies let through at M = s.M frames (S x N <= 6144: fc1
+// 2 x 3072, qkv 2 x 2304, fc2 / pos-conv 4 x 768), never more than the fixed cap those checks use.  The conv GEMMs of one clip
+// have M = L[i] > s.M rows: they split only where their partials fit too (nomad_ctx::splitk_cur_floats).
+size_t layers_splitk_floats(const Shapes& s) {
+    return s.M < kSplitKLayersMaxM ? std::min(kSplitKPartFloats, (size_t)6144 * (size_t)s.M) : 0;
+}
+
 struct Layout {
     size_t stats, scale, shift, conv[7], featln, xpad, x, x2, y, qkv, ctxb, h, splitk, total;
 };
@@ -108,9 +116,8 @@ Layout make_layout(const Shapes& s, bool keep) {
     l.h = take(act * 4);
     // partial products of the split-K GEMMs of a small layer-output forward (forward_run): part of the CALL's workspace, so that
     // whether such a forward splits depends on its shape alone - not on which streams other calls are running on
-    // Sized from the shape: S x M x N floats for the largest problem splitk_applies / posconv_splitk_applies let through at this M
-    // (S x N <= 6144: fc1 2 x 3072, qkv 2 x 2304, fc2 / pos-conv 4 x 768), never more than the fixed cap those checks use.
-    l.splitk = s.M < kSplitKLayersMaxM ? take(std::min(kSplitKPartFloats, (size_t)6144 * (size_t)s.M) * sizeof(float)) : 0;
+    const size_t sk = layers_splitk_floats(s);
+    l.splitk = sk ? take(sk * sizeof(float)) : 0;
     l.total = off;
     return l;
 }
@@ -501,7 +508,9 @@ static bool splitk_applies(const nomad_ctx* c, const GemmParams& p, int groups, 
     const long long tiles = (long long)((p.M + 63) / 64) * (p.N / 64);
     if (tiles >= 512 || p.K < 768) return false;
     *S = p.K >= 2304 ? 4 : 2;
-    return p.K % (*S * 32) == 0 && (size_t)*S * p.N <= 6144 && (size_t)*S * p.M * p.N <= kSplitKPartFloats;   // (make_layout sizes the block by these two)
+    // S x M x N partials must fit the block being written: layers_splitk_floats sizes a layer-output forward's by the transformer
+    // GEMMs, and a one-clip conv GEMM (M = L[i] rows, several times the frames) can exceed it
+    return p.K % (*S * 32) == 0 && (size_t)*S * p.N <= 6144 && (size_t)*S * p.M * p.N <= c->splitk_cur_floats;
 }
 
 static int run_gemm_splitk(nomad_ctx* c, const GemmParams& p, int S, hipStream_t s) {
@@ -552,7 +561,7 @@ static bool posconv_splitk_applies(const nomad_ctx* c, const GemmParams& p, int 
     if (!c->tune.splitk_posconv || !c->splitk_ok || !c->splitk_cur || groups != 16 || tile != 48) return false;
     if (p.DG || p.K != 6144 || p.kchunk != p.K || p.n_valid != 48 || p.c_goff != 48) return false;
     const bool c_plain = p.cmap.clip_rows >= p.M && p.cmap.off == 0 && p.cmap.ld == 768;
-    return c_plain && (long long)((p.M + 255) / 256) * 16 < 256 && (size_t)4 * p.M * 768 <= kSplitKPartFloats;
+    return c_plain && (long long)((p.M + 255) / 256) * 16 < 256 && (size_t)4 * p.M * 768 <= c->splitk_cur_floats;
 }
 
 static int run_posconv_splitk(nomad_ctx* c, const GemmParams& p, hipStream_t s) {
@@ -919,10 +928,11 @@ struct F32Bufs {
 
 // The fp32 forward, over an equal-length or a ragged batch.  sv == nullptr: scoring mode (intermediates alias inside the
 // workspace).  sv != nullptr: training mode - every tensor the backward needs is written to its slot in `sv` instead.
-// splitk_block: the workspace's split-K block of an equal-length layer-output forward, or nullptr.  The training inputs (sv,
-// its dropout and LayerDrop, layers_out, split-K) are for equal-length batches only.
+// splitk_block: the workspace's split-K block of an equal-length layer-output forward (splitk_floats floats), or nullptr.  The
+// training inputs (sv, its dropout and LayerDrop, layers_out, split-K) are for equal-length batches only.
 static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const F32Bufs& bf, const float* head_w,
-                       const float* head_b, float* emb, float* layers_out, float* splitk_block, hipStream_t s, const Saved* sv) {
+                       const float* head_b, float* emb, float* layers_out, float* splitk_block, size_t splitk_floats, hipStream_t s,
+                       const Saved* sv) {
     if (g.ragged() && (sv || layers_out || splitk_block))
         return fail(NOMAD_ERR_INVALID, "fp32 forward: training inputs, layer outputs and split-K need an equal-length batch");
     const int B = g.B, T = g.T, M = (int)g.rows[6];
@@ -936,8 +946,15 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
     float* const loss_block = (sv == nullptr && layers_out != nullptr && splitk_block != nullptr && c->tune.splitk_layers) ? splitk_block : nullptr;
     const SplitKScope splitk(c, (sv != nullptr || loss_block != nullptr) && !c->train_ready);
     float* const prev_cur = c->splitk_cur;
+    const size_t prev_cur_floats = c->splitk_cur_floats;
     c->splitk_cur = sv != nullptr ? c->splitk_part : loss_block;
-    struct CurRestore { nomad_ctx* c; float* v; ~CurRestore() { c->splitk_cur = v; } } cur_restore{c, prev_cur};
+    c->splitk_cur_floats = sv != nullptr ? kSplitKPartFloats : loss_block != nullptr ? splitk_floats : 0;
+    struct CurRestore {
+        nomad_ctx* c;
+        float* v;
+        size_t n;
+        ~CurRestore() { c->splitk_cur = v; c->splitk_cur_floats = n; }
+    } cur_restore{c, prev_cur, prev_cur_floats};
     int rc;
     // model.train() regularisation: only in the training-mode forward, only when switched on
     const bool reg = sv != nullptr;
@@ -1152,7 +1169,7 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(lay.conv[i]);
     return forward_run(c, wav, geom_uniform(sh), bf, head_w, head_b, emb, layers_out, lay.splitk != 0 ? F(lay.splitk) : nullptr,
-                       static_cast<hipStream_t>(stream), sv);
+                       layers_splitk_floats(sh), static_cast<hipStream_t>(stream), sv);
 }
 
 static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, const float* head_w,
@@ -1169,7 +1186,7 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
     F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.convb), F(lay.xpad), F(lay.x),
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(i % 2 ? lay.convb : lay.conva);   // conv6 lands in conva, LN(512) writes to convb
-    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, nullptr, nullptr, s, nullptr);
+    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, nullptr, nullptr, 0, s, nullptr);
 }
 
 // One backward GEMM: C[M][N] = A[M][K] * Wt[N][K]^T (Wt = transposed forward weight), optional GELU' and residual.
@@ -2246,8 +2263,15 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
     const int T = sh.T, M = sh.M;
     const SplitKScope splitk(c, !train && !c->train_ready);  // d loss / d waveform of Nomad.forward(): small-M GEMMs may split K
     float* const prev_cur_b = c->splitk_cur;
+    const size_t prev_cur_floats_b = c->splitk_cur_floats;
     c->splitk_cur = c->splitk_part;
-    struct CurRestoreB { nomad_ctx* c; float* v; ~CurRestoreB() { c->splitk_cur = v; } } cur_restore_b{c, prev_cur_b};
+    c->splitk_cur_floats = kSplitKPartFloats;
+    struct CurRestoreB {
+        nomad_ctx* c;
+        float* v;
+        size_t n;
+        ~CurRestoreB() { c->splitk_cur = v; c->splitk_cur_floats = n; }
+    } cur_restore_b{c, prev_cur_b, prev_cur_floats_b};
     float *gx = F(lay.gx), *dya = F(lay.dya), *dyb = F(lay.dyb), *dh = F(lay.dh), *dqkv = F(lay.dqkv);
     int rc;
     // the regularisation of the forward this backward belongs to (the caller re-sets it: nomad_train_set_stochastic)
