@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full     # + every measurement beyond the headline (below)
     python bench.py --gpus N --steps K --warmup W        # N > 1 from a plain shell: spawns the N ranks itself (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -19,11 +20,18 @@ Per-GPU work is fixed as N grows (weak scaling); value = all ranks' clips / max-
 Inputs are resident in HBM before the timed region.  Weights: real nomad_best_model.pt when present,
 otherwise a seeded random parameter set of the same architecture (no network for checkpoints).
 
-Also on the JSON line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline fields, the
+rank census and the model's FLOP rate against the MFMA peak.  Everything that takes work of its own runs only with --full,
+after the timed steps and never part of `value`:
   roofline      the dominant kernel (fp32 MFMA GEMM, all launches): algorithmic FLOPs / summed
-                hipEvent durations of those launches inside the timed region, vs the 157.3 TF fp32 MFMA peak
+                hipEvent durations of those launches, vs the 157.3 TF fp32 MFMA peak.  With the two-stream batch split
+                on (the default) they are timed in a second, profiled pass with the split off: --full only.  With it
+                off (--single-stream) they are timed inside the timed steps themselves, in a plain run too.
+  roofline.traffic  on a 1-GPU headline run, two rocprofv3 --pmc passes as child processes (--full only; otherwise
+                the committed profiles/pmc_traffic.json, labelled as such)
   cpu_baseline  the CPU oracle (PyTorch fp32 restatement of the reference path, batch-1 loop like
                 nomad.py:171-183 + float64 cdist) timed on this box's host cores over a bounded sample
+  also_measured*  the same workload in bf16x3; configs[2], configs[3] and configs[4]; the peaky-weight loops
 """
 import argparse
 import json
@@ -384,9 +392,13 @@ def main():
                     help="without a real checkpoint: seeded = PyTorch-default-style random init (near-zero attention logits); "
                          "peaky = the same with q/k gain 6 (logit sigma ~ 6: softmax rows with a few dominant keys, as "
                          "trained models have) - the attention kernels are data dependent")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run everything else this script measures: the CPU baseline, the "
+                         "bf16x3 / configs[2-4] / peaky-weight legs, the roofline's own profiled pass and its live rocprofv3 "
+                         "traffic passes (a plain run only times the steps)")
     ap.add_argument("--live-traffic", choices=("auto", "off"), default="auto",
-                    help="auto: a 1-GPU headline run takes the two rocprofv3 --pmc passes behind roofline.traffic itself (child "
-                         "processes, ~15 s); off: replay profiles/pmc_traffic.json")
+                    help="auto: a 1-GPU --full headline run takes the two rocprofv3 --pmc passes behind roofline.traffic itself "
+                         "(child processes, ~15 s); off: replay profiles/pmc_traffic.json")
     ap.add_argument("--spawn", action="store_true",
                     help="start the ranks through torch.distributed.run even for --gpus 1 (what --gpus N > 1 does by itself)")
     ap.add_argument("--single-stream", action="store_true",
@@ -468,10 +480,12 @@ def main():
     profile = not args.no_profile
     # Every precision embeds a batch as two halves on two streams (Engine.embed*): launches overlap, so per-kernel event
     # durations no longer add up to wall time.  Its roofline comes from a second, profiled pass with the split off;
-    # `value` from the un-profiled pass the product actually runs.
-    split_attr = {"bf16x3": "X3_SPLIT_ROWS", "bf16": "BF16_SPLIT_ROWS", "f32": "F32_SPLIT_ROWS"}.get(args.dtype)
-    split_prof = profile and split_attr is not None and getattr(eng, split_attr)
-    if profile and not split_prof:
+    # `value` from the un-profiled pass the product actually runs.  That second pass is a run of its own: --full only.
+    split_attr = {"bf16x3": "X3_SPLIT_ROWS", "bf16": "BF16_SPLIT_ROWS", "f32": "F32_SPLIT_ROWS"}[args.dtype]
+    split_on = bool(getattr(eng, split_attr))
+    inband_prof = profile and not split_on
+    split_prof = profile and split_on and args.full
+    if inband_prof:
         eng.profile_enable(True)
         eng.profile_reset()
     t0 = time.perf_counter()
@@ -483,8 +497,8 @@ def main():
     if args.dump_outputs and rank == 0:   # outside the timed window, before any later pass reuses the engine
         dump_outputs(args.dump_outputs, {"scores": mean.cpu().numpy(), "distances": d.cpu().numpy(),
                                          "ref_embeddings": ref_all_seen.cpu().numpy()})
-    prof = eng.profile_read() if profile and not split_prof else None
-    if profile and not split_prof:
+    prof = eng.profile_read() if inband_prof else None
+    if inband_prof:
         eng.profile_enable(False)
     if split_prof:
         keep = getattr(eng, split_attr)
@@ -506,10 +520,12 @@ def main():
     assert torch.isfinite(mean).all()
     census = rank_census(world, rank, local_rank, use_pg, my_elapsed, args.steps, ref_all_seen.shape[0], n_ref)
 
-    # After the headline measurement (never part of `value`): the same workload through the bf16x3 precision mode,
-    # timed the same way, and how far its scores are from the fp32 ones just computed.
+    # With --full, after the headline measurement (never part of `value`): the same workload through the bf16x3 precision
+    # mode, timed the same way, and how far its scores are from the fp32 ones just computed.
+    extras = args.full and args.dtype == "f32" and not args.no_also
+    headline = extras and n_samples == 64000 and B == 256
     also = None
-    if args.dtype == "f32" and not args.no_also:
+    if extras:
         try:
             sc3 = ShardedScorer(eng.embed_bf16x3, eng.pairwise, equal_shards=True, force_collective=use_pg)
             for _ in range(args.warmup):
@@ -531,7 +547,7 @@ def main():
     # ... and BASELINE.json configs[4] (long-form 30 s clips, bf16, batch 32 per GPU), a few steps (~25 ms each), so that
     # the driver's run carries a number for it too.  Only next to the default headline workload.
     also_c5 = None
-    if args.dtype == "f32" and not args.no_also and n_samples == 64000 and B == 256:
+    if headline:
         try:
             g5 = torch.Generator().manual_seed(2000 + rank)
             wav5 = (0.1 * torch.randn(32, 480000, generator=g5)).clamp(-1, 1).cuda()
@@ -631,7 +647,6 @@ def main():
     # (nomad.forward() latency, one GPU: rank 0), and the attention kernels' sensitivity to the weights: the headline
     # workload and configs[4] once more on the "peaky" seeded weights.  All after the headline, never part of `value`.
     also_c3 = also_c4 = also_peaky = None
-    headline = args.dtype == "f32" and not args.no_also and n_samples == 64000 and B == 256
     if headline:
         try:
             also_c3 = time_c3(eng, world, rank, use_pg, fence)
@@ -735,13 +750,13 @@ def main():
         tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
         if args.dtype == "f32" and n_samples == 64000 and B == 256:
             # HBM-side bytes per launch from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command
-            # (fabric-side counters, Infinity-Cache hits included).  On a 1-GPU headline run the two passes are taken NOW, as
+            # (fabric-side counters, Infinity-Cache hits included).  On a 1-GPU --full headline run the two passes are taken NOW, as
             # child processes (tools/pmc_traffic.py:collect, ~15 s; this process is idle meanwhile); otherwise, or if that
             # fails, the table committed under profiles/ (same passes, taken by tools/gpu_pmc_traffic.sh) is replayed and says so.
             # (never from inside a profiler: a bench.py that is itself the target of rocprofv3 would start nested profiled runs)
             under_profiler = any(k in os.environ for k in ("ROCP_TOOL_LIBRARIES", "ROCPROFILER_METRICS_PATH")) or \
                 "rocprof" in os.environ.get("LD_PRELOAD", "")
-            if world == 1 and prof and args.live_traffic != "off" and not under_profiler:
+            if world == 1 and prof and args.full and args.live_traffic != "off" and not under_profiler:
                 try:
                     sys.path.insert(0, os.path.join(ROOT, "tools"))
                     import pmc_traffic
@@ -810,7 +825,7 @@ def main():
             out["also_measured_c4"] = also_c4
         if also_peaky:
             out["also_measured_peaky"] = also_peaky
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, n_samples)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)

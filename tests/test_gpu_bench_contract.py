@@ -21,7 +21,7 @@ def _run(args, launcher=()):
 
 
 def test_bench_line_contract():
-    out = _run(["--steps", "2", "--warmup", "1", "--batch", "16", "--refs", "4", "--no-cpu-baseline"])
+    out = _run(["--steps", "2", "--warmup", "1", "--batch", "16", "--refs", "4", "--no-cpu-baseline", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in out, key
@@ -38,6 +38,24 @@ def test_bench_line_contract():
     assert "also_measured_c5" not in out                                                     # only next to the headline workload
     also = out["also_measured"]
     assert also["unit"] == "clips/s" and also["value"] > 0 and also["max_abs_score_diff_vs_f32"] < 1e-4
+
+
+def test_bench_plain_line_is_lean():
+    """Without --full the run times its steps and nothing else: the same contract fields, no extra legs, no CPU baseline,
+    and no roofline where that would take a profiled pass of its own (the default two-stream split).  With the split off
+    the kernels are timed inside the timed steps, so --single-stream still reports them."""
+    args = ["--steps", "2", "--warmup", "1", "--batch", "16", "--refs", "4"]
+    out = _run(args)
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "ranks_seen"):
+        assert key in out, key
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert abs(out["value"] - 16 * 2 / (out["ms_per_step"] * 2e-3)) / out["value"] < 1e-3
+    extra = [k for k in out if k.startswith("also_measured") or k in ("cpu_baseline", "roofline", "kernel_time_ms_per_step")]
+    assert extra == [], extra
+    one = _run(args + ["--single-stream"])
+    assert one["roofline"]["achieved"] > 0 and "kernel_time_ms_per_step" in one
+    assert not [k for k in one if k.startswith("also_measured") or k == "cpu_baseline"]
 
 
 def test_bench_dump_outputs_repeat_run_to_run(tmp_path):
@@ -109,7 +127,7 @@ def test_bench_headline_extras_small():
 def test_bench_line_bf16_long_form():
     """configs[4] (bf16, 30 s clips) through the same contract, small batch."""
     out = _run(["--dtype", "bf16", "--seconds", "30", "--batch", "4", "--refs", "1", "--steps", "2", "--warmup", "1",
-                "--no-cpu-baseline"])
+                "--no-cpu-baseline", "--full"])
     assert out["dtype"] == "bf16" and out["config"]["workload"].startswith("configs[4]")
     assert out["roofline"]["peak"] == 2500.0 and out["roofline"]["achieved"] > 0
     assert "also_measured" not in out and out["value"] > 0

@@ -1,11 +1,11 @@
 #!/bin/bash
-# full GPU suite + default bench (+ rocprofv3 kernel stats of it).  Usage: bash tools/gpu_full.sh <tag>
+# full GPU suite + bench.py --full (+ rocprofv3 kernel stats of the headline steps).  Usage: bash tools/gpu_full.sh <tag>
 TAG=${1:-full}
 ROOTDIR=$(pwd); OUT=$ROOTDIR/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -q -m gpu -x --timeout 900 > $OUT/pytest_gpu.log 2>&1; echo "pytest exit $?" | tee -a $OUT/summary.txt
 tail -n 5 $OUT/pytest_gpu.log
-timeout 900 python bench.py --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?" | tee -a $OUT/summary.txt
+timeout 900 python bench.py --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?" | tee -a $OUT/summary.txt
 python3 - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

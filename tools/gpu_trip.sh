@@ -9,7 +9,7 @@
 #   c5ab:<VAR>:<v1,v2,..>:<reps>[:extra bench flags]   configs[4] bench alternating over the values of one NOMAD_* switch (diag library)
 #   c2ab:<VAR>:<v1,v2,..>:<reps>[:extra bench flags]   the same for the fp32 headline ('+' in the extra flags stands for a space: --dtype+bf16x3)
 #   c4ab:<VAR>:<v1,v2,..>:<reps>                       the same for configs[3] (tools/bench_c4.py)
-#   bench                    default bench.py (the driver's line) -> bench.json
+#   bench                    bench.py --full (the headline line and every extra measurement) -> bench.json
 #   c5table:<name>[:VAR=val,..]   rocprofv3 kernel trace of the single-stream configs[4] bench -> layer_table_<name>.json + kernel_stats_<name>.csv
 #   c2stats:<name>           rocprofv3 --kernel-trace --stats of bench.py --single-stream -> kernel_stats_<name>.csv
 #   c4table:<name>[:VAR=val,..]   kernel trace of configs[3] -> c4_trace_table_<name>.txt
@@ -54,7 +54,7 @@ for step in "$@"; do
         fi
       done; done ;;
     bench)
-      timeout 1500 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?: $(val $OUT/bench.json value ms_per_step)" | tee -a $SUM ;;
+      timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?: $(val $OUT/bench.json value ms_per_step)" | tee -a $SUM ;;
     c5table|c4table|c2stats)
       NAME=${S[1]:-x}; ENVS=$(echo "${S[2]}" | tr ',' ' ')
       if [ ${S[0]} = c5table ]; then CMD="$ROOTDIR/bench.py $C5FLAGS --steps 5 --warmup 2 --single-stream"
