@@ -235,7 +235,8 @@ int nomad_embed_backward(nomad_ctx* ctx, const float* wav_dev, int B, int n_samp
  *   nomad_triplet_loss        loss [1] = mean_i max(||a-p+eps|| - ||a-n+eps|| + margin, 0), eps = 1e-6
  *                             (torch.pairwise_distance); da/dp/dn [B][256] nullable together (validation pass)
  *   nomad_train_adam_step     torch.optim.Adam update (amsgrad off, no weight decay) with the step count kept in
- *                             the context, then rebuilds the derived kernel-layout weights
+ *                             the context, then rebuilds the derived kernel-layout weights.  beta1 / beta2 are doubles:
+ *                             1 - beta and 1 - beta^t are formed in double (1.0f - 0.999f is off by 1.3e-5 relative)
  *   nomad_train_read / write  copy a whole vector out of / into the context (device pointers, async on stream);
  *                             what: 0 parameters, 1 gradients, 2 exp_avg, 3 exp_avg_sq
  *   nomad_train_set_step      set Adam's step counter (resume)
@@ -271,7 +272,7 @@ int nomad_train_backward(nomad_ctx* ctx, const float* wav_dev, int B, int n_samp
 int nomad_triplet_loss(nomad_ctx* ctx, const float* a_dev, const float* p_dev, const float* n_dev, int B,
                        float margin, float* loss_dev, float* da_dev, float* dp_dev, float* dn_dev,
                        nomad_stream_t stream);
-int nomad_train_adam_step(nomad_ctx* ctx, float lr_body, float lr_head, float beta1, float beta2, float eps,
+int nomad_train_adam_step(nomad_ctx* ctx, float lr_body, float lr_head, double beta1, double beta2, float eps,
                           nomad_stream_t stream);
 int nomad_train_read(nomad_ctx* ctx, int what, float* dst_dev, nomad_stream_t stream);
 int nomad_train_write(nomad_ctx* ctx, int what, const float* src_dev, nomad_stream_t stream);

@@ -72,7 +72,7 @@ SIGNATURES = {
     "nomad_train_zero_grad": (C.c_int, [C.c_void_p, _fp]),
     "nomad_train_backward": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp, _fp, C.c_size_t, _fp]),
     "nomad_triplet_loss": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, C.c_float, _fp, _fp, _fp, _fp, _fp]),
-    "nomad_train_adam_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _fp]),
+    "nomad_train_adam_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, _fp]),
     "nomad_train_read": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp]),
     "nomad_train_write": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp]),
     "nomad_train_set_step": (C.c_int, [C.c_void_p, C.c_longlong]),

@@ -2922,21 +2922,21 @@ int nomad_triplet_loss(nomad_ctx* c, const float* a, const float* p, const float
     return 0;
 }
 
-int nomad_train_adam_step(nomad_ctx* c, float lr_body, float lr_head, float beta1, float beta2, float eps,
+int nomad_train_adam_step(nomad_ctx* c, float lr_body, float lr_head, double beta1, double beta2, float eps,
                           nomad_stream_t stream) {
     if (!c || !c->train_ready) return fail(NOMAD_ERR_INVALID, "nomad_train_adam_step: call nomad_train_enable first");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const ParamOffsets po = make_param_offsets();
     c->adam_t += 1;
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)c->adam_t);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)c->adam_t);
+    const double bc1 = 1.0 - std::pow(beta1, (double)c->adam_t);
+    const double bc2 = 1.0 - std::pow(beta2, (double)c->adam_t);
     const long long n4 = (long long)po.total / 4;
     {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
         hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(c->theta),
                            reinterpret_cast<const float4*>(c->grad), reinterpret_cast<float4*>(c->adam_m),
-                           reinterpret_cast<float4*>(c->adam_v), n4, (long long)po.emb_w / 4, lr_body, lr_head, beta1, beta2,
-                           eps, (float)bc1, (float)std::sqrt(bc2));
+                           reinterpret_cast<float4*>(c->adam_v), n4, (long long)po.emb_w / 4, lr_body, lr_head, (float)(1.0 - beta1),
+                           (float)beta2, (float)(1.0 - beta2), eps, (float)bc1, (float)std::sqrt(bc2));
     }
     HIP_TRY(hipGetLastError());
     return refresh_weights(c, s);

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import ref64
 from oracle import nomad_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -326,15 +327,8 @@ def test_merged_branches_match_oracle(teng, sd_train, masks):
     B, n, margin = (2, 6000, 1.0) if masks[0] != 0x0F0 else (2, 40000, 1.0)  # one case with several attention tiles (T = 124)
     A, P, N = _triplet_batch(B, n, seed=31)
     st = O.Stochastic(seed=(77 << 33) + 5, dropout=0.1, attention_dropout=0.1, dropout_input=0.1, branch_masks=masks)
-    # oracle: one forward over the concatenated batch, loss on its three thirds
-    sd = {k: v.clone() for k, v in sd_train.items()}
-    keys = O.trainable_keys(sd)
-    for k in keys:
-        sd[k].requires_grad_(True)
-    e = O.triplet_forward(sd, torch.cat([A, P, N]), st)
-    ref_loss = torch.nn.TripletMarginLoss(margin=margin)(e[:B], e[B:2 * B], e[2 * B:])
-    grads = torch.autograd.grad(ref_loss, [sd[k] for k in keys], allow_unused=True)
-    ref = {k: (gk if gk is not None else torch.zeros_like(sd[k])) for k, gk in zip(keys, grads)}  # None: layer dropped by all
+    # oracle: one forward over the concatenated batch, loss on its three thirds; zeros for a layer dropped by all
+    ref_loss, e, ref = ref64.merged_triplet_step(sd_train, A, P, N, margin, st)
     # engine: merged batch, per-branch masks
     w = torch.cat([A, P, N]).cuda()
     teng.train_set_stochastic(st.dropout, st.attention_dropout, st.dropout_input, st.seed, 0xFFF)
