@@ -12,6 +12,11 @@
  *                                  backbone (fairseq Wav2Vec2Model, call sites nomad.py:226,245)
  *                                  + mean/ReLU/Linear/L2-normalise head
  *   nomad_pairwise                 scipy cdist + np.mean(axis=1) (nomad.py:108-111)
+ *   nomad_embed_features[_ragged]  Origw2v.forward (src/models/networks.py:29-34): the backbone's output averaged over time,
+ *                                  the raw wav2vec 2.0 baseline of the evaluation experiments (eval_w2v: True)
+ *   nomad_cdist                    cdist + np.mean(axis=1) of src/training/train_triplet.py (:281-282, :327-328, :385-386)
+ *                                  on rows of any width (768 for the baseline)
+ *   nomad_paired_distance          np.diag(cdist(test, ref)) (train_triplet.py:438-439) without the matrix
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
  *
@@ -149,6 +154,37 @@ int nomad_embed_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, 
  */
 int nomad_pairwise(nomad_ctx* ctx, const float* deg_dev, int Nd, const float* ref_dev, int Nr,
                    double* dist_dev, double* mean_dev, nomad_stream_t stream);
+
+/*
+ * nomad_pairwise with the row width as an argument: a_dev [Na][D], b_dev [Nb][D] fp32, D a positive multiple of 4, at most 4096.
+ * Arithmetic contract (both functions): per pair ONE float64 accumulator, e = (double)a_k - (double)b_k, acc = fma(e, e, acc), k
+ * ascending from 0, then sqrt(acc); row sums per 64-column tile in column order, tiles added in order.  At D = 256 nomad_cdist
+ * returns the bits of nomad_pairwise.  Scratch: the context's per-stream block of nomad_pairwise, under the same rules.
+ *   dist_dev  optional [Na][Nb] float64 (out) or NULL;  mean_dev [Na] float64 (out)
+ * NOMAD_ERR_INVALID: a NULL operand or mean_dev, Na / Nb <= 0, D not a multiple of 4 or outside 4 .. 4096.
+ */
+int nomad_cdist(nomad_ctx* ctx, const float* a_dev, int Na, const float* b_dev, int Nb, int D,
+                double* dist_dev, double* mean_dev, nomad_stream_t stream);
+/* out_dev[i] = ||a_i - b_i|| for i < N, [N] float64: bit-identical to the diagonal of nomad_cdist(a, N, b, N, D), without the
+ * other N - 1 columns.  No scratch, no allocation.  NOMAD_ERR_INVALID as for nomad_cdist. */
+int nomad_paired_distance(nomad_ctx* ctx, const float* a_dev, const float* b_dev, int N, int D,
+                          double* out_dev, nomad_stream_t stream);
+
+/*
+ * Pooled backbone features, Origw2v.forward (networks.py:29-34): the last encoder layer's output averaged over time - no
+ * ReLU, no Linear, no normalisation, no embedding.  feat_dev [B][768] fp32 (out).  `precision` selects the forward: the one of
+ * nomad_embed / nomad_embed_bf16x3 / nomad_embed_bf16 (and their ragged forms), with that entry point's preconditions
+ * (nomad_enable_bf16x3 / nomad_enable_bf16 first), its workspace size (nomad_workspace_bytes* of that precision and geometry)
+ * and its statuses for bad arguments; an unknown precision is NOMAD_ERR_INVALID.  Asynchronous, no allocation,
+ * deterministic; a clip's 768 values do not depend on the batch it is in: the ragged call is bit-identical to one uniform
+ * call per clip.
+ */
+enum { NOMAD_PRECISION_F32 = 0, NOMAD_PRECISION_BF16X3 = 1, NOMAD_PRECISION_BF16 = 2 };
+int nomad_embed_features(nomad_ctx* ctx, const float* wav_dev, int B, int n_samples, int precision,
+                         float* feat_dev, void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
+int nomad_embed_features_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host,
+                                int precision, float* feat_dev, void* workspace_dev, size_t workspace_bytes,
+                                nomad_stream_t stream);
 
 /*
  * NomadLoss: sum_{i<12} mean|a_layers[i]-b_layers[i]| + mean|a_emb-b_emb|.

@@ -7,9 +7,9 @@ Here the instance is built on first use rather than at import time (the referenc
 downloads weights - on import).  As in the reference, ``from nomad_amd.nomad import Nomad`` still reaches the
 implementation module through ``sys.modules``.
 """
-from .nomad import Nomad, TripletModel, LossNetLayers, NomadLoss  # noqa: F401
+from .nomad import Nomad, TripletModel, Origw2v, LossNetLayers, NomadLoss  # noqa: F401
 
-__all__ = ["Nomad", "TripletModel", "LossNetLayers", "NomadLoss", "nomad"]
+__all__ = ["Nomad", "TripletModel", "Origw2v", "LossNetLayers", "NomadLoss", "nomad"]
 
 
 class _LazyNomad:

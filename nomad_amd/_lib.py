@@ -46,6 +46,11 @@ SIGNATURES = {
     "nomad_embed_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp, _fp, _fp,
                                      C.c_size_t, _fp]),
     "nomad_pairwise": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp]),
+    "nomad_cdist": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "nomad_paired_distance": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
+    "nomad_embed_features": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_embed_features_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp,
+                                              C.c_size_t, _fp]),
     "nomad_wav_probe": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(WavInfo), C.POINTER(C.c_int), C.c_int]),
     "nomad_wav_frames_at": (C.c_int, [C.POINTER(WavInfo), C.c_int, C.POINTER(C.c_longlong)]),
     "nomad_wav_read_rows": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(WavInfo), C.c_int, C.POINTER(C.c_int), _fp, C.c_longlong,
@@ -149,6 +154,9 @@ def load(diag=None):
     _libs[diag] = lib
     return lib
 
+
+# precision argument of nomad_embed_features* (include/nomad_hip.h)
+PRECISION = {"fp32": 0, "bf16x3": 1, "bf16": 2}
 
 # nomad_status (include/nomad_hip.h)
 NOMAD_OK, NOMAD_ERR_INVALID, NOMAD_ERR_NO_DEVICE, NOMAD_ERR_HIP, NOMAD_ERR_WORKSPACE, NOMAD_ERR_IO, NOMAD_ERR_FORMAT = 0, -1, -2, -3, -4, -5, -6

@@ -49,6 +49,7 @@ constexpr int kConvS[7] = {5, 2, 2, 2, 2, 2, 2};
 constexpr int kSplitKLayersMaxM = 4096;   // a forward that returns the layer outputs of fewer frames than this may split K (forward_run)
 constexpr size_t kSplitKPartFloats = (size_t)4 * 512 * 64 * 64;  // 4 slices of the largest problem that is split (< 512 tiles of 64 x 64)
 constexpr long long kPairScratchDoubles = 1 << 21;  // 16 MB: e.g. 16 ref tiles x 131 072 deg rows per launch pair
+constexpr int kCdistMaxD = 4096;  // nomad_cdist / nomad_paired_distance: widest row
 constexpr int kEventChunk = 8192;  // the profiling event pool grows by this many events whenever it runs out
 const int* const kNoInts = nullptr;  // "uniform batch" for the kernels' optional ragged-metadata pointers
 const hipStream_t kNoStream = reinterpret_cast<hipStream_t>(~uintptr_t(0));  // nomad_pairwise: a scratch block bound to no stream

@@ -622,12 +622,14 @@ int run_layernorm(nomad_ctx* c, const float* in, const float* g, const float* b,
 
 // mean/ReLU/Linear/normalise head in two stages (rowops.hip.h).  T: frames per clip (the longest clip's with tpref);
 // pool: scratch of at least (M / 64 + B) * 768 floats (M = total frames) - every caller passes its FFN hidden buffer.
+// features (nomad_embed_features*): `emb` is [B][768] and takes the time means themselves (head_mean_kernel) - no embedding.
 template <typename TIn>
 int run_head(nomad_ctx* c, const TIn* x, int B, int T, const float* w, const float* b, float* emb, const int* tpref,
-             float* pool, hipStream_t s) {
-    Scope sc(c, s, NOMAD_K_ROW, 2.0 * B * 768 * 256);
+             float* pool, hipStream_t s, bool features = false) {
+    Scope sc(c, s, NOMAD_K_ROW, features ? 0.0 : 2.0 * B * 768 * 256);
     hipLaunchKernelGGL(head_pool_kernel<TIn>, dim3((T + kHeadChunk - 1) / kHeadChunk, B), dim3(256), 0, s, x, tpref ? 0 : T, pool, tpref);
-    hipLaunchKernelGGL(head_kernel, dim3(B), dim3(1024), 0, s, pool, tpref ? 0 : T, w, b, emb, tpref);
+    if (features) hipLaunchKernelGGL(head_mean_kernel, dim3(B), dim3(256), 0, s, pool, tpref ? 0 : T, emb, tpref);
+    else hipLaunchKernelGGL(head_kernel, dim3(B), dim3(1024), 0, s, pool, tpref ? 0 : T, w, b, emb, tpref);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -932,7 +934,7 @@ struct F32Bufs {
 // training inputs (sv, its dropout and LayerDrop, layers_out, split-K) are for equal-length batches only.
 static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const F32Bufs& bf, const float* head_w,
                        const float* head_b, float* emb, float* layers_out, float* splitk_block, size_t splitk_floats, hipStream_t s,
-                       const Saved* sv) {
+                       const Saved* sv, bool features = false) {
     if (g.ragged() && (sv || layers_out || splitk_block))
         return fail(NOMAD_ERR_INVALID, "fp32 forward: training inputs, layer outputs and split-K need an equal-length batch");
     const int B = g.B, T = g.T, M = (int)g.rows[6];
@@ -1150,34 +1152,35 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
 
     // ---- head -----------------------------------------------------------------------------------
     // the FFN hidden buffer is dead by now: scratch for the time sums
-    return run_head<float>(c, x, B, g.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb, g.pref[6], bf.h, s);
+    return run_head<float>(c, x, B, g.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb, g.pref[6], bf.h, s, features);
 }
 
-// nomad_embed / nomad_embed_train: an equal-length batch in the Layout of make_layout
+// nomad_embed / nomad_embed_train: an equal-length batch in the Layout of make_layout.  who: the entry point the errors name;
+// features: nomad_embed_features (`emb` is [B][768], see run_head).
 static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
                         float* emb, float* layers_out, void* workspace, size_t workspace_bytes, nomad_stream_t stream,
-                        const Saved* sv) {
+                        const Saved* sv, const char* who = "nomad_embed", bool features = false) {
     Shapes sh;
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed: bad argument (B=%d, n_samples=%d)", B, n_samples);
+        return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d, n_samples=%d)", who, B, n_samples);
     const Layout lay = make_layout(sh, c->keep);
     if (workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed: workspace %zu < required %zu", workspace_bytes, lay.total);
+        return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, lay.total);
     char* ws = static_cast<char*>(workspace);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.featln), F(lay.xpad), F(lay.x),
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(lay.conv[i]);
     return forward_run(c, wav, geom_uniform(sh), bf, head_w, head_b, emb, layers_out, lay.splitk != 0 ? F(lay.splitk) : nullptr,
-                       layers_splitk_floats(sh), static_cast<hipStream_t>(stream), sv);
+                       layers_splitk_floats(sh), static_cast<hipStream_t>(stream), sv, features);
 }
 
 static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, const float* head_w,
                           const float* head_b, float* emb, void* workspace, size_t workspace_bytes,
-                          nomad_stream_t stream) {
+                          nomad_stream_t stream, const char* who = "nomad_embed_ragged", bool features = false) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     RaggedBatch r;
-    if (int rc = ragged_prologue("nomad_embed_ragged", c, c && wav && emb && workspace, B, stride, lens_host, sizeof(float), 0, &r,
+    if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, sizeof(float), 0, &r,
                                  workspace, workspace_bytes, s))
         return rc;
     char* ws = static_cast<char*>(workspace);
@@ -1186,7 +1189,7 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
     F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.convb), F(lay.xpad), F(lay.x),
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(i % 2 ? lay.convb : lay.conva);   // conv6 lands in conva, LN(512) writes to convb
-    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, nullptr, nullptr, 0, s, nullptr);
+    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, nullptr, nullptr, 0, s, nullptr, features);
 }
 
 // One backward GEMM: C[M][N] = A[M][K] * Wt[N][K]^T (Wt = transposed forward weight), optional GELU' and residual.
@@ -1369,7 +1372,7 @@ static void launch_ln_bf16(const bf16_t* in, const float* g, const float* b, bf1
 // ragged batch (mixed-length long-form files, config C5 through predict: every clip sees the arithmetic of its own
 // single-clip call).  The diag library's checksum / snapshot stages are recorded on equal-length calls only.
 static int forward_bf16_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const ActLayout& lay, float* emb, char* ws,
-                            hipStream_t s) {
+                            hipStream_t s, bool features = false) {
     auto H = [&](size_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
     auto asf = [](const bf16_t* p_) { return reinterpret_cast<const float*>(p_); };  // GemmParams carries typeless pointers
     auto asfm = [](bf16_t* p_) { return reinterpret_cast<float*>(p_); };
@@ -1496,33 +1499,34 @@ static int forward_bf16_run(nomad_ctx* c, const float* wav, const BatchGeom& g, 
         }
         CK(x, B, clip768);
     }
-    rc = run_head<bf16_t>(c, x, B, g.max_t, c->emb_w, c->emb_b, emb, g.pref[6], reinterpret_cast<float*>(hb), s);
-    CK(emb, B, sizeof(float) * 256);
+    rc = run_head<bf16_t>(c, x, B, g.max_t, c->emb_w, c->emb_b, emb, g.pref[6], reinterpret_cast<float*>(hb), s, features);
+    CK(emb, B, sizeof(float) * (features ? 768 : 256));
     return rc;
 }
 
 static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, float* emb, void* workspace,
-                        size_t workspace_bytes, nomad_stream_t stream) {
+                        size_t workspace_bytes, nomad_stream_t stream, const char* who = "nomad_embed_bf16", bool features = false) {
     Shapes sh;
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16: bad argument (B=%d, n_samples=%d)", B, n_samples);
-    if (!c->bf16_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16: call nomad_enable_bf16 first");
+        return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d, n_samples=%d)", who, B, n_samples);
+    if (!c->bf16_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_bf16 first", who);
     const BatchGeom g = geom_uniform(sh);
     const ActLayout lay = make_act_layout(g, sizeof(bf16_t), 0);
     if (workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_bf16: workspace %zu < required %zu", workspace_bytes, lay.total);
-    return forward_bf16_run(c, wav, g, lay, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream));
+        return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, lay.total);
+    return forward_bf16_run(c, wav, g, lay, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), features);
 }
 
 static int forward_ragged_bf16(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, float* emb,
-                               void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
-    if (c && !c->bf16_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16: call nomad_enable_bf16 first");
+                               void* workspace, size_t workspace_bytes, nomad_stream_t stream,
+                               const char* who = "nomad_embed_ragged_bf16", bool features = false) {
+    if (c && !c->bf16_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_bf16 first", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
     RaggedBatch r;
-    if (int rc = ragged_prologue("nomad_embed_ragged_bf16", c, c && wav && emb && workspace, B, stride, lens_host, sizeof(bf16_t), 0,
+    if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, sizeof(bf16_t), 0,
                                  &r, workspace, workspace_bytes, s))
         return rc;
-    return forward_bf16_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s);
+    return forward_bf16_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, features);
 }
 
 
@@ -1577,7 +1581,7 @@ constexpr int kX3Split = 27, kX3F32 = 28;
 
 static int forward_x3_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const ActLayout& lay, float* emb,
                           char* ws, hipStream_t s, const float* head_w = nullptr, const float* head_b = nullptr,
-                          float* layers_out = nullptr) {
+                          float* layers_out = nullptr, bool features = false) {
     auto S = [&](size_t off) { return reinterpret_cast<bf16s_t*>(ws + off); };
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const int B = g.B, M = (int)g.rows[6];
@@ -1704,33 +1708,34 @@ static int forward_x3_run(nomad_ctx* c, const float* wav, const BatchGeom& g, co
         else if ((rc = run_layernorm(c, y, d.ln2_w, d.ln2_b, reinterpret_cast<float*>(x), lo, M, 768, s))) return rc;
     }
     return run_head<float>(c, reinterpret_cast<const float*>(x), B, g.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb,
-                           tpref, reinterpret_cast<float*>(hb), s);
+                           tpref, reinterpret_cast<float*>(hb), s, features);
 }
 
 static int forward_x3(nomad_ctx* c, const float* wav, int B, int n_samples, float* emb, void* workspace,
                       size_t workspace_bytes, nomad_stream_t stream, const float* head_w = nullptr, const float* head_b = nullptr,
-                      float* layers_out = nullptr) {
+                      float* layers_out = nullptr, const char* who = "nomad_embed_bf16x3", bool features = false) {
     Shapes sh;
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh) || (!head_w != !head_b))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16x3: bad argument (B=%d, n_samples=%d)", B, n_samples);
-    if (!c->x3_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_bf16x3: call nomad_enable_bf16x3 first");
+        return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d, n_samples=%d)", who, B, n_samples);
+    if (!c->x3_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_bf16x3 first", who);
     const BatchGeom g = geom_uniform(sh);
     const ActLayout lay = make_act_layout(g, 4, kXpadSlack);
     if (workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_bf16x3: workspace %zu < required %zu", workspace_bytes, lay.total);
+        return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, lay.total);
     return forward_x3_run(c, wav, g, lay, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), head_w, head_b,
-                          layers_out);
+                          layers_out, features);
 }
 
 static int forward_ragged_x3(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, float* emb,
-                             void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
-    if (c && !c->x3_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_ragged_bf16x3: call nomad_enable_bf16x3 first");
+                             void* workspace, size_t workspace_bytes, nomad_stream_t stream,
+                             const char* who = "nomad_embed_ragged_bf16x3", bool features = false) {
+    if (c && !c->x3_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_bf16x3 first", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
     RaggedBatch r;
-    if (int rc = ragged_prologue("nomad_embed_ragged_bf16x3", c, c && wav && emb && workspace, B, stride, lens_host, 4, kXpadSlack,
+    if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, 4, kXpadSlack,
                                  &r, workspace, workspace_bytes, s))
         return rc;
-    return forward_x3_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s);
+    return forward_x3_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, nullptr, nullptr, nullptr, features);
 }
 
 extern "C" {
@@ -2099,6 +2104,35 @@ int nomad_workspace_bytes_ragged(const nomad_ctx* c, int B, const int* lengths_h
 int nomad_embed_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, const float* head_w,
                        const float* head_b, float* emb, void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
     return forward_ragged(c, wav, B, stride, lengths_host, head_w, head_b, emb, workspace, workspace_bytes, stream);
+}
+
+// Pooled backbone features (Origw2v.forward): the forward of `precision` with head_mean_kernel as its last stage.
+int nomad_embed_features(nomad_ctx* c, const float* wav, int B, int n_samples, int precision, float* feat, void* workspace,
+                         size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_features";
+    switch (precision) {
+        case NOMAD_PRECISION_F32:
+            return forward_impl(c, wav, B, n_samples, nullptr, nullptr, feat, nullptr, workspace, workspace_bytes, stream, nullptr, who, true);
+        case NOMAD_PRECISION_BF16X3:
+            return forward_x3(c, wav, B, n_samples, feat, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, who, true);
+        case NOMAD_PRECISION_BF16:
+            return forward_bf16(c, wav, B, n_samples, feat, workspace, workspace_bytes, stream, who, true);
+    }
+    return fail(NOMAD_ERR_INVALID, "%s: unknown precision %d", who, precision);
+}
+
+int nomad_embed_features_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, int precision,
+                                float* feat, void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_features_ragged";
+    switch (precision) {
+        case NOMAD_PRECISION_F32:
+            return forward_ragged(c, wav, B, stride, lengths_host, nullptr, nullptr, feat, workspace, workspace_bytes, stream, who, true);
+        case NOMAD_PRECISION_BF16X3:
+            return forward_ragged_x3(c, wav, B, stride, lengths_host, feat, workspace, workspace_bytes, stream, who, true);
+        case NOMAD_PRECISION_BF16:
+            return forward_ragged_bf16(c, wav, B, stride, lengths_host, feat, workspace, workspace_bytes, stream, who, true);
+    }
+    return fail(NOMAD_ERR_INVALID, "%s: unknown precision %d", who, precision);
 }
 
 int nomad_saved_bytes(const nomad_ctx* c, int B, int n_samples, size_t* bytes) {
@@ -3026,15 +3060,15 @@ int nomad_build_flags(void) {
     return f;
 }
 
-int nomad_pairwise(nomad_ctx* c, const float* deg, int Nd, const float* ref, int Nr, double* dist, double* mean,
-                   nomad_stream_t stream) {
-    if (!c || !deg || !ref || !mean || Nd <= 0 || Nr <= 0)
-        return fail(NOMAD_ERR_INVALID, "nomad_pairwise: bad argument (Nd=%d, Nr=%d)", Nd, Nr);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+}  // extern "C"
+
+// The context's scratch block of launch stream s (nomad_pairwise, nomad_cdist).
+static int pair_scratch_for(nomad_ctx* c, hipStream_t s, double** out) {
     // per-(ref tile, deg row) partial sums live in a context-owned scratch, one block per launch stream (calls on the same
     // stream are ordered, calls on different streams must not share it): the block of nomad_create goes to the first
     // stream that calls, any further stream allocates its own on its first call
     double* scratch = nullptr;
+    *out = nullptr;
     std::unique_lock<std::mutex> pair_lock(c->pair_mu);   // look-up, binding and allocation of a stream's block: one thread at a time
     for (const auto& e : c->pair_scratch)
         if (e.first == s) {
@@ -3067,6 +3101,19 @@ int nomad_pairwise(nomad_ctx* c, const float* deg, int Nd, const float* ref, int
         }
     }
     pair_lock.unlock();
+    *out = scratch;
+    return 0;
+}
+
+extern "C" {
+
+int nomad_pairwise(nomad_ctx* c, const float* deg, int Nd, const float* ref, int Nr, double* dist, double* mean,
+                   nomad_stream_t stream) {
+    if (!c || !deg || !ref || !mean || Nd <= 0 || Nr <= 0)
+        return fail(NOMAD_ERR_INVALID, "nomad_pairwise: bad argument (Nd=%d, Nr=%d)", Nd, Nr);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* scratch = nullptr;
+    if (int rc = pair_scratch_for(c, s, &scratch)) return rc;
     Scope sc(c, s, NOMAD_K_PAIR, 3.0 * 256 * (double)Nd * Nr);
     // deg rows are processed in slabs that fit the scratch
     const int ntiles = (Nr + kPairTile - 1) / kPairTile;
@@ -3074,10 +3121,44 @@ int nomad_pairwise(nomad_ctx* c, const float* deg, int Nd, const float* ref, int
     if (slab_max < kPairTile) return fail(NOMAD_ERR_INVALID, "nomad_pairwise: Nr=%d is too large for the scratch", Nr);
     for (long long d0 = 0; d0 < Nd; d0 += slab_max) {
         const int nd = (int)std::min<long long>(slab_max, Nd - d0);
-        hipLaunchKernelGGL(pairwise_tile_kernel, dim3(ntiles, (nd + kPairTile - 1) / kPairTile), dim3(256), 0, s, deg + d0 * 256, nd,
-                           ref, Nr, dist ? dist + d0 * Nr : nullptr, scratch);
+        hipLaunchKernelGGL(pairwise_tile_kernel<256>, dim3(ntiles, (nd + kPairTile - 1) / kPairTile), dim3(256), 0, s, deg + d0 * 256, nd,
+                           ref, Nr, 256, dist ? dist + d0 * Nr : nullptr, scratch);
         hipLaunchKernelGGL(pairwise_mean_kernel, dim3((nd + 255) / 256), dim3(256), 0, s, scratch, ntiles, nd, Nr, mean + d0);
     }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// nomad_pairwise with the row width as an argument (pairwise_tile_kernel<0>: the same arithmetic chain, bit-identical at D = 256).
+int nomad_cdist(nomad_ctx* c, const float* a, int Na, const float* b, int Nb, int D, double* dist, double* mean,
+                nomad_stream_t stream) {
+    if (!c || !a || !b || !mean || Na <= 0 || Nb <= 0 || D <= 0 || D % 4 || D > kCdistMaxD)
+        return fail(NOMAD_ERR_INVALID, "nomad_cdist: bad argument (Na=%d, Nb=%d, D=%d: a positive multiple of 4, at most %d)", Na, Nb, D,
+                    kCdistMaxD);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* scratch = nullptr;
+    if (int rc = pair_scratch_for(c, s, &scratch)) return rc;
+    Scope sc(c, s, NOMAD_K_PAIR, 3.0 * D * (double)Na * Nb);
+    const int ntiles = (Nb + kPairTile - 1) / kPairTile;
+    const long long slab_max = (kPairScratchDoubles / ntiles) / kPairTile * kPairTile;   // rows of `a` per launch pair
+    if (slab_max < kPairTile) return fail(NOMAD_ERR_INVALID, "nomad_cdist: Nb=%d is too large for the scratch", Nb);
+    for (long long d0 = 0; d0 < Na; d0 += slab_max) {
+        const int nd = (int)std::min<long long>(slab_max, Na - d0);
+        hipLaunchKernelGGL(pairwise_tile_kernel<0>, dim3(ntiles, (nd + kPairTile - 1) / kPairTile), dim3(256), 0, s, a + d0 * D, nd, b, Nb, D,
+                           dist ? dist + d0 * Nb : nullptr, scratch);
+        hipLaunchKernelGGL(pairwise_mean_kernel, dim3((nd + 255) / 256), dim3(256), 0, s, scratch, ntiles, nd, Nb, mean + d0);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int nomad_paired_distance(nomad_ctx* c, const float* a, const float* b, int N, int D, double* out, nomad_stream_t stream) {
+    if (!c || !a || !b || !out || N <= 0 || D <= 0 || D % 4 || D > kCdistMaxD)
+        return fail(NOMAD_ERR_INVALID, "nomad_paired_distance: bad argument (N=%d, D=%d: a positive multiple of 4, at most %d)", N, D,
+                    kCdistMaxD);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scope sc(c, s, NOMAD_K_PAIR, 3.0 * D * (double)N);
+    hipLaunchKernelGGL(paired_distance_kernel, dim3((N + kPairTile - 1) / kPairTile), dim3(256), 0, s, a, b, N, D, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

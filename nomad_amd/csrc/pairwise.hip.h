@@ -22,9 +22,15 @@ namespace nomad {
 
 constexpr int kPairTile = 64;
 
-__global__ __launch_bounds__(256) void pairwise_tile_kernel(const float* __restrict__ deg, int Nd,
-                                                            const float* __restrict__ ref, int Nr,
-                                                            double* __restrict__ dist, double* __restrict__ part) {
+// kD: the row width at compile time (256: nomad_pairwise, the shape the comment above describes), or 0: the width is the
+// argument D, a positive multiple of 4 (nomad_cdist).  The arithmetic is one chain for every width - per pair one float64
+// accumulator, e = a_k - b_k, acc = fma(e, e, acc), k ascending from 0 - so nomad_cdist at D = 256 returns the bits of
+// nomad_pairwise.  A last k-chunk shorter than 64 is staged with zeros on both sides: e = 0 and fma(0, 0, acc) = acc, they add
+// exactly nothing.  (D is a multiple of 4, so a staged float4 lies wholly inside or wholly outside the row.)
+template <int kD>
+__global__ __launch_bounds__(256) void pairwise_tile_kernel(const float* __restrict__ deg, int Nd, const float* __restrict__ ref,
+                                                            int Nr, int Drt, double* __restrict__ dist, double* __restrict__ part) {
+    const int D = kD ? kD : Drt;
     __shared__ __attribute__((aligned(16))) double As[64][kPairTile];  // [k][deg row]
     __shared__ __attribute__((aligned(16))) double Bs[64][kPairTile];  // [k][ref]
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
@@ -37,15 +43,18 @@ __global__ __launch_bounds__(256) void pairwise_tile_kernel(const float* __restr
     // staging: lane -> row tid & 63 (consecutive lanes write consecutive doubles of one LDS row: conflict-free), the four
     // waves take k columns 4 * wave + 16 q .. + 3 of the chunk
     const int srow = tid & 63, skq = (tid >> 6) * 4;
-    const float* ap = deg + (long long)min(d0 + srow, Nd - 1) * 256 + skq;
-    const float* bp = ref + (long long)min(r0 + srow, Nr - 1) * 256 + skq;
-    for (int k0 = 0; k0 < 256; k0 += 64) {
+    const float* ap = deg + (long long)min(d0 + srow, Nd - 1) * D + skq;
+    const float* bp = ref + (long long)min(r0 + srow, Nr - 1) * D + skq;
+    for (int k0 = 0; k0 < D; k0 += 64) {
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int kk = skq + 16 * q;
-            const float4 a = *reinterpret_cast<const float4*>(ap + k0 + 16 * q);
-            const float4 b = *reinterpret_cast<const float4*>(bp + k0 + 16 * q);
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+            if ((kD && kD % 64 == 0) || k0 + kk < D) {
+                a = *reinterpret_cast<const float4*>(ap + k0 + 16 * q);
+                b = *reinterpret_cast<const float4*>(bp + k0 + 16 * q);
+            }
             As[kk][srow] = (double)a.x; As[kk + 1][srow] = (double)a.y; As[kk + 2][srow] = (double)a.z; As[kk + 3][srow] = (double)a.w;
             Bs[kk][srow] = (double)b.x; Bs[kk + 1][srow] = (double)b.y; Bs[kk + 2][srow] = (double)b.z; Bs[kk + 3][srow] = (double)b.w;
         }
@@ -111,6 +120,48 @@ __global__ __launch_bounds__(256) void pairwise_mean_kernel(const double* __rest
     double s = 0.0;
     for (int t = 0; t < ntiles; ++t) s += part[(long long)t * Nd + d];
     mean[d] = s / (double)Nr;
+}
+
+// paired_distance_kernel: out[i] = ||a_i - b_i||, the chain of pairwise_tile_kernel for the pair (i, i) - bit-identical to the
+// diagonal of the matrix, without the other N - 1 columns (10 000 pairs: 8 x 10^4 bytes written instead of 8 x 10^8).
+// grid: ceil(N / 64) workgroups of 256 threads, one per 64 pairs.  A 64-deep k-chunk of both operands is staged through LDS as
+// fp32 [k][row]: in a wave 16 lanes read 256 contiguous bytes of each of 4 rows (a thread walking its own row would read 4
+// bytes of 64 different cache lines per instruction), and the rows are 65 floats apart, so the staging writes (lane (row r,
+// quad q) -> bank 4q + r + j) and the reads of the chain (lane = row) both touch 64 different banks.  Wave 0 then runs the 64
+// chains, one pair per lane; the other three waves only stage (a chain is sequential by contract: the kernel is bound by the
+// latency of D dependent fp64 fused multiply-adds, ~10 us at D = 768, whatever N up to one workgroup per CU).
+constexpr int kPairedLd = kPairTile + 1;
+__global__ __launch_bounds__(256) void paired_distance_kernel(const float* __restrict__ a, const float* __restrict__ b, int N,
+                                                              int D, double* __restrict__ out) {
+    __shared__ float As[64][kPairedLd];  // [k][pair]
+    __shared__ float Bs[64][kPairedLd];
+    const int tid = threadIdx.x, kq = (tid & 15) * 4, rr = tid >> 4;
+    const int p0 = blockIdx.x * kPairTile;
+    double acc = 0.0;
+    for (int k0 = 0; k0 < D; k0 += 64) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = rr + 16 * q;
+            const long long row = min(p0 + r, N - 1);
+            float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
+            if (k0 + kq < D) {
+                va = *reinterpret_cast<const float4*>(a + row * D + k0 + kq);
+                vb = *reinterpret_cast<const float4*>(b + row * D + k0 + kq);
+            }
+            As[kq][r] = va.x; As[kq + 1][r] = va.y; As[kq + 2][r] = va.z; As[kq + 3][r] = va.w;
+            Bs[kq][r] = vb.x; Bs[kq + 1][r] = vb.y; Bs[kq + 2][r] = vb.z; Bs[kq + 3][r] = vb.w;
+        }
+        __syncthreads();
+        if (tid < kPairTile) {
+#pragma unroll 8
+            for (int k = 0; k < 64; ++k) {
+                const double e = (double)As[k][tid] - (double)Bs[k][tid];
+                acc = fma(e, e, acc);
+            }
+        }
+    }
+    if (tid < kPairTile && p0 + tid < N) out[p0 + tid] = sqrt(acc);
 }
 
 }  // namespace nomad

@@ -229,6 +229,33 @@ __global__ __launch_bounds__(1024) void head_kernel(const float* __restrict__ po
     }
 }
 
+// Stage 2 of the pooled backbone features (Origw2v.forward, networks.py:29-34: res['x'].mean(1), no ReLU, no Linear, no
+// normalisation).  grid: B blocks of 256 threads.  pool (stage 1) -> feat [B][768]: a clip's chunks folded in order and
+// `sum * (1 / T)`, the expression head_kernel forms before its ReLU.
+__global__ __launch_bounds__(256) void head_mean_kernel(const float* __restrict__ pool, int T, float* __restrict__ feat,
+                                                        const int* __restrict__ tpref = nullptr) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    long long row0 = (long long)b * T;
+    if (tpref) {
+        row0 = tpref[b];
+        T = tpref[b + 1] - tpref[b];
+    }
+    const float* pb = pool + (row0 / kHeadChunk + b) * 768;
+    const int nchunk = (T + kHeadChunk - 1) / kHeadChunk;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int j = 0; j < nchunk; ++j) {  // chunks in order
+        const float* r = pb + (long long)j * 768;
+        s0 += r[tid];
+        s1 += r[tid + 256];
+        s2 += r[tid + 512];
+    }
+    const float inv = 1.0f / (float)T;
+    float* o = feat + (long long)b * 768;
+    o[tid] = s0 * inv;
+    o[tid + 256] = s1 * inv;
+    o[tid + 512] = s2 * inv;
+}
+
 // NomadLoss.  Stage 1: per-block fp64 partial sums of |a-b| over the 12 layer tensors (n_layer
 // float4s in total) and over the embeddings; stage 2: one block folds the partials in fixed order.
 constexpr int kL1Blocks = 1024;

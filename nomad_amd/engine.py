@@ -307,6 +307,136 @@ class Engine:
         cur.wait_stream(ss)
         return emb
 
+    # ---- pooled backbone features (the raw wav2vec 2.0 baseline, Origw2v) ----------------------------------------------
+    def _feature_precision(self, precision: str) -> int:
+        if precision not in _lib.PRECISION:
+            raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
+        if precision != "fp32":
+            enable = self.lib.nomad_enable_bf16 if precision == "bf16" else self.lib.nomad_enable_bf16x3
+            _lib.check(enable(self.ctx), f"nomad_enable_{precision}")
+        return _lib.PRECISION[precision]
+
+    def embed_features(self, wav: torch.Tensor, precision: str = "fp32") -> torch.Tensor:
+        """wav (B,N) or (B,1,N) fp32 on the GPU -> (B,768) fp32: the backbone's output averaged over time
+        (``Origw2v.forward``), by the forward of ``precision``.  Batches split over two streams by the rule of that
+        precision's ``embed*``; a clip's values do not depend on the batch it is in, so the split changes no bit."""
+        if wav.dim() == 3:
+            wav = wav.squeeze(1)
+        self._check_dev(wav, "wav")
+        B, N = wav.shape
+        T = num_frames(N)
+        if T < 1:
+            raise ValueError(f"clip of {N} samples is shorter than the conv stack's receptive field")
+        prec = self._feature_precision(precision)
+        size = {"fp32": self.lib.nomad_workspace_bytes, "bf16": self.lib.nomad_workspace_bytes_bf16,
+                "bf16x3": self.lib.nomad_workspace_bytes_bf16x3}[precision]
+        feat = torch.empty(B, 768, dtype=torch.float32, device=self.device)
+
+        def run(w, f, side):
+            b = w.shape[0]
+            ws = self._workspace(self._size(size, b, N, "nomad_workspace_bytes"), side)
+            _lib.check(self.lib.nomad_embed_features(self.ctx, w.data_ptr(), b, N, prec, f.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     self._stream()), "nomad_embed_features")
+
+        rows = B * T
+        split = B >= 2 and ((precision == "bf16x3" and self.X3_SPLIT_ROWS and rows >= self.X3_SPLIT_ROWS) or
+                            (precision == "bf16" and self.BF16_SPLIT_ROWS and rows >= self.BF16_SPLIT_ROWS) or
+                            (precision == "fp32" and self.F32_SPLIT_ROWS and self.F32_SPLIT_ROWS <= rows < self.F32_SPLIT_MAX_ROWS))
+        self.lib.nomad_set_concurrent_parts(self.ctx, 2 if split else 1)   # tile-shape hint only: results never depend on it
+        if not split:
+            run(wav, feat, False)
+            return feat
+        h = B // 2
+        cur, ss = torch.cuda.current_stream(self.device), self.side_stream()
+        ss.wait_stream(cur)
+        with torch.cuda.stream(ss):
+            run(wav[h:], feat[h:], True)
+        run(wav[:h], feat[:h], False)
+        cur.wait_stream(ss)
+        return feat
+
+    def embed_features_ragged(self, waves=None, precision: str = "fp32",
+                              packed: Optional[Tuple[torch.Tensor, list]] = None) -> torch.Tensor:
+        """``embed_features`` for clips of different lengths in ONE launch sequence: (B,768) fp32, bit-identical to one
+        ``embed_features`` call per clip.  waves / packed, the staging and the two-stream split: as in ``embed_ragged``."""
+        prec = self._feature_precision(precision)
+        if packed is not None:
+            host, lens = packed
+            B, stride = host.shape
+            buf = host.to(self.device, non_blocking=True)
+        else:
+            flat = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in waves]
+            lens = [int(w.numel()) for w in flat]
+            B, stride = len(flat), (max(lens) + 3) // 4 * 4
+            if all(w.is_cuda for w in flat):
+                buf = torch.empty(B, stride, dtype=torch.float32, device=self.device)
+                for i, w in enumerate(flat):
+                    buf[i, :lens[i]] = w
+            else:
+                host, lens = self.pack_ragged_host(flat)
+                buf = host.to(self.device, non_blocking=True)
+        feat = torch.empty(B, 768, dtype=torch.float32, device=self.device)
+        size = {"fp32": self.lib.nomad_workspace_bytes_ragged, "bf16": self.lib.nomad_workspace_bytes_ragged_bf16,
+                "bf16x3": self.lib.nomad_workspace_bytes_ragged_bf16x3}[precision]
+
+        def run(lo, hi, side):
+            n = hi - lo
+            arr = (C.c_int * n)(*lens[lo:hi])
+            nb = C.c_size_t()
+            _lib.check(size(self.ctx, n, arr, C.byref(nb)), "nomad_workspace_bytes_ragged")
+            ws = self._workspace(nb.value, side)
+            _lib.check(self.lib.nomad_embed_features_ragged(self.ctx, buf[lo:hi].data_ptr(), n, stride, arr, prec,
+                                                            feat[lo:hi].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                       "nomad_embed_features_ragged")
+
+        rows = sum(num_frames(n) for n in lens)
+        split = B >= 2 and ((precision == "bf16x3" and self.X3_SPLIT_ROWS and rows >= self.X3_SPLIT_ROWS) or
+                            (precision == "bf16" and self.BF16_SPLIT_ROWS and rows >= self.BF16_SPLIT_ROWS) or
+                            (precision == "fp32" and self.F32_SPLIT_ROWS and self.F32_SPLIT_ROWS <= rows < self.F32_SPLIT_MAX_ROWS))
+        if not split:
+            run(0, B, False)
+            return feat
+        acc, h = 0, 1
+        for i, n in enumerate(lens[:-1]):   # two halves by audio length, as in embed_ragged
+            acc += n
+            h = i + 1
+            if 2 * acc >= sum(lens):
+                break
+        cur, ss = torch.cuda.current_stream(self.device), self.side_stream()
+        ss.wait_stream(cur)
+        with torch.cuda.stream(ss):
+            run(h, B, True)
+        run(0, h, False)
+        cur.wait_stream(ss)
+        return feat
+
+    def cdist(self, a: torch.Tensor, b: torch.Tensor, want_matrix: bool = True):
+        """a (Na,D), b (Nb,D) fp32 on the GPU, D a multiple of 4 up to 4096 -> (dist (Na,Nb) float64 or None, mean (Na,)
+        float64): ``pairwise`` for rows of any width (the same bits at D = 256)."""
+        self._check_dev(a, "a")
+        self._check_dev(b, "b")
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError("a and b must be matrices with rows of one width")
+        Na, Nb, D = a.shape[0], b.shape[0], a.shape[1]
+        dist = torch.empty(Na, Nb, dtype=torch.float64, device=self.device) if want_matrix else None
+        mean = torch.empty(Na, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.nomad_cdist(self.ctx, a.data_ptr(), Na, b.data_ptr(), Nb, D,
+                                        dist.data_ptr() if dist is not None else None, mean.data_ptr(), self._stream()),
+                   "nomad_cdist")
+        return dist, mean
+
+    def paired_distance(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """a, b (N,D) fp32 on the GPU -> (N,) float64, out[i] = ||a_i - b_i||: the diagonal of ``cdist(a, b)`` bit for bit,
+        without the matrix."""
+        self._check_dev(a, "a")
+        self._check_dev(b, "b")
+        if a.dim() != 2 or a.shape != b.shape:
+            raise ValueError("a and b must be matrices of one shape")
+        out = torch.empty(a.shape[0], dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.nomad_paired_distance(self.ctx, a.data_ptr(), b.data_ptr(), a.shape[0], a.shape[1], out.data_ptr(),
+                                                  self._stream()), "nomad_paired_distance")
+        return out
+
     def pairwise(self, deg: torch.Tensor, ref: torch.Tensor, want_matrix: bool = True):
         """deg (Nd,256), ref (Nr,256) fp32 on GPU -> (dist (Nd,Nr) float64 or None, mean (Nd,) float64)."""
         self._check_dev(deg, "deg")
@@ -590,6 +720,12 @@ class Engine:
         return dl, de
 
     # ---- triplet fine-tuning step (train_triplet.py:112-133) ---------------------------------------
+    @property
+    def train_enabled(self) -> bool:
+        """True once ``train_enable`` has allocated the master parameters, gradients and Adam moments (scoring and the
+        evaluation experiments never do)."""
+        return self._train_segments is not None
+
     def train_enable(self):
         """Allocate master parameters / gradients / Adam moments and re-point the engine at them."""
         if self._train_segments is not None:

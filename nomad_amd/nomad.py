@@ -72,6 +72,25 @@ class TripletModel:
         return self.engine.embed(wav.to(self.engine.device, torch.float32).contiguous())
 
 
+class Origw2v:
+    """``Origw2v.forward(wav)`` (src/models/networks.py:23-34) on the engine: the wav2vec 2.0 backbone's output averaged
+    over time, (B, 768) - the baseline the evaluation experiments compare NOMAD with (``eval_w2v: True``).  Handed to
+    ``get_embeddings_csv`` as ``model`` it makes the file pipeline produce these 768 columns."""
+
+    def __init__(self, engine: Engine, precision: str = "fp32"):
+        self.engine = engine
+        self.precision = precision
+
+    def eval(self):
+        return self
+
+    def __call__(self, wav: torch.Tensor) -> torch.Tensor:
+        return self.forward(wav)
+
+    def forward(self, wav: torch.Tensor) -> torch.Tensor:
+        return self.engine.embed_features(wav.to(self.engine.device, torch.float32).contiguous(), precision=self.precision)
+
+
 def _takes_bf16x3(precision: str, wav: torch.Tensor) -> bool:
     return precision == "bf16x3" and wav.numel() >= BF16X3_MIN_SAMPLES
 
@@ -527,6 +546,19 @@ class Nomad:
         self.lossnet_layers = LossNetLayers(self.engine, SSL_OUT_DIM, EMB_DIM, precision)
         self.nomad_loss = NomadLoss(self.engine)
 
+    @classmethod
+    def from_engine(cls, engine: Engine, precision: str = "fp32", group=None) -> "Nomad":
+        """A ``Nomad`` over an engine that exists already (``nomad_amd.train.Training`` shares its own with the file pipeline)."""
+        if precision not in ("fp32", "bf16x3", "bf16"):
+            raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
+        self = cls.__new__(cls)
+        self.precision, self.group, self.engine = precision, group, engine
+        self.DEVICE = f"cuda:{engine.device_index}"
+        self.model = TripletModel(engine)
+        self.lossnet_layers = LossNetLayers(engine, SSL_OUT_DIM, EMB_DIM, precision)
+        self.nomad_loss = NomadLoss(engine)
+        return self
+
     # ------------------------------------------------------------------------------------------
     def predict(self, mode="dir", nmr="data/nmr-data", deg="data/test-data", results_path=None):
         if nmr is None:
@@ -636,8 +668,9 @@ class Nomad:
             raise Exception(f"Path {path} does not exist")
         return self.get_embeddings_csv(self.model, data)
 
-    def _embed_files_into(self, paths, embeddings: np.ndarray, max_batch_samples: int) -> None:
-        """The file pipeline over ``paths`` -> rows of ``embeddings`` (same order)."""
+    def _embed_files_into(self, paths, embeddings: np.ndarray, max_batch_samples: int, features: bool = False) -> None:
+        """The file pipeline over ``paths`` -> rows of ``embeddings`` (same order).  features: the 768 pooled backbone
+        features of ``Origw2v`` instead of the 256-dimensional embeddings."""
         pending = None                                   # (row indices, host copy in flight) of the previous batch
         for idxs, packed, uploaded in _staged_batches(paths, lambda p: self.load_processing(p, trim=False),
                                                       self.engine.pack_ragged_host, max_batch_samples, self.DECODE_THREADS,
@@ -649,7 +682,8 @@ class Nomad:
                 # which is the faster one there.  Its GEMM products follow Engine.gemm_precision, and Nomad(precision="bf16x3") has
                 # set that to "bf16x3" - so these embeddings are bf16x3-class (~1e-6 from fp32) too, not exact fp32
                 prec = "fp32"
-            emb = self.engine.embed_ragged(None, precision=prec, packed=packed)   # asynchronous
+            embed = self.engine.embed_features_ragged if features else self.engine.embed_ragged
+            emb = embed(None, precision=prec, packed=packed)                       # asynchronous
             uploaded()                                                             # the staging slot is free once the copy is done
             fetch = self.engine.fetch_async(emb)                                   # D2H enqueued right behind it
             if pending is not None:
@@ -670,7 +704,10 @@ class Nomad:
         Like the reference, which holds one clip at a time, memory does not grow with the size of the directory:
         never more than ``PIPELINE_BATCHES`` staged batches (plus the decode look-ahead) are alive.
         Inside a ``torch.distributed`` job (one process per GPU) every rank embeds its contiguous slice of the list
-        and one all-gather gives every rank the whole table."""
+        and one all-gather gives every rank the whole table.
+        ``model``: an ``Origw2v`` yields its 768 feature columns (the raw wav2vec 2.0 baseline) through the same pipeline;
+        anything else (the reference passes ``self.model``) the 256-dimensional NOMAD embeddings."""
+        features = isinstance(model, Origw2v)
         file_names_arr = np.array(file_names)
         paths = []
         for row in file_names_arr:
@@ -681,10 +718,13 @@ class Nomad:
         world, rank, collective = _dist_info(getattr(self, "group", None))
         lo, hi = partition(len(paths), world, rank) if collective else (0, len(paths))
         mine = paths[lo:hi]
-        embeddings = np.zeros((len(mine), EMB_DIM), dtype=np.float32)
+        embeddings = np.zeros((len(mine), SSL_OUT_DIM if features else EMB_DIM), dtype=np.float32)
         failure = None
         try:
-            self._embed_files_into(mine, embeddings, max_batch_samples)
+            if features:
+                self._embed_files_into(mine, embeddings, max_batch_samples, features=True)
+            else:
+                self._embed_files_into(mine, embeddings, max_batch_samples)
         except Exception as e:  # noqa: BLE001 - inside a job the other ranks must hear about it before anybody raises
             if not collective:
                 raise

@@ -7,9 +7,16 @@ Same names, same config keys, same control flow:
     train_obj = Training("src/config/train_triplet.yaml")     # train_triplet.py:44-110
     train_obj.training_loop()                                  # :161-205
 
+and its evaluation experiments (``quality_nmr``, ``valid_rank``, ``intensity``, ``quality_fr``: train_triplet.py:203-489,
+dispatched by ``main`` like the reference's main.py:26-44):
+
+    Training("eval.yaml").eval_audio_quality(config["nomad_model_path"])
+
 Every FLOP of a step - three forwards, nn.TripletMarginLoss, backward to every trainable parameter, Adam - runs in
 libnomad_hip.so (nomad_embed_train / nomad_triplet_loss / nomad_train_backward / nomad_train_adam_step); this file
-is data loading, the epoch loop, the learning-rate schedule and checkpoint writing.
+is data loading, the epoch loop, the learning-rate schedule and checkpoint writing.  The evaluation experiments embed their
+files through ``Nomad.get_embeddings_csv`` (nomad_embed_ragged / nomad_embed_features_ragged), take their distances from
+nomad_cdist / nomad_paired_distance, and leave the pandas / SciPy statistics of the reference as they are.
 
 Differences, on purpose:
 * none in the freeze switches: ``freeze_convnet: True`` (the shipped config; backbone at 1e-5, head at ``lr``),
@@ -18,6 +25,11 @@ Differences, on purpose:
 * ``checkpoint_path`` may be a NOMAD-layout state dict (keys of nomad_best_model.pt), a fairseq ``wav2vec_small.pt``
   ({'model': state_dict}; the head is then initialised like ``nn.Linear`` under ``torch.manual_seed(0)``), or the word
   ``seeded`` (random weights, for tests).  fairseq itself is not needed.
+* evaluation: ``nomad_model_path`` is a NOMAD-layout checkpoint (what ``Training.save`` writes) or ``seeded``; the config key
+  ``precision`` (``fp32`` default, ``bf16x3``, ``bf16``; not a reference key) picks the forward of the embeddings; each
+  ``eval_*`` method returns what it printed from (the reference returns nothing); figures are drawn with matplotlib alone
+  (no seaborn) and skipped with one printed line when matplotlib is missing; the dead PCA block (``pca_plot = False``) is not
+  built; no optimiser state is allocated.
 * model.train() regularisation (fairseq BASE config: dropout 0.1, attention_dropout 0.1, dropout_input 0.1,
   encoder_layerdrop 0.05) uses the engine's counter-based masks; torch's RNG stream of the reference's device cannot
   be reproduced on any other device, so runs are statistically, not bit-wise, equivalent to the reference's.
@@ -35,6 +47,7 @@ import torch.distributed as dist
 
 from . import wavio
 from .engine import Engine
+from .nomad import Nomad, Origw2v, TripletModel
 from .weights import EMB_DIM, EMBED_DIM, check_state_dict, expected_shapes, load_checkpoint, seeded_state_dict
 
 SEED = 0  # train_triplet.py:29-33
@@ -141,6 +154,173 @@ class ExponentialLR:
         return list(self.lrs)
 
 
+EVAL_EXPERIMENTS = ("quality_nmr", "valid_rank", "intensity", "quality_fr")
+
+
+def order_three(x, a, b, c, d):
+    """train_triplet.py:227-228: the third-order map from distance to MOS."""
+    return a * x + b * x ** 2 + c * x ** 3 + d
+
+
+def filter_test_data(test_data, db=None, conds=None):
+    """train_triplet.py:240-249: the databases (``db``: a list, None = all) and conditions (``conds``: substrings joined into
+    one regular expression, None = all) under test."""
+    if db is not None:
+        test_data = test_data[test_data["db"].isin(db)]
+    if conds is not None:
+        print(f"Testing DB: {db}, conds: {conds}")
+        test_data = test_data[test_data["condition"].str.contains("|".join(conds))]
+    return test_data
+
+
+def _emb_values(df) -> np.ndarray:
+    """The embedding columns of a table whose index is the file name, as the fp32 values they were computed in."""
+    return np.ascontiguousarray(df.to_numpy(dtype=np.float32))
+
+
+def mos_statistics(df_dist) -> dict:
+    """train_triplet.py:276-303 / :447-474 on a per-condition table with ``Distance`` and ``mos``: the cubic map (``curve_fit``,
+    default arguments), ``Distance_map``, Spearman and Pearson with and without the map, printed as the reference prints
+    them.  -> {table, popt, SRCC, SRCC_map, PCC, PCC_map}."""
+    from scipy.optimize import curve_fit
+    from scipy.stats import pearsonr, spearmanr
+    popt3, _ = curve_fit(order_three, df_dist["Distance"].values, df_dist["mos"].values)
+    a3, b3, c3, d3 = popt3
+    df_dist["Distance_map"] = df_dist["Distance"].apply(lambda x: order_three(x, a3, b3, c3, d3))
+    SRCC, _ = spearmanr(df_dist["Distance"], df_dist["mos"])
+    print(f"SRCC: {np.round(SRCC, 2)}")
+    SRCC_map, _ = spearmanr(df_dist["Distance_map"], df_dist["mos"])
+    print(f"SRCC 3rd map: {np.round(SRCC_map, 2)}")
+    PCC, _ = pearsonr(df_dist["Distance"], df_dist["mos"])
+    print(f"PCC: {np.round(PCC, 2)}")
+    PCC_map, _ = pearsonr(df_dist["Distance_map"], df_dist["mos"])
+    print(f"PCC 3rd map: {np.round(PCC_map, 2)}")
+    return dict(table=df_dist, popt=np.asarray(popt3), SRCC=float(SRCC), SRCC_map=float(SRCC_map), PCC=float(PCC),
+                PCC_map=float(PCC_map))
+
+
+def quality_nmr_stats(df_emb, db, ref_embeddings, nmr_mean) -> dict:
+    """One database of ``eval_audio_quality`` (train_triplet.py:262-303).  df_emb: ``get_embeddings_csv`` of
+    ``db['filepath_deg']``; ref_embeddings: the non-matching references, indexed by ``reference``;
+    nmr_mean(test, ref) -> (N,) float64: the mean over the references of the Euclidean distances (cdist + np.mean(axis=1))."""
+    import pandas as pd
+    test_embeddings = df_emb.set_index("filepath_deg")
+    test_names = df_emb.merge(db, on="filepath_deg")[["filepath_deg", "condition", "mos"]]
+    avg_dist_nmr = nmr_mean(_emb_values(test_embeddings), _emb_values(ref_embeddings))
+    df_dist = pd.DataFrame({"filepath_deg": test_embeddings.index, "Distance": avg_dist_nmr})
+    df_dist = df_dist.merge(test_names, on="filepath_deg").set_index("filepath_deg")
+    df_dist = df_dist.groupby("condition").mean()
+    out = mos_statistics(df_dist)
+    out["embeddings"] = df_emb
+    return out
+
+
+def valid_rank_labels(anchors):
+    """train_triplet.py:332: the condition of a validation anchor, from its file name."""
+    return [x.split("_")[1] + " " + x.split("_")[2].split(".")[0] for x in anchors]
+
+
+def valid_rank_stats(df_emb, ref_embeddings, nmr_mean) -> dict:
+    """``eval_degr_level`` (train_triplet.py:317-333).  df_emb: ``get_embeddings_csv`` of the validation anchors (column
+    ``Anchor`` first); ref_embeddings: ``get_nmr_embeddings()`` (column ``reference`` first).
+    -> {table (per file, sorted by Distance, with ``condition``), order (conditions by mean distance)}."""
+    import pandas as pd
+    test_embeddings = np.ascontiguousarray(df_emb.iloc[:, 1:].to_numpy(dtype=np.float32))
+    avg_dist_nmr = nmr_mean(test_embeddings, np.ascontiguousarray(ref_embeddings.iloc[:, 1:].to_numpy(dtype=np.float32)))
+    df_dist = pd.DataFrame({"Anchor": df_emb["Anchor"], "Distance": avg_dist_nmr})
+    df_dist.sort_values(by="Distance", inplace=True)
+    df_dist["condition"] = valid_rank_labels(df_dist["Anchor"])
+    order = df_dist.groupby("condition")["Distance"].mean().sort_values().index
+    return dict(table=df_dist, order=list(order), embeddings=df_emb)
+
+
+def intensity_stats(df_emb, deg_data, ref_embeddings, nmr_mean, deg_name="") -> dict:
+    """One degradation of ``eval_degradation_intensity`` (train_triplet.py:369-393): mean distance per ``Condition`` (the
+    degradation's level) and its rank correlation with the level.  -> {table, SRCC}."""
+    import pandas as pd
+    from scipy.stats import spearmanr
+    test_embeddings = df_emb.set_index("filepath_deg")
+    test_names = df_emb.merge(deg_data, on="filepath_deg")[["filepath_deg", "Condition"]]
+    avg_dist_nmr = nmr_mean(_emb_values(test_embeddings), _emb_values(ref_embeddings))
+    df_dist = pd.DataFrame({"filepath_deg": test_embeddings.index, "Distance": avg_dist_nmr})
+    df_dist = df_dist.merge(test_names, on="filepath_deg")
+    df_dist.set_index("filepath_deg", inplace=True)
+    df_dist = df_dist.groupby("Condition").mean().reset_index()
+    df_dist.sort_values(by="Distance", inplace=True)
+    SRCC, _ = spearmanr(df_dist["Distance"], df_dist["Condition"])
+    print(f"Degradation: {deg_name}")
+    print(f"SRCC: {np.round(SRCC, 2)}")
+    return dict(table=df_dist, SRCC=float(SRCC), embeddings=df_emb)
+
+
+def quality_fr_stats(df_emb_test, df_emb_ref, db, paired) -> dict:
+    """One database of ``eval_full_reference`` (train_triplet.py:433-474).  df_emb_test / df_emb_ref: ``get_embeddings_csv`` of
+    ``db['filepath_deg']`` / ``db['filepath_ref']``, row i of one matching row i of the other;
+    paired(test, ref) -> (N,) float64: the distance of each file to ITS reference (np.diag(cdist(test, ref)))."""
+    import pandas as pd
+    test = df_emb_test.set_index("filepath_deg")
+    ref = df_emb_ref.set_index("filepath_ref")
+    test_names = df_emb_test.merge(db, on="filepath_deg")[["filepath_deg", "condition", "mos"]]
+    fr_distance = paired(_emb_values(test), _emb_values(ref))
+    df_dist = pd.DataFrame({"filepath_deg": test.index, "Distance": fr_distance})
+    df_dist = df_dist.merge(test_names, on="filepath_deg")
+    # (the reference leaves the file-name column in the frame here; pandas 2 no longer drops it silently from a mean)
+    df_dist = df_dist.groupby("condition").mean(numeric_only=True)
+    out = mos_statistics(df_dist)
+    out["embeddings"], out["ref_embeddings"] = df_emb_test, df_emb_ref
+    return out
+
+
+def _figure():
+    """(Figure, FigureCanvasAgg) or None with one printed line: matplotlib alone, no pyplot state, no display."""
+    try:
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+    except Exception as e:  # noqa: BLE001 - an absent or broken matplotlib only costs the picture
+        print(f"matplotlib is not available ({type(e).__name__}): figure skipped")
+        return None
+    return Figure, FigureCanvasAgg
+
+
+def save_mos_scatter(df_dist, path: str, ylabel: str) -> Optional[str]:
+    """train_triplet.py:282-291: MOS against the mapped distance, both axes 1 .. 5."""
+    mpl = _figure()
+    if mpl is None:
+        return None
+    fig = mpl[0]()
+    mpl[1](fig)
+    ax = fig.add_subplot(111)
+    ax.scatter(df_dist["mos"], df_dist["Distance_map"])
+    ax.set_xlabel("Actual MOS")
+    ax.set_ylabel(ylabel)
+    ax.set_xlim([1, 5])
+    ax.set_ylim([1, 5])
+    fig.tight_layout()
+    fig.savefig(path)
+    return path
+
+
+def save_rank_boxplot(df_dist, order, path: str) -> Optional[str]:
+    """train_triplet.py:329-342: one box per condition, conditions ordered by their mean distance, means marked."""
+    mpl = _figure()
+    if mpl is None:
+        return None
+    fig = mpl[0](figsize=(50, 20))
+    mpl[1](fig)
+    ax = fig.add_subplot(111)
+    ax.boxplot([df_dist.loc[df_dist["condition"] == c, "Distance"].to_numpy() for c in order], showmeans=True, widths=0.8,
+               meanprops={"markerfacecolor": "white", "markeredgecolor": "blue", "markersize": 50},
+               boxprops={"linewidth": 6}, whiskerprops={"linewidth": 6}, capprops={"linewidth": 6}, medianprops={"linewidth": 6})
+    ax.set_xticks(range(1, len(order) + 1))
+    ax.set_xticklabels(list(order), rotation=65)
+    ax.tick_params(labelsize=60)
+    ax.set_ylabel("NOMAD", fontsize=80)
+    ax.set_xlabel("Condition", fontsize=80)
+    fig.tight_layout()
+    fig.savefig(path)
+    return path
+
+
 class Training:
     def __init__(self, config_file, device: int = 0, engine: Optional[Engine] = None,
                  regularisation: Optional[dict] = None, merge_branches: bool = True, group=None):
@@ -157,8 +337,27 @@ class Training:
         random.seed(SEED)
         np.random.seed(SEED)
         torch.manual_seed(SEED)
+        self.group = group                       # torch.distributed group (None: the default group, if any)
+        self.precision = self.config.get("precision", "fp32")   # not a reference key: the forward of the evaluation embeddings
+        if self.precision not in ("fp32", "bf16x3", "bf16"):
+            raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
+        self._device_index = device
+        if self.config["experiment_name"] in EVAL_EXPERIMENTS:
+            # The evaluation experiments need no optimiser state (no train_enable).  eval_w2v: the model is an Origw2v over the
+            # weights of checkpoint_path (train_triplet.py:67-68).  Otherwise the reference builds a TripletModel over
+            # checkpoint_path and then overwrites every one of its parameters from `model_path` (load_state_dict of a NOMAD
+            # checkpoint, :234): the engine is created from `model_path` itself, when the experiment names it (_load_model).
+            self.engine = engine
+            self._loaded_from = None if engine is None else "engine"
+            if self.config.get("eval_w2v") and engine is None:
+                self.engine = Engine(load_pretrained(self.config["checkpoint_path"], self.config.get("allow_unsafe_pickle")), device)
+                self._loaded_from = self.config["checkpoint_path"]
+            self.model = None
+            self._bind_model()
+            return
         if self.config.get("eval_w2v"):
-            raise NotImplementedError("eval_w2v (raw wav2vec features) is outside the NOMAD hot path")
+            raise NotImplementedError("eval_w2v (raw wav2vec features) is for the evaluation experiments quality_nmr and intensity; "
+                                      "'Training' fine-tunes the TripletModel")
         self.engine = engine if engine is not None else Engine(
             load_pretrained(self.config["checkpoint_path"], self.config.get("allow_unsafe_pickle")), device)
         # gemm_precision (not a reference key): "bf16x3" forms the products of every GEMM of the step - forward, dX and the
@@ -179,7 +378,6 @@ class Training:
         self.reg.update(regularisation or {})
         self._rng = np.random.RandomState(SEED)  # LayerDrop draws + per-call dropout seeds
         self.merge_branches = merge_branches     # A/P/N as one 3B-clip launch sequence when their padded lengths agree
-        self.group = group                       # torch.distributed group for data-parallel training (None: default group)
         if self.config["experiment_name"] == "Training":
             self.current_level = self.config.get("current_level")
             g = torch.Generator()
@@ -318,10 +516,143 @@ class Training:
         return best_valid_loss
 
 
+    # ---- evaluation (train_triplet.py:201-489) -----------------------------------------------------------------------
+    def _bind_model(self):
+        """self.model / self.nomad over the current engine: an Origw2v with eval_w2v, a TripletModel otherwise."""
+        if self.engine is None:
+            return
+        if self.precision == "bf16x3":
+            # as Nomad(precision="bf16x3"): the few files that stay on fp32 buffers form their GEMM products the bf16x3 way too
+            self.engine.gemm_precision = "bf16x3"
+        self.nomad = Nomad.from_engine(self.engine, precision=self.precision, group=self.group)
+        self.model = Origw2v(self.engine, self.precision) if self.config.get("eval_w2v") else self.nomad.model
+
+    def _load_model(self, model_path: str, allow_w2v: bool):
+        """``self.model.load_state_dict(torch.load(model_path))`` of the evaluation experiments.  With eval_w2v the reference
+        skips the load in quality_nmr and intensity (train_triplet.py:233, :345); in valid_rank and quality_fr it loads
+        unconditionally, which fails on an Origw2v (no embedding layer to load into): refused here with that explanation."""
+        if self.config.get("eval_w2v"):
+            if not allow_w2v:
+                raise ValueError(f"experiment {self.config['experiment_name']!r} loads nomad_model_path into the model "
+                                 "unconditionally (train_triplet.py:307, :422), which an Origw2v (eval_w2v: True) cannot take; "
+                                 "the raw wav2vec 2.0 baseline is evaluated by quality_nmr and intensity only")
+            return
+        if self._loaded_from in ("engine", model_path):   # the caller's engine is the model; or loaded already
+            return
+        if self.engine is not None:
+            torch.cuda.synchronize(self.DEVICE)
+            self.engine.close()
+        self.engine = Engine(load_pretrained(model_path, self.config.get("allow_unsafe_pickle")), self._device_index)
+        self._loaded_from = model_path
+        self._bind_model()
+
+    def _figure_dir(self) -> str:
+        """train_triplet.py:289: next to nomad_model_path; under ``out_dir`` when that is the word ``seeded``."""
+        path = self.config["nomad_model_path"]
+        out_dir = self.config.get("out_dir", ".") if path == "seeded" else "/".join(path.split("/")[:-1])
+        out_dir = out_dir or "."
+        os.makedirs(out_dir, exist_ok=True)
+        return out_dir
+
+    def get_embeddings_csv(self, model, file_names, root=False):
+        """train_triplet.py:203-225, through the file pipeline of ``Nomad.get_embeddings_csv`` (ragged batches, bit-identical to
+        one call per file; 768 feature columns for an Origw2v, 256 embedding columns otherwise)."""
+        return self.nomad.get_embeddings_csv(model, file_names, root=root)
+
+    def order_three(self, x, a, b, c, d):
+        return order_three(x, a, b, c, d)
+
+    def get_nmr_embeddings(self):
+        """train_triplet.py:476-484: the embeddings of every file of ``non_match_dir``, column ``reference`` first."""
+        import pandas as pd
+        ref_files = pd.DataFrame(os.listdir(self.config["non_match_dir"]))
+        ref_files.columns = ["reference"]
+        ref_files["reference"] = [os.path.join(self.config["non_match_dir"], x) for x in ref_files["reference"]]
+        return self.get_embeddings_csv(self.model, ref_files)
+
+    def euclidean_dist(self, emb_a, emb_b):
+        """train_triplet.py:487-489 (the reference's own cross-check of cdist)."""
+        return np.sqrt(np.dot(emb_a - emb_b, (emb_a - emb_b).T))
+
+    def _nmr_mean(self, test: np.ndarray, ref: np.ndarray) -> np.ndarray:
+        """cdist(test, ref) + np.mean(axis=1) on the GPU (nomad_cdist: float64, difference form; the matrix is not stored)."""
+        dev = self.engine.device
+        _, mean = self.engine.cdist(torch.from_numpy(test).to(dev), torch.from_numpy(ref).to(dev), want_matrix=False)
+        return mean.cpu().numpy()
+
+    def _paired(self, test: np.ndarray, ref: np.ndarray) -> np.ndarray:
+        """np.diag(cdist(test, ref)) on the GPU without the N x N matrix (nomad_paired_distance)."""
+        dev = self.engine.device
+        return self.engine.paired_distance(torch.from_numpy(test).to(dev), torch.from_numpy(ref).to(dev)).cpu().numpy()
+
+    def eval_audio_quality(self, model_path):
+        """``quality_nmr`` (train_triplet.py:231-303): per database, the mean distance to the non-matching references per
+        condition against MOS.  -> {db: {table, popt, SRCC, SRCC_map, PCC, PCC_map, embeddings, ref_embeddings, figure}}."""
+        import pandas as pd
+        self._load_model(model_path, allow_w2v=True)
+        test_data = filter_test_data(pd.read_csv(self.config["test_db_file"]), self.config.get("db"), self.config.get("conds"))
+        ref_embeddings = self.get_nmr_embeddings()
+        ref_embeddings.set_index("reference", inplace=True)
+        results = {}
+        for db_name, db in test_data.groupby("db"):
+            print(db_name)
+            df_emb = self.get_embeddings_csv(self.model, db["filepath_deg"], root=self.config["test_root_wav"])
+            res = quality_nmr_stats(df_emb, db, ref_embeddings, self._nmr_mean)
+            res["ref_embeddings"] = ref_embeddings
+            res["figure"] = save_mos_scatter(res["table"], os.path.join(self._figure_dir(), f"{db_name}_embeddings.png"),
+                                             "Dist w.r.t. clean embeddings")
+            results[db_name] = res
+        return results
+
+    def eval_degr_level(self, model_path):
+        """``valid_rank`` (train_triplet.py:305-342): the validation anchors ranked by their mean distance to the non-matching
+        references.  -> {table, order, embeddings, ref_embeddings, figure}."""
+        self._load_model(model_path, allow_w2v=False)
+        valid_set = TripletDataset(self.config, data_mode="valid_df", level=self.config.get("current_level"))
+        df_emb = self.get_embeddings_csv(self.model, valid_set.dataset["Anchor"], root=self.config["root"])
+        ref_embeddings = self.get_nmr_embeddings()
+        res = valid_rank_stats(df_emb, ref_embeddings, self._nmr_mean)
+        res["ref_embeddings"] = ref_embeddings
+        res["figure"] = save_rank_boxplot(res["table"], res["order"], os.path.join(self._figure_dir(), "validset_embeddings.png"))
+        return res
+
+    def eval_degradation_intensity(self, model_path):
+        """``intensity`` (train_triplet.py:344-401): per degradation, the rank correlation of the mean distance with the
+        degradation's level.  -> {degradation: {table, SRCC, embeddings, ref_embeddings}}."""
+        import pandas as pd
+        self._load_model(model_path, allow_w2v=True)
+        ref_embeddings = self.get_nmr_embeddings()
+        ref_embeddings.set_index("reference", inplace=True)
+        test_data = pd.read_csv(self.config["test_mono_data"])
+        results = {}
+        for deg_name, deg_data in test_data.groupby("Degradation"):
+            df_emb = self.get_embeddings_csv(self.model, deg_data["filepath_deg"], root=self.config["test_mono_wav"])
+            res = intensity_stats(df_emb, deg_data, ref_embeddings, self._nmr_mean, deg_name)
+            res["ref_embeddings"] = ref_embeddings
+            results[deg_name] = res
+        return results
+
+    def eval_full_reference(self, model_path):
+        """``quality_fr`` (train_triplet.py:421-474): per database, the distance of each file to its own clean reference per
+        condition against MOS.  -> {db: {table, popt, SRCC, SRCC_map, PCC, PCC_map, embeddings, ref_embeddings, figure}}."""
+        import pandas as pd
+        self._load_model(model_path, allow_w2v=False)
+        test_data = pd.read_csv(self.config["test_db_file_fr"])
+        results = {}
+        for db_name, db in test_data.groupby("db"):
+            print(db_name)
+            df_emb_ref = self.get_embeddings_csv(self.model, db["filepath_ref"], root=self.config["test_root_wav"])
+            df_emb_test = self.get_embeddings_csv(self.model, db["filepath_deg"], root=self.config["test_root_wav"])
+            res = quality_fr_stats(df_emb_test, df_emb_ref, db, self._paired)
+            res["figure"] = save_mos_scatter(res["table"], os.path.join(self._figure_dir(), f"fr_{db_name}_embeddings.png"),
+                                             "Dist w.r.t Reference")
+            results[db_name] = res
+        return results
+
+
 def main(argv=None):
-    """``python -m nomad_amd.train --config_file cfg.yaml``: the 'Training' branch of /root/reference/main.py:7-46
-    (the evaluation experiments - quality_nmr, valid_rank, intensity, quality_fr - are plotting / statistics scripts
-    around ``predict`` and are not part of this build)."""
+    """``python -m nomad_amd.train --config_file cfg.yaml``: the experiment choice of /root/reference/main.py:7-46 -
+    ``Training``, ``quality_nmr``, ``valid_rank``, ``intensity``, ``quality_fr``."""
     import argparse
     import yaml
     ap = argparse.ArgumentParser(prog="python -m nomad_amd.train")
@@ -330,9 +661,19 @@ def main(argv=None):
     args = ap.parse_args(argv)
     with open(args.config_file) as file:
         config = yaml.load(file, Loader=yaml.FullLoader)
-    if config["experiment_name"] != "Training":
-        raise SystemExit(f"experiment_name {config['experiment_name']!r}: only 'Training' is implemented here")
-    Training(args.config_file, device=args.device).training_loop()
+    name = config["experiment_name"]
+    if name != "Training" and name not in EVAL_EXPERIMENTS:
+        raise SystemExit(f"experiment_name {name!r}: expected one of {('Training',) + EVAL_EXPERIMENTS}")
+    train_obj = Training(args.config_file, device=args.device)
+    if name == "Training":
+        return train_obj.training_loop()
+    if name == "quality_nmr":       # non-matching-reference audio quality
+        return train_obj.eval_audio_quality(config["nomad_model_path"])
+    if name == "valid_rank":        # ranking of the validation set's conditions
+        return train_obj.eval_degr_level(config["nomad_model_path"])
+    if name == "intensity":         # ranking of degradation intensities
+        return train_obj.eval_degradation_intensity(config["nomad_model_path"])
+    return train_obj.eval_full_reference(config["nomad_model_path"])   # quality_fr: full-reference audio quality
 
 
 if __name__ == "__main__":
