@@ -251,6 +251,67 @@ int nomad_embed_backward(nomad_ctx* ctx, const float* wav_dev, int B, int n_samp
                          const void* saved_dev, size_t saved_bytes, const float* dlayers_dev, const float* demb_dev,
                          float* dwav_dev, void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
 
+/* ---- exact-length (ragged) batches on the gradient paths ------------------------------------------------
+ * The calls above over clips of DIFFERENT lengths, with no padding in the arithmetic - the layout of nomad_embed_ragged:
+ * wav_dev / dwav_dev are [B][stride], clip b in the first lengths_host[b] samples of its row (the rest is never read);
+ * every per-frame tensor is packed, M = sum_c T_c rows (T_c = nomad_num_frames(lengths_host[c])): layers_dev / dlayers_dev
+ * are [12][M][768], emb / demb [B][256].  Sizes are functions of (B, lengths_host) and the context's switches only; the
+ * forward's workspace is nomad_workspace_bytes_ragged.
+ *
+ *   nomad_embed_train_ragged     saved_dev == NULL (with saved_bytes == 0): the 12 layer outputs and the embedding, nothing kept,
+ *                                no regularisation (the no-gradient branch of the loss; LossNetLayers over a ragged batch).
+ *                                Else also fills saved_dev (nomad_saved_bytes_ragged) for the backward.
+ *   nomad_embed_backward_ragged  dlayers_dev (nullable), demb_dev -> dwav_dev [B][stride]; the samples of a row behind its clip's
+ *                                length are written as zero.  feature_grad_mult as in nomad_embed_backward.
+ *   nomad_train_backward_ragged  accumulates into the context's gradient vector like nomad_train_backward.
+ *   nomad_l1_loss_ragged / nomad_l1_loss_backward_ragged   (M, B) in place of (B, T): each layer term is the mean over the
+ *                                M * 768 valid elements, the embedding term the mean over B * 256 - F.l1_loss on the
+ *                                concatenation of the clips' valid frames.  With M = B * T the bits of the equal-length calls.
+ *
+ * Contract:
+ *   - A clip's forward values (embedding, its rows of layers_dev, its saved activations) and its row of dwav_dev do not depend
+ *     on the batch it is in: the ragged entry points NEVER split K, in fine-tuning mode or outside it (the equal-length loss
+ *     path outside fine-tuning mode does, see nomad_enable_backward).  After nomad_train_enable they are the bits of the clip's
+ *     own nomad_embed_train / nomad_embed_backward call at B = 1, and the embedding the bits of nomad_embed_ragged; an
+ *     equal-length batch handed to the ragged entry points gives the bits of the equal-length entry points, the gradient
+ *     vector included (same rows, same summation order).
+ *   - nomad_train_set_stochastic / nomad_train_set_branches work as for equal lengths.  Mask element indices are those of the
+ *     packed tensors: activation sites index [M][768] (dropout_input: row m of the packed post_extract_proj output),
+ *     attention probabilities index clip c's [12][T_c][T_c] block at offset 12 * sum_{j<c} T_j^2 (64-bit) - an equal-length
+ *     batch draws exactly the masks of the equal-length entry points.  Branches are equal groups of CLIPS (B % branches == 0),
+ *     of any lengths.
+ *   - Not supported, refused with NOMAD_ERR_INVALID: a trainable conv feature extractor (nomad_train_set_convnet(1); its dW
+ *     operands are laid out per clip in equal column blocks) together with a ragged call.  nomad_train_set_frozen and
+ *     nomad_set_gemm_precision(ctx, 1) work.
+ *   - Asynchronous; no allocation; the only host-to-device traffic is the metadata copy (a few ints per clip) queued on the
+ *     stream ahead of the kernels.  Argument errors return their status before anything is queued.
+ */
+/* The per-clip metadata every ragged entry point derives from lengths_host and copies ahead of its kernels (pure host arithmetic, no
+ * context): *count ints - [lengths (B) | then arrays of B + 1 prefix sums: frames per conv level 0..6 | padded pos-conv frames
+ * (T_c + 128) | bf16x3 pos-conv blocks | output pairs of conv1..4 (ceil(L_i / 2)) | padded dU rows per level 0..6 (L_i + 2) |
+ * even frames of levels 0..3 (ceil(L_i / 2)) | odd frames of levels 0..3 (floor(L_i / 2))].  out_host == NULL: the count only. */
+int nomad_ragged_metadata(int B, const int* lengths_host, int* out_host, size_t capacity, size_t* count);
+int nomad_saved_bytes_ragged(const nomad_ctx* ctx, int B, const int* lengths_host, size_t* bytes);
+int nomad_backward_workspace_bytes_ragged(const nomad_ctx* ctx, int B, const int* lengths_host, size_t* bytes);
+int nomad_train_workspace_bytes_ragged(const nomad_ctx* ctx, int B, const int* lengths_host, size_t* bytes);
+int nomad_embed_train_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host,
+                             const float* head_w_dev, const float* head_b_dev, float* emb_dev, float* layers_dev,
+                             void* saved_dev, size_t saved_bytes, void* workspace_dev, size_t workspace_bytes,
+                             nomad_stream_t stream);
+int nomad_embed_backward_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host,
+                                const float* head_w_dev, const float* head_b_dev, const float* layers_dev,
+                                const void* saved_dev, size_t saved_bytes, const float* dlayers_dev, const float* demb_dev,
+                                float* dwav_dev, void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
+int nomad_train_backward_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host,
+                                const float* layers_dev, const void* saved_dev, size_t saved_bytes, const float* demb_dev,
+                                void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
+int nomad_l1_loss_ragged(nomad_ctx* ctx, const float* a_layers_dev, const float* b_layers_dev, const float* a_emb_dev,
+                         const float* b_emb_dev, long long M, int B, float* loss_dev, void* scratch_dev,
+                         nomad_stream_t stream);
+int nomad_l1_loss_backward_ragged(nomad_ctx* ctx, const float* a_layers_dev, const float* b_layers_dev,
+                                  const float* a_emb_dev, const float* b_emb_dev, long long M, int B,
+                                  const float* upstream_dev, float* dlayers_dev, float* demb_dev, nomad_stream_t stream);
+
 /* ---- triplet fine-tuning step (src/training/train_triplet.py:112-133, src/config/train_triplet.yaml) ---- */
 /*
  * The reference fine-tunes wav2vec 2.0 + head with A/P/N forwards, nn.TripletMarginLoss(margin),

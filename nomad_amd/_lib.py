@@ -69,6 +69,18 @@ SIGNATURES = {
     "nomad_l1_loss_backward": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
     "nomad_embed_backward": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp,
                                        _fp, _fp, C.c_size_t, _fp]),
+    "nomad_ragged_metadata": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "nomad_saved_bytes_ragged": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "nomad_backward_workspace_bytes_ragged": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "nomad_train_workspace_bytes_ragged": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "nomad_embed_train_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp, _fp, _fp, _fp,
+                                           C.c_size_t, _fp, C.c_size_t, _fp]),
+    "nomad_embed_backward_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp, _fp, _fp,
+                                              C.c_size_t, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_train_backward_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp, C.c_size_t, _fp,
+                                              _fp, C.c_size_t, _fp]),
+    "nomad_l1_loss_ragged": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp, _fp, _fp]),
+    "nomad_l1_loss_backward_ragged": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp, _fp, _fp, _fp]),
     "nomad_train_param_count": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "nomad_train_num_segments": (C.c_int, []),
     "nomad_train_segment": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

@@ -95,6 +95,28 @@ __device__ __forceinline__ void attn_tile(const float* __restrict__ Ks, const fl
         }
 }
 
+// Attention-dropout mask offset of clip b of a ragged batch: its [12][T_b][T_b] block sits behind those of the clips in front,
+// 12 * sum_{j < b} T_j^2 (64-bit) - what (b * 12) * T * T is for an equal-length batch.
+__device__ __forceinline__ unsigned long long attn_mask_base(const int* __restrict__ tpref, int b) {
+    unsigned long long s = 0;
+    for (int j = 0; j < b; ++j) {
+        const unsigned long long t = (unsigned long long)(tpref[j + 1] - tpref[j]);
+        s += t * t;
+    }
+    return 12ull * s;
+}
+
+// clip of packed row m in a ragged batch: the largest c with pref[c] <= m (the search of the GEMM's row maps)
+__device__ __forceinline__ int clip_of_row(const int* __restrict__ pref, int nclips, int m) {
+    int lo = 0, hi = nclips;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pref[mid] <= m) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // This is the kernel for SHORT clips (fewer than kAttnV2MinT frames: config C4's T = 50, short files of a ragged batch)
 // and for the training forward with attention dropout; longer clips take attention_f32_v2_kernel (attention_f32_v2.hip.h).
 // Which kernel a clip gets depends on ITS frame count only, never on the batch it is in.
@@ -112,11 +134,16 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const T_* __restrict
     __shared__ __attribute__((aligned(16))) float Vs[64 * kAttnLD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qi = lane & 15, g = lane >> 4;
-    const int bh = blockIdx.y, b = bh / 12, h = bh - b * 12;
+    const int bh = blockIdx.y;
+    int b = bh / 12;
+    const int h = bh - b * 12;
     long long row0 = (long long)b * T;
+    unsigned long long mask0 = (unsigned long long)(bh0 + bh) * T * T;   // first element of this (clip, head)'s [T][T] mask block
     if (tpref) {
+        b += bh0 / 12;   // ragged batch: tpref is the whole batch's, bh0 the first (clip, head) of this launch
         row0 = tpref[b];
         T = tpref[b + 1] - tpref[b];
+        if (DROP) mask0 = attn_mask_base(tpref, b) + (unsigned long long)h * T * T;
         if ((int)blockIdx.x * 64 >= T) return;  // whole workgroup: no barrier has been reached yet
         if (t_below && T >= t_below) return;     // ragged batch: clips of t_below frames or more belong to attention_f32_v2_kernel
     }
@@ -167,7 +194,7 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const T_* __restrict
         if (kt + 1 < ntiles) fetch(kt + 1);
         if (!wave_active) continue;
         const int valid = T - kt * 64;  // valid keys in this tile (>= 1)
-        const unsigned long long drow = ((unsigned long long)(bh0 + bh) * T + q_ld) * T + kt * 64;
+        const unsigned long long drow = mask0 + (unsigned long long)q_ld * T + kt * 64;
         if (valid >= 64) attn_tile<4, DROP>(Ks, Vs, qf, o, m_run, l_run, qi, g, 64, &dc, site, drow);
         else if (valid > 48) attn_tile<4, DROP>(Ks, Vs, qf, o, m_run, l_run, qi, g, valid, &dc, site, drow);
         else if (valid > 32) attn_tile<3, DROP>(Ks, Vs, qf, o, m_run, l_run, qi, g, valid, &dc, site, drow);
@@ -178,7 +205,7 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const T_* __restrict
     float l_tot = l_run + __shfl_xor(l_run, 16);
     l_tot += __shfl_xor(l_tot, 32);
     const float inv = 1.0f / l_tot;
-    if (lse && q_row < T && g == 0) lse[(long long)bh * T + q_row] = m_run + logf(l_tot);
+    if (lse && q_row < T && g == 0) lse[12 * row0 + (long long)h * T + q_row] = m_run + logf(l_tot);   // ragged: [12][T_c] per clip, packed
     if (q_row < T) {
         TO_* dst = out + (row0 + q_row) * 768 + h * 64 + g * 4;
 #pragma unroll

@@ -15,6 +15,12 @@
 //       dQ^T[d][q] += sum_key K[key][d] dS^T[key][q]        A = K from LDS, B = the dS^T accumulator itself
 //
 // qkv / dqkv: [B*T][2304] = [q (pre-scaled by 1/8) | k | v]; dO: [B*T][768]; lse, D: [B*12][T].
+// Ragged batches (tpref: the WHOLE batch's frame prefix sums; a launch covers the clips from (clip, head) bh0 on): rows are packed,
+// lse / D hold clip c's [12][T_c] block at 12 * tpref[c], the attention-dropout mask of clip c its [12][T_c][T_c] block at
+// attn_mask_base(tpref, c).  Every pointer is then the whole batch's.  Which form a clip takes - the fused kernel (T_c <= 64, no
+// dropout) or the three kernels - is decided by the CLIP's length, never the batch's, so that a clip runs the same kernel and comes
+// out with the same bits in every batch (the rule run_attention states for the forward): a mixed batch launches both, each kernel
+// leaves the other's clips alone (t_skip / t_min).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,10 +32,24 @@ namespace nomad {
 
 // grid: ceil(M/4) blocks of 256 threads, one wave per row m = b*T + t; 16 lanes per head.
 __global__ __launch_bounds__(256) void attn_bwd_rowdot_kernel(const float* __restrict__ o, const float* __restrict__ dO,
-                                                              float* __restrict__ D, int M, int T) {
-    const int lane = threadIdx.x & 63, m = blockIdx.x * 4 + (threadIdx.x >> 6);
+                                                              float* __restrict__ D, int M, int T,
+                                                              const int* __restrict__ tpref = nullptr, int nclips = 0,
+                                                              int m0 = 0, int t_min = 0) {
+    const int lane = threadIdx.x & 63, m = m0 + blockIdx.x * 4 + (threadIdx.x >> 6);   // (ragged: rows m0 .. M - 1 of the batch)
     if (m >= M) return;
-    const int b = m / T, t = m - b * T;
+    int b, t;
+    long long d0;   // D of (clip b, head 0, frame 0)
+    if (tpref) {
+        b = clip_of_row(tpref, nclips, m);
+        t = m - tpref[b];
+        T = tpref[b + 1] - tpref[b];
+        if (T < t_min) return;   // the fused kernel's clip
+        d0 = 12LL * tpref[b];
+    } else {
+        b = m / T;
+        t = m - b * T;
+        d0 = (long long)b * 12 * T;
+    }
     const float4* op = reinterpret_cast<const float4*>(o + (long long)m * 768);
     const float4* gp = reinterpret_cast<const float4*>(dO + (long long)m * 768);
 #pragma unroll
@@ -40,7 +60,7 @@ __global__ __launch_bounds__(256) void attn_bwd_rowdot_kernel(const float* __res
         s += __shfl_xor(s, 2);
         s += __shfl_xor(s, 4);
         s += __shfl_xor(s, 8);
-        if ((lane & 15) == 0) D[((long long)b * 12 + (lane >> 4) + 4 * i) * T + t] = s;
+        if ((lane & 15) == 0) D[d0 + (long long)((lane >> 4) + 4 * i) * T + t] = s;
     }
 }
 
@@ -66,19 +86,31 @@ __device__ __forceinline__ void abw_store(float* __restrict__ dst, const f32x4 (
 template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dO,
                                                            const float* __restrict__ lse, const float* __restrict__ D,
-                                                           float* __restrict__ dqkv, int T, DropCfg dc, uint32_t site, int bh0) {
+                                                           float* __restrict__ dqkv, int T, DropCfg dc, uint32_t site, int bh0,
+                                                           const int* __restrict__ tpref = nullptr, int t_min = 0) {
     __shared__ __attribute__((aligned(16))) float Qs[64 * kAttnLD];
     __shared__ __attribute__((aligned(16))) float Gs[64 * kAttnLD];  // dO tile
     __shared__ __attribute__((aligned(16))) float lse_s[64];
     __shared__ __attribute__((aligned(16))) float D_s[64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fi = lane & 15, g = lane >> 4;
-    const int bh = blockIdx.y, b = bh / 12, h = bh - b * 12;
+    const int bh = blockIdx.y;
+    int b = bh / 12;
+    const int h = bh - b * 12;
     const int k0 = blockIdx.x * 64;
-    const float* qb = qkv + (long long)b * T * 2304 + h * 64;
-    const float* gb = dO + (long long)b * T * 768 + h * 64;
-    const float* lb = lse + (long long)bh * T;
-    const float* Db = D + (long long)bh * T;
+    long long row0 = (long long)b * T;
+    unsigned long long mask0 = (unsigned long long)(bh0 + bh) * T * T;   // this (clip, head)'s [T][T] block of the dropout mask
+    if (tpref) {
+        b += bh0 / 12;
+        row0 = tpref[b];
+        T = tpref[b + 1] - tpref[b];
+        if (k0 >= T || T < t_min) return;   // whole workgroup, before any barrier
+        if (DROP) mask0 = attn_mask_base(tpref, b) + (unsigned long long)h * T * T;
+    }
+    const float* qb = qkv + row0 * 2304 + h * 64;
+    const float* gb = dO + row0 * 768 + h * 64;
+    const float* lb = lse + 12 * row0 + (long long)h * T;
+    const float* Db = D + 12 * row0 + (long long)h * T;
     const int key = k0 + wave * 16 + fi;
     const int key_ld = key < T ? key : T - 1;
     const bool wave_active = k0 + wave * 16 < T;  // wave-uniform
@@ -144,7 +176,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const float* __restri
                 const int q = q0 + sub * 16 + g * 4 + r;
                 const bool ok = q < T && key < T;
                 const float p = ok ? fast_exp(s[r] - lv[r]) : 0.f;
-                const float mk = (DROP && ok) ? drop_mult(dc, site, ((unsigned long long)(bh0 + bh) * T + q) * T + key) : 1.0f;
+                const float mk = (DROP && ok) ? drop_mult(dc, site, mask0 + (unsigned long long)q * T + key) : 1.0f;
                 pm[r] = p * mk;
                 ds[r] = p * (dp[r] * mk - Dv[r]);
             }
@@ -166,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const float* __restri
     for (int r = 0; r < 4; ++r) {
         const int kk = k0 + wave * 16 + g * 4 + r;
         if (kk < T) {
-            float* dst = dqkv + ((long long)b * T + kk) * 2304 + h * 64 + fi;
+            float* dst = dqkv + (row0 + kk) * 2304 + h * 64 + fi;
 #pragma unroll
             for (int di = 0; di < 4; ++di) {
                 dst[768 + di * 16] = dk[di][r];
@@ -179,14 +211,26 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const float* __restri
 template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ dO,
                                                           const float* __restrict__ lse, const float* __restrict__ D,
-                                                          float* __restrict__ dqkv, int T, DropCfg dc, uint32_t site, int bh0) {
+                                                          float* __restrict__ dqkv, int T, DropCfg dc, uint32_t site, int bh0,
+                                                          const int* __restrict__ tpref = nullptr, int t_min = 0) {
     __shared__ __attribute__((aligned(16))) float Ks[64 * kAttnLD];
     __shared__ __attribute__((aligned(16))) float Vs[64 * kAttnLD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fi = lane & 15, g = lane >> 4;
-    const int bh = blockIdx.y, b = bh / 12, h = bh - b * 12;
-    const float* qb = qkv + (long long)b * T * 2304 + h * 64;
-    const float* gb = dO + (long long)b * T * 768 + h * 64;
+    const int bh = blockIdx.y;
+    int b = bh / 12;
+    const int h = bh - b * 12;
+    long long row0 = (long long)b * T;
+    unsigned long long mask0 = (unsigned long long)(bh0 + bh) * T * T;
+    if (tpref) {
+        b += bh0 / 12;
+        row0 = tpref[b];
+        T = tpref[b + 1] - tpref[b];
+        if ((int)blockIdx.x * 64 >= T || T < t_min) return;   // whole workgroup, before any barrier
+        if (DROP) mask0 = attn_mask_base(tpref, b) + (unsigned long long)h * T * T;
+    }
+    const float* qb = qkv + row0 * 2304 + h * 64;
+    const float* gb = dO + row0 * 768 + h * 64;
     const int q = blockIdx.x * 64 + wave * 16 + fi;
     const int q_ld = q < T ? q : T - 1;
     const bool wave_active = blockIdx.x * 64 + wave * 16 < T;
@@ -197,7 +241,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float* __restric
         qf[dd] = *reinterpret_cast<const f32x4*>(qb + (long long)q_ld * 2304 + dd * 16 + g * 4);
         gf[dd] = *reinterpret_cast<const f32x4*>(gb + (long long)q_ld * 768 + dd * 16 + g * 4);
     }
-    const float lse_q = lse[(long long)bh * T + q_ld], D_q = D[(long long)bh * T + q_ld];
+    const float lse_q = lse[12 * row0 + (long long)h * T + q_ld], D_q = D[12 * row0 + (long long)h * T + q_ld];
     f32x4 dq[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) dq[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -240,7 +284,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float* __restric
                 const int key = k0 + sub * 16 + g * 4 + r;
                 const bool ok = q < T && key < T;
                 const float p = ok ? fast_exp(s[r] - lse_q) : 0.f;
-                const float mk = (DROP && ok) ? drop_mult(dc, site, ((unsigned long long)(bh0 + bh) * T + q) * T + key) : 1.0f;
+                const float mk = (DROP && ok) ? drop_mult(dc, site, mask0 + (unsigned long long)q * T + key) : 1.0f;
                 ds[r] = p * (dp[r] * mk - D_q);
             }
 #pragma unroll
@@ -253,7 +297,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float* __restric
         }
     }
     if (q < T) {  // dQ^T accumulators: row d = 16*di + 4g + r, column = this lane's query
-        float* dst = dqkv + ((long long)b * T + q) * 2304 + h * 64 + g * 4;
+        float* dst = dqkv + (row0 + q) * 2304 + h * 64 + g * 4;
 #pragma unroll
         for (int di = 0; di < 4; ++di) {
             *reinterpret_cast<f32x4*>(dst + di * 16) = dq[di];
@@ -271,7 +315,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float* __restric
 constexpr int kAttnBwdSmallLds = (4 * 64 * kAttnLD + 128) * 4;
 __global__ __launch_bounds__(256) void attn_bwd_small_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                              const float* __restrict__ dO, const float* __restrict__ lse,
-                                                             float* __restrict__ D, float* __restrict__ dqkv, int T) {
+                                                             float* __restrict__ D, float* __restrict__ dqkv, int T,
+                                                             const int* __restrict__ tpref = nullptr, int bh0 = 0) {
     extern __shared__ __attribute__((aligned(16))) float abw_smem[];   // kAttnBwdSmallLds bytes (four 64 x 68 tiles: over the 64 KB static limit)
     float* const Qs = abw_smem;
     float* const Gs = Qs + 64 * kAttnLD;  // dO
@@ -281,10 +326,20 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(const float* __rest
     float* const D_s = lse_s + 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fi = lane & 15, g = lane >> 4;
-    const int bh = blockIdx.x, b = bh / 12, h = bh - b * 12;
-    const float* qb = qkv + (long long)b * T * 2304 + h * 64;
-    const float* gb = dO + (long long)b * T * 768 + h * 64;
-    const float* ob = o + (long long)b * T * 768 + h * 64;
+    const int bh = blockIdx.x;
+    int b = bh / 12;
+    const int h = bh - b * 12;
+    long long row0 = (long long)b * T;
+    if (tpref) {   // ragged batch: clips of more than 64 frames belong to the three kernels
+        b += bh0 / 12;
+        row0 = tpref[b];
+        T = tpref[b + 1] - tpref[b];
+        if (T > 64) return;   // whole workgroup, before any barrier
+    }
+    const long long ld0 = 12 * row0 + (long long)h * T;   // this (clip, head)'s row of lse / D
+    const float* qb = qkv + row0 * 2304 + h * 64;
+    const float* gb = dO + row0 * 768 + h * 64;
+    const float* ob = o + row0 * 768 + h * 64;
     {
         f32x4 r0[4], r1[4], r2[4], r3[4];
         abw_fetch(r0, qb, 2304, 0, T, tid);
@@ -305,10 +360,10 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(const float* __rest
             sdot += __shfl_xor(sdot, 8);
             if (j == 0) {
                 D_s[q] = q < T ? sdot : 0.f;
-                if (q < T) D[(long long)bh * T + q] = sdot;
+                if (q < T) D[ld0 + q] = sdot;
             }
         }
-        if (tid < 64) lse_s[tid] = tid < T ? lse[(long long)bh * T + tid] : 0.f;
+        if (tid < 64) lse_s[tid] = tid < T ? lse[ld0 + tid] : 0.f;
         abw_store(Qs, r0, tid);
         abw_store(Gs, r1, tid);
         abw_store(Ks, r2, tid);
@@ -368,7 +423,7 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(const float* __rest
         for (int r = 0; r < 4; ++r) {
             const int kk = wave * 16 + g * 4 + r;
             if (kk < T) {
-                float* dst = dqkv + ((long long)b * T + kk) * 2304 + h * 64 + fi;
+                float* dst = dqkv + (row0 + kk) * 2304 + h * 64 + fi;
 #pragma unroll
                 for (int di = 0; di < 4; ++di) {
                     dst[768 + di * 16] = dk[di][r];
@@ -420,7 +475,7 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(const float* __rest
             }
         }
         if (q < T) {
-            float* dst = dqkv + ((long long)b * T + q) * 2304 + h * 64 + g * 4;
+            float* dst = dqkv + (row0 + q) * 2304 + h * 64 + g * 4;
 #pragma unroll
             for (int di = 0; di < 4; ++di) *reinterpret_cast<f32x4*>(dst + di * 16) = dq[di];
         }
@@ -436,17 +491,44 @@ inline hipError_t launch_attention_bwd(const float* qkv, const float* o, const f
     if (T <= 64 && !dc.threshold && !force_three) {   // by the clip's length only: one fused launch (bit-identical to the three below)
         static LdsAttrOnce attr_set;
         if (hipError_t e = attr_set.ensure(reinterpret_cast<const void*>(attn_bwd_small_kernel), kAttnBwdSmallLds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(attn_bwd_small_kernel, dim3(B * 12), dim3(256), kAttnBwdSmallLds, s, qkv, o, dO, lse, D, dqkv, T);
+        hipLaunchKernelGGL(attn_bwd_small_kernel, dim3(B * 12), dim3(256), kAttnBwdSmallLds, s, qkv, o, dO, lse, D, dqkv, T, static_cast<const int*>(nullptr), 0);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(attn_bwd_rowdot_kernel, dim3((M + 3) / 4), dim3(256), 0, s, o, dO, D, M, T);
+    hipLaunchKernelGGL(attn_bwd_rowdot_kernel, dim3((M + 3) / 4), dim3(256), 0, s, o, dO, D, M, T, static_cast<const int*>(nullptr), 0, 0, 0);
     const dim3 grid((T + 63) / 64, B * 12);
     if (dc.threshold) {
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, T, dc, site, bh0);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, T, dc, site, bh0);
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, T, dc, site, bh0, static_cast<const int*>(nullptr), 0);
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, T, dc, site, bh0, static_cast<const int*>(nullptr), 0);
     } else {
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, T, dc, site, bh0);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, T, dc, site, bh0);
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, T, dc, site, bh0, static_cast<const int*>(nullptr), 0);
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, T, dc, site, bh0, static_cast<const int*>(nullptr), 0);
+    }
+    return hipGetLastError();
+}
+
+// The same over clips [c0, c0 + nc) of a ragged batch of `nclips` clips (every pointer and tpref: the whole batch's; rows
+// [m0, m1) are those clips' frames; max_t / min_t: the batch's longest / shortest clip).
+inline hipError_t launch_attention_bwd_ragged(const float* qkv, const float* o, const float* dO, const float* lse, float* D,
+                                              float* dqkv, const int* tpref, int nclips, int c0, int nc, int m0, int m1, int max_t,
+                                              int min_t, const DropCfg& dc, uint32_t site, hipStream_t s, bool force_three = false) {
+    const bool fused = !dc.threshold && !force_three;   // clips of at most 64 frames take the fused kernel
+    const int bh0 = c0 * 12;
+    if (fused && min_t <= 64) {
+        static LdsAttrOnce attr_set;
+        if (hipError_t e = attr_set.ensure(reinterpret_cast<const void*>(attn_bwd_small_kernel), kAttnBwdSmallLds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(attn_bwd_small_kernel, dim3(nc * 12), dim3(256), kAttnBwdSmallLds, s, qkv, o, dO, lse, D, dqkv, 0, tpref, bh0);
+    }
+    if (!fused || max_t > 64) {
+        const int t_min = fused ? 65 : 0;
+        hipLaunchKernelGGL(attn_bwd_rowdot_kernel, dim3((m1 - m0 + 3) / 4), dim3(256), 0, s, o, dO, D, m1, 0, tpref, nclips, m0, t_min);
+        const dim3 grid((max_t + 63) / 64, nc * 12);
+        if (dc.threshold) {
+            hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, 0, dc, site, bh0, tpref, t_min);
+            hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, 0, dc, site, bh0, tpref, t_min);
+        } else {
+            hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, 0, dc, site, bh0, tpref, t_min);
+            hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, dim3(256), 0, s, qkv, dO, lse, D, dqkv, 0, dc, site, bh0, tpref, t_min);
+        }
     }
     return hipGetLastError();
 }

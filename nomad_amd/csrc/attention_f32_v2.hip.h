@@ -38,7 +38,8 @@ constexpr int attn_f32_v2_lds() { return 2 * kF2Buf; }
 // (k-step (j, e) contracts d = 16 j + e + {0, 4, 8, 12}), V^T as chunks of keys 16 sk + 4 g .. + 3: eight ds_read_b128 per operand and
 // 32-key tile as before, 64 + 64 MFMAs of half the length (+ 4 for the reference maximum until round 5).  The clip's last, partial key tile skips its second 16-key half
 // entirely (scores and P.V) when it is empty.
-// lse (nullable): [B*12][T] natural-log log-sum-exp of every score row (the backward recomputes P from it).
+// lse (nullable): [B*12][T] natural-log log-sum-exp of every score row (the backward recomputes P from it); a ragged batch:
+// clip c's [12][T_c] block at 12 * tpref[c].
 // grid: 1-D, ceil(T / 128) * B * 12 workgroups of 256 threads; dynamic LDS attn_f32_v2_lds().
 // tpref (nullable): ragged batches - clip b owns rows tpref[b] .. tpref[b+1]-1; T is then the longest clip's.
 __device__ __forceinline__ float f2_max4(float x) {   // maximum over the four lanes fi, fi + 16, fi + 32, fi + 48, in all of them
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(256, 3) void attention_f32_v2_kernel(const float* _
         const int q_row = q_base + 16 * sq + fi;
         if (q_row < T) {
             if (lse && g == 0)  // natural-log units; the two terms are large and nearly cancel in fp32: one float64 expression per query
-                lse[(long long)bh * T + q_row] = (float)(((double)m_ref[sq] + log2((double)l_tot)) * 0.69314718055994531);
+                lse[12 * row0 + (long long)hd * T + q_row] = (float)(((double)m_ref[sq] + log2((double)l_tot)) * 0.69314718055994531);
             float* dst = out + (row0 + q_row) * 768 + hd * 64 + 4 * g;
 #pragma unroll
             for (int sd = 0; sd < 4; ++sd)

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "attention.hip.h"
 #include "dropout.hip.h"
 #include "gemm_f32.hip.h"
 #include "rowops.hip.h"
@@ -161,17 +162,42 @@ __global__ __launch_bounds__(256) void zero_rows512_kernel(float* __restrict__ b
     for (int i = threadIdx.x; i < (b1 - b0) * 128; i += 256) reinterpret_cast<float4*>(p + (long long)b0 * 512)[i] = z;
 }
 
+// The same for a ragged batch: clip c's block starts at row ubase[c] of the buffer and holds Lin_c + 2 rows (Lin_c from pin);
+// the GEMMs cover 2 * Lout_c frames (k2, Lout_c from pout) or all Lin_c.  grid: B blocks of 256.
+__global__ __launch_bounds__(256) void zero_rows512_ragged_kernel(float* __restrict__ base, const int* __restrict__ ubase,
+                                                                  const int* __restrict__ pin, const int* __restrict__ pout, int k2) {
+    const int c = blockIdx.x, Lin = pin[c + 1] - pin[c], Lout = pout[c + 1] - pout[c];
+    const int b0 = (k2 ? 2 * Lout : Lin) + 1, b1 = Lin + 2;
+    float* p = base + (long long)ubase[c] * 512;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = threadIdx.x; i < 128; i += 256) reinterpret_cast<float4*>(p)[i] = z;
+    for (int i = threadIdx.x; i < (b1 - b0) * 128; i += 256) reinterpret_cast<float4*>(p + (long long)b0 * 512)[i] = z;
+}
+
 // Pos-conv: dug[grp][clip][64 + t][48] = dy0[m][grp*48 + c] * gelu'(upc[m][grp*48 + c])   (group-major, padded)
 // grid: M blocks of 192 threads (one float4 each).
 __global__ __launch_bounds__(192) void dgelu_to_groups_kernel(const float* __restrict__ g, const float* __restrict__ u,
-                                                              float* __restrict__ dug, int T, long long grp_stride) {
-    const int m = blockIdx.x, b = m / T, t = m - b * T;
+                                                              float* __restrict__ dug, int T, long long grp_stride,
+                                                              const int* __restrict__ tpref = nullptr,
+                                                              const int* __restrict__ ppref = nullptr, int B = 0) {
+    const int m = blockIdx.x;
+    int b, t;
+    long long frame0;   // the clip's first frame in a group of the padded buffer
+    if (tpref) {        // ragged batch: packed rows, padded-frame prefix sums
+        b = clip_of_row(tpref, B, m);
+        t = m - tpref[b];
+        frame0 = ppref[b];
+    } else {
+        b = m / T;
+        t = m - b * T;
+        frame0 = (long long)b * (T + 128);
+    }
     const float4 a = reinterpret_cast<const float4*>(g + (long long)m * 768)[threadIdx.x];
     const float4 c = reinterpret_cast<const float4*>(u + (long long)m * 768)[threadIdx.x];
     float4 r;
     r.x = a.x * dgelu_erf(c.x); r.y = a.y * dgelu_erf(c.y); r.z = a.z * dgelu_erf(c.z); r.w = a.w * dgelu_erf(c.w);
     const int col = threadIdx.x * 4, grp = col / 48, cc = col - grp * 48;
-    float* dst = dug + grp * grp_stride + ((long long)b * (T + 128) + 64 + t) * 48 + cc;
+    float* dst = dug + grp * grp_stride + (frame0 + 64 + t) * 48 + cc;
     *reinterpret_cast<float4*>(dst) = r;
 }
 
@@ -184,11 +210,17 @@ __global__ __launch_bounds__(192) void dgelu_to_groups_kernel(const float* __res
 __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict__ x, int T, const float* __restrict__ w,
                                                         const float* __restrict__ bias, const float* __restrict__ de,
                                                         float* __restrict__ gx, float* __restrict__ pooled_out = nullptr,
-                                                        float* __restrict__ dz_out = nullptr) {
+                                                        float* __restrict__ dz_out = nullptr,
+                                                        const int* __restrict__ tpref = nullptr) {
     __shared__ float mask[768], z[256], dz[256], red[4], red2[4];
     __shared__ __attribute__((aligned(16))) float pooled[768], psum[4][768];   // (both are read as float4)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* xb = x + (long long)b * T * 768;
+    long long row0 = (long long)b * T;
+    if (tpref) {      // ragged batch: this clip's own frame range
+        row0 = tpref[b];
+        T = tpref[b + 1] - tpref[b];
+    }
+    const float* xb = x + row0 * 768;
     if (wave < 4) {   // time sum: wave w takes frames w, w+4, ... (16-byte loads), the four partial sums are combined in fixed order
         float4 acc[3];
 #pragma unroll
@@ -283,7 +315,7 @@ __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict_
     float4 gv[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) gv[i] = reinterpret_cast<const float4*>(pooled)[lane + 64 * i];
-    float* gb = gx + (long long)b * T * 768;
+    float* gb = gx + row0 * 768;
     for (int t = wave; t < T; t += 16) {
         float4* r = reinterpret_cast<float4*>(gb + (long long)t * 768);
 #pragma unroll
@@ -341,9 +373,17 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const float* __restri
                                                            const float* __restrict__ w0, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, const float* __restrict__ gmean,
                                                            const float* __restrict__ grstd, const float* __restrict__ G,
-                                                           float* __restrict__ partial) {
+                                                           float* __restrict__ partial,
+                                                           const int* __restrict__ pref0 = nullptr) {
     __shared__ float xs[kGnStatsChunk * 5 + 8];
-    const int b = blockIdx.y, t0 = blockIdx.x * kGnStatsChunk, nfr = min(kGnStatsChunk, L0 - t0), tid = threadIdx.x;
+    const int b = blockIdx.y, t0 = blockIdx.x * kGnStatsChunk, tid = threadIdx.x;
+    long long g0 = (long long)b * L0;   // the clip's first row of G
+    if (pref0) {   // ragged batch (n_samples: the row stride): the grid covers the longest clip's chunks
+        g0 = pref0[b];
+        L0 = pref0[b + 1] - pref0[b];
+        if (t0 >= L0) return;   // whole workgroup, before the barrier
+    }
+    const int nfr = min(kGnStatsChunk, L0 - t0);
     const float* x = wav + (long long)b * n_samples + 5 * t0;
     for (int i = tid; i < 5 * nfr + 5; i += 256) xs[i] = x[i];
     float w[2][10], sc[2], sh[2], mean[2], rstd[2];
@@ -357,7 +397,7 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const float* __restri
     }
     __syncthreads();
     float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-    const float* g = G + ((long long)b * L0 + t0) * 512;
+    const float* g = G + (g0 + t0) * 512;
     for (int tb = 0; tb < nfr; tb += 4) {   // four frames' loads in flight; the sums keep the frame order
         float gv[4][2];
 #pragma unroll
@@ -392,11 +432,16 @@ __global__ __launch_bounds__(512) void gn_bwd_fold_kernel(const float* __restric
                                                           const float* __restrict__ w0, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, const float* __restrict__ gmean,
                                                           const float* __restrict__ grstd, float* __restrict__ fold,
-                                                          float* __restrict__ cwtab) {
+                                                          float* __restrict__ cwtab, const int* __restrict__ pref0 = nullptr) {
     const int b = blockIdx.x, c = threadIdx.x;
+    const int slots = nchunks;   // chunk slots per clip in `partial`
+    if (pref0) {   // ragged batch: this clip's own frames and chunks (the slots behind them were never written)
+        L0 = pref0[b + 1] - pref0[b];
+        nchunks = (L0 + kGnStatsChunk - 1) / kGnStatsChunk;
+    }
     float a1 = 0.f, a2 = 0.f;
     for (int k = 0; k < nchunks; ++k) {
-        const float* p = partial + ((long long)b * nchunks + k) * 1024;
+        const float* p = partial + ((long long)b * slots + k) * 1024;
         a1 += p[c];
         a2 += p[512 + c];
     }
@@ -422,16 +467,23 @@ __global__ __launch_bounds__(512) void gn_bwd_fold_kernel(const float* __restric
 constexpr int kC0Frames = 64;
 __global__ __launch_bounds__(256) void conv0_bwd_kernel(const float* __restrict__ wav, int n_samples, int L0,
                                                         const float* __restrict__ cwtab, const float* __restrict__ G,
-                                                        float* __restrict__ dwav) {
+                                                        float* __restrict__ dwav, const int* __restrict__ pref0 = nullptr) {
     __shared__ float xs[kC0Frames * 5 + 8];
     __shared__ float gt[kC0Frames][65];        // G chunk: [frame][channel of the chunk]
     __shared__ __attribute__((aligned(16))) float cw[64][16];   // per channel of the chunk: w[0..9], sc, sh, mean, rstd, m1, m2
     __shared__ float red[4][kC0Frames][10];
-    const int b = blockIdx.y, t0 = blockIdx.x * kC0Frames, nfr = min(kC0Frames, L0 - t0), tid = threadIdx.x;
+    const int b = blockIdx.y, t0 = blockIdx.x * kC0Frames, tid = threadIdx.x;
+    long long g0 = (long long)b * L0;
+    if (pref0) {   // ragged batch, as in gn_bwd_stats_kernel
+        g0 = pref0[b];
+        L0 = pref0[b + 1] - pref0[b];
+        if (t0 >= L0) return;
+    }
+    const int nfr = min(kC0Frames, L0 - t0);
     const int f = tid & 63, g = tid >> 6;
     const float* x = wav + (long long)b * n_samples + 5 * t0;
     for (int i = tid; i < 5 * nfr + 5; i += 256) xs[i] = x[i];
-    const float* gbase = G + ((long long)b * L0 + t0) * 512;
+    const float* gbase = G + (g0 + t0) * 512;
     const float4* ctab = reinterpret_cast<const float4*>(cwtab + (long long)b * 512 * 16);
     // staging map: G slice as float4 - thread -> (frame tid / 16 + 16 i, channels 4 (tid % 16) .. + 3); constants: float4 tid of the chunk
     float4 greg[4], creg;

@@ -267,7 +267,7 @@ struct nomad_ctx {
     std::vector<void*> allocs;
     // host copies of the last ragged batches' metadata (sources of asynchronous H2D copies); a ring, so that two
     // forwards enqueued back to back on different streams do not share a staging vector
-    std::vector<int> ragged_meta_ring[4];
+    std::vector<int> ragged_meta_ring[16];   // kMetaRing (nomad_hip.hip: ragged_upload)
     unsigned ragged_seq = 0;
     // profiling
     bool prof = false;

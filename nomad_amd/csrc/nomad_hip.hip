@@ -135,17 +135,27 @@ struct RaggedShapes {
     long long P = 0;          // total padded pos-conv frames, sum (T_c + 128)
     long long blocks = 0;     // total pos-conv frame blocks, sum ceil(T_c / kPosBlk) (bf16x3 path)
     long long pairs[5] = {};  // total output pairs of conv1 .. conv4 (Winograd form), sum ceil(L_i / 2)
-    std::vector<int> meta;    // [lens(B) | pref_0 (B+1) | ... | pref_6 (B+1) | ppref (B+1) | bpref (B+1) | pairpref_1 .. pairpref_4 (B+1)]
+    long long even[4] = {}, odd[4] = {};   // backward: total even / odd frames of conv levels 0 .. 3, sum ceil(L_i / 2) / sum floor(L_i / 2)
+    // [lens(B) | pref_0 (B+1) | ... | pref_6 (B+1) | ppref (B+1) | bpref (B+1) | pairpref_1 .. pairpref_4 (B+1) |
+    //  upref_0 .. upref_6 | epref_0 .. epref_3 | opref_0 .. opref_3 (B+1 each)]: the last three groups are the backward's -
+    //  upref_i[c] = pref_i[c] + 2 c, clip c's first row in a padded dU buffer of level i (every clip: L_i + 2 rows); epref_i /
+    //  opref_i: prefix sums of the even (ceil(L_i / 2)) and odd (floor(L_i / 2)) frames of level i, the rows of the two GEMMs of a
+    //  k = 3 / stride 2 transposed convolution
+    std::vector<int> meta;
     size_t off_lens() const { return 0; }
     size_t off_pref(int i) const { return (size_t)B + (size_t)i * (B + 1); }
     size_t off_ppref() const { return (size_t)B + (size_t)7 * (B + 1); }
     size_t off_bpref() const { return (size_t)B + (size_t)8 * (B + 1); }
     size_t off_pairpref(int i) const { return (size_t)B + (size_t)(8 + i) * (B + 1); }   // i = 1 .. 4
+    size_t off_upref(int i) const { return (size_t)B + (size_t)(13 + i) * (B + 1); }     // i = 0 .. 6
+    size_t off_epref(int i) const { return (size_t)B + (size_t)(20 + i) * (B + 1); }     // i = 0 .. 3
+    size_t off_opref(int i) const { return (size_t)B + (size_t)(24 + i) * (B + 1); }     // i = 0 .. 3
 };
 
 bool make_ragged(int B, const int* lens, RaggedShapes* r) {
+    *r = RaggedShapes{};   // (the totals below accumulate)
     r->B = B;
-    r->meta.assign((size_t)B + 13 * (size_t)(B + 1), 0);
+    r->meta.assign((size_t)B + 28 * (size_t)(B + 1), 0);
     for (int c = 0; c < B; ++c) {
         Shapes sh;
         if (!make_shapes(1, lens[c], &sh)) return false;
@@ -157,6 +167,13 @@ bool make_ragged(int B, const int* lens, RaggedShapes* r) {
         for (int i = 1; i <= 4; ++i) {
             r->meta[r->off_pairpref(i) + c + 1] = r->meta[r->off_pairpref(i) + c] + (sh.L[i] + 1) / 2;
             r->pairs[i] += (sh.L[i] + 1) / 2;
+        }
+        for (int i = 0; i < 7; ++i) r->meta[r->off_upref(i) + c + 1] = r->meta[r->off_upref(i) + c] + sh.L[i] + 2;
+        for (int i = 0; i < 4; ++i) {
+            r->meta[r->off_epref(i) + c + 1] = r->meta[r->off_epref(i) + c] + (sh.L[i] + 1) / 2;
+            r->meta[r->off_opref(i) + c + 1] = r->meta[r->off_opref(i) + c] + sh.L[i] / 2;
+            r->even[i] += (sh.L[i] + 1) / 2;
+            r->odd[i] += sh.L[i] / 2;
         }
         r->meta[r->off_ppref() + c + 1] = r->meta[r->off_ppref() + c] + sh.T + 128;
         r->P += sh.T + 128;
@@ -194,7 +211,15 @@ struct BatchGeom {
     long long pos_blocks = 0;
     RowMap blk_amap{}, blk_cmap{}, blk_rmap{};
     double attn_flops = 0.0;
+    // the backward's: padded dU rows, even / odd frames of conv levels 0 .. 3 and their prefix sums (ragged), and the HOST copy of
+    // the encoder's frame prefix sums (ragged; LayerDrop branches are clip ranges) - valid as long as the RaggedShapes it came from
+    const int* upref[7] = {};
+    const int* epref[4] = {};
+    const int* opref[4] = {};
+    long long even[4] = {}, odd[4] = {};
+    const int* host_tpref = nullptr;
     bool ragged() const { return meta_ints != 0; }
+    long long clip_row0(int c) const { return host_tpref ? host_tpref[c] : (long long)c * T; }   // first encoder frame of clip c
 };
 
 // allocates nothing: the equal-length forwards build one per call
@@ -221,6 +246,10 @@ BatchGeom geom_uniform(const Shapes& sh) {
     g.blk_rmap = RowMap{64LL * 48, pad_ld, nb, kPosBlk * 48};
     g.blk_cmap = RowMap{0, (long long)sh.T * 768, nb, kPosBlk * 768};
     g.attn_flops = 4.0 * sh.B * 12.0 * (double)sh.T * sh.T * 64;
+    for (int i = 0; i < 4; ++i) {
+        g.even[i] = (long long)sh.B * ((sh.L[i] + 1) / 2);
+        g.odd[i] = (long long)sh.B * (sh.L[i] / 2);
+    }
     return g;
 }
 
@@ -252,6 +281,14 @@ BatchGeom geom_ragged(const RaggedShapes& rs, int stride, const int* meta) {
     g.blk_amap = RowMap{0, 0, 0, kPosBlk * 48, bpref, g.ppref, rs.B, 48};
     g.blk_rmap = RowMap{64LL * 48, 0, 0, kPosBlk * 48, bpref, g.ppref, rs.B, 48};
     g.blk_cmap = RowMap{0, 0, 0, kPosBlk * 768, bpref, g.pref[6], rs.B, 768};
+    for (int i = 0; i < 7; ++i) g.upref[i] = at(rs.off_upref(i));
+    for (int i = 0; i < 4; ++i) {
+        g.epref[i] = at(rs.off_epref(i));
+        g.opref[i] = at(rs.off_opref(i));
+        g.even[i] = rs.even[i];
+        g.odd[i] = rs.odd[i];
+    }
+    g.host_tpref = rs.meta.data() + rs.off_pref(6);
     for (int i = 0; i < rs.B; ++i) {
         const double t = rs.meta[rs.off_pref(6) + i + 1] - rs.meta[rs.off_pref(6) + i];
         g.attn_flops += 4.0 * 12.0 * t * t * 64;
@@ -302,26 +339,41 @@ struct RaggedBatch {
     ActLayout lay;
 };
 
-// What every ragged entry point does first: the argument checks (ok: the caller's own), the metadata and the workspace layout.
-// c == nullptr: nomad_workspace_bytes_ragged*, sizing only.  Else a forward: the stride and workspace checks, then the
-// metadata's copy into the workspace, queued on s ahead of every kernel of the call, and the geometry over that copy.
-// Errors name the entry point `who`.
+constexpr unsigned kMetaRing = 16;   // staged host copies of ragged metadata (nomad_ctx::ragged_meta_ring)
+
+// What every ragged entry point does first, in three steps that the forwards run through ragged_prologue and the training-mode
+// forward / the backward run one by one (their own size checks sit between the second and the third).  Errors name `who`.
+// 1. ragged_shapes: the argument checks (ok: the caller's own) and the prefix sums; stride >= 0: no clip longer than its row.
+int ragged_shapes(const char* who, bool ok, int B, int stride, const int* lens_host, RaggedShapes* rs) {
+    if (!ok || !lens_host || B <= 0 || !make_ragged(B, lens_host, rs)) return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d)", who, B);
+    for (int i = 0; stride >= 0 && i < B; ++i)
+        if (lens_host[i] > stride) return fail(NOMAD_ERR_INVALID, "%s: clip %d longer than the row stride", who, i);
+    return 0;
+}
+// 2. the geometry without device pointers (geom_ragged(rs, stride, nullptr)) and the caller's layout over it: sizing.
+// 3. ragged_upload: the metadata's copy to `meta` (inside the call's workspace), queued on s ahead of every kernel of the call, and
+//    the geometry over that copy.  The host copy must outlive the asynchronous transfer: it is staged in a ring of kMetaRing vectors
+//    in the context.  A loss step with a gradient to both arguments queues four such copies (two forwards, two backwards), a
+//    fine-tuning step two, so a slot is written again only kMetaRing / 4 = 4 steps later - and a later step's calls are queued
+//    behind this one's kernels on the caller's stream, which consume the metadata's device copy long before.
+int ragged_upload(nomad_ctx* c, const RaggedShapes& rs, int stride, int* meta, hipStream_t s, BatchGeom* g) {
+    std::vector<int>& staged = c->ragged_meta_ring[c->ragged_seq++ % kMetaRing];
+    staged = rs.meta;
+    HIP_TRY(hipMemcpyAsync(meta, staged.data(), sizeof(int) * staged.size(), hipMemcpyHostToDevice, s));
+    *g = geom_ragged(rs, stride, meta);
+    return 0;
+}
+
+// The scoring forwards' prologue: the three steps over the ActLayout.  c == nullptr: nomad_workspace_bytes_ragged*, sizing only.
 int ragged_prologue(const char* who, nomad_ctx* c, bool ok, int B, int stride, const int* lens_host, size_t elem_bytes,
                     size_t xpad_slack, RaggedBatch* r, void* workspace = nullptr, size_t workspace_bytes = 0, hipStream_t s = nullptr) {
-    if (!ok || !lens_host || B <= 0 || !make_ragged(B, lens_host, &r->rs)) return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d)", who, B);
+    if (int rc = ragged_shapes(who, ok, B, c ? stride : -1, lens_host, &r->rs)) return rc;
     r->g = geom_ragged(r->rs, stride, nullptr);
     r->lay = make_act_layout(r->g, elem_bytes, xpad_slack);
     if (!c) return 0;
-    for (int i = 0; i < B; ++i)
-        if (lens_host[i] > stride) return fail(NOMAD_ERR_INVALID, "%s: clip %d longer than the row stride", who, i);
     if (workspace_bytes < r->lay.total)
         return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, r->lay.total);
-    int* meta = reinterpret_cast<int*>(static_cast<char*>(workspace) + r->lay.meta);
-    std::vector<int>& staged = c->ragged_meta_ring[c->ragged_seq++ & 3];  // must outlive the asynchronous copy
-    staged = r->rs.meta;
-    HIP_TRY(hipMemcpyAsync(meta, staged.data(), sizeof(int) * staged.size(), hipMemcpyHostToDevice, s));
-    r->g = geom_ragged(r->rs, stride, meta);
-    return 0;
+    return ragged_upload(c, r->rs, stride, reinterpret_cast<int*>(static_cast<char*>(workspace) + r->lay.meta), s, &r->g);
 }
 
 // What a training-mode forward keeps for the backward pass (all fp32, carved from the caller's `saved` block).
@@ -337,7 +389,7 @@ struct Saved {
     size_t total;
 };
 
-Saved make_saved(const Shapes& s, void* base) {
+Saved make_saved(const BatchGeom& s, void* base) {
     Saved v{};
     size_t off = 0;
     char* b = static_cast<char*>(base);
@@ -346,12 +398,12 @@ Saved make_saved(const Shapes& s, void* base) {
         off += align_up(floats * sizeof(float));
         return ptr;
     };
-    const size_t M = s.M;
+    const size_t M = (size_t)s.rows[6];
     v.gn_scale = take(512 * (size_t)s.B);
     v.gn_shift = take(512 * (size_t)s.B);
     v.gn_mean = take(512 * (size_t)s.B);
     v.gn_rstd = take(512 * (size_t)s.B);
-    for (int i = 1; i < 7; ++i) v.u[i] = take(512 * (size_t)s.B * s.L[i]);
+    for (int i = 1; i < 7; ++i) v.u[i] = take(512 * (size_t)s.rows[i]);
     v.c6 = take(512 * M);
     v.y0 = take(768 * M);
     v.upc = take(768 * M);
@@ -370,7 +422,7 @@ Saved make_saved(const Shapes& s, void* base) {
 // Scratch of nomad_embed_backward.  train = true adds what the parameter gradients need (nomad_train_backward):
 // two transposed operand buffers [3072][Mp], split-K partial products, the recomputed pos-conv input.
 struct BwdLayout {
-    size_t gx, dya, dyb, dh, dqkv, dug, f1, f2, bufa, bufb, partial, gnfold, cwtab, attnd, total;
+    size_t meta, gx, dya, dyb, dh, dqkv, dug, f1, f2, bufa, bufb, partial, gnfold, cwtab, attnd, total;   // meta: ragged batches only
     int nchunks, nstat;   // frame chunks of the conv0 parameter-gradient pass / of the GroupNorm-backward statistics pass
     size_t ta, tb, kpart, xg, dwe, lnpart, headp, headdz, dmask;
     int Mp, pos_split, ln_blocks;
@@ -382,7 +434,7 @@ constexpr size_t kSplitPartFloats = (size_t)16 * 2304 * 768;  // >= S * Nout * K
 
 inline long long conv_lp(int L) { return ((long long)L + 511) / 512 * 512; }  // a clip's columns in the conv dW operands
 
-BwdLayout make_bwd_layout(const Shapes& s, bool train = false, bool train_conv = false) {
+BwdLayout make_bwd_layout(const BatchGeom& s, bool train = false, bool train_conv = false) {
     BwdLayout l{};
     size_t off = 0;
     auto take = [&](size_t floats) {
@@ -390,41 +442,42 @@ BwdLayout make_bwd_layout(const Shapes& s, bool train = false, bool train_conv =
         off += align_up(floats * sizeof(float));
         return o;
     };
-    const size_t M = s.M;
+    const size_t M = (size_t)s.rows[6];
+    l.meta = take(sizeof(int) * s.meta_ints / sizeof(float));   // (nothing for an equal-length batch)
     l.gx = take(768 * M);
     l.dya = take(768 * M);
     l.dyb = take(768 * M);
     l.dh = take(3072 * M);
     l.dqkv = take(2304 * M);
-    l.dug = take(768 * (size_t)s.B * (s.T + 128));
+    l.dug = take(768 * (size_t)s.pad_rows);
     l.f1 = take(512 * M);
     l.f2 = take(512 * M);
-    l.bufa = take(512 * (size_t)s.B * (s.L[0] + 2));
-    l.bufb = take(512 * (size_t)s.B * (s.L[1] + 2));
-    l.nchunks = (s.L[0] + kGnChunk - 1) / kGnChunk;
-    l.nstat = (s.L[0] + kGnStatsChunk - 1) / kGnStatsChunk;
+    l.bufa = take(512 * (size_t)(s.rows[0] + 2LL * s.B));
+    l.bufb = take(512 * (size_t)(s.rows[1] + 2LL * s.B));
+    l.nchunks = (s.max_l0 + kGnChunk - 1) / kGnChunk;
+    l.nstat = (s.max_l0 + kGnStatsChunk - 1) / kGnStatsChunk;
     l.partial = take(1024 * (size_t)s.B * l.nstat);
     l.gnfold = take(1024 * (size_t)s.B);
     l.cwtab = take((size_t)512 * 16 * s.B);
     l.attnd = take(12 * M);
     if (train) {
-        l.Mp = (s.M + 511) / 512 * 512;  // contraction length of the dW GEMMs: any split S | 16 keeps K % 32 == 0
+        l.Mp = ((int)M + 511) / 512 * 512;  // contraction length of the dW GEMMs: any split S | 16 keeps K % 32 == 0
         l.pos_split = s.B < 4 ? s.B : 4;
-        l.ln_blocks = (s.M + kLnRows - 1) / kLnRows;
+        l.ln_blocks = ((int)M + kLnRows - 1) / kLnRows;
         // conv dW GEMMs (freeze_convnet: False): dU^T [512][cols] and the transposed im2col [taps * 512][cols]
         l.conv_cols = train_conv ? (long long)s.B * conv_lp(s.L[1]) : 0;
         l.ta = take(std::max((size_t)3072 * l.Mp, (size_t)(512 * l.conv_cols)));
         l.tb = take(std::max((size_t)3072 * l.Mp, (size_t)(1536 * l.conv_cols)));
         const size_t pos_part = (size_t)l.pos_split * 16 * 128 * 2304;
         l.kpart = take(pos_part > kSplitPartFloats ? pos_part : kSplitPartFloats);
-        l.xg = take(768 * (size_t)s.B * (s.T + 128));
+        l.xg = take(768 * (size_t)s.pad_rows);
         l.dwe = take((size_t)768 * 6144);
         l.lnpart = take(std::max((size_t)l.ln_blocks * 2 * 768, (size_t)16 * kPbChunks * 48));  // also the pos-conv bias partials
         l.headp = take((size_t)s.B * 768);
         l.headdz = take((size_t)s.B * 256);
         l.dmask = take(768 * M);
         if (train_conv) {
-            l.h0 = take(512 * (size_t)s.B * s.L[0]);
+            l.h0 = take(512 * (size_t)s.rows[0]);
             l.convtmp = take((size_t)512 * 1536);
             l.c0part = take((size_t)5120 * s.B * l.nchunks);
         }
@@ -649,14 +702,21 @@ DropCfg make_drop(const nomad_ctx* c, float p) {
 // A ragged one: every clip.
 int run_attention(nomad_ctx* c, const BatchGeom& g, const float* qkv, float* out, float* lse, hipStream_t s,
                   const DropCfg* dc = nullptr, uint32_t site = 0, int c0 = 0, int nc = 0) {
-    if (g.ragged()) {
+    if (g.ragged()) {   // clips [c0, c0 + nc) (nc = 0: all); qkv / out / lse are the whole batch's
         Scope sc(c, s, NOMAD_K_ATTN, g.attn_flops);
+        const int nb = nc ? nc : g.B;
+        if (dc && dc->threshold) {   // attention dropout: this kernel for every clip, as for an equal-length batch; mask offsets per clip
+            hipLaunchKernelGGL((attention_f32_kernel<float, true>), dim3((g.max_t + 63) / 64, nb * 12), dim3(256), 0, s, qkv, out, lse, 0,
+                               g.pref[6], *dc, site, c0 * 12);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
         // clips of kAttnV2MinT frames or more: attention_f32_v2_kernel; shorter ones: attention_f32_kernel (each skips the
         // other's clips) - exactly the kernel the clip would get in a batch of its own
-        if (g.max_t >= kAttnV2MinT) HIP_TRY(launch_attention_f32_v2(qkv, out, lse, g.B, g.max_t, g.pref[6], s, kAttnV2MinT));
+        if (g.max_t >= kAttnV2MinT) HIP_TRY(launch_attention_f32_v2(qkv, out, lse, nb, g.max_t, g.pref[6] + c0, s, kAttnV2MinT));
         if (g.min_t < kAttnV2MinT)
-            hipLaunchKernelGGL(attention_f32_kernel<float>, dim3((std::min(g.max_t, kAttnV2MinT - 1) + 63) / 64, g.B * 12), dim3(256), 0,
-                               s, qkv, out, lse, 0, g.pref[6], DropCfg{}, 0u, 0, 0LL, kAttnV2MinT);
+            hipLaunchKernelGGL(attention_f32_kernel<float>, dim3((std::min(g.max_t, kAttnV2MinT - 1) + 63) / 64, nb * 12), dim3(256), 0,
+                               s, qkv, out, lse, 0, g.pref[6], DropCfg{}, 0u, c0 * 12, 0LL, kAttnV2MinT);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -930,13 +990,13 @@ struct F32Bufs {
 
 // The fp32 forward, over an equal-length or a ragged batch.  sv == nullptr: scoring mode (intermediates alias inside the
 // workspace).  sv != nullptr: training mode - every tensor the backward needs is written to its slot in `sv` instead.
-// splitk_block: the workspace's split-K block of an equal-length layer-output forward (splitk_floats floats), or nullptr.  The
-// training inputs (sv, its dropout and LayerDrop, layers_out, split-K) are for equal-length batches only.
+// splitk_block: the workspace's split-K block of an equal-length layer-output forward (splitk_floats floats), or nullptr.
+// A ragged batch takes sv, its dropout and LayerDrop (branches: equal groups of clips, of any lengths) and layers_out like an
+// equal-length one, packed; it never splits K, so that a clip's values never depend on the batch it is in.
 static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const F32Bufs& bf, const float* head_w,
                        const float* head_b, float* emb, float* layers_out, float* splitk_block, size_t splitk_floats, hipStream_t s,
                        const Saved* sv, bool features = false) {
-    if (g.ragged() && (sv || layers_out || splitk_block))
-        return fail(NOMAD_ERR_INVALID, "fp32 forward: training inputs, layer outputs and split-K need an equal-length batch");
+    if (g.ragged() && splitk_block) return fail(NOMAD_ERR_INVALID, "fp32 forward: split-K needs an equal-length batch");
     const int B = g.B, T = g.T, M = (int)g.rows[6];
     // the loss forward of Nomad.forward() (saving activations, not fine-tuning): small-M GEMMs may split K.  Round 4: so may the
     // other branch of that loss - a forward that returns the 12 layer outputs (LossNetLayers: `clean`, or `estimate` under
@@ -946,7 +1006,7 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
     // were two context-wide blocks handed to launch streams by hipEventQuery: whether a third stream's forward split depended on
     // timing).  Tuning::splitk_layers = 0 switches the case off (A/B, diag library).
     float* const loss_block = (sv == nullptr && layers_out != nullptr && splitk_block != nullptr && c->tune.splitk_layers) ? splitk_block : nullptr;
-    const SplitKScope splitk(c, (sv != nullptr || loss_block != nullptr) && !c->train_ready);
+    const SplitKScope splitk(c, (sv != nullptr || loss_block != nullptr) && !c->train_ready && !g.ragged());
     float* const prev_cur = c->splitk_cur;
     const size_t prev_cur_floats = c->splitk_cur_floats;
     c->splitk_cur = sv != nullptr ? c->splitk_part : loss_block;
@@ -1032,7 +1092,7 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
     }
     if (d_in.threshold) {  // dropout_input: on the features that feed both the pos-conv and its residual
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        hipLaunchKernelGGL(dropout_groups_kernel, dim3(M), dim3(192), 0, s, xpad, T, g.grp_stride, d_in, kSiteInput);
+        hipLaunchKernelGGL(dropout_groups_kernel, dim3(M), dim3(192), 0, s, xpad, T, g.grp_stride, d_in, kSiteInput, g.pref[6], g.ppref, B);
     }
     // ---- pos-conv: 16 groups x (M x 48 x 6144), x + gelu(conv + bias) -------------------------
     {
@@ -1071,8 +1131,8 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
     // decided differently for the branches.  Rows are independent, so a sub-range call is the same arithmetic.
     auto run_layer = [&](int l, int c0, int nc) -> int {
         const LayerDev& d = c->layers[l];
-        const long long r0 = (long long)c0 * T;
-        const int Ms = nc == B ? M : nc * T;   // (branches: equal-length batches only)
+        const long long r0 = g.clip_row0(c0);   // (a ragged batch: the clips' prefix sums)
+        const int Ms = nc == B ? M : (int)(g.clip_row0(c0 + nc) - r0);
         const long long acts = (long long)Ms * 768;
         float* xs = x + r0 * 768;
         float* x2s = x2 + r0 * 768;
@@ -1081,13 +1141,16 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
         float* ctxb = (sv ? sv->L[l].ctx : bf.ctxb) + r0 * 768;
         float* y1 = (sv ? sv->L[l].y1 : y) + r0 * 768;
         float* y2 = (sv ? sv->L[l].y2 : y) + r0 * 768;
-        float* lse = sv ? sv->L[l].lse + (long long)c0 * 12 * T : nullptr;
+        float* lse = sv ? sv->L[l].lse + 12 * r0 : nullptr;
         float* lo = layers_out ? layers_out + (size_t)l * M * 768 + r0 * 768 : nullptr;
         const unsigned long long idx0 = (unsigned long long)r0 * 768;
         int rc;
         if ((rc = run_gemm(c, dense(xs, 768, d.qkv_w, d.qkv_b, nullptr, qkv, Ms, 2304, 768, 0), 1, pick_tile(c, Ms, 2304, 768), s)))
             return rc;
-        if ((rc = run_attention(c, g, qkv, ctxb, lse, s, &d_att, site_attn(l), c0, nc))) return rc;
+        // (a ragged batch: the attention kernels address clips through the whole batch's prefix sums - whole-batch pointers)
+        if (g.ragged() ? (rc = run_attention(c, g, qkv - r0 * 2304, ctxb - r0 * 768, lse ? lse - 12 * r0 : nullptr, s, &d_att, site_attn(l), c0, nc))
+                       : (rc = run_attention(c, g, qkv, ctxb, lse, s, &d_att, site_attn(l), c0, nc)))
+            return rc;
         // residual dropout: y = x + dropout(W a + b) needs the branch on its own, so the residual add moves out
         // of the GEMM epilogue into the dropout kernel
         // (the LayerNorm behind a residual GEMM: inside the GEMM's split-K epilogue where it has one - configs[3] - else on its own)
@@ -1142,9 +1205,9 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
             if ((bmask[br] >> l) & 1u) {
                 if ((rc = run_layer(l, c0, nc))) return rc;
             } else if (layers_out) {
-                const long long r0 = (long long)c0 * T;
+                const long long r0 = g.clip_row0(c0), nr = g.clip_row0(c0 + nc) - r0;
                 HIP_TRY(hipMemcpyAsync(layers_out + (size_t)l * M * 768 + r0 * 768, x + r0 * 768,
-                                       sizeof(float) * (size_t)nc * T * 768, hipMemcpyDeviceToDevice, s));
+                                       sizeof(float) * (size_t)nr * 768, hipMemcpyDeviceToDevice, s));
             }
         }
         (void)any;
@@ -1175,21 +1238,31 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
                        layers_splitk_floats(sh), static_cast<hipStream_t>(stream), sv, features);
 }
 
+// layers_out / saved (nomad_embed_train_ragged): the packed layer outputs and, with a saved block, the training-mode forward.
 static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, const float* head_w,
                           const float* head_b, float* emb, void* workspace, size_t workspace_bytes,
-                          nomad_stream_t stream, const char* who = "nomad_embed_ragged", bool features = false) {
+                          nomad_stream_t stream, const char* who = "nomad_embed_ragged", bool features = false,
+                          float* layers_out = nullptr, void* saved = nullptr, size_t saved_bytes = 0) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     RaggedBatch r;
-    if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, sizeof(float), 0, &r,
-                                 workspace, workspace_bytes, s))
-        return rc;
+    if (int rc = ragged_shapes(who, c && wav && emb && workspace, B, stride, lens_host, &r.rs)) return rc;
+    r.g = geom_ragged(r.rs, stride, nullptr);
+    r.lay = make_act_layout(r.g, sizeof(float), 0);
+    if (workspace_bytes < r.lay.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, r.lay.total);
+    Saved sv{};
+    if (saved) {   // every check before the first byte is queued
+        sv = make_saved(r.g, saved);
+        if (saved_bytes < sv.total) return fail(NOMAD_ERR_WORKSPACE, "%s: saved block %zu < required %zu", who, saved_bytes, sv.total);
+        if (c->branches > 1 && B % c->branches) return fail(NOMAD_ERR_INVALID, "%s: B=%d is not %d equal branches", who, B, c->branches);
+    }
+    if (int rc = ragged_upload(c, r.rs, stride, reinterpret_cast<int*>(static_cast<char*>(workspace) + r.lay.meta), s, &r.g)) return rc;
     char* ws = static_cast<char*>(workspace);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const ActLayout& lay = r.lay;
     F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.convb), F(lay.xpad), F(lay.x),
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(i % 2 ? lay.convb : lay.conva);   // conv6 lands in conva, LN(512) writes to convb
-    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, nullptr, nullptr, 0, s, nullptr, features);
+    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, layers_out, nullptr, 0, s, saved ? &sv : nullptr, features);
 }
 
 // One backward GEMM: C[M][N] = A[M][K] * Wt[N][K]^T (Wt = transposed forward weight), optional GELU' and residual.
@@ -2139,7 +2212,7 @@ int nomad_saved_bytes(const nomad_ctx* c, int B, int n_samples, size_t* bytes) {
     Shapes sh;
     if (!c || !bytes || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "nomad_saved_bytes: bad shape B=%d N=%d", B, n_samples);
-    *bytes = make_saved(sh, nullptr).total;
+    *bytes = make_saved(geom_uniform(sh), nullptr).total;
     return 0;
 }
 
@@ -2147,7 +2220,7 @@ int nomad_backward_workspace_bytes(const nomad_ctx* c, int B, int n_samples, siz
     Shapes sh;
     if (!c || !bytes || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "nomad_backward_workspace_bytes: bad shape B=%d N=%d", B, n_samples);
-    *bytes = make_bwd_layout(sh).total;
+    *bytes = make_bwd_layout(geom_uniform(sh)).total;
     return 0;
 }
 
@@ -2157,10 +2230,60 @@ int nomad_embed_train(nomad_ctx* c, const float* wav, int B, int n_samples, cons
     Shapes sh;
     if (!c || !saved || !layers_out || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "nomad_embed_train: bad argument");
-    const Saved sv = make_saved(sh, saved);
+    const Saved sv = make_saved(geom_uniform(sh), saved);
     if (saved_bytes < sv.total)
         return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_train: saved block %zu < required %zu", saved_bytes, sv.total);
     return forward_impl(c, wav, B, n_samples, head_w, head_b, emb, layers_out, workspace, workspace_bytes, stream, &sv);
+}
+
+static int ragged_geom_for_size(const char* who, const nomad_ctx* c, int B, const int* lens, size_t* bytes, RaggedShapes* rs) {
+    if (!c || !bytes || !lens || B <= 0 || !make_ragged(B, lens, rs)) return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d)", who, B);
+    return 0;
+}
+
+int nomad_ragged_metadata(int B, const int* lengths_host, int* out_host, size_t capacity, size_t* count) {
+    RaggedShapes rs;
+    if (!count || !lengths_host || B <= 0 || !make_ragged(B, lengths_host, &rs))
+        return fail(NOMAD_ERR_INVALID, "nomad_ragged_metadata: bad argument (B=%d)", B);
+    *count = rs.meta.size();
+    if (out_host) {
+        if (capacity < rs.meta.size()) return fail(NOMAD_ERR_WORKSPACE, "nomad_ragged_metadata: room for %zu ints < %zu", capacity, rs.meta.size());
+        std::copy(rs.meta.begin(), rs.meta.end(), out_host);
+    }
+    return 0;
+}
+
+int nomad_saved_bytes_ragged(const nomad_ctx* c, int B, const int* lengths_host, size_t* bytes) {
+    RaggedShapes rs;
+    if (int rc = ragged_geom_for_size("nomad_saved_bytes_ragged", c, B, lengths_host, bytes, &rs)) return rc;
+    *bytes = make_saved(geom_ragged(rs, 0, nullptr), nullptr).total;
+    return 0;
+}
+
+int nomad_backward_workspace_bytes_ragged(const nomad_ctx* c, int B, const int* lengths_host, size_t* bytes) {
+    RaggedShapes rs;
+    if (int rc = ragged_geom_for_size("nomad_backward_workspace_bytes_ragged", c, B, lengths_host, bytes, &rs)) return rc;
+    *bytes = make_bwd_layout(geom_ragged(rs, 0, nullptr)).total;
+    return 0;
+}
+
+int nomad_train_workspace_bytes_ragged(const nomad_ctx* c, int B, const int* lengths_host, size_t* bytes) {
+    RaggedShapes rs;
+    if (int rc = ragged_geom_for_size("nomad_train_workspace_bytes_ragged", c, B, lengths_host, bytes, &rs)) return rc;
+    *bytes = make_bwd_layout(geom_ragged(rs, 0, nullptr), true, false).total;
+    return 0;
+}
+
+int nomad_embed_train_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, const float* head_w,
+                             const float* head_b, float* emb, float* layers_out, void* saved, size_t saved_bytes, void* workspace,
+                             size_t workspace_bytes, nomad_stream_t stream) {
+    if (!c || !layers_out || (saved == nullptr) != (saved_bytes == 0))
+        return fail(NOMAD_ERR_INVALID, "nomad_embed_train_ragged: bad argument");
+    if (saved && c->train_ready && c->train_convnet)
+        return fail(NOMAD_ERR_INVALID,
+                    "nomad_embed_train_ragged: a trainable conv feature extractor (nomad_train_set_convnet) needs an equal-length batch");
+    return forward_ragged(c, wav, B, stride, lengths_host, head_w, head_b, emb, workspace, workspace_bytes, stream,
+                          "nomad_embed_train_ragged", false, layers_out, saved, saved_bytes);
 }
 
 }  // extern "C"
@@ -2219,13 +2342,15 @@ int nomad_enable_backward(nomad_ctx* c) {
     return 0;
 }
 
-int nomad_l1_loss_backward(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb,
-                           const float* b_emb, int B, int T, const float* upstream, float* dlayers, float* demb,
-                           nomad_stream_t stream) {
-    if (!c || !a_layers || !b_layers || !a_emb || !b_emb || !upstream || !dlayers || !demb || B <= 0 || T <= 0)
-        return fail(NOMAD_ERR_INVALID, "nomad_l1_loss_backward: bad argument");
+}  // extern "C"
+
+static int l1_backward_rows(const char* who, nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb,
+                            const float* b_emb, long long rows, int B, const float* upstream, float* dlayers, float* demb,
+                            nomad_stream_t stream) {
+    if (!c || !a_layers || !b_layers || !a_emb || !b_emb || !upstream || !dlayers || !demb || B <= 0 || rows < B)
+        return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long per_layer = (long long)B * T * 768;
+    const long long per_layer = rows * 768;
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
     hipLaunchKernelGGL(l1_bwd_kernel, dim3(2048), dim3(256), 0, s, reinterpret_cast<const float4*>(a_layers),
                        reinterpret_cast<const float4*>(b_layers), per_layer * 12 / 4, 1.0f / (float)per_layer, upstream,
@@ -2235,6 +2360,21 @@ int nomad_l1_loss_backward(nomad_ctx* c, const float* a_layers, const float* b_l
                        reinterpret_cast<float4*>(demb));
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+extern "C" {
+
+int nomad_l1_loss_backward(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb,
+                           const float* b_emb, int B, int T, const float* upstream, float* dlayers, float* demb,
+                           nomad_stream_t stream) {
+    return l1_backward_rows("nomad_l1_loss_backward", c, a_layers, b_layers, a_emb, b_emb, T > 0 ? (long long)B * T : 0, B, upstream,
+                            dlayers, demb, stream);
+}
+
+int nomad_l1_loss_backward_ragged(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb,
+                                  const float* b_emb, long long M, int B, const float* upstream, float* dlayers, float* demb,
+                                  nomad_stream_t stream) {
+    return l1_backward_rows("nomad_l1_loss_backward_ragged", c, a_layers, b_layers, a_emb, b_emb, M, B, upstream, dlayers, demb, stream);
 }
 
 }  // extern "C"
@@ -2275,27 +2415,19 @@ static int dw_gemm(nomad_ctx* c, const float* TA, const float* TB, int Nout, int
     return 0;
 }
 
-static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
-                         const float* layers_out, const void* saved, size_t saved_bytes, const float* dlayers,
-                         const float* demb, float* dwav, void* workspace, size_t workspace_bytes,
-                         nomad_stream_t stream, bool train) {
-    Shapes sh;
-    if (!c || !wav || !layers_out || !saved || !demb || (!dwav && !train) || !workspace || B <= 0 ||
-        !make_shapes(B, n_samples, &sh))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: bad argument");
-    if (!c->bwd_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: call nomad_enable_backward first");
-    if (train && !c->train_ready) return fail(NOMAD_ERR_INVALID, "nomad_train_backward: call nomad_train_enable first");
-    const Saved sv = make_saved(sh, const_cast<void*>(saved));
+// The backward sequence, over an equal-length or a ragged batch (the geometry of the forward it belongs to): one sequence serves
+// both, the way forward_run does.  Ragged: per-frame tensors are packed, the padded dU buffers of the conv stack hold clip c's
+// L_i(c) + 2 rows at row upref_i[c], the kernels that care about clip boundaries read the prefix sums; small-M GEMMs never split
+// K (a clip's gradient does not depend on its batch).  The conv feature extractor's parameter gradients need an equal-length batch.
+static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const Saved& sv, const BwdLayout& lay, const float* head_w,
+                        const float* head_b, const float* layers_out, const float* dlayers, const float* demb, float* dwav,
+                        char* ws, hipStream_t s, bool train) {
     const bool conv_pg = train && c->train_convnet;  // parameter gradients of the conv feature extractor too
-    const BwdLayout lay = make_bwd_layout(sh, train, conv_pg);
-    if (saved_bytes < sv.total || workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_backward: saved %zu/%zu, workspace %zu/%zu", saved_bytes, sv.total,
-                    workspace_bytes, lay.total);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    const int T = sh.T, M = sh.M;
-    const SplitKScope splitk(c, !train && !c->train_ready);  // d loss / d waveform of Nomad.forward(): small-M GEMMs may split K
+    const int B = g.B, T = g.T, M = (int)g.rows[6], n_samples = g.wav_ld;
+    const bool rg = g.ragged();
+    const int* const tpref = g.pref[6];   // kNoInts for an equal-length batch
+    const SplitKScope splitk(c, !train && !c->train_ready && !rg);  // d loss / d waveform of Nomad.forward(): small-M GEMMs may split K
     float* const prev_cur_b = c->splitk_cur;
     const size_t prev_cur_floats_b = c->splitk_cur_floats;
     c->splitk_cur = c->splitk_part;
@@ -2352,7 +2484,7 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
         hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(1024), 0, s, layers_out + (size_t)11 * M * 768, T,
                            head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, demb, gx,
-                           train ? F(lay.headp) : nullptr, train ? F(lay.headdz) : nullptr);
+                           train ? F(lay.headp) : nullptr, train ? F(lay.headdz) : nullptr, tpref);
         if (train)
             hipLaunchKernelGGL(head_param_grad_kernel, dim3(256), dim3(256), 0, s, F(lay.headp), F(lay.headdz), B,
                                G(po.emb_w), G(po.emb_b));
@@ -2366,13 +2498,13 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
     auto bwd_layer = [&](int l, int c0, int nc) -> int {
         const LayerDev& d = c->layers[l];
         const LayerOffsets& lo = po.L[l];
-        const long long r0 = (long long)c0 * T;
-        const int Ms = nc * T, Mps = (Ms + 511) / 512 * 512;
+        const long long r0 = g.clip_row0(c0);   // (a ragged batch: the clips' prefix sums)
+        const int Ms = (int)(g.clip_row0(c0 + nc) - r0), Mps = (Ms + 511) / 512 * 512;
         const long long acts = (long long)Ms * 768;
         const unsigned long long idx0 = (unsigned long long)r0 * 768;
         const SavedLayer& sl0 = sv.L[l];
         const float *y2 = sl0.y2 + r0 * 768, *y1 = sl0.y1 + r0 * 768, *u = sl0.u + r0 * 3072, *qkv = sl0.qkv + r0 * 2304,
-                    *ctx = sl0.ctx + r0 * 768, *lse = sl0.lse + (long long)c0 * 12 * T;
+                    *ctx = sl0.ctx + r0 * 768, *lse = sl0.lse + 12 * r0;
         float *gxs = gx + r0 * 768, *dyas = dya + r0 * 768, *dybs = dyb + r0 * 768, *dhs = dh + r0 * 3072,
               *dqkvs = dqkv + r0 * 2304, *dmasks = dmask ? dmask + r0 * 768 : nullptr;
         const float* dl = dlayers ? dlayers + (size_t)l * M * 768 + r0 * 768 : nullptr;
@@ -2424,7 +2556,11 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
             if ((rc = dw_gemm(c, TA, TB, 768, 768, Mps, part, G(lo.o_w), 0, 1.0f, s))) return rc;
         }
         if ((rc = bwd_gemm(c, dy1b, c->o_wT[l], dybs, Ms, 768, 768, nullptr, nullptr, s))) return rc;  // dctx
-        {
+        if (rg) {   // the whole batch's pointers and prefix sums, clips [c0, c0 + nc); fused or three kernels by each CLIP's length
+            Scope sc(c, s, NOMAD_K_ATTN, 3.5 * g.attn_flops * nc / B);
+            HIP_TRY(launch_attention_bwd_ragged(sl0.qkv, sl0.ctx, dyb, sl0.lse, F(lay.attnd), dqkv, tpref, B, c0, nc, (int)r0, (int)r0 + Ms,
+                                                g.max_t, g.min_t, d_att, site_attn(l), s, !c->tune.attn_bwd_small));
+        } else {
             Scope sc(c, s, NOMAD_K_ATTN, 14.0 * nc * 12.0 * (double)T * T * 64);  // 7 T x T x 64 products (S, dP twice)
             HIP_TRY(launch_attention_bwd(qkv, ctx, dybs, lse, F(lay.attnd), dqkvs, nc, T, d_att, site_attn(l), s, c0 * 12, !c->tune.attn_bwd_small));
         }
@@ -2475,17 +2611,18 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
     if (d_res.threshold && (rc = run_dropout(c, gx, nullptr, gx, act, d_res, kSiteEncoder, s))) return rc;
     if (!lnb_prefused && (rc = run_ln_bwd(c, sv.y0, gx, nullptr, c->eln_w, dya, M, 768, s))) return rc;   // dy0
     if (pg) ln_params(sv.y0, gx, nullptr, 768, G(po.eln_w), G(po.eln_b), M);
-    const long long grp_stride = (long long)B * (T + 128) * 48;
+    const long long grp_stride = g.grp_stride;
     {
         float* dug = F(lay.dug);
         {
             Scope sc(c, s, NOMAD_K_ROW, 0.0);
-            hipLaunchKernelGGL(zero_pad_rows_kernel<float>, dim3(16 * B), dim3(256), 0, s, dug, T, kNoInts, kNoInts, B);
-            hipLaunchKernelGGL(dgelu_to_groups_kernel, dim3(M), dim3(192), 0, s, dya, sv.upc, dug, T, grp_stride);
+            hipLaunchKernelGGL(zero_pad_rows_kernel<float>, dim3(16 * B), dim3(256), 0, s, dug, T, tpref, g.ppref, B);
+            hipLaunchKernelGGL(dgelu_to_groups_kernel, dim3(M), dim3(192), 0, s, dya, sv.upc, dug, T, grp_stride, tpref, g.ppref, B);
         }
         GemmParams p{};
         p.A = dug;
-        p.amap = RowMap{48, (long long)(T + 128) * 48, T, 48};  // row (clip, t) starts at buffer frame t + 1
+        p.amap = g.pos_amap;  // row (clip, t) starts at buffer frame t + 1
+        p.amap.off = 48;
         p.a_goff = grp_stride;
         p.K = 6144;
         p.kchunk = 6144;
@@ -2511,30 +2648,29 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
         // ---- pos-conv parameters: bias, then weight_g / weight_v through the weight norm --------------------
         {
             Scope sc(c, s, NOMAD_K_ROW, 0.0);
-            hipLaunchKernelGGL(posconv_bias_partial_kernel, dim3(kPbChunks, 16), dim3(256), 0, s, dug, (long long)B * (T + 128),
-                               F(lay.lnpart));
+            hipLaunchKernelGGL(posconv_bias_partial_kernel, dim3(kPbChunks, 16), dim3(256), 0, s, dug, g.pad_rows, F(lay.lnpart));
             hipLaunchKernelGGL(posconv_bias_final_kernel, dim3(1), dim3(768), 0, s, F(lay.lnpart), G(po.pos_b));
         }
         // the conv's input (post_extract_proj output, group-major, zero padded) is recomputed, not saved
         {
             Scope sc(c, s, NOMAD_K_ROW, 0.0);
-            hipLaunchKernelGGL(zero_pad_rows_kernel<float>, dim3(16 * B), dim3(256), 0, s, xg, T, kNoInts, kNoInts, B);
+            hipLaunchKernelGGL(zero_pad_rows_kernel<float>, dim3(16 * B), dim3(256), 0, s, xg, T, tpref, g.ppref, B);
         }
         {
             GemmParams p = dense(featln, 512, c->proj_w, c->proj_b, nullptr, xg, M, 768, 512, 0);
-            p.cmap = RowMap{64LL * 48, (long long)(T + 128) * 48, T, 48};
+            p.cmap = g.pad_map;
             p.c_colblk = 48;
             p.c_colblk_stride = grp_stride;
             if ((rc = run_gemm(c, p, 1, pick_tile(c, M, 768, 512), s))) return rc;
         }
         if (d_in.threshold) {
             Scope sc(c, s, NOMAD_K_ROW, 0.0);
-            hipLaunchKernelGGL(dropout_groups_kernel, dim3(M), dim3(192), 0, s, xg, T, grp_stride, d_in, kSiteInput);
+            hipLaunchKernelGGL(dropout_groups_kernel, dim3(M), dim3(192), 0, s, xg, T, grp_stride, d_in, kSiteInput, tpref, g.ppref, B);
         }
         {
             const int S = lay.pos_split, cps = (B + S - 1) / S;
             Scope sc(c, s, NOMAD_K_GEMM, 2.0 * M * 768.0 * 48 * 128);
-            hipLaunchKernelGGL(posconv_dw_kernel, dim3(128 / kPdwTaps, 16, S), dim3(256), 0, s, dug, xg, part, B, T, cps);
+            hipLaunchKernelGGL(posconv_dw_kernel, dim3(128 / kPdwTaps, 16, S), dim3(256), 0, s, dug, xg, part, B, T, cps, tpref, g.ppref, grp_stride);
             hipLaunchKernelGGL(posconv_dw_gather_kernel, dim3(768), dim3(256), 0, s, part, S, dwe);
             hipLaunchKernelGGL(tap_dot_partial_kernel, dim3(576), dim3(256), 0, s, dwe, c->theta + po.pos_v, c->tap_partial);
             hipLaunchKernelGGL(tap_sum_final_kernel, dim3(1), dim3(1024), 0, s, c->tap_partial, 576, c->tap_dot);
@@ -2561,7 +2697,7 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
     // d W_i of conv layer i (freeze_convnet: False): dU_i^T x im2col(input)^T contracted over all frames, per-clip column
     // blocks of conv_lp(L_i) (zero padded), the same split-K dW GEMM as the encoder's, then back to [co][ci][tap]
     auto conv_dw = [&](int i, const float* dU, const float* in, long long in_clip, bool gelu_in) -> int {
-        const int Lout = sh.L[i], taps = kConvK[i], Kin = taps * 512;
+        const int Lout = g.L[i], taps = kConvK[i], Kin = taps * 512;   // (equal-length batches only)
         const int Lp = (int)conv_lp(Lout);
         const long long cols = (long long)B * Lp;
         {
@@ -2586,9 +2722,9 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
     if ((rc = run_ln_bwd(c, sv.c6, F(lay.f1), nullptr, c->fln_w, F(lay.f2), M, 512, s))) return rc;
     float* bufs[2] = {F(lay.bufa), F(lay.bufb)};  // dU6 -> a, dU5 -> b, ..., dU1 -> b, G0 -> a
     {
-        HIP_TRY(hipMemsetAsync(bufs[0], 0, sizeof(float) * 512 * (size_t)B * (T + 2), s));
+        HIP_TRY(hipMemsetAsync(bufs[0], 0, sizeof(float) * 512 * (size_t)(M + 2LL * B), s));
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        const RowMap om{512, (long long)(T + 2) * 512, T, 512};
+        const RowMap om = rg ? RowMap{512, 0, 0, 512, tpref, g.upref[6], B, 512} : RowMap{512, (long long)(T + 2) * 512, T, 512};
         // GradMultiply(features, feature_grad_mult) sits on the extractor's (post-GELU) output: its backward scales the
         // gradient that enters GELU'
         hipLaunchKernelGGL(dgelu_rows512_kernel, dim3(M), dim3(128), 0, s, F(lay.f2), sv.u[6], bufs[0], om, M,
@@ -2596,27 +2732,42 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
     }
     // ---- conv6..conv1: transposed strided convolutions as GEMMs over the padded dU buffers -------------
     for (int i = 6; i >= 1; --i) {
-        const float* dU = bufs[i % 2];        // [B][L_i + 2][512], data at rows 1..L_i
+        const float* dU = bufs[i % 2];        // [B][L_i + 2][512], data at rows 1..L_i (ragged: clip c's L_i(c) + 2 rows at row upref_i[c])
         float* out = bufs[(i + 1) % 2];
-        const int Lout = sh.L[i], Lin = sh.L[i - 1];
+        const int Lout = g.L[i], Lin = g.L[i - 1];   // (0 for a ragged batch: the maps below read the prefix sums)
         const bool to_g0 = (i == 1);          // conv0's output gradient is compact and gets no GELU' here
         const long long out_clip = to_g0 ? (long long)Lin * 512 : (long long)(Lin + 2) * 512;
         const long long out_off = to_g0 ? 0 : 512;
+        const int* const obase = to_g0 ? g.pref[0] : g.upref[i - 1];   // ragged: the clips' first rows in `out`
+        // logical rows by `pref` (ragged) or `rows` per clip: the A rows in dU, the C rows in out, the GELU' rows in the saved u
+        auto amap_of = [&](long long off, int rows, const int* pref) {
+            return rg ? RowMap{off, 0, 0, 512, pref, g.upref[i], B, 512} : RowMap{off, (long long)(Lout + 2) * 512, rows, 512};
+        };
+        auto cmap_of = [&](long long off, int rows, const int* pref) {
+            return rg ? RowMap{off, 0, 0, 1024, pref, obase, B, 512} : RowMap{off, out_clip, rows, 1024};
+        };
+        auto dgmap_of = [&](long long off, int rows, const int* pref) {
+            return rg ? RowMap{off, 0, 0, 1024, pref, g.pref[i - 1], B, 512} : RowMap{off, (long long)Lin * 512, rows, 1024};
+        };
         // the two GEMMs below write frames 0 .. covered - 1 of every clip (k = 3: every input frame; k = 2: 2 L_out of them); what they
         // do not write is zeroed here: the two pad rows of a padded buffer and the frames behind the last window (a full memset of
         // the buffer cost 20-40 us per layer at configs[3]'s size)
         if (!to_g0) {
             const int covered = kConvK[i] == 2 ? 2 * Lout : Lin;
             Scope sc(c, s, NOMAD_K_ROW, 0.0);
-            hipLaunchKernelGGL(zero_rows512_kernel, dim3(B), dim3(256), 0, s, out, out_clip, 0, 1, covered + 1, Lin + 2);
+            if (rg)
+                hipLaunchKernelGGL(zero_rows512_ragged_kernel, dim3(B), dim3(256), 0, s, out, g.upref[i - 1], g.pref[i - 1], g.pref[i],
+                                   kConvK[i] == 2 ? 1 : 0);
+            else
+                hipLaunchKernelGGL(zero_rows512_kernel, dim3(B), dim3(256), 0, s, out, out_clip, 0, 1, covered + 1, Lin + 2);
         } else if (kConvK[i] == 2) {
-            HIP_TRY(hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * out_clip, s));   // (not reached: conv1 has k = 3 and writes every frame of G0)
+            HIP_TRY(hipMemsetAsync(out, 0, sizeof(float) * 512 * (size_t)g.rows[0], s));   // (not reached: conv1 has k = 3 and writes every frame of G0)
         }
         if (conv_pg) {  // input of layer i: gelu(u_{i-1}) recomputed in the transpose; for i = 1 conv0's output, recomputed whole
             if (i == 1) {
                 Scope sc(c, s, NOMAD_K_FRONT, 0.0);
-                hipLaunchKernelGGL(conv0_gn_gelu_kernel<float>, dim3((sh.L[0] + kConv0Frames - 1) / kConv0Frames, B), dim3(256), 0, s, wav,
-                                   n_samples, sh.L[0], c->conv0_w, sv.gn_scale, sv.gn_shift, F(lay.h0), kNoInts, kNoInts, 0LL);
+                hipLaunchKernelGGL(conv0_gn_gelu_kernel<float>, dim3((g.L[0] + kConv0Frames - 1) / kConv0Frames, B), dim3(256), 0, s, wav,
+                                   n_samples, g.L[0], c->conv0_w, sv.gn_scale, sv.gn_shift, F(lay.h0), kNoInts, kNoInts, 0LL);
             }
             const float* in = i == 1 ? F(lay.h0) : sv.u[i - 1];
             if ((rc = conv_dw(i, dU, in, (long long)Lin * 512, i != 1))) return rc;
@@ -2627,36 +2778,36 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
         p.DG = to_g0 ? nullptr : sv.u[i - 1];
         p.rmap = plain_map(1, 1);
         if (kConvK[i] == 2) {
-            p.amap = RowMap{512, (long long)(Lout + 2) * 512, Lout, 512};
+            p.amap = amap_of(512, Lout, g.pref[i]);
             p.K = 512;
             p.W = c->conv_bw2[i];
             p.N = 1024;
-            p.M = B * Lout;
-            p.cmap = RowMap{out_off, out_clip, Lout, 1024};
-            p.dgmap = RowMap{0, (long long)Lin * 512, Lout, 1024};
+            p.M = (int)g.rows[i];
+            p.cmap = cmap_of(out_off, Lout, g.pref[i]);
+            p.dgmap = dgmap_of(0, Lout, g.pref[i]);
             p.kchunk = p.K; p.ldw = p.K; p.n_valid = p.N;
             if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s))) return rc;
         } else {
             const int E = (Lin + 1) / 2, O = Lin / 2;
             // even input frames 2t': dU[t'-1] W_tap2 + dU[t'] W_tap0
-            p.amap = RowMap{0, (long long)(Lout + 2) * 512, E, 512};
+            p.amap = amap_of(0, E, g.epref[i - 1]);
             p.K = 1024;
             p.W = c->conv_bw_even[i];
             p.N = 512;
-            p.M = B * E;
-            p.cmap = RowMap{out_off, out_clip, E, 1024};
-            p.dgmap = RowMap{0, (long long)Lin * 512, E, 1024};
+            p.M = (int)g.even[i - 1];
+            p.cmap = cmap_of(out_off, E, g.epref[i - 1]);
+            p.dgmap = dgmap_of(0, E, g.epref[i - 1]);
             p.kchunk = p.K; p.ldw = p.K; p.n_valid = p.N;
             if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s))) return rc;
             // odd input frames 2t'+1: dU[t'] W_tap1
-            p.amap = RowMap{512, (long long)(Lout + 2) * 512, O, 512};
+            p.amap = amap_of(512, O, g.opref[i - 1]);
             p.K = 512;
             p.W = c->conv_bw_odd[i];
-            p.M = B * O;
-            p.cmap = RowMap{out_off + 512, out_clip, O, 1024};
-            p.dgmap = RowMap{512, (long long)Lin * 512, O, 1024};
+            p.M = (int)g.odd[i - 1];
+            p.cmap = cmap_of(out_off + 512, O, g.opref[i - 1]);
+            p.dgmap = dgmap_of(512, O, g.opref[i - 1]);
             p.kchunk = p.K; p.ldw = p.K;
-            if (O > 0 && (rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s))) return rc;
+            if (p.M > 0 && (rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s))) return rc;
         }
     }
     // ---- conv0 + GroupNorm -> d loss / d waveform -------------------------------------------------------
@@ -2667,15 +2818,17 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
         Scope sc(c, s, NOMAD_K_FRONT, 0.0);
         const dim3 grid(lay.nchunks, B);
         float* fold = F(lay.gnfold);
-        hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(lay.nstat, B), dim3(256), 0, s, wav, n_samples, sh.L[0], c->conv0_w, sv.gn_scale,
-                           sv.gn_shift, sv.gn_mean, sv.gn_rstd, G0, partial);
-        hipLaunchKernelGGL(gn_bwd_fold_kernel, dim3(B), dim3(512), 0, s, partial, lay.nstat, sh.L[0], c->conv0_w, sv.gn_scale, sv.gn_shift,
-                           sv.gn_mean, sv.gn_rstd, fold, F(lay.cwtab));
+        // (a ragged batch: grids over the longest clip's chunks, a clip's workgroups leave behind its last frame; dwav behind a
+        // clip's length keeps the zeros of the memset above)
+        hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(lay.nstat, B), dim3(256), 0, s, wav, n_samples, g.L[0], c->conv0_w, sv.gn_scale,
+                           sv.gn_shift, sv.gn_mean, sv.gn_rstd, G0, partial, g.pref[0]);
+        hipLaunchKernelGGL(gn_bwd_fold_kernel, dim3(B), dim3(512), 0, s, partial, lay.nstat, g.L[0], c->conv0_w, sv.gn_scale, sv.gn_shift,
+                           sv.gn_mean, sv.gn_rstd, fold, F(lay.cwtab), g.pref[0]);
         if (dwav)
-            hipLaunchKernelGGL(conv0_bwd_kernel, dim3((sh.L[0] + kC0Frames - 1) / kC0Frames, B), dim3(256), 0, s, wav, n_samples, sh.L[0],
-                               F(lay.cwtab), G0, dwav);
+            hipLaunchKernelGGL(conv0_bwd_kernel, dim3((g.max_l0 + kC0Frames - 1) / kC0Frames, B), dim3(256), 0, s, wav, n_samples, g.L[0],
+                               F(lay.cwtab), G0, dwav, g.pref[0]);
         if (conv_pg) {  // conv0 weight, GroupNorm gamma / beta
-            hipLaunchKernelGGL(conv0_param_partial_kernel, grid, dim3(256), 0, s, wav, n_samples, sh.L[0], c->conv0_w, sv.gn_scale,
+            hipLaunchKernelGGL(conv0_param_partial_kernel, grid, dim3(256), 0, s, wav, n_samples, g.L[0], c->conv0_w, sv.gn_scale,
                                sv.gn_shift, sv.gn_mean, sv.gn_rstd, G0, fold, lay.nchunks, F(lay.c0part));
             hipLaunchKernelGGL(conv0_param_final_kernel, dim3(24), dim3(256), 0, s, F(lay.c0part), fold, B, lay.nchunks,
                                G(po.conv0_w), G(po.gn_w), G(po.gn_b));
@@ -2683,6 +2836,52 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
+                         const float* layers_out, const void* saved, size_t saved_bytes, const float* dlayers,
+                         const float* demb, float* dwav, void* workspace, size_t workspace_bytes,
+                         nomad_stream_t stream, bool train) {
+    Shapes sh;
+    if (!c || !wav || !layers_out || !saved || !demb || (!dwav && !train) || !workspace || B <= 0 ||
+        !make_shapes(B, n_samples, &sh))
+        return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: bad argument");
+    if (!c->bwd_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: call nomad_enable_backward first");
+    if (train && !c->train_ready) return fail(NOMAD_ERR_INVALID, "nomad_train_backward: call nomad_train_enable first");
+    const BatchGeom g = geom_uniform(sh);
+    const Saved sv = make_saved(g, const_cast<void*>(saved));
+    const BwdLayout lay = make_bwd_layout(g, train, train && c->train_convnet);
+    if (saved_bytes < sv.total || workspace_bytes < lay.total)
+        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_backward: saved %zu/%zu, workspace %zu/%zu", saved_bytes, sv.total,
+                    workspace_bytes, lay.total);
+    if (train && c->branches > 1 && B % c->branches)
+        return fail(NOMAD_ERR_INVALID, "nomad_train_backward: B=%d is not %d equal branches", B, c->branches);
+    return backward_run(c, wav, g, sv, lay, head_w, head_b, layers_out, dlayers, demb, dwav, static_cast<char*>(workspace),
+                        static_cast<hipStream_t>(stream), train);
+}
+
+// nomad_embed_backward_ragged / nomad_train_backward_ragged: the ragged prologue's steps over the BwdLayout.
+static int backward_ragged(const char* who, nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, const float* head_w,
+                           const float* head_b, const float* layers_out, const void* saved, size_t saved_bytes, const float* dlayers,
+                           const float* demb, float* dwav, void* workspace, size_t workspace_bytes, nomad_stream_t stream,
+                           bool train) {
+    RaggedShapes rs;
+    if (int rc = ragged_shapes(who, c && wav && layers_out && saved && demb && (dwav || train) && workspace, B, stride, lens_host, &rs))
+        return rc;
+    if (!c->bwd_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_backward first", who);
+    if (train && !c->train_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_train_enable first", who);
+    if (train && c->train_convnet)
+        return fail(NOMAD_ERR_INVALID, "%s: a trainable conv feature extractor (nomad_train_set_convnet) needs an equal-length batch", who);
+    BatchGeom g = geom_ragged(rs, stride, nullptr);
+    const BwdLayout lay = make_bwd_layout(g, train, false);
+    const Saved sv = make_saved(g, const_cast<void*>(saved));
+    if (saved_bytes < sv.total || workspace_bytes < lay.total)
+        return fail(NOMAD_ERR_WORKSPACE, "%s: saved %zu/%zu, workspace %zu/%zu", who, saved_bytes, sv.total, workspace_bytes, lay.total);
+    if (train && c->branches > 1 && B % c->branches) return fail(NOMAD_ERR_INVALID, "%s: B=%d is not %d equal branches", who, B, c->branches);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    if (int rc = ragged_upload(c, rs, stride, reinterpret_cast<int*>(ws + lay.meta), s, &g)) return rc;
+    return backward_run(c, wav, g, sv, lay, head_w, head_b, layers_out, dlayers, demb, dwav, ws, s, train);
 }
 
 // ---- fine-tuning state ------------------------------------------------------------------------------------
@@ -2833,6 +3032,15 @@ int nomad_embed_backward(nomad_ctx* c, const float* wav, int B, int n_samples, c
                          workspace, workspace_bytes, stream, false);
 }
 
+int nomad_embed_backward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, const float* head_w,
+                                const float* head_b, const float* layers_out, const void* saved, size_t saved_bytes,
+                                const float* dlayers, const float* demb, float* dwav, void* workspace, size_t workspace_bytes,
+                                nomad_stream_t stream) {
+    if (!dwav) return fail(NOMAD_ERR_INVALID, "nomad_embed_backward_ragged: bad argument");
+    return backward_ragged("nomad_embed_backward_ragged", c, wav, B, stride, lengths_host, head_w, head_b, layers_out, saved, saved_bytes,
+                           dlayers, demb, dwav, workspace, workspace_bytes, stream, false);
+}
+
 int nomad_train_num_segments(void) { return (int)segments().size(); }
 
 int nomad_train_segment(int i, char* name, size_t name_cap, size_t* offset, size_t* count) {
@@ -2928,7 +3136,7 @@ int nomad_train_workspace_bytes(const nomad_ctx* c, int B, int n_samples, size_t
     Shapes sh;
     if (!c || !bytes || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "nomad_train_workspace_bytes: bad shape B=%d N=%d", B, n_samples);
-    *bytes = make_bwd_layout(sh, true, c->train_convnet).total;
+    *bytes = make_bwd_layout(geom_uniform(sh), true, c->train_convnet).total;
     return 0;
 }
 
@@ -2943,6 +3151,13 @@ int nomad_train_backward(nomad_ctx* c, const float* wav, int B, int n_samples, c
                          nomad_stream_t stream) {
     return backward_impl(c, wav, B, n_samples, nullptr, nullptr, layers_out, saved, saved_bytes, nullptr, demb, nullptr,
                          workspace, workspace_bytes, stream, true);
+}
+
+int nomad_train_backward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, const float* layers_out,
+                                const void* saved, size_t saved_bytes, const float* demb, void* workspace, size_t workspace_bytes,
+                                nomad_stream_t stream) {
+    return backward_ragged("nomad_train_backward_ragged", c, wav, B, stride, lengths_host, nullptr, nullptr, layers_out, saved, saved_bytes,
+                           nullptr, demb, nullptr, workspace, workspace_bytes, stream, true);
 }
 
 int nomad_triplet_loss(nomad_ctx* c, const float* a, const float* p, const float* n, int B, float margin, float* loss,
@@ -3165,12 +3380,15 @@ int nomad_paired_distance(nomad_ctx* c, const float* a, const float* b, int N, i
 
 size_t nomad_l1_scratch_bytes(void) { return sizeof(double) * (kL1Blocks + 8); }
 
-int nomad_l1_loss(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb, const float* b_emb,
-                  int B, int T, float* loss, void* scratch, nomad_stream_t stream) {
-    if (!c || !a_layers || !b_layers || !a_emb || !b_emb || !loss || !scratch || B <= 0 || T <= 0)
-        return fail(NOMAD_ERR_INVALID, "nomad_l1_loss: bad argument");
+}  // extern "C"
+
+// The L1 loss over `rows` frames of B clips: rows = B * T (nomad_l1_loss) or the packed frames of a ragged batch.
+static int l1_loss_rows(const char* who, nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb,
+                        const float* b_emb, long long rows, int B, float* loss, void* scratch, nomad_stream_t stream) {
+    if (!c || !a_layers || !b_layers || !a_emb || !b_emb || !loss || !scratch || B <= 0 || rows < B)
+        return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long per_layer = (long long)B * T * 768;
+    const long long per_layer = rows * 768;
     const long long n4 = per_layer * 12 / 4;
     double* partial = static_cast<double*>(scratch);
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
@@ -3179,6 +3397,18 @@ int nomad_l1_loss(nomad_ctx* c, const float* a_layers, const float* b_layers, co
     hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(256), 0, s, partial, (double)per_layer, (double)B * 256, loss);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+extern "C" {
+
+int nomad_l1_loss(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb, const float* b_emb,
+                  int B, int T, float* loss, void* scratch, nomad_stream_t stream) {
+    return l1_loss_rows("nomad_l1_loss", c, a_layers, b_layers, a_emb, b_emb, T > 0 ? (long long)B * T : 0, B, loss, scratch, stream);
+}
+
+int nomad_l1_loss_ragged(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb, const float* b_emb,
+                         long long M, int B, float* loss, void* scratch, nomad_stream_t stream) {
+    return l1_loss_rows("nomad_l1_loss_ragged", c, a_layers, b_layers, a_emb, b_emb, M, B, loss, scratch, stream);
 }
 
 // ---- measurement -----------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 
 #include <cstdint>
 
+#include "attention.hip.h"
 #include "backward.hip.h"
 #include "dropout.hip.h"
 #include "gemm_f32.hip.h"
@@ -280,13 +281,14 @@ __global__ __launch_bounds__(256) void head_param_grad_kernel(const float* __res
 constexpr int kPdwTaps = 8, kPdwChunk = 64;
 __global__ __launch_bounds__(256) void posconv_dw_kernel(const float* __restrict__ dug, const float* __restrict__ xg,
                                                          float* __restrict__ partial, int B, int T,
-                                                         int clips_per_split) {
+                                                         int clips_per_split, const int* __restrict__ tpref = nullptr,
+                                                         const int* __restrict__ ppref = nullptr, long long grp_stride = 0) {
     __shared__ __attribute__((aligned(16))) float dUs[kPdwChunk * 48];
     __shared__ __attribute__((aligned(16))) float Xs[(kPdwChunk + kPdwTaps) * 48];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fi = lane & 15, g4 = lane >> 4;
     const int t0 = blockIdx.x * kPdwTaps, grp = blockIdx.y, sp = blockIdx.z;
-    const int P = T + 128;
+    int P = T + 128;
     f32x4 acc[2][3][3];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -296,8 +298,14 @@ __global__ __launch_bounds__(256) void posconv_dw_kernel(const float* __restrict
             for (int j = 0; j < 3; ++j) acc[a][i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int b_end = min(B, (sp + 1) * clips_per_split);
     for (int b = sp * clips_per_split; b < b_end; ++b) {
-        const float* dub = dug + ((long long)grp * B + b) * P * 48;
-        const float* xb = xg + ((long long)grp * B + b) * P * 48;
+        long long clip0 = ((long long)grp * B + b) * P * 48;
+        if (tpref) {   // ragged batch: the clip's own frames, its block at padded frame ppref[b] of the group
+            T = tpref[b + 1] - tpref[b];
+            P = T + 128;
+            clip0 = grp * grp_stride + (long long)ppref[b] * 48;
+        }
+        const float* dub = dug + clip0;
+        const float* xb = xg + clip0;
         for (int tau0 = 0; tau0 < T; tau0 += kPdwChunk) {
             __syncthreads();
             // dU frames 64+tau0 .. +63 (always inside the clip's padded block), X frames tau0+t0 .. +71
@@ -540,10 +548,19 @@ __global__ __launch_bounds__(256) void dropout_add_kernel(const float4* __restri
 // In-place dropout of the group-major pos-conv input xg[grp][clip][64 + t][48] (element index m*768 + c as if the
 // tensor were the plain [M][768] post_extract_proj output).  grid: M blocks of 192 threads.
 __global__ __launch_bounds__(192) void dropout_groups_kernel(float* __restrict__ xg, int T, long long grp_stride,
-                                                             DropCfg d, uint32_t site) {
-    const int m = blockIdx.x, b = m / T, t = m - b * T;
+                                                             DropCfg d, uint32_t site, const int* __restrict__ tpref = nullptr,
+                                                             const int* __restrict__ ppref = nullptr, int B = 0) {
+    const int m = blockIdx.x;
+    long long frame;   // row m's frame in a group of the padded buffer
+    if (tpref) {       // ragged batch: packed rows (the mask index stays m * 768 + c), padded-frame prefix sums
+        const int lo = clip_of_row(tpref, B, m);
+        frame = (long long)ppref[lo] + 64 + (m - tpref[lo]);
+    } else {
+        const int b = m / T;
+        frame = (long long)b * (T + 128) + 64 + (m - b * T);
+    }
     const int col = threadIdx.x * 4, grp = col / 48, cc = col - grp * 48;
-    float4* p = reinterpret_cast<float4*>(xg + grp * grp_stride + ((long long)b * (T + 128) + 64 + t) * 48 + cc);
+    float4* p = reinterpret_cast<float4*>(xg + grp * grp_stride + frame * 48 + cc);
     const unsigned long long e = (unsigned long long)m * 768 + col;
     float4 v = *p;
     v.x *= drop_mult(d, site, e); v.y *= drop_mult(d, site, e + 1);

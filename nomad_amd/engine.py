@@ -454,10 +454,15 @@ class Engine:
     def l1_loss(self, a_layers, b_layers, a_emb, b_emb) -> torch.Tensor:
         for t, n in ((a_layers, "a_layers"), (b_layers, "b_layers"), (a_emb, "a_emb"), (b_emb, "b_emb")):
             self._check_dev(t, n)
-        _, B, T, _ = a_layers.shape
         if self._l1_scratch is None:
             self._l1_scratch = torch.empty(self.lib.nomad_l1_scratch_bytes(), dtype=torch.uint8, device=self.device)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        if a_layers.dim() == 3:   # packed layers (12, M, 768) of a ragged batch: means over the valid frames
+            _lib.check(self.lib.nomad_l1_loss_ragged(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(), a_emb.data_ptr(),
+                                                     b_emb.data_ptr(), a_layers.shape[1], a_emb.shape[0], loss.data_ptr(),
+                                                     self._l1_scratch.data_ptr(), self._stream()), "nomad_l1_loss_ragged")
+            return loss[0]
+        _, B, T, _ = a_layers.shape
         _lib.check(self.lib.nomad_l1_loss(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(), a_emb.data_ptr(),
                                           b_emb.data_ptr(), B, T, loss.data_ptr(), self._l1_scratch.data_ptr(),
                                           self._stream()), "nomad_l1_loss")
@@ -710,14 +715,106 @@ class Engine:
 
     def l1_loss_backward(self, a_layers, b_layers, a_emb, b_emb, upstream: torch.Tensor):
         """(d loss/d a_layers, d loss/d a_emb) for NomadLoss, scaled by the 0-dim device tensor `upstream`."""
-        _, B, T, _ = a_layers.shape
         dl = torch.empty_like(a_layers)
         de = torch.empty_like(a_emb)
         up = upstream.to(self.device, torch.float32).reshape(1).contiguous()
+        if a_layers.dim() == 3:   # packed layers (12, M, 768) of a ragged batch
+            _lib.check(self.lib.nomad_l1_loss_backward_ragged(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(), a_emb.data_ptr(),
+                                                              b_emb.data_ptr(), a_layers.shape[1], a_emb.shape[0], up.data_ptr(),
+                                                              dl.data_ptr(), de.data_ptr(), self._stream()),
+                       "nomad_l1_loss_backward_ragged")
+            return dl, de
+        _, B, T, _ = a_layers.shape
         _lib.check(self.lib.nomad_l1_loss_backward(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(), a_emb.data_ptr(),
                                                    b_emb.data_ptr(), B, T, up.data_ptr(), dl.data_ptr(), de.data_ptr(),
                                                    self._stream()), "nomad_l1_loss_backward")
         return dl, de
+
+    # ---- exact-length (ragged) batches on the gradient paths ------------------------------------------
+    def pack_ragged(self, waves, lengths=None):
+        """Clips -> (device (B, stride) fp32 buffer, lengths): what the ragged gradient calls take.  waves: a list of 1-D (or
+        (1,N)) tensors / arrays as ``embed_ragged`` takes them, or a padded (B,N) / (B,1,N) device tensor plus ``lengths``
+        (used as it is, no copy: samples behind a length are never read)."""
+        if lengths is not None:
+            wav = waves.squeeze(1) if waves.dim() == 3 else waves
+            self._check_dev(wav, "wav")
+            lens = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            if wav.dim() != 2 or len(lens) != wav.shape[0]:
+                raise ValueError("lengths must hold one entry per row of the (B,N) waveform tensor")
+            if any(n > wav.shape[1] for n in lens):
+                raise ValueError("a length exceeds the padded waveform tensor")
+            return wav, lens
+        flat = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in waves]
+        lens = [int(w.numel()) for w in flat]
+        if all(w.is_cuda for w in flat):
+            buf = torch.empty(len(flat), (max(lens) + 3) // 4 * 4, dtype=torch.float32, device=self.device)
+            for i, w in enumerate(flat):
+                buf[i, :lens[i]] = w
+            return buf, lens
+        host, lens = self.pack_ragged_host(flat)
+        return host.to(self.device, non_blocking=True), lens
+
+    def _size_ragged(self, fn, lens, what):
+        n = C.c_size_t()
+        _lib.check(fn(self.ctx, len(lens), (C.c_int * len(lens))(*lens), C.byref(n)), what)
+        return n.value
+
+    def embed_train_ragged(self, waves, lengths=None, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                           save: bool = True, side: bool = False):
+        """``embed_train`` over clips of different lengths in ONE launch sequence, no padding in the arithmetic:
+        -> (emb (B,256), packed layers (12,M,768) with M = sum of the clips' frames, saved block, (buffer, lengths)).
+        save=False: layer outputs only (no saved block - None -, no regularisation): the ragged ``LossNetLayers`` forward.
+        The last item is what ``embed_backward_ragged`` / ``train_backward_ragged`` take as their batch."""
+        buf, lens = self.pack_ragged(waves, lengths)
+        if save:
+            self.enable_backward()
+        B, stride = buf.shape
+        M = sum(num_frames(n) for n in lens)
+        arr = (C.c_int * B)(*lens)
+        emb = torch.empty(B, 256, dtype=torch.float32, device=self.device)
+        layers = torch.empty(12, M, 768, dtype=torch.float32, device=self.device)
+        saved = torch.empty(self._size_ragged(self.lib.nomad_saved_bytes_ragged, lens, "nomad_saved_bytes_ragged"),
+                            dtype=torch.uint8, device=self.device) if save else None
+        hw, hb = head if head is not None else (None, None)
+        ws = self._workspace(self._size_ragged(self.lib.nomad_workspace_bytes_ragged, lens, "nomad_workspace_bytes_ragged"), side)
+        _lib.check(self.lib.nomad_embed_train_ragged(self.ctx, buf.data_ptr(), B, stride, arr,
+                                                     hw.data_ptr() if hw is not None else None,
+                                                     hb.data_ptr() if hb is not None else None,
+                                                     emb.data_ptr(), layers.data_ptr(),
+                                                     saved.data_ptr() if save else None, saved.numel() if save else 0,
+                                                     ws.data_ptr(), ws.numel(), self._stream()), "nomad_embed_train_ragged")
+        return emb, layers, saved, (buf, lens)
+
+    def embed_backward_ragged(self, batch, layers, saved, dlayers, demb, head=None) -> torch.Tensor:
+        """d loss / d wav (B, stride) of an ``embed_train_ragged`` call (``batch``: its last result) from d loss / d layers
+        (12,M,768 or None) and d loss / d emb (B,256); zero behind every clip's length."""
+        buf, lens = batch
+        B, stride = buf.shape
+        self.enable_backward()
+        ws = self._workspace(self._size_ragged(self.lib.nomad_backward_workspace_bytes_ragged, lens,
+                                               "nomad_backward_workspace_bytes_ragged"))
+        dwav = torch.empty(B, stride, dtype=torch.float32, device=self.device)
+        hw, hb = head if head is not None else (None, None)
+        _lib.check(self.lib.nomad_embed_backward_ragged(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens),
+                                                        hw.data_ptr() if hw is not None else None,
+                                                        hb.data_ptr() if hb is not None else None,
+                                                        layers.data_ptr(), saved.data_ptr(), saved.numel(),
+                                                        dlayers.data_ptr() if dlayers is not None else None, demb.data_ptr(),
+                                                        dwav.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_embed_backward_ragged")
+        return dwav
+
+    def train_backward_ragged(self, batch, layers: torch.Tensor, saved: torch.Tensor, demb: torch.Tensor):
+        """Accumulate d loss / d parameters for one ``embed_train_ragged`` call, given d loss / d emb (B,256)."""
+        buf, lens = batch
+        self._check_dev(demb, "demb")
+        B, stride = buf.shape
+        ws = self._workspace(self._size_ragged(self.lib.nomad_train_workspace_bytes_ragged, lens,
+                                               "nomad_train_workspace_bytes_ragged"))
+        _lib.check(self.lib.nomad_train_backward_ragged(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens),
+                                                        layers.data_ptr(), saved.data_ptr(), saved.numel(), demb.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_train_backward_ragged")
 
     # ---- triplet fine-tuning step (train_triplet.py:112-133) ---------------------------------------
     @property

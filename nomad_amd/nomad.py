@@ -110,11 +110,19 @@ class LossNetLayers:
         self.embedding_weight = lin.weight.detach().to(engine.device).contiguous()
         self.embedding_bias = lin.bias.detach().to(engine.device).contiguous()
 
-    def __call__(self, wav):
-        return self.forward(wav)
+    def __call__(self, wav, lengths=None):
+        return self.forward(wav, lengths)
 
-    def forward(self, wav: torch.Tensor) -> List[torch.Tensor]:
+    def forward(self, wav: torch.Tensor, lengths=None) -> List[torch.Tensor]:
+        """lengths (B ints, tensor or list; ``wav`` (B,1,N) or (B,N), samples behind a length are never read): the clips at their
+        exact lengths in one launch sequence - 12 PACKED layer outputs (M,768), M = the sum of the clips' frames, clip after
+        clip, + the (B,256) embedding.  fp32 buffers whatever ``precision`` says (products follow ``Engine.gemm_precision``):
+        there is no ragged layer-output forward on split bf16 storage."""
         wav = wav.to(self.engine.device, torch.float32).contiguous()
+        if lengths is not None:
+            lens = check_lengths(wav, lengths)
+            emb, layers, _, _ = self.engine.embed_train_ragged(wav, lens, head=(self.embedding_weight, self.embedding_bias), save=False)
+            return [layers[i] for i in range(12)] + [emb]
         fwd = self.engine.embed_bf16x3 if _takes_bf16x3(self.precision, wav) else self.engine.embed
         emb, layers = fwd(wav, head=(self.embedding_weight, self.embedding_bias), want_layers=True)
         return [layers[i] for i in range(12)] + [emb]
@@ -145,10 +153,31 @@ class NomadLoss:
         return self.engine.l1_loss(test_layers, ref_layers, nomad_test[12].contiguous(), nomad_ref[12].contiguous())
 
 
+MIN_SAMPLES = 400   # one encoder frame (the conv stack's receptive field)
+
+
+def check_lengths(wav: torch.Tensor, lengths) -> List[int]:
+    """The ``lengths`` argument of ``Nomad.forward`` / ``LossNetLayers.forward`` as a list of ints, checked against ``wav``
+    ((B,1,N) or (B,N)): one entry per clip, each at least one encoder frame (400 samples) and at most N."""
+    if wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+        raise ValueError(f"with lengths the waveforms must be (B,1,N) or (B,N), got {tuple(wav.shape)}")
+    if torch.is_tensor(lengths):
+        if lengths.dim() != 1 or lengths.is_floating_point():
+            raise ValueError("lengths must be a 1-D integer tensor or a list of ints")
+        lengths = lengths.tolist()
+    lens = [int(n) for n in lengths]
+    if len(lens) != wav.shape[0]:
+        raise ValueError(f"lengths has {len(lens)} entries for a batch of {wav.shape[0]} clips")
+    for i, n in enumerate(lens):
+        if n < MIN_SAMPLES or n > wav.shape[-1]:
+            raise ValueError(f"lengths[{i}] = {n} is outside [{MIN_SAMPLES}, {wav.shape[-1]}]")
+    return lens
+
+
 def _stack_layers(layers) -> torch.Tensor:
-    """The 12 tensors LossNetLayers returns are views of one (12,B,T,768) buffer: reuse it."""
+    """The 12 tensors LossNetLayers returns are views of one (12,B,T,768) buffer (a ragged batch: (12,M,768)): reuse it."""
     base = layers[0]._base if layers[0]._base is not None else None
-    if base is not None and base.dim() == 4 and base.shape[0] == 12 and all(
+    if base is not None and base.dim() == layers[0].dim() + 1 and base.shape[0] == 12 and all(
             l._base is base and l.data_ptr() == base[i].data_ptr() for i, l in enumerate(layers)):
         return base
     return torch.stack([l.contiguous() for l in layers])
@@ -214,6 +243,55 @@ class _NomadLossFn(torch.autograd.Function):
             dl, de = eng.l1_loss_backward(c_layers, e_layers, c_emb, e_emb, grad_out)
             dcln = eng.embed_backward(cln, c_layers, saved_c, dl, de, head).reshape(ctx.shapes[1])
         return dwav, dcln, None
+
+
+class _NomadLossRaggedFn(torch.autograd.Function):
+    """``_NomadLossFn`` over clips at their exact lengths (``Nomad.forward(estimate, clean, lengths)``): both branches run the ragged
+    forward on fp32 buffers (no padding in the arithmetic, packed layer outputs), the loss terms are means over the valid frames, and
+    the gradient is zero behind every length."""
+
+    @staticmethod
+    def forward(ctx, estimate, clean, nomad, lens):
+        eng = nomad.engine
+        head = (nomad.lossnet_layers.embedding_weight, nomad.lossnet_layers.embedding_bias)
+        est = estimate.detach().to(eng.device, torch.float32).contiguous()
+        cln = clean.detach().to(eng.device, torch.float32).contiguous()
+        need_grad = estimate.requires_grad
+        need_clean_grad = clean.requires_grad
+        cur = torch.cuda.current_stream(eng.device)
+        if need_clean_grad:   # (one training-mode workspace per context: on the caller's stream, as in _NomadLossFn)
+            c_emb, c_layers, saved_c, c_batch = eng.embed_train_ragged(cln, lens, head)
+        else:
+            side = eng.side_stream()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                c_emb, c_layers, saved_c, c_batch = eng.embed_train_ragged(cln, lens, head, save=False, side=True)
+        e_emb, e_layers, saved, e_batch = eng.embed_train_ragged(est, lens, head, save=need_grad)
+        if not need_clean_grad:
+            cur.wait_stream(side)
+            for t in (c_emb, c_layers, cln):
+                t.record_stream(cur)
+        loss = eng.l1_loss(e_layers, c_layers, e_emb, c_emb)
+        if need_grad or need_clean_grad:
+            ctx.nomad = nomad
+            ctx.lens = lens
+            ctx.shapes = (estimate.shape, clean.shape)
+            ctx.save_for_backward(e_batch[0], e_layers, e_emb, c_batch[0], c_layers, c_emb, saved, saved_c)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        est, e_layers, e_emb, cln, c_layers, c_emb, saved, saved_c = ctx.saved_tensors
+        eng = ctx.nomad.engine
+        head = (ctx.nomad.lossnet_layers.embedding_weight, ctx.nomad.lossnet_layers.embedding_bias)
+        dwav = dcln = None
+        if saved is not None and ctx.needs_input_grad[0]:
+            dl, de = eng.l1_loss_backward(e_layers, c_layers, e_emb, c_emb, grad_out)
+            dwav = eng.embed_backward_ragged((est, ctx.lens), e_layers, saved, dl, de, head).reshape(ctx.shapes[0])
+        if saved_c is not None and ctx.needs_input_grad[1]:
+            dl, de = eng.l1_loss_backward(c_layers, e_layers, c_emb, e_emb, grad_out)
+            dcln = eng.embed_backward_ragged((cln, ctx.lens), c_layers, saved_c, dl, de, head).reshape(ctx.shapes[1])
+        return dwav, dcln, None, None
 
 
 class GraphedLoss:
@@ -632,18 +710,33 @@ class Nomad:
             _write_rounded_csv(df_dm.reset_index(), results_scores_path)
         return df_avg_nomad, df_dm
 
-    def forward(self, estimate, clean):
+    def forward(self, estimate, clean, lengths=None):
         """NOMAD loss (nomad.py:142-146), differentiable w.r.t. ``estimate``.
+
+        lengths (B ints, tensor or list; ``estimate`` and ``clean`` (B,1,N) or (B,N)): the exact-length loss - utterance b is the
+        first ``lengths[b]`` samples of its row, the samples behind are never read, and nothing is padded in the arithmetic
+        (zero padding would change GroupNorm statistics, attention and the time mean, hence the loss).  Every layer term is the
+        mean over the valid frames of all clips, as ``F.l1_loss`` on their concatenation; the gradient is zero behind each
+        length.  Differentiable in ``estimate`` (and in ``clean`` when it requires a gradient); the no-gradient branch runs on the
+        side stream.  With ``precision="bf16x3"`` both branches stay on fp32 buffers with bf16x3 products: there is no ragged
+        layer-output forward on split bf16 storage.  ``lengths=None`` is the equal-length path, unchanged.
 
         The whole forward and backward run in the HIP engine (``torch.autograd.Function`` glue only).  As in the
         reference, the gradient that reaches ``estimate`` carries fairseq's ``feature_grad_mult`` (0.1 for wav2vec 2.0
         BASE; ``Nomad(feature_grad_mult=...)`` / ``self.engine.feature_grad_mult``).  The backbone is frozen: the reference would also accumulate parameter gradients nobody reads
         (the freeze is commented out at nomad.py:74-76); ``clean`` receives no gradient."""
+        if lengths is not None:
+            if estimate.shape != clean.shape:
+                raise ValueError(f"estimate {tuple(estimate.shape)} and clean {tuple(clean.shape)} must have one shape")
+            return _NomadLossRaggedFn.apply(estimate, clean, self, check_lengths(estimate, lengths))
         return _NomadLossFn.apply(estimate, clean, self)
 
-    def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor) -> "GraphedLoss":
+    def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor, lengths=None) -> "GraphedLoss":
         """``forward`` + backward for inputs of this shape, captured as one HIP graph (see ``GraphedLoss``): for training loops with
         a fixed batch shape - the per-step launch overhead of ~440 small kernels disappears, the bits do not change."""
+        if lengths is not None:
+            raise ValueError("GraphedLoss captures ONE batch shape: exact lengths (a different geometry every step) are not captured; "
+                             "use nomad.forward(estimate, clean, lengths)")
         return GraphedLoss(self, estimate, clean)
 
     def _all_gather_rows(self, x: torch.Tensor) -> torch.Tensor:

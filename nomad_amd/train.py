@@ -30,6 +30,13 @@ Differences, on purpose:
   ``eval_*`` method returns what it printed from (the reference returns nothing); figures are drawn with matplotlib alone
   (no seaborn) and skipped with one printed line when matplotlib is missing; the dead PCA block (``pca_plot = False``) is not
   built; no optimiser state is allocated.
+* ``pad_mode`` (not a reference key): ``"batch"`` (default) zero-pads each of A / P / N to its own batch maximum with no mask, as
+  the reference's collate does - a clip's training embedding then depends on the longest clip that happens to share its batch.
+  ``"exact"`` departs from the reference on purpose: the collate keeps the lengths, a step is ALWAYS one merged launch sequence
+  over the 3B clips at their exact lengths (nomad_embed_train_ragged / nomad_train_backward_ragged, LayerDrop per branch) and
+  validation embeds through nomad_embed_ragged - the arithmetic ``predict`` and the evaluation experiments score the model
+  with, and no time spent on padded frames.  ``freeze_convnet: False`` is refused with it (the conv extractor's parameter
+  gradients need equal-length batches).
 * model.train() regularisation (fairseq BASE config: dropout 0.1, attention_dropout 0.1, dropout_input 0.1,
   encoder_layerdrop 0.05) uses the engine's counter-based masks; torch's RNG stream of the reference's device cannot
   be reproduced on any other device, so runs are statistically, not bit-wise, equivalent to the reference's.
@@ -51,6 +58,18 @@ from .nomad import Nomad, Origw2v, TripletModel
 from .weights import EMB_DIM, EMBED_DIM, check_state_dict, expected_shapes, load_checkpoint, seeded_state_dict
 
 SEED = 0  # train_triplet.py:29-33
+PAD_MODES = ("batch", "exact")   # config key pad_mode (module docstring)
+
+
+def check_pad_mode(config) -> str:
+    """The config's ``pad_mode`` (default "batch"), validated together with the switches it excludes."""
+    mode = config.get("pad_mode", "batch")
+    if mode not in PAD_MODES:
+        raise ValueError(f"pad_mode must be one of {PAD_MODES}, got {mode!r}")
+    if mode == "exact" and not config.get("freeze_convnet", True) and not config.get("freeze_all"):
+        raise ValueError("pad_mode 'exact' needs freeze_convnet: True: the conv feature extractor's parameter gradients are built for "
+                         "equal-length batches only")
+    return mode
 
 # fairseq wav2vec 2.0 BASE pre-training config (what wav2vec_small.pt carries in its cfg)
 W2V_BASE_REGULARISATION = dict(dropout=0.1, attention_dropout=0.1, dropout_input=0.1, encoder_layerdrop=0.05)
@@ -73,6 +92,7 @@ class TripletDataset(torch.utils.data.Dataset):
         if level is not None:
             self.dataset = self.dataset[self.dataset["db"].isin(level)]
         self.dataset = self.dataset.drop_duplicates()
+        self.pad_mode = check_pad_mode(self.config)
 
     def __len__(self):
         return len(self.dataset)
@@ -84,7 +104,21 @@ class TripletDataset(torch.utils.data.Dataset):
 
     def collate_fn(self, batch):  # zero padding at batch level
         A, P, N = zip(*batch)
+        if getattr(self, "pad_mode", "batch") == "exact":
+            return self.collate_exact(A, P, N)
         return self.zero_pad_wav(A), self.zero_pad_wav(P), self.zero_pad_wav(N)
+
+    @staticmethod
+    def collate_exact(A, P, N):
+        """pad_mode "exact": every branch as (rows (B,1,Nmax), lengths (B,) int32) with ONE Nmax for the 3B clips, so that the step
+        stacks them without a copy per clip; the samples behind a length are storage only - the engine never reads them."""
+        max_len = max(w.shape[1] for w in A + P + N)
+        def rows(wavs):
+            out = torch.zeros(len(wavs), 1, max_len, dtype=torch.float32)
+            for i, w in enumerate(wavs):
+                out[i, 0, :w.shape[1]] = w[0]
+            return out, torch.tensor([w.shape[1] for w in wavs], dtype=torch.int32)
+        return rows(A), rows(P), rows(N)
 
     @staticmethod
     def zero_pad_wav(wavs):
@@ -330,6 +364,7 @@ class Training:
         else:
             with open(config_file) as file:
                 self.config = yaml.load(file, Loader=yaml.FullLoader)
+        self.pad_mode = check_pad_mode(self.config)   # (a config error is reported as one, with or without a GPU)
         if not torch.cuda.is_available():
             raise RuntimeError("nomad_amd.train needs an MI355X: the engine has no CPU path")
         self.DEVICE = torch.device("cuda", device)
@@ -417,6 +452,8 @@ class Training:
         """A_embs = model(A); P_embs = model(P); N_embs = model(N); loss = criterion(...); zero_grad; backward; step.
         Returns the loss as a 1-element device tensor (no host sync here)."""
         eng = self.engine
+        if isinstance(A, (tuple, list)):   # pad_mode "exact": (rows, lengths) per branch
+            return self._step_exact(A, P, N, training)
         wavs = [w.to(self.DEVICE, torch.float32, non_blocking=True).squeeze(1).contiguous() for w in (A, P, N)]
         if not training:
             # model.eval(): clips are independent and the engine is batch invariant bit for bit, so the three
@@ -458,6 +495,36 @@ class Training:
         eng.train_set_stochastic()
         if self.group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
             allreduce_mean_gradients(eng, self.group)  # data parallel: every rank saw its own triplets
+        lr_body, lr_head = self.lr_scheduler.get_last_lr()
+        eng.adam_step(lr_body, lr_head)
+        return loss
+
+    def _step_exact(self, A, P, N, training: bool) -> torch.Tensor:
+        """``train_step`` for pad_mode "exact": A / P / N are (rows (B,1,Nmax) or (B,Nmax), lengths (B,)) with one Nmax.  Always ONE
+        launch sequence over the 3B clips at their exact lengths; validation (training=False) embeds through ``embed_ragged``."""
+        eng = self.engine
+        rows = [w.to(self.DEVICE, torch.float32, non_blocking=True) for w, _ in (A, P, N)]
+        rows = [w.squeeze(1) if w.dim() == 3 else w for w in rows]
+        if not (rows[0].shape == rows[1].shape == rows[2].shape):
+            raise ValueError("pad_mode 'exact': the three branches must share one (B, Nmax) storage shape (TripletDataset.collate_exact)")
+        lens = [int(n) for _, l in (A, P, N) for n in (l.tolist() if torch.is_tensor(l) else l)]
+        B = rows[0].shape[0]
+        w = torch.cat(rows, dim=0).contiguous()
+        if not training:
+            e = eng.embed_ragged(None, packed=(w, lens))
+            return eng.triplet_loss(e[:B].contiguous(), e[B:2 * B].contiguous(), e[2 * B:].contiguous(), self.margin,
+                                    want_grad=False)[0]
+        draws = [self._draw() for _ in range(3)]
+        eng.train_set_stochastic(**dict(draws[0], layer_mask=0xFFF))
+        eng.train_set_branches([x["layer_mask"] for x in draws])
+        emb, layers, saved, batch = eng.embed_train_ragged(w, lens)
+        loss, da, dp, dn = eng.triplet_loss(emb[:B].contiguous(), emb[B:2 * B].contiguous(), emb[2 * B:].contiguous(), self.margin)
+        eng.train_zero_grad()
+        eng.train_backward_ragged(batch, layers, saved, torch.cat([da, dp, dn], dim=0))
+        eng.train_set_branches(None)
+        eng.train_set_stochastic()
+        if self.group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            allreduce_mean_gradients(eng, self.group)
         lr_body, lr_head = self.lr_scheduler.get_last_lr()
         eng.adam_step(lr_body, lr_head)
         return loss
