@@ -312,6 +312,61 @@ int nomad_l1_loss_backward_ragged(nomad_ctx* ctx, const float* a_layers_dev, con
                                   const float* a_emb_dev, const float* b_emb_dev, long long M, int B,
                                   const float* upstream_dev, float* dlayers_dev, float* demb_dev, nomad_stream_t stream);
 
+/* ---- NomadLoss with layer weights and per-utterance terms; the encoder cut at depth ------------------------
+ * The reference's NomadLoss loops `for i in range(self.L)` (nomad.py:264, :276; L = 13): a caller who lowers L trains against the first
+ * L terms only.  These entry points give that, a weight per term, and one loss per utterance - and let the encoder stop behind the
+ * deepest layer the loss reads.  The 13-term mean of nomad_l1_loss[_ragged] and its kernels are untouched.
+ *
+ * nomad_l1_loss_weighted: both layouts of the layer tensors in one call - a_layers_dev / b_layers_dev are [12][M][768], M frames in
+ * all, clip b's rows being frames_host[b] consecutive ones (HOST array of B counts, each >= 1, summing to M; NULL: M / B frames each,
+ * i.e. [12][B][T][768]); a_emb_dev / b_emb_dev [B][256].
+ *   S[i][b]       sum of fabsf(a - b) over clip b's rows of layer i (i = 12: its 256 embedding values): differences in fp32,
+ *                 accumulated in fp64 over chunks of 16 frames counted from the clip's first frame, chunk sums folded in chunk order.
+ *                 No atomics: identical run to run, and a function of the clip's own values only.
+ *   weights_host  [13] fp32 on the HOST, finite, >= 0, not all 0 (term 12 is the embedding).  A weight of 0 means the term's tensors
+ *                 are NOT READ (not multiplied by 0): behind a cut encoder they hold whatever the caller's buffer held, and the
+ *                 pointers of tensors no term with a weight reads may be NULL.
+ *   reduction     NOMAD_L1_PER_CLIP: loss_dev[b] = (float) sum_i w_i S[i][b] / n[i][b], n = T_b * 768 (256 for the embedding), [B];
+ *                 NOMAD_L1_BATCH:    loss_dev[0] = (float) sum_i w_i (sum_b S[i][b]) / (sum_b n[i][b]) - the meaning of
+ *                 nomad_l1_loss[_ragged], with weights.  i and b ascending, combined in fp64.
+ *   terms_dev     optional [13][B] float64 (out): the per-clip means S / n; 0 where the weight is 0.  NULL: not wanted.
+ *   scratch_dev   nomad_l1_weighted_scratch_bytes(M, B) bytes - a function of (M, B) only.
+ * nomad_l1_loss_weighted_backward: dlayers_dev [12][M][768], rows of clip b in layer i = sign(a - b) * w_i / n * upstream (one
+ * rounding) - per clip upstream_dev[b] ([B]) and n = n[i][b]; batch upstream_dev[0] and n = sum_b n[i][b]; demb_dev [B][256] by the
+ * same rule.  `depth` (1 .. 12; below 12 every weight from `depth` on must be 0): layers below it with weight 0 are written as zeros,
+ * layers at or above it are NOT WRITTEN; demb_dev is not written when w_12 = 0 and may then be NULL.
+ * Contract: asynchronous, no allocation; the prefix sums of frames_host are copied into the scratch ahead of the kernels, as the
+ * ragged entry points queue their metadata; argument errors return their status before anything is queued.  Per clip, loss[b] and the
+ * clip's rows of dlayers depend on that clip's values only: on the outputs of the ragged forward (which never splits K) loss[b] is
+ * the bits of the clip's own B = 1 call.
+ */
+enum { NOMAD_L1_BATCH = 0, NOMAD_L1_PER_CLIP = 1 };
+int nomad_l1_weighted_scratch_bytes(long long M, int B, size_t* bytes);
+int nomad_l1_loss_weighted(nomad_ctx* ctx, const float* a_layers_dev, const float* b_layers_dev, const float* a_emb_dev,
+                           const float* b_emb_dev, long long M, int B, const int* frames_host, const float* weights_host,
+                           int reduction, float* loss_dev, double* terms_dev, void* scratch_dev, size_t scratch_bytes,
+                           nomad_stream_t stream);
+int nomad_l1_loss_weighted_backward(nomad_ctx* ctx, const float* a_layers_dev, const float* b_layers_dev, const float* a_emb_dev,
+                                    const float* b_emb_dev, long long M, int B, const int* frames_host, const float* weights_host,
+                                    int reduction, int depth, const float* upstream_dev, float* dlayers_dev, float* demb_dev,
+                                    void* scratch_dev, size_t scratch_bytes, nomad_stream_t stream);
+/*
+ * Encoder depth, per context like nomad_set_feature_grad_mult: 1 .. 12, default 12.  While it is k < 12
+ *   - nomad_embed WITH layers_dev, nomad_embed_train and nomad_embed_train_ragged run the conv stack, the projection, the pos-conv and
+ *     encoder layers 0 .. k - 1, then stop: rows [k, 12) of layers_dev and emb_dev are not written, the head is not launched.
+ *     Workspace and saved-block sizes stay functions of the geometry (their tail is unused);
+ *   - nomad_embed_backward[_ragged] start at layer k - 1 with dlayers_dev[k - 1] as the only incoming gradient: no head backward,
+ *     demb_dev is ignored and may be NULL, rows >= k of dlayers_dev are not read, dlayers_dev itself is required;
+ *   - every other forward and the fine-tuning backward return NOMAD_ERR_INVALID with a message that names the depth (nomad_embed without
+ *     layers_dev, nomad_embed_ragged, nomad_embed_features*, every bf16 / bf16x3 entry point, nomad_train_backward*): a truncated
+ *     encoder behind a score or a fine-tuning step is never a silent result.
+ * Bits: with loss weights that are 0 from layer k on (w_12 = 0 too) layer outputs 0 .. k - 1, the loss and dwav of the run at depth k
+ * are those of the run at depth 12 - there the upper layers only propagate exact zeros - and the equal-length path's split-K choice
+ * depends on the batch's frames, not on the depth.
+ */
+int nomad_set_encoder_depth(nomad_ctx* ctx, int depth);
+int nomad_get_encoder_depth(const nomad_ctx* ctx, int* depth);
+
 /* ---- triplet fine-tuning step (src/training/train_triplet.py:112-133, src/config/train_triplet.yaml) ---- */
 /*
  * The reference fine-tunes wav2vec 2.0 + head with A/P/N forwards, nn.TripletMarginLoss(margin),

@@ -81,6 +81,13 @@ SIGNATURES = {
                                               _fp, C.c_size_t, _fp]),
     "nomad_l1_loss_ragged": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp, _fp, _fp]),
     "nomad_l1_loss_backward_ragged": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp, _fp, _fp, _fp]),
+    "nomad_l1_weighted_scratch_bytes": (C.c_int, [C.c_longlong, C.c_int, C.POINTER(C.c_size_t)]),
+    "nomad_l1_loss_weighted": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_float), C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_l1_loss_weighted_backward": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_float), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_set_encoder_depth": (C.c_int, [C.c_void_p, C.c_int]),
+    "nomad_get_encoder_depth": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "nomad_train_param_count": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "nomad_train_num_segments": (C.c_int, []),
     "nomad_train_segment": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -166,6 +173,9 @@ def load(diag=None):
     _libs[diag] = lib
     return lib
 
+
+# reduction argument of nomad_l1_loss_weighted* (include/nomad_hip.h)
+L1_REDUCTION = {"mean": 0, "none": 1}
 
 # precision argument of nomad_embed_features* (include/nomad_hip.h)
 PRECISION = {"fp32": 0, "bf16x3": 1, "bf16": 2}

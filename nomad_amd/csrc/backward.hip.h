@@ -339,6 +339,52 @@ __global__ __launch_bounds__(256) void l1_bwd_kernel(const float4* __restrict__ 
     }
 }
 
+// nomad_l1_loss_weighted's backward, over the chunks of l1w_partial_kernel (rowops.hip.h).  grid: (chunks of the batch, depth + 1 if the
+// embedding has a weight).  Rows of clip b in layer i < depth: sign(a - b) * w_i / n * upstream, formed in fp64 and rounded once - per
+// clip n = T_b * 768 and upstream[b], else n = M * 768 and upstream[0] (the embedding: 256 / B * 256); a layer with weight 0 is written
+// as zeros without a read.  Layers >= depth are not written.
+__global__ __launch_bounds__(256) void l1w_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, long long M,
+                                                      const float* __restrict__ ea, const float* __restrict__ eb, int B,
+                                                      const int* __restrict__ meta, L1Weights wt, int depth, int per_clip,
+                                                      const float* __restrict__ upstream, float* __restrict__ dl,
+                                                      float* __restrict__ de) {
+    const int i = (int)blockIdx.y < depth ? (int)blockIdx.y : 12;
+    const float w = wt.w[i];
+    if (i == 12) {
+        if ((int)blockIdx.x >= B) return;
+        const int clip = blockIdx.x;
+        const float sc = (float)((double)w * (double)upstream[per_clip ? clip : 0] / (per_clip ? 256.0 : (double)B * 256.0));
+        const long long e = (long long)clip * 256 + threadIdx.x;
+        const float x = ea[e], y = eb[e];
+        de[e] = x > y ? sc : (x < y ? -sc : 0.f);
+        return;
+    }
+    const int* pref = meta;
+    const int* cpref = meta + B + 1;
+    const int clip = l1w_clip_of(cpref, B, (int)blockIdx.x);
+    const long long f0 = pref[clip] + (long long)((int)blockIdx.x - cpref[clip]) * kL1wChunk;
+    const long long left = pref[clip + 1] - f0;
+    const int n4 = (int)(left < kL1wChunk ? left : kL1wChunk) * 192;
+    float4* o4 = reinterpret_cast<float4*>(dl + ((long long)i * M + f0) * 768);
+    if (w == 0.f) {
+        for (int k = threadIdx.x; k < n4; k += 256) o4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const double n = per_clip ? (double)(pref[clip + 1] - pref[clip]) * 768.0 : (double)M * 768.0;
+    const float sc = (float)((double)w * (double)upstream[per_clip ? clip : 0] / n);
+    const float4* a4 = reinterpret_cast<const float4*>(a + ((long long)i * M + f0) * 768);
+    const float4* b4 = reinterpret_cast<const float4*>(b + ((long long)i * M + f0) * 768);
+    for (int k = threadIdx.x; k < n4; k += 256) {
+        const float4 x = a4[k], y = b4[k];
+        float4 r;
+        r.x = x.x > y.x ? sc : (x.x < y.x ? -sc : 0.f);
+        r.y = x.y > y.y ? sc : (x.y < y.y ? -sc : 0.f);
+        r.z = x.z > y.z ? sc : (x.z < y.z ? -sc : 0.f);
+        r.w = x.w > y.w ? sc : (x.w < y.w ? -sc : 0.f);
+        o4[k] = r;
+    }
+}
+
 // (attention backward: attention_bwd.hip.h)
 
 // ---- conv0 + GroupNorm backward ---------------------------------------------------------------------

@@ -253,6 +253,9 @@ struct nomad_ctx {
     // fairseq Wav2Vec2Model.feature_grad_mult: the gradient entering the conv feature extractor is scaled by this
     // (GradMultiply on the extractor's output); 0.1 in the wav2vec 2.0 BASE config that wav2vec_small.pt carries
     float feature_grad_mult = 0.1f;
+    // nomad_set_encoder_depth: the layer-output forwards of the loss (nomad_embed with layers_dev, nomad_embed_train[_ragged]) and
+    // nomad_embed_backward[_ragged] run encoder layers 0 .. encoder_depth - 1 only; every other forward refuses while it is below 12
+    int encoder_depth = NOMAD_NUM_LAYERS;
     // nomad_set_gemm_precision: 1 = the fp32-layout GEMMs (forward, nomad_embed_train, backward, dW) form their products as
     // three bf16 MFMA products over hi / lo halves split in registers (gemm_f32_glds_kernel<..., X3>); buffers stay fp32
     int gemm_x3 = 0;
@@ -269,6 +272,9 @@ struct nomad_ctx {
     // forwards enqueued back to back on different streams do not share a staging vector
     std::vector<int> ragged_meta_ring[16];   // kMetaRing (nomad_hip.hip: ragged_upload)
     unsigned ragged_seq = 0;
+    // the same for the frame / chunk prefix sums of nomad_l1_loss_weighted[_backward] (a ring of its own: a loss step queues up to three)
+    std::vector<int> l1w_meta_ring[16];
+    unsigned l1w_seq = 0;
     // profiling
     bool prof = false;
     std::vector<hipEvent_t> ev;   // grows on demand (Scope): a long timed region is never silently truncated

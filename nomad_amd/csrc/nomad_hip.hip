@@ -752,6 +752,14 @@ int run_dropout(nomad_ctx* c, const float* x, const float* resid, float* y, long
     return 0;
 }
 
+// nomad_set_encoder_depth below 12: only the loss's layer-output forwards and their backward run a cut encoder; every other entry
+// point refuses before anything is queued - a truncated encoder behind a score or a fine-tuning step is never a silent result.
+int refuse_cut(const nomad_ctx* c, const char* who) {
+    if (!c || c->encoder_depth == NOMAD_NUM_LAYERS) return 0;
+    return fail(NOMAD_ERR_INVALID, "%s: the encoder depth is %d (nomad_set_encoder_depth): only nomad_embed with layers_dev, "
+                "nomad_embed_train[_ragged] and nomad_embed_backward[_ragged] run a cut encoder", who, c->encoder_depth);
+}
+
 }  // namespace
 
 extern "C" {
@@ -998,6 +1006,9 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
                        const Saved* sv, bool features = false) {
     if (g.ragged() && splitk_block) return fail(NOMAD_ERR_INVALID, "fp32 forward: split-K needs an equal-length batch");
     const int B = g.B, T = g.T, M = (int)g.rows[6];
+    // nomad_set_encoder_depth: layers 0 .. depth - 1, then stop - no head, rows [depth, 12) of layers_out and emb stay unwritten
+    const int depth = c->encoder_depth;
+    if (depth < NOMAD_NUM_LAYERS && (!layers_out || features)) return refuse_cut(c, "fp32 forward");
     // the loss forward of Nomad.forward() (saving activations, not fine-tuning): small-M GEMMs may split K.  Round 4: so may the
     // other branch of that loss - a forward that returns the 12 layer outputs (LossNetLayers: `clean`, or `estimate` under
     // no_grad) on fewer than 4096 frames.  The split is a function of the GEMM shape only (fixed slices, ordered fold): the
@@ -1190,7 +1201,7 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
         if (d_res.threshold && (rc = run_dropout(c, y2, x2s, y2, acts, d_res, site_ffn(l), s, idx0))) return rc;
         return ln_after(y2, d.ln2_w, d.ln2_b, xs, lo);
     };
-    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
+    for (int l = 0; l < depth; ++l) {
         unsigned all = 1u, any = 0u;
         for (int br = 0; br < nbr; ++br) {
             all &= (bmask[br] >> l) & 1u;
@@ -1215,6 +1226,9 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
 
     // ---- head -----------------------------------------------------------------------------------
     // the FFN hidden buffer is dead by now: scratch for the time sums
+    // (a cut encoder has no embedding: every layer's LayerNorm - fused into a split-K epilogue or not - and its copy into layers_out
+    // are complete when run_layer returns, so there is nothing else to flush)
+    if (depth < NOMAD_NUM_LAYERS) return 0;
     return run_head<float>(c, x, B, g.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb, g.pref[6], bf.h, s, features);
 }
 
@@ -1881,6 +1895,7 @@ int nomad_workspace_bytes_bf16(const nomad_ctx* c, int B, int n_samples, size_t*
 
 int nomad_embed_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, float* emb, void* workspace,
                      size_t workspace_bytes, nomad_stream_t stream) {
+    if (int rc = refuse_cut(c, "nomad_embed_bf16")) return rc;
     return forward_bf16(c, wav, B, n_samples, emb, workspace, workspace_bytes, stream);
 }
 
@@ -1948,17 +1963,20 @@ int nomad_workspace_bytes_ragged_bf16x3(const nomad_ctx* c, int B, const int* le
 
 int nomad_embed_ragged_bf16x3(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, float* emb,
                               void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    if (int rc = refuse_cut(c, "nomad_embed_ragged_bf16x3")) return rc;
     return forward_ragged_x3(c, wav, B, stride, lengths_host, emb, workspace, workspace_bytes, stream);
 }
 
 int nomad_embed_bf16x3(nomad_ctx* c, const float* wav, int B, int n_samples, float* emb, void* workspace,
                        size_t workspace_bytes, nomad_stream_t stream) {
+    if (int rc = refuse_cut(c, "nomad_embed_bf16x3")) return rc;
     return forward_x3(c, wav, B, n_samples, emb, workspace, workspace_bytes, stream);
 }
 
 int nomad_embed_layers_bf16x3(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
                               float* emb, float* layers_out, void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
     if (!layers_out) return fail(NOMAD_ERR_INVALID, "nomad_embed_layers_bf16x3: layers_out is NULL");
+    if (int rc = refuse_cut(c, "nomad_embed_layers_bf16x3")) return rc;   // (no depth cut on split bf16 storage)
     return forward_x3(c, wav, B, n_samples, emb, workspace, workspace_bytes, stream, head_w, head_b, layers_out);
 }
 
@@ -2004,6 +2022,7 @@ int nomad_workspace_bytes_ragged_bf16(const nomad_ctx* c, int B, const int* leng
 
 int nomad_embed_ragged_bf16(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, float* emb,
                             void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    if (int rc = refuse_cut(c, "nomad_embed_ragged_bf16")) return rc;
     return forward_ragged_bf16(c, wav, B, stride, lengths_host, emb, workspace, workspace_bytes, stream);
 }
 
@@ -2164,6 +2183,8 @@ int nomad_diag_gemm_bf16(nomad_ctx* c, const void* A, const void* W, const float
 
 int nomad_embed(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
                 float* emb, float* layers_out, void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    if (!layers_out)   // the scoring forward; with layers_out it is the loss's no-gradient branch, which runs a cut encoder
+        if (int rc = refuse_cut(c, "nomad_embed without layers_dev")) return rc;
     return forward_impl(c, wav, B, n_samples, head_w, head_b, emb, layers_out, workspace, workspace_bytes, stream, nullptr);
 }
 
@@ -2176,6 +2197,7 @@ int nomad_workspace_bytes_ragged(const nomad_ctx* c, int B, const int* lengths_h
 
 int nomad_embed_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, const float* head_w,
                        const float* head_b, float* emb, void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    if (int rc = refuse_cut(c, "nomad_embed_ragged")) return rc;
     return forward_ragged(c, wav, B, stride, lengths_host, head_w, head_b, emb, workspace, workspace_bytes, stream);
 }
 
@@ -2183,6 +2205,7 @@ int nomad_embed_ragged(nomad_ctx* c, const float* wav, int B, int stride, const 
 int nomad_embed_features(nomad_ctx* c, const float* wav, int B, int n_samples, int precision, float* feat, void* workspace,
                          size_t workspace_bytes, nomad_stream_t stream) {
     static const char who[] = "nomad_embed_features";
+    if (int rc = refuse_cut(c, who)) return rc;
     switch (precision) {
         case NOMAD_PRECISION_F32:
             return forward_impl(c, wav, B, n_samples, nullptr, nullptr, feat, nullptr, workspace, workspace_bytes, stream, nullptr, who, true);
@@ -2197,6 +2220,7 @@ int nomad_embed_features(nomad_ctx* c, const float* wav, int B, int n_samples, i
 int nomad_embed_features_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, int precision,
                                 float* feat, void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
     static const char who[] = "nomad_embed_features_ragged";
+    if (int rc = refuse_cut(c, who)) return rc;
     switch (precision) {
         case NOMAD_PRECISION_F32:
             return forward_ragged(c, wav, B, stride, lengths_host, nullptr, nullptr, feat, workspace, workspace_bytes, stream, who, true);
@@ -2479,8 +2503,13 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
     // parameter gradients of the ENCODER (pos-conv, encoder LayerNorm, the 12 layers): not with freeze_all, where only
     // post_extract_proj, the feature LayerNorm and the head stay trainable (train_triplet.py:76-79)
     const bool pg = train && !c->freeze_encoder;
+    // nomad_set_encoder_depth: the forward stopped behind layer depth - 1.  No head; the gradient that enters that layer is
+    // dlayers[depth - 1] alone, so its LayerNorm backward reads it in gx's place (first_cut) - what the uncut run computes from a gx
+    // of exact zeros plus that row.  Rows >= depth of dlayers and demb are not read.
+    const int depth = train ? NOMAD_NUM_LAYERS : c->encoder_depth;
+    bool first_cut = depth < NOMAD_NUM_LAYERS;
     // ---- head -> d loss / d x_12 -------------------------------------------------------------------
-    {
+    if (!first_cut) {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
         hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(1024), 0, s, layers_out + (size_t)11 * M * 768, T,
                            head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, demb, gx,
@@ -2509,7 +2538,10 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
               *dqkvs = dqkv + r0 * 2304, *dmasks = dmask ? dmask + r0 * 768 : nullptr;
         const float* dl = dlayers ? dlayers + (size_t)l * M * 768 + r0 * 768 : nullptr;
         int rc;
-        if (!lnb_prefused && (rc = run_ln_bwd(c, y2, gxs, dl, d.ln2_w, dyas, Ms, 768, s))) return rc;   // dy2 (prefused: by the layer above's last GEMM)
+        if (first_cut) {
+            if ((rc = run_ln_bwd(c, y2, dl, nullptr, d.ln2_w, dyas, Ms, 768, s))) return rc;
+        } else if (!lnb_prefused && (rc = run_ln_bwd(c, y2, gxs, dl, d.ln2_w, dyas, Ms, 768, s))) return rc;   // dy2 (prefused: by the layer above's last GEMM)
+        first_cut = false;
         lnb_prefused = false;
         // dy2 feeds the residual as is and the fc2 branch through its dropout mask
         const float* dy2b = dyas;
@@ -2595,7 +2627,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
         c->pending_lnb = {};
         return rc;
     };
-    for (int l = NOMAD_NUM_LAYERS - 1; l >= 0; --l) {
+    for (int l = depth - 1; l >= 0; --l) {
         unsigned all = 1u;
         for (int br = 0; br < nbr; ++br) all &= (bmask[br] >> l) & 1u;
         if (all) {
@@ -2843,9 +2875,10 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
                          const float* demb, float* dwav, void* workspace, size_t workspace_bytes,
                          nomad_stream_t stream, bool train) {
     Shapes sh;
-    if (!c || !wav || !layers_out || !saved || !demb || (!dwav && !train) || !workspace || B <= 0 ||
+    const bool cut = c && c->encoder_depth < NOMAD_NUM_LAYERS;   // a cut encoder has no embedding: demb is ignored, dlayers carries everything
+    if (!c || !wav || !layers_out || !saved || (cut ? !dlayers : !demb) || (!dwav && !train) || !workspace || B <= 0 ||
         !make_shapes(B, n_samples, &sh))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: bad argument");
+        return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: bad argument%s", cut ? " (encoder depth below 12: dlayers_dev is required)" : "");
     if (!c->bwd_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: call nomad_enable_backward first");
     if (train && !c->train_ready) return fail(NOMAD_ERR_INVALID, "nomad_train_backward: call nomad_train_enable first");
     const BatchGeom g = geom_uniform(sh);
@@ -2866,7 +2899,9 @@ static int backward_ragged(const char* who, nomad_ctx* c, const float* wav, int 
                            const float* demb, float* dwav, void* workspace, size_t workspace_bytes, nomad_stream_t stream,
                            bool train) {
     RaggedShapes rs;
-    if (int rc = ragged_shapes(who, c && wav && layers_out && saved && demb && (dwav || train) && workspace, B, stride, lens_host, &rs))
+    const bool cut = c && c->encoder_depth < NOMAD_NUM_LAYERS;   // (a cut encoder: demb is ignored, dlayers is required)
+    if (int rc = ragged_shapes(who, c && wav && layers_out && saved && (cut ? dlayers != nullptr : demb != nullptr) && (dwav || train) && workspace,
+                               B, stride, lens_host, &rs))
         return rc;
     if (!c->bwd_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_backward first", who);
     if (train && !c->train_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_train_enable first", who);
@@ -3023,6 +3058,19 @@ int nomad_get_feature_grad_mult(const nomad_ctx* c, float* mult) {
     return 0;
 }
 
+int nomad_set_encoder_depth(nomad_ctx* c, int depth) {
+    if (!c || depth < 1 || depth > NOMAD_NUM_LAYERS)
+        return fail(NOMAD_ERR_INVALID, "nomad_set_encoder_depth: depth %d is outside 1 .. %d", depth, NOMAD_NUM_LAYERS);
+    c->encoder_depth = depth;
+    return 0;
+}
+
+int nomad_get_encoder_depth(const nomad_ctx* c, int* depth) {
+    if (!c || !depth) return fail(NOMAD_ERR_INVALID, "nomad_get_encoder_depth: null argument");
+    *depth = c->encoder_depth;
+    return 0;
+}
+
 int nomad_embed_backward(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
                          const float* layers_out, const void* saved, size_t saved_bytes, const float* dlayers,
                          const float* demb, float* dwav, void* workspace, size_t workspace_bytes,
@@ -3149,6 +3197,7 @@ int nomad_train_zero_grad(nomad_ctx* c, nomad_stream_t stream) {
 int nomad_train_backward(nomad_ctx* c, const float* wav, int B, int n_samples, const float* layers_out, const void* saved,
                          size_t saved_bytes, const float* demb, void* workspace, size_t workspace_bytes,
                          nomad_stream_t stream) {
+    if (int rc = refuse_cut(c, "nomad_train_backward")) return rc;
     return backward_impl(c, wav, B, n_samples, nullptr, nullptr, layers_out, saved, saved_bytes, nullptr, demb, nullptr,
                          workspace, workspace_bytes, stream, true);
 }
@@ -3156,6 +3205,7 @@ int nomad_train_backward(nomad_ctx* c, const float* wav, int B, int n_samples, c
 int nomad_train_backward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, const float* layers_out,
                                 const void* saved, size_t saved_bytes, const float* demb, void* workspace, size_t workspace_bytes,
                                 nomad_stream_t stream) {
+    if (int rc = refuse_cut(c, "nomad_train_backward_ragged")) return rc;
     return backward_ragged("nomad_train_backward_ragged", c, wav, B, stride, lengths_host, nullptr, nullptr, layers_out, saved, saved_bytes,
                            nullptr, demb, nullptr, workspace, workspace_bytes, stream, true);
 }
@@ -3409,6 +3459,133 @@ int nomad_l1_loss(nomad_ctx* c, const float* a_layers, const float* b_layers, co
 int nomad_l1_loss_ragged(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb, const float* b_emb,
                          long long M, int B, float* loss, void* scratch, nomad_stream_t stream) {
     return l1_loss_rows("nomad_l1_loss_ragged", c, a_layers, b_layers, a_emb, b_emb, M, B, loss, scratch, stream);
+}
+
+}  // extern "C"
+
+// ---- weighted, per-utterance NomadLoss -----------------------------------------------------------
+namespace {
+
+// Scratch of nomad_l1_loss_weighted[_backward], a function of (M, B) only: the prefix sums | the chunk sums [13][cmax], cmax = M / 16 + B
+// bounding the chunks of any split of M frames over B clips | S [13][B].
+struct L1wLayout {
+    size_t meta, partial, sums, total;
+    long long cmax;
+};
+
+L1wLayout l1w_layout(long long M, int B) {
+    L1wLayout l{};
+    l.cmax = M / kL1wChunk + B;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
+    l.meta = take(sizeof(int) * 2 * ((size_t)B + 1));
+    l.partial = take(sizeof(double) * 13 * (size_t)l.cmax);
+    l.sums = take(sizeof(double) * 13 * (size_t)B);
+    l.total = off;
+    return l;
+}
+
+struct L1wPlan {
+    L1wLayout lay;
+    L1Weights wt;
+    std::vector<int> meta;   // pref[B + 1] | cpref[B + 1]
+    int chunks = 0;
+    bool any_layer = false;
+};
+
+// Every argument check of the two entry points (nothing is queued before it has passed) and the host side of the metadata.
+int l1w_plan(const char* who, const nomad_ctx* c, long long M, int B, const int* frames_host, const float* weights_host, int reduction,
+             const void* scratch, size_t scratch_bytes, L1wPlan* p) {
+    if (!c || !weights_host || !scratch || B <= 0 || M < B || M > 0x7fffffffLL || (reduction != NOMAD_L1_BATCH && reduction != NOMAD_L1_PER_CLIP))
+        return fail(NOMAD_ERR_INVALID, "%s: bad argument (M=%lld, B=%d, reduction=%d)", who, M, B, reduction);
+    bool any = false;
+    for (int i = 0; i < 13; ++i) {
+        const float w = weights_host[i];
+        if (!(w >= 0.f) || !std::isfinite(w)) return fail(NOMAD_ERR_INVALID, "%s: weight %d is not a finite number >= 0", who, i);
+        p->wt.w[i] = w;
+        any = any || w != 0.f;
+        p->any_layer = p->any_layer || (i < 12 && w != 0.f);
+    }
+    if (!any) return fail(NOMAD_ERR_INVALID, "%s: every weight is 0", who);
+    if (!frames_host && M % B) return fail(NOMAD_ERR_INVALID, "%s: M=%lld is not B=%d equal clips and frames_host is NULL", who, M, B);
+    p->meta.assign(2 * ((size_t)B + 1), 0);
+    int* pref = p->meta.data();
+    int* cpref = pref + B + 1;
+    for (int b = 0; b < B; ++b) {
+        const long long t = frames_host ? frames_host[b] : M / B;
+        if (t < 1 || pref[b] + t > M) return fail(NOMAD_ERR_INVALID, "%s: frames_host[%d] = %lld (at least 1 each, M=%lld in all)", who, b, t, M);
+        pref[b + 1] = pref[b] + (int)t;
+        cpref[b + 1] = cpref[b] + (int)((t + kL1wChunk - 1) / kL1wChunk);
+    }
+    if (pref[B] != M) return fail(NOMAD_ERR_INVALID, "%s: frames_host sums to %d, M is %lld", who, pref[B], M);
+    p->chunks = cpref[B];
+    p->lay = l1w_layout(M, B);
+    if (scratch_bytes < p->lay.total) return fail(NOMAD_ERR_WORKSPACE, "%s: scratch %zu < required %zu", who, scratch_bytes, p->lay.total);
+    return 0;
+}
+
+// The prefix sums' copy into the scratch, queued ahead of the kernels; the host copy is staged in the context's ring (ragged_upload).
+int l1w_upload(nomad_ctx* c, const L1wPlan& p, char* scratch, hipStream_t s) {
+    std::vector<int>& staged = c->l1w_meta_ring[c->l1w_seq++ % 16];
+    staged = p.meta;
+    HIP_TRY(hipMemcpyAsync(scratch + p.lay.meta, staged.data(), sizeof(int) * staged.size(), hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nomad_l1_weighted_scratch_bytes(long long M, int B, size_t* bytes) {
+    if (!bytes || B <= 0 || M < B) return fail(NOMAD_ERR_INVALID, "nomad_l1_weighted_scratch_bytes: bad argument (M=%lld, B=%d)", M, B);
+    *bytes = l1w_layout(M, B).total;
+    return 0;
+}
+
+int nomad_l1_loss_weighted(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb, const float* b_emb,
+                           long long M, int B, const int* frames_host, const float* weights_host, int reduction, float* loss,
+                           double* terms, void* scratch, size_t scratch_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_l1_loss_weighted";
+    L1wPlan p;
+    if (int rc = l1w_plan(who, c, M, B, frames_host, weights_host, reduction, scratch, scratch_bytes, &p)) return rc;
+    if (!loss || (p.any_layer && (!a_layers || !b_layers)) || (p.wt.w[12] != 0.f && (!a_emb || !b_emb)))
+        return fail(NOMAD_ERR_INVALID, "%s: a tensor with a non-zero weight (or loss_dev) is NULL", who);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* sc = static_cast<char*>(scratch);
+    if (int rc = l1w_upload(c, p, sc, s)) return rc;
+    const int* meta = reinterpret_cast<const int*>(sc + p.lay.meta);
+    double* partial = reinterpret_cast<double*>(sc + p.lay.partial);
+    Scope scope(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(l1w_partial_kernel, dim3(p.chunks, 13), dim3(256), 0, s, a_layers, b_layers, M, a_emb, b_emb, B, meta, p.wt,
+                       p.lay.cmax, partial);
+    hipLaunchKernelGGL(l1w_final_kernel, dim3(1), dim3(256), 0, s, partial, p.lay.cmax, meta, B, p.wt, reduction == NOMAD_L1_PER_CLIP ? 1 : 0,
+                       reinterpret_cast<double*>(sc + p.lay.sums), loss, terms);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int nomad_l1_loss_weighted_backward(nomad_ctx* c, const float* a_layers, const float* b_layers, const float* a_emb,
+                                    const float* b_emb, long long M, int B, const int* frames_host, const float* weights_host,
+                                    int reduction, int depth, const float* upstream, float* dlayers, float* demb, void* scratch,
+                                    size_t scratch_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_l1_loss_weighted_backward";
+    L1wPlan p;
+    if (int rc = l1w_plan(who, c, M, B, frames_host, weights_host, reduction, scratch, scratch_bytes, &p)) return rc;
+    if (depth < 1 || depth > NOMAD_NUM_LAYERS) return fail(NOMAD_ERR_INVALID, "%s: depth %d is outside 1 .. %d", who, depth, NOMAD_NUM_LAYERS);
+    for (int i = depth; i < 13; ++i)   // (the embedding needs the whole encoder)
+        if (depth < NOMAD_NUM_LAYERS && p.wt.w[i] != 0.f)
+            return fail(NOMAD_ERR_INVALID, "%s: weight %d is not 0 but the depth is %d: its gradient would not be written", who, i, depth);
+    const bool emb = p.wt.w[12] != 0.f;
+    if (!upstream || !dlayers || (p.any_layer && (!a_layers || !b_layers)) || (emb && (!a_emb || !b_emb || !demb)))
+        return fail(NOMAD_ERR_INVALID, "%s: a tensor with a non-zero weight (or upstream_dev / dlayers_dev) is NULL", who);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* sc = static_cast<char*>(scratch);
+    if (int rc = l1w_upload(c, p, sc, s)) return rc;
+    Scope scope(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(l1w_bwd_kernel, dim3(p.chunks, depth + (emb ? 1 : 0)), dim3(256), 0, s, a_layers, b_layers, M, a_emb, b_emb, B,
+                       reinterpret_cast<const int*>(sc + p.lay.meta), p.wt, depth, reduction == NOMAD_L1_PER_CLIP ? 1 : 0, upstream, dlayers, demb);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // ---- measurement -----------------------------------------------------------------------------

@@ -299,4 +299,106 @@ __global__ __launch_bounds__(256) void l1_final_kernel(const double* __restrict_
     }
 }
 
+// Weighted, per-utterance NomadLoss (nomad_l1_loss_weighted).  A (layer, clip) slab - the clip's rows pref[b] .. pref[b + 1] of layer i,
+// contiguous in [12][B][T][768] and in packed [12][M][768] alike - is cut into chunks of kL1wChunk frames counted from the CLIP's first
+// frame, one workgroup each: differences in fp32, accumulated in fp64, the fixed fold of l1_partial_kernel.  A chunk's sum depends on
+// the clip's own values only, whatever batch it is in.  Stage 2 folds a slab's chunk sums in chunk order into S[13][B] and combines
+// them (below).  No atomics: the result is identical run to run.  A term with weight 0 is never read.
+// meta (device ints): pref[B + 1] frame prefix sums | cpref[B + 1] chunk prefix sums.
+constexpr int kL1wChunk = 16;
+struct L1Weights {
+    float w[13];
+};
+
+__device__ __forceinline__ int l1w_clip_of(const int* __restrict__ cpref, int B, int chunk) {
+    int lo = 0, hi = B;   // the clip b with cpref[b] <= chunk < cpref[b + 1] (every clip has at least one chunk)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cpref[mid] <= chunk) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// grid: (chunks of the batch, 13).  y < 12: chunk x of layer y -> partial[y * cstride + x]; y = 12: workgroup x < B takes clip x's 256
+// embedding values -> partial[12 * cstride + x].
+__global__ __launch_bounds__(256) void l1w_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, long long M,
+                                                          const float* __restrict__ ea, const float* __restrict__ eb, int B,
+                                                          const int* __restrict__ meta, L1Weights wt, long long cstride,
+                                                          double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int i = blockIdx.y;
+    if (wt.w[i] == 0.f) return;   // (uniform over the workgroup)
+    double s = 0.0;
+    if (i == 12) {
+        if ((int)blockIdx.x >= B) return;
+        const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+        s = (double)fabsf(ea[e] - eb[e]);
+    } else {
+        const int* pref = meta;
+        const int* cpref = meta + B + 1;
+        const int clip = l1w_clip_of(cpref, B, (int)blockIdx.x);
+        const long long f0 = pref[clip] + (long long)((int)blockIdx.x - cpref[clip]) * kL1wChunk;
+        const long long left = pref[clip + 1] - f0;
+        const int n4 = (int)(left < kL1wChunk ? left : kL1wChunk) * 192;
+        const float4* a4 = reinterpret_cast<const float4*>(a + ((long long)i * M + f0) * 768);
+        const float4* b4 = reinterpret_cast<const float4*>(b + ((long long)i * M + f0) * 768);
+        for (int k = threadIdx.x; k < n4; k += 256) {
+            const float4 x = a4[k], y = b4[k];
+            // (every |a - b| enters the fp64 sum on its own: the terms then differ from any other fp64 summation by its order alone)
+            s += ((double)fabsf(x.x - y.x) + (double)fabsf(x.y - y.y)) + ((double)fabsf(x.z - y.z) + (double)fabsf(x.w - y.w));
+        }
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(long long)i * cstride + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One workgroup.  S[i][b] = the slab's chunk sums in chunk order; terms[i][b] = S / n (0 where the weight is 0), n = T_b * 768 (256 for
+// the embedding).  per_clip: loss[b] = sum_i w_i S[i][b] / n[i][b]; else loss[0] = sum_i w_i (sum_b S[i][b]) / (sum_b n[i][b]) - i and
+// b ascending, in fp64.
+__global__ __launch_bounds__(256) void l1w_final_kernel(const double* __restrict__ partial, long long cstride,
+                                                        const int* __restrict__ meta, int B, L1Weights wt, int per_clip,
+                                                        double* __restrict__ S, float* __restrict__ loss, double* __restrict__ terms) {
+    __shared__ double lsum[13];
+    const int* pref = meta;
+    const int* cpref = meta + B + 1;
+    for (int p = threadIdx.x; p < 13 * B; p += 256) {
+        const int i = p / B, b = p - i * B;
+        double s = 0.0;
+        if (wt.w[i] != 0.f) {
+            if (i == 12) s = partial[12 * cstride + b];
+            else
+                for (int ch = cpref[b]; ch < cpref[b + 1]; ++ch) s += partial[(long long)i * cstride + ch];
+        }
+        S[p] = s;
+        if (terms) terms[p] = wt.w[i] != 0.f ? s / (i == 12 ? 256.0 : (double)(pref[b + 1] - pref[b]) * 768.0) : 0.0;
+    }
+    __syncthreads();
+    if (per_clip) {
+        for (int b = threadIdx.x; b < B; b += 256) {
+            const double nl = (double)(pref[b + 1] - pref[b]) * 768.0;
+            double l = 0.0;
+            for (int i = 0; i < 13; ++i)
+                if (wt.w[i] != 0.f) l += (double)wt.w[i] * (S[i * B + b] / (i == 12 ? 256.0 : nl));
+            loss[b] = (float)l;
+        }
+        return;
+    }
+    if (threadIdx.x < 13) {
+        double s = 0.0;
+        if (wt.w[threadIdx.x] != 0.f)
+            for (int b = 0; b < B; ++b) s += S[threadIdx.x * B + b];
+        lsum[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+        for (int i = 0; i < 13; ++i)
+            if (wt.w[i] != 0.f) l += (double)wt.w[i] * (lsum[i] / (i == 12 ? (double)B * 256.0 : (double)pref[B] * 768.0));
+        loss[0] = (float)l;
+    }
+}
+
 }  // namespace nomad

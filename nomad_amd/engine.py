@@ -88,6 +88,7 @@ class Engine:
         self._ws_side: Dict[int, torch.Tensor] = {}     # further workspaces for concurrent forwards on side streams
         self._side_streams: Dict[int, "torch.cuda.Stream"] = {}
         self._l1_scratch: Optional[torch.Tensor] = None
+        self._l1w_scratch: Optional[torch.Tensor] = None
         # A library built WITH packed-FP32 instructions (NOMAD_PACKED_FP32=1 / the _pk A/B variants) must not run two of its
         # forwards concurrently: v_pk_fma_f32 can lose a product next to the other forward's bf16 128 x 128 GEMM (DESIGN.md
         # "The packed-FP32 hazard").  The shipped build reports 0 here; with the bit set every two-stream batch split is off.
@@ -468,6 +469,87 @@ class Engine:
                                           self._stream()), "nomad_l1_loss")
         return loss[0]
 
+    def _l1w_call(self, a_layers, b_layers, a_emb, b_emb, weights, reduction, frames):
+        """Checked arguments of ``nomad_l1_loss_weighted*``: (M, B, frames array or None, weights array, reduction code, scratch)."""
+        if reduction not in _lib.L1_REDUCTION:
+            raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+        w = [float(x) for x in weights]
+        if len(w) != 13:
+            raise ValueError(f"13 weights (12 layers + the embedding) are needed, got {len(w)}")
+        if a_layers.shape != b_layers.shape or a_layers.dim() not in (3, 4) or a_layers.shape[0] != 12 or a_layers.shape[-1] != 768:
+            raise ValueError(f"layer tensors must both be (12,B,T,768) or (12,M,768), got {tuple(a_layers.shape)} and {tuple(b_layers.shape)}")
+        for t, n in ((a_layers, "a_layers"), (b_layers, "b_layers")):
+            self._check_dev(t, n)
+        if w[12] != 0.0:   # (a cut encoder leaves the embeddings unwritten: unread, so unchecked, when their weight is 0)
+            self._check_dev(a_emb, "a_emb")
+            self._check_dev(b_emb, "b_emb")
+            if a_emb.shape != b_emb.shape:
+                raise ValueError(f"embeddings must have one shape, got {tuple(a_emb.shape)} and {tuple(b_emb.shape)}")
+        if a_layers.dim() == 4:
+            B, M = a_layers.shape[1], a_layers.shape[1] * a_layers.shape[2]
+            if frames is not None:
+                raise ValueError("frames goes with packed (12,M,768) layers")
+        else:
+            M = a_layers.shape[1]
+            if frames is None:
+                raise ValueError("packed (12,M,768) layers need the clips' frame counts")
+            B = len(frames)
+        if w[12] != 0.0 and a_emb.shape[0] != B:
+            raise ValueError(f"{a_emb.shape[0]} embeddings for {B} clips")
+        arr = (C.c_int * B)(*[int(t) for t in frames]) if frames is not None else None
+        n = C.c_size_t()
+        _lib.check(self.lib.nomad_l1_weighted_scratch_bytes(M, B, C.byref(n)), "nomad_l1_weighted_scratch_bytes")
+        if self._l1w_scratch is None or self._l1w_scratch.numel() < n.value:
+            self._l1w_scratch = None
+            self._l1w_scratch = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+        self._l1w_scratch.record_stream(torch.cuda.current_stream(self.device))
+        return M, B, arr, (C.c_float * 13)(*w), _lib.L1_REDUCTION[reduction], self._l1w_scratch
+
+    def l1_loss_weighted(self, a_layers, b_layers, a_emb, b_emb, weights, reduction: str = "mean", frames=None,
+                         want_terms: bool = True):
+        """NomadLoss with a weight per term and, with reduction="none", one loss per clip -> (loss, terms).
+
+        a_layers / b_layers (12,B,T,768), or packed (12,M,768) with ``frames`` (the clips' frame counts); weights: 13 numbers >= 0
+        (index 12 = the embedding) - a term with weight 0 is not read, so behind a cut encoder (``encoder_depth``) its tensors may
+        hold anything.  "mean": a 0-dim loss, every term the mean over the batch's valid elements (``l1_loss`` with weights);
+        "none": (B,), every term the mean over the clip's own elements.  terms: (13,B) float64 per-clip means (0 where the
+        weight is 0), or None with want_terms=False."""
+        M, B, arr, w, red, scratch = self._l1w_call(a_layers, b_layers, a_emb, b_emb, weights, reduction, frames)
+        loss = torch.empty(B if reduction == "none" else 1, dtype=torch.float32, device=self.device)
+        terms = torch.empty(13, B, dtype=torch.float64, device=self.device) if want_terms else None
+        _lib.check(self.lib.nomad_l1_loss_weighted(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(),
+                                                   a_emb.data_ptr() if a_emb is not None else None,
+                                                   b_emb.data_ptr() if b_emb is not None else None, M, B, arr, w, red,
+                                                   loss.data_ptr(), terms.data_ptr() if want_terms else None,
+                                                   scratch.data_ptr(), scratch.numel(), self._stream()), "nomad_l1_loss_weighted")
+        return (loss if reduction == "none" else loss[0]), terms
+
+    def l1_loss_weighted_backward(self, a_layers, b_layers, a_emb, b_emb, upstream: torch.Tensor, weights,
+                                  reduction: str = "mean", frames=None, depth: Optional[int] = None, dlayers=None, demb=None):
+        """(d loss / d a_layers, d loss / d a_emb or None) of ``l1_loss_weighted``; upstream: 0-dim ("mean") or (B,) ("none").
+        depth (default: ``encoder_depth``): layers below it with weight 0 are written as zeros, layers from it on are left
+        untouched (``dlayers``: a buffer to write into, else a fresh uninitialised one); the embedding gradient is None when its
+        weight is 0."""
+        M, B, arr, w, red, scratch = self._l1w_call(a_layers, b_layers, a_emb, b_emb, weights, reduction, frames)
+        depth = self.encoder_depth if depth is None else int(depth)
+        dl = torch.empty_like(a_layers) if dlayers is None else dlayers
+        self._check_dev(dl, "dlayers")
+        if dl.shape != a_layers.shape:
+            raise ValueError("dlayers must have the layers' shape")
+        de = None
+        if w[12] != 0.0:
+            de = torch.empty_like(a_emb) if demb is None else demb
+        up = upstream.to(self.device, torch.float32).reshape(-1).contiguous()
+        if up.numel() != (B if reduction == "none" else 1):
+            raise ValueError(f"upstream has {up.numel()} values for reduction={reduction!r} over {B} clips")
+        _lib.check(self.lib.nomad_l1_loss_weighted_backward(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(),
+                                                            a_emb.data_ptr() if a_emb is not None else None,
+                                                            b_emb.data_ptr() if b_emb is not None else None, M, B, arr, w, red, depth,
+                                                            up.data_ptr(), dl.data_ptr(), de.data_ptr() if de is not None else None,
+                                                            scratch.data_ptr(), scratch.numel(), self._stream()),
+                   "nomad_l1_loss_weighted_backward")
+        return dl, de
+
     # ---- bf16 path (long-form clips, config C5) -----------------------------------------------------
     # Like the bf16x3 path below, bf16 batches with at least this many frames are embedded as two halves on two streams:
     # every GEMM of the path runs one 256 x 256 workgroup per CU, so the partial last round of one half's tiles (the
@@ -651,6 +733,20 @@ class Engine:
         _lib.check(self.lib.nomad_set_feature_grad_mult(self.ctx, float(mult)), "nomad_set_feature_grad_mult")
 
     @property
+    def encoder_depth(self) -> int:
+        """How many encoder layers the loss's layer-output forwards (``embed(want_layers=True)``, ``embed_train``,
+        ``embed_train_ragged``) and ``embed_backward[_ragged]`` run: 1 .. 12, default 12.  Below 12 the forwards stop behind layer
+        depth - 1 (layer outputs from ``depth`` on and the embedding stay unwritten) and every scoring / bf16 / fine-tuning entry
+        point raises (``nomad_set_encoder_depth``)."""
+        v = C.c_int()
+        _lib.check(self.lib.nomad_get_encoder_depth(self.ctx, C.byref(v)), "nomad_get_encoder_depth")
+        return int(v.value)
+
+    @encoder_depth.setter
+    def encoder_depth(self, depth: int):
+        _lib.check(self.lib.nomad_set_encoder_depth(self.ctx, int(depth)), "nomad_set_encoder_depth")
+
+    @property
     def gemm_precision(self) -> str:
         """"fp32" (exact fp32 MFMA, the default) or "bf16x3" (three bf16 MFMA products over hi / lo halves split in
         registers, fp32 accumulation) for the GEMMs of ``embed`` / ``embed_ragged`` / ``embed_train`` / the backward passes;
@@ -695,7 +791,8 @@ class Engine:
         return emb, layers, saved
 
     def embed_backward(self, wav, layers, saved, dlayers, demb, head=None) -> torch.Tensor:
-        """d loss / d wav (B,N) from d loss / d layers (12,B,T,768 or None) and d loss / d emb (B,256)."""
+        """d loss / d wav (B,N) from d loss / d layers (12,B,T,768 or None) and d loss / d emb (B,256; None only while
+        ``encoder_depth`` is below 12, where it is ignored)."""
         if wav.dim() == 3:
             wav = wav.squeeze(1)
         B, N = wav.shape
@@ -708,7 +805,8 @@ class Engine:
                                                  hw.data_ptr() if hw is not None else None,
                                                  hb.data_ptr() if hb is not None else None,
                                                  layers.data_ptr(), saved.data_ptr(), saved.numel(),
-                                                 dlayers.data_ptr() if dlayers is not None else None, demb.data_ptr(),
+                                                 dlayers.data_ptr() if dlayers is not None else None,
+                                                 demb.data_ptr() if demb is not None else None,
                                                  dwav.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
                    "nomad_embed_backward")
         return dwav
@@ -799,7 +897,8 @@ class Engine:
                                                         hw.data_ptr() if hw is not None else None,
                                                         hb.data_ptr() if hb is not None else None,
                                                         layers.data_ptr(), saved.data_ptr(), saved.numel(),
-                                                        dlayers.data_ptr() if dlayers is not None else None, demb.data_ptr(),
+                                                        dlayers.data_ptr() if dlayers is not None else None,
+                                                        demb.data_ptr() if demb is not None else None,
                                                         dwav.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
                    "nomad_embed_backward_ragged")
         return dwav

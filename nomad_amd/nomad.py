@@ -24,6 +24,7 @@ What differs, deliberately:
 """
 from __future__ import annotations
 
+import math
 import os
 from datetime import datetime
 from typing import Dict, List, Union
@@ -35,7 +36,7 @@ import torch
 from . import wavio
 from .dist import partition
 from .engine import Engine
-from .weights import find_checkpoint, find_feature_grad_mult, load_checkpoint, seeded_state_dict
+from .weights import find_checkpoint, find_feature_grad_mult, load_checkpoint, num_frames, seeded_state_dict
 
 SSL_OUT_DIM = 768
 EMB_DIM = 256
@@ -128,12 +129,45 @@ class LossNetLayers:
         return [layers[i] for i in range(12)] + [emb]
 
 
+def loss_selection(L, layer_weights=None):
+    """(``NomadLoss.L``, ``layer_weights``) -> (13 weights, encoder depth): which terms of the loss count, and how many encoder
+    layers they need.  Pure host arithmetic.
+
+    layer_weights None: the reference's ``for i in range(self.L)`` (nomad.py:276) - weights ``[1] * L + [0] * (13 - L)`` for an
+    integer L in 1 .. 13.  The reference returns the float 0.0 at L = 0 (nothing to call ``backward`` on) and raises IndexError
+    above 13 (``LossNetLayers`` returns 13 entries); both are a ValueError here.  Otherwise 13 finite numbers >= 0, not all 0:
+    the 12 layers' weights, then the embedding's.  depth: 12 when the embedding counts (it is computed from the last layer), else
+    1 + the deepest layer with a weight."""
+    if layer_weights is None:
+        if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= int(L) <= 13:
+            raise ValueError(f"nomad_loss.L must be an integer in 1 .. 13 (12 transformer layers + the embedding), got {L!r}")
+        weights = [1.0] * int(L) + [0.0] * (13 - int(L))
+    else:
+        if torch.is_tensor(layer_weights):
+            layer_weights = layer_weights.detach().reshape(-1).tolist()
+        weights = [float(w) for w in layer_weights]
+        if len(weights) != 13:
+            raise ValueError(f"layer_weights needs 13 numbers (12 transformer layers + the embedding), got {len(weights)}")
+        if any(not math.isfinite(w) or w < 0.0 for w in weights):
+            raise ValueError("layer_weights must be finite and >= 0")
+        if not any(w != 0.0 for w in weights):
+            raise ValueError("layer_weights are all zero: the loss would have no term")
+    depth = 12 if weights[12] != 0.0 else 1 + max(i for i in range(12) if weights[i] != 0.0)
+    return weights, depth
+
+
+def check_reduction(reduction) -> str:
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+    return reduction
+
+
 class NomadLoss:
-    """``NomadLoss.forward(nomad_ref, nomad_test)`` (nomad.py:267-282): sum of 13 L1 means."""
+    """``NomadLoss.forward(nomad_ref, nomad_test)`` (nomad.py:267-282): sum of the first ``L`` of 13 L1 means (``L = 13``)."""
 
     def __init__(self, engine: Engine):
         self.engine = engine
-        self.L = 13
+        self.L = 13   # read by Nomad.forward (loss_selection) and by forward below, like the reference's `for i in range(self.L)`
         self.only_embedding = False
 
     def eval(self):
@@ -150,6 +184,13 @@ class NomadLoss:
             return (test - ref).abs().mean()
         ref_layers = _stack_layers(nomad_ref[:12])
         test_layers = _stack_layers(nomad_test[:12])
+        if self.L != 13:
+            if test_layers.dim() != 4:
+                raise ValueError("NomadLoss.L below 13 over packed (exact-length) layer outputs needs the clips' lengths: use "
+                                 "Nomad.forward(estimate, clean, lengths)")
+            weights, _ = loss_selection(self.L)
+            return self.engine.l1_loss_weighted(test_layers, ref_layers, nomad_test[12].contiguous(), nomad_ref[12].contiguous(),
+                                                weights, want_terms=False)[0]
         return self.engine.l1_loss(test_layers, ref_layers, nomad_test[12].contiguous(), nomad_ref[12].contiguous())
 
 
@@ -294,6 +335,99 @@ class _NomadLossRaggedFn(torch.autograd.Function):
         return dwav, dcln, None, None
 
 
+class _NomadLossSelectFn(torch.autograd.Function):
+    """``_NomadLossFn`` / ``_NomadLossRaggedFn`` (lens None / a list) with a weight per term, a loss per clip (reduction "none") and
+    the encoder cut behind the deepest layer with a weight.  The engine's depth is set around the engine calls of the forward and
+    again around those of the backward, and restored each time: nothing else that uses the engine ever sees a cut encoder."""
+
+    @staticmethod
+    def forward(ctx, estimate, clean, nomad, lens, weights, depth, reduction):
+        eng = nomad.engine
+        head = (nomad.lossnet_layers.embedding_weight, nomad.lossnet_layers.embedding_bias)
+        est = estimate.detach().to(eng.device, torch.float32).contiguous()
+        cln = clean.detach().to(eng.device, torch.float32).contiguous()
+        need_grad = estimate.requires_grad
+        need_clean_grad = clean.requires_grad
+        cur = torch.cuda.current_stream(eng.device)
+        frames = None if lens is None else [num_frames(n) for n in lens]
+        saved = saved_c = None
+        prev = eng.encoder_depth
+        eng.encoder_depth = depth
+        try:
+            if lens is None:
+                # a cut encoder exists on fp32 buffers only (products follow Engine.gemm_precision): no embed_bf16x3 below depth 12
+                fwd = eng.embed_bf16x3 if depth == 12 and _takes_bf16x3(nomad.precision, cln) else eng.embed
+                if need_clean_grad:
+                    c_emb, c_layers, saved_c = eng.embed_train(cln, head)
+                else:
+                    side = eng.side_stream()
+                    side.wait_stream(cur)
+                    with torch.cuda.stream(side):
+                        c_emb, c_layers = fwd(cln, head=head, want_layers=True, side=True)
+                if need_grad:
+                    e_emb, e_layers, saved = eng.embed_train(est, head)
+                else:
+                    e_emb, e_layers = fwd(est, head=head, want_layers=True)
+            else:
+                if need_clean_grad:
+                    c_emb, c_layers, saved_c, c_batch = eng.embed_train_ragged(cln, lens, head)
+                else:
+                    side = eng.side_stream()
+                    side.wait_stream(cur)
+                    with torch.cuda.stream(side):
+                        c_emb, c_layers, saved_c, c_batch = eng.embed_train_ragged(cln, lens, head, save=False, side=True)
+                e_emb, e_layers, saved, e_batch = eng.embed_train_ragged(est, lens, head, save=need_grad)
+                est, cln = e_batch[0], c_batch[0]
+            if not need_clean_grad:
+                cur.wait_stream(side)
+                for t in (c_emb, c_layers, cln):
+                    t.record_stream(cur)
+            loss, _ = eng.l1_loss_weighted(e_layers, c_layers, e_emb, c_emb, weights, reduction, frames, want_terms=False)
+        finally:
+            eng.encoder_depth = prev
+        if need_grad or need_clean_grad:
+            ctx.nomad = nomad
+            ctx.sel = (lens, frames, weights, depth, reduction)
+            ctx.shapes = (estimate.shape, clean.shape)
+            ctx.save_for_backward(est, e_layers, e_emb, cln, c_layers, c_emb, saved, saved_c)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        est, e_layers, e_emb, cln, c_layers, c_emb, saved, saved_c = ctx.saved_tensors
+        eng = ctx.nomad.engine
+        lens, frames, weights, depth, reduction = ctx.sel
+        head = (ctx.nomad.lossnet_layers.embedding_weight, ctx.nomad.lossnet_layers.embedding_bias)
+
+        # Per utterance, clip b's rows are linear in upstream[b]: the chain runs with upstream 1 - every clip's own gradient, the
+        # bits of its B = 1 call - and row b is scaled once at the end.  (Scaled at the start, v_b * gradient would carry the
+        # rounding of the whole chain again, ~2e-6 of it for a v_b that is no power of two.)
+        per_clip = reduction == "none"
+        up = torch.ones(grad_out.numel(), dtype=torch.float32, device=eng.device) if per_clip else grad_out
+
+        def branch(wav, layers, emb, o_layers, o_emb, sv):   # |e - c| is symmetric: the clean side is the same call, arguments swapped
+            dl, de = eng.l1_loss_weighted_backward(layers, o_layers, emb, o_emb, up, weights, reduction, frames, depth)
+            if de is None and depth == 12:   # the whole encoder, no embedding term: its head backward gets zeros
+                de = torch.zeros_like(emb)
+            if lens is None:
+                d = eng.embed_backward(wav, layers, sv, dl, de, head)
+            else:
+                d = eng.embed_backward_ragged((wav, lens), layers, sv, dl, de, head)
+            return d * grad_out.to(d.device, torch.float32).reshape(-1, 1) if per_clip else d
+
+        dwav = dcln = None
+        prev = eng.encoder_depth
+        eng.encoder_depth = depth
+        try:
+            if saved is not None and ctx.needs_input_grad[0]:
+                dwav = branch(est, e_layers, e_emb, c_layers, c_emb, saved).reshape(ctx.shapes[0])
+            if saved_c is not None and ctx.needs_input_grad[1]:
+                dcln = branch(cln, c_layers, c_emb, e_layers, e_emb, saved_c).reshape(ctx.shapes[1])
+        finally:
+            eng.encoder_depth = prev
+        return dwav, dcln, None, None, None, None, None
+
+
 class GraphedLoss:
     """``nomad.forward`` + its backward to ``estimate`` for ONE input shape, captured once as a HIP graph and replayed per step.
 
@@ -324,6 +458,9 @@ class GraphedLoss:
 
     def __init__(self, nomad: "Nomad", estimate: torch.Tensor, clean: torch.Tensor, warmup: int = 3):
         self.nomad = nomad
+        if nomad.nomad_loss.L != 13:
+            raise ValueError(f"GraphedLoss captures the 13-term mean only (nomad_loss.L is {nomad.nomad_loss.L!r}): layer selections and "
+                             "per-utterance losses go through nomad.forward()")
         self._check_not_stochastic("capture")
         # the graph reads the head through these addresses: keep the tensors alive and notice a replacement
         self._head = (nomad.lossnet_layers.embedding_weight, nomad.lossnet_layers.embedding_bias)
@@ -710,8 +847,18 @@ class Nomad:
             _write_rounded_csv(df_dm.reset_index(), results_scores_path)
         return df_avg_nomad, df_dm
 
-    def forward(self, estimate, clean, lengths=None):
+    def forward(self, estimate, clean, lengths=None, *, layer_weights=None, reduction="mean"):
         """NOMAD loss (nomad.py:142-146), differentiable w.r.t. ``estimate``.
+
+        Which terms count: ``self.nomad_loss.L`` as in the reference (``for i in range(self.L)``, nomad.py:276) - the first L of the
+        12 transformer layers + the embedding, L in 1 .. 13 - or ``layer_weights``, 13 numbers >= 0 (the layers' weights, then the
+        embedding's; see ``loss_selection``, which also says what the reference does at L = 0 and above 13: a ValueError here).  The
+        encoder stops behind the deepest layer with a weight, forward and backward, in both branches; a term with weight 0 costs
+        nothing.  reduction="none": a (B,) tensor, one loss per utterance - every term the mean over the utterance's own frames
+        (with ``lengths``: bit-identical to the utterance's own call at B = 1) - whose backward takes the (B,) upstream;
+        "mean" (default): every term the mean over the batch.  ``L == 13`` without weights and "mean" is the path, the kernels
+        and the bits of before.  Below depth 12 the no-gradient branch stays on fp32 buffers whatever ``precision`` says (products
+        follow ``Engine.gemm_precision``).
 
         lengths (B ints, tensor or list; ``estimate`` and ``clean`` (B,1,N) or (B,N)): the exact-length loss - utterance b is the
         first ``lengths[b]`` samples of its row, the samples behind are never read, and nothing is padded in the arithmetic
@@ -724,12 +871,19 @@ class Nomad:
         The whole forward and backward run in the HIP engine (``torch.autograd.Function`` glue only).  As in the
         reference, the gradient that reaches ``estimate`` carries fairseq's ``feature_grad_mult`` (0.1 for wav2vec 2.0
         BASE; ``Nomad(feature_grad_mult=...)`` / ``self.engine.feature_grad_mult``).  The backbone is frozen: the reference would also accumulate parameter gradients nobody reads
-        (the freeze is commented out at nomad.py:74-76); ``clean`` receives no gradient."""
+        (the freeze is commented out at nomad.py:74-76)."""
+        check_reduction(reduction)
+        lens = None
         if lengths is not None:
             if estimate.shape != clean.shape:
                 raise ValueError(f"estimate {tuple(estimate.shape)} and clean {tuple(clean.shape)} must have one shape")
-            return _NomadLossRaggedFn.apply(estimate, clean, self, check_lengths(estimate, lengths))
-        return _NomadLossFn.apply(estimate, clean, self)
+            lens = check_lengths(estimate, lengths)
+        weights, depth = loss_selection(self.nomad_loss.L, layer_weights)
+        if layer_weights is None and self.nomad_loss.L == 13 and reduction == "mean":
+            if lens is not None:
+                return _NomadLossRaggedFn.apply(estimate, clean, self, lens)
+            return _NomadLossFn.apply(estimate, clean, self)
+        return _NomadLossSelectFn.apply(estimate, clean, self, lens, weights, depth, reduction)
 
     def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor, lengths=None) -> "GraphedLoss":
         """``forward`` + backward for inputs of this shape, captured as one HIP graph (see ``GraphedLoss``): for training loops with

@@ -25,6 +25,9 @@ def main():
                                                   "then the padded width (at least the longest)")
     ap.add_argument("--pad-mode", choices=("batch", "exact"), default="exact",
                     help="with --lengths: 'exact' passes them to nomad.forward, 'batch' runs the zero-padded equal-length loss")
+    ap.add_argument("--layers", type=int, default=13, help="nomad_loss.L: the first K of the 13 terms (12 transformer layers + the embedding); "
+                                                           "below 13 the encoder stops behind layer K, forward and backward")
+    ap.add_argument("--reduction", choices=("mean", "none"), default="mean", help="'none': one loss per utterance (summed for the backward)")
     a = ap.parse_args()
     lens = None
     if a.lengths:
@@ -38,6 +41,7 @@ def main():
         lens = [int(x * 16000) for x in secs]
         a.samples = max(a.samples, max(lens))
     nmd = Nomad(weights="seeded", precision=a.precision)
+    nmd.nomad_loss.L = a.layers
     g = torch.Generator().manual_seed(0)
     clean = (0.1 * torch.randn(a.batch, 1, a.samples, generator=g)).clamp(-1, 1).cuda()
     est0 = (clean + 0.02 * torch.randn(a.batch, 1, a.samples, generator=g).cuda()).clamp(-1, 1)
@@ -48,6 +52,8 @@ def main():
             est0[i, 0, n:] = 0.0
         if a.pad_mode == "exact":
             kw = {"lengths": lens}
+    if a.reduction != "mean":   # (the default call keeps the signature every earlier commit has: A/B runs against them)
+        kw["reduction"] = a.reduction
 
     def fwd():
         return nmd.forward(est0, clean, **kw)
@@ -55,10 +61,11 @@ def main():
     def fwd_bwd():
         est = est0.clone().requires_grad_(True)
         loss = nmd.forward(est, clean, **kw)
-        loss.backward()
+        loss.sum().backward() if loss.dim() else loss.backward()
         return est.grad
 
-    out = {"config": f"C4: nomad.forward() on 2x({a.batch},1,{a.samples}), {a.precision}, 1 GPU", "steps": a.steps}
+    out = {"config": f"C4: nomad.forward() on 2x({a.batch},1,{a.samples}), {a.precision}, 1 GPU", "steps": a.steps,
+           "layers": a.layers, "reduction": a.reduction}
     if lens is not None:
         from nomad_amd.weights import num_frames
         Ts, Tp = [num_frames(n) for n in lens], num_frames(a.samples)
