@@ -557,9 +557,9 @@ int nomad_diag_gemm_bf16x3(nomad_ctx* ctx, const void* A_dev, const void* W_dev,
  * waves per (clip, head). */
 int nomad_diag_attention_bf16x3(nomad_ctx* ctx, const void* qkv_dev, void* out_dev, int B, int T, int waves,
                                 nomad_stream_t stream);
-/* bf16 attention: qkv [B*T][2304] bf16 (q pre-scaled by 64^-0.5) -> out [B*T][768] bf16.  q_has_log2e != 0: q is
+/* bf16 attention: qkv [B*T][2304] bf16 (q pre-scaled by 64^-0.5) -> out [B*T][768] bf16.  q_has_log2e must be != 0: q is
  * additionally scaled by log2(e), as the bf16 forward's QKV projection produces it (the kernel works in log2 units);
- * 0: plain q, scaled (and re-rounded to bf16) inside the kernel. */
+ * 0 (plain q, scaled inside the kernel) is NOMAD_ERR_INVALID: that kernel went with round 5's move to 16x16x32. */
 int nomad_diag_attention_bf16(nomad_ctx* ctx, const void* qkv_dev, void* out_dev, int B, int T, int q_has_log2e,
                               nomad_stream_t stream);
 /* out[M][N] = LayerNorm(in[M][N]) * gamma + beta, N in {512, 768}, eps 1e-5. */

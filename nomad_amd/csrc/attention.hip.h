@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const T_* __restrict
 
 // ---------------------------------------------------------------------------------------------------
 // Building blocks of the bf16 MFMA attention tiles (the bf16x3 kernels below; the plain bf16 kernel of config C5 is in
-// attention_bf16_v2.hip.h).  Same transposed structure with v_mfma_f32_16x16x32_bf16 (lane l: A[row l&15][k = 8(l>>4)+j], B likewise):
+// attention_bf16_v3.hip.h).  Same transposed structure with v_mfma_f32_16x16x32_bf16 (lane l: A[row l&15][k = 8(l>>4)+j], B likewise):
 //   S^T = K Q^T   : A = K rows from LDS (ds_read_b128, 144-B padded rows), B = Q from registers
 //   O^T += V^T P^T: B = the S^T accumulators converted to bf16 in place - k-slot (g, j) of a 32-key block is
 //                   key 16*s0 + 4g + j (j < 4) or 16*s1 + 4g + j - 4 (j >= 4), i.e. the lane's own registers of the

@@ -1,9 +1,12 @@
 // bf16 self-attention for long clips on the 16-wide matrix shape (round 5; BASELINE config C5: 30 s, T = 1499).
 //
-// attention_bf16_v2.hip.h computes both products with v_mfma_f32_32x32x16_bf16; the chip holds 1994 MHz of its 2400 under that
-// kernel (profiles/NOTEBOOK.md, "Open at the end of round 4") - the 32-wide shape moves twice the accumulator registers per
+// The kernel this replaced (removed; its history is in profiles/NOTEBOOK.md) computed both products with v_mfma_f32_32x32x16_bf16, and
+// the chip held 1994 MHz of its 2400 under it ("Open at the end of round 4") - the 32-wide shape moves twice the accumulator registers per
 // multiply-add, the same effect that cost the fp32 GEMM and the fp32 attention 3-4 % of clock until they moved to 16x16x4.
-// Same algorithm here on v_mfma_f32_16x16x32_bf16, with lane = (fr = lane & 15, fq = lane >> 4):
+// ctx[b,t,h*64:(h+1)*64] = softmax_j(q[b,t,h] . k[b,j,h]) v[b,j,h] on qkv[B*T][2304] = [q*64^-0.5*log2(e) | k | v] bf16 (the fused QKV
+// GEMM's output), fp32 accumulation and softmax statistics.  A workgroup is NW waves x 32 query rows of one (clip, head), and the
+// workgroups of a head are placed on one XCD (1-D grid, XCD-aware remap) so that their K / V re-reads are L2 hits.
+// On v_mfma_f32_16x16x32_bf16, with lane = (fr = lane & 15, fq = lane >> 4):
 //   * a wave owns 32 queries as two 16-query sub-blocks qs; a 32-key block is two 16-key sub-blocks kb.  Both products are
 //     TRANSPOSED: S^T[kb][qs] = K[kb] Q[qs]^T leaves lane (fr, fq) the scores of query fr for keys 4 fq + r, and those four registers of
 //     kb = 0 and kb = 1, converted to bf16 in place, ARE the B operand of O^T[db][qs] += V^T[db] P^T[qs] once the contraction slot
@@ -18,19 +21,48 @@
 //     (v_permlane16_swap + v_permlane32_swap);
 //   * K rows keep the GEMM's chunk swizzle ((row >> 1) & 7); V rows are swizzled in 32-byte pairs by (row >> 1) & 3, which spreads
 //     the 8 rows x 32 bytes a 32-lane half gathers per transposing read over all 64 banks once.
-// Scores in log2 units (q carries log2 e), p = 2^(s - m_ref) <= 2^kA2Thr between rescales, fp32 accumulation of O and of the row sums, K / V
-// tiles of KT keys double-buffered by LDS-DMA with one barrier per tile: as attention_bf16_v2.hip.h.
+// Scores in log2 units (q carries log2 e), p = 2^(s - m_ref) <= 2^kA2Thr between rescales (deferred rescale: m_ref moves only when a block's
+// maximum exceeds it by more than kA2Thr; p <= 2^kA2Thr instead of <= 1 is harmless in fp32 accumulation), fp32 accumulation of O and of
+// the row sums; keys past the end of the clip are set to -1e30 in the one partial block only.  K / V tiles of KT keys are double-buffered
+// in LDS by LDS-DMA with ONE barrier per tile: a wave's instruction fills 1 KB = 8 rows linearly, the next tile's DMA is issued at the top
+// of an iteration into the buffer the previous iteration's barrier released and waited for (vmcnt(0)) just before this iteration's barrier.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 #include <utility>
 
-#include "attention_bf16_v2.hip.h"
-#include "attention_f32_v2.hip.h"
+#include "attention.hip.h"
 #include "gemm_f32.hip.h"
 
 namespace nomad {
+
+// ---- shared with the fp32 kernel (attention_f32_v2.hip.h) ----
+constexpr float kA2Thr = 8.0f;  // deferred-rescale threshold in log2 units (p <= 256: exact enough in bf16 P / fp32 accumulation)
+constexpr float kLog2e = 1.44269504088896341f;
+
+constexpr int attn_bf16_lds(int KT) { return 2 * KT * 256; }  // two buffers of K [KT][128 B] + V [KT][128 B]
+
+__device__ __forceinline__ float a2_max3(float a, float b, float c) {
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// {x of lanes 0-31, x of lanes 32-63}, each in all lanes of... the caller combines the two (max / sum)
+__device__ __forceinline__ void a2_halves(float x, float& lo, float& hi) {
+    const unsigned u = __float_as_uint(x);
+    const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    lo = __uint_as_float(sw[0]);
+    hi = __uint_as_float(sw[1]);
+}
+__device__ __forceinline__ float f2_max4(float x) {   // maximum over the four lanes fi, fi + 16, fi + 32, fi + 48, in all of them
+    const unsigned u = __float_as_uint(x);
+    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    const float y = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+    float lo, hi;
+    a2_halves(y, lo, hi);
+    return fmaxf(lo, hi);
+}
 
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}) (the transposing reads below take
 // their LDS offset as an instruction immediate, so the block index has to be a constant expression).
@@ -63,25 +95,24 @@ __device__ __forceinline__ void a3_lds_wait(bf16x4& lo, bf16x4& hi) {   // (the 
     else asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(lo), "+v"(hi));
 }
 
-// grid: 1-D, workgroups of 64 * NW threads, one per work item; dynamic LDS attn_bf16_v2_lds(KT).  The work items of a batch are the
-// nqblk * B * 12 pairs (clip-head bh, query block qb), item = bh * nqblk + qb, nqblk = ceil(T / (16 QS NW)); a launch covers items
+// grid: 1-D, workgroups of 64 * NW threads, one per work item; dynamic LDS attn_bf16_lds(KT).  The work items of a batch are the
+// nqblk * B * 12 pairs (clip-head bh, query block qb), item = bh * nqblk + qb, nqblk = ceil(T / (32 NW)); a launch covers items
 // virt0 .. virt0 + gridDim.x - 1 (round 6: the items of a sparsely filled last round go to a second launch with half-size workgroups,
 // nomad_hip.hip run_attention_bf16).
 // tpref (nullable): ragged batches - clip b owns rows tpref[b] .. tpref[b+1]-1 of qkv / out; T is then the longest clip's.
 // q must carry the factor log2(e) (nomad_enable_bf16 folds it into the q rows of the QKV weight).
-// QS: 16-query sub-blocks per wave (2 or 4).  Round 5, second step: with 32 queries per wave the kernel is co-limited by LDS bandwidth - a
-// 32-key block costs a wave 8 KB of fragment reads (4 ds_read_b128 of K, 8 transposing reads of V) for 16 MFMAs, and sixteen such waves
-// per CU read 128 KB per block step = 1024 cycles at 128 bytes per clock, exactly the 4 x 256 cycles the four waves of a SIMD spend in
-// MFMAs - which is why the 16-wide shape alone (QS = 2: 11 % fewer matrix cycles, no per-block lane exchange) changed nothing in the
-// forward (profiles/r05_c5_layer_table.txt).  QS = 4 reuses every K / V fragment for twice the queries: half the LDS bytes per MFMA, at
-// 2 waves per SIMD instead of 4 (about 190 registers).
-// ASMV: the V reads through a3_tr_pair (false: the builtin, A/B runs of libnomad_diag.so).
-// HOLD (round 6): -m_ref moved in place and the ones operand / V addresses held in registers (false: round 5's form, A/B runs).
-template <int NW, int KT, int OCC, int QS = 2, bool ASMV = true, bool HOLD = true>
+// OCC: waves per SIMD the register allocation must allow (__launch_bounds__' second argument).
+// 32 queries per wave (QS = 2 sub-blocks of 16).  With them the kernel is co-limited by LDS bandwidth - a 32-key block costs a wave 8 KB of
+// fragment reads (4 ds_read_b128 of K, 8 transposing reads of V) for 16 MFMAs, and sixteen such waves per CU read 128 KB per block step =
+// 1024 cycles at 128 bytes per clock, exactly the 4 x 256 cycles the four waves of a SIMD spend in MFMAs.  64 queries per wave (half the LDS
+// bytes per MFMA at 2 waves per SIMD) measured no faster - 262 / 271 / 310 us best launch at C5's shape for 32 queries, 64 x 4 waves, 64 x 8
+// waves (profiles/r05_attention_bf16_variants.txt) - nor did 16 waves per workgroup; both forms were removed.
+template <int NW, int KT, int OCC>
 __global__ __launch_bounds__(64 * NW, OCC) void attention_bf16_v3_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                                          int T, int nqblk, const int* __restrict__ tpref, int virt0) {
     extern __shared__ __attribute__((aligned(16))) char a3_lds[];
     constexpr int NT = 64 * NW;       // threads
+    constexpr int QS = 2;             // 16-query sub-blocks per wave
     constexpr int QW = 16 * QS;       // queries per wave
     constexpr int QB = QW * NW;       // queries per workgroup
     constexpr int NB = KT / 32;       // 32-key blocks per tile
@@ -119,7 +150,6 @@ __global__ __launch_bounds__(64 * NW, OCC) void attention_bf16_v3_kernel(const b
     // refreshed by four v_mov_b64 in EVERY block, and for want of those 8 registers re-made the ones operand and the four V addresses per
     // block as well (10 of the 48 vector instructions of a block, in a loop bound by vector-instruction issue).
     f32x4 negm[QS];
-    float m_ref[QS];    // (HOLD = false only)
     // Row sums on the matrix core (round 5): lsum[qs] += ones[16 x 32] P^T[qs] - every row of the result is the sum of the block's 32
     // values of p for query fr, over ALL four lanes' contraction slots.  Two MFMAs per block instead of 16 v_add_f32 + a final lane
     // reduction: the kernel is bound by vector-instruction ISSUE (an MFMA holds the SIMD's issue for 8 cycles, a v_add for 4; see the
@@ -130,13 +160,12 @@ __global__ __launch_bounds__(64 * NW, OCC) void attention_bf16_v3_kernel(const b
     for (int j = 0; j < 8; ++j) ones_f[j] = (bf16_t)1.0f;
     // (laundered, like va[] below: hipcc re-makes a constant operand and an address sum in every block rather than hold them - 2 v_mov_b64 and
     // 4 v_add_u32 per block, in a loop bound by vector-instruction issue, with registers to spare since the -m_ref quads are moved in place)
-    if (HOLD) asm volatile("" : "+v"(ones_f));
+    asm volatile("" : "+v"(ones_f));
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) {
 #pragma unroll
         for (int db = 0; db < 4; ++db) o[db][qs] = (f32x4){0.f, 0.f, 0.f, 0.f};
         negm[qs] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        m_ref[qs] = 0.f;
         lsum[qs] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     float inf_v;   // +inf, opaque to the compiler (see the block maxima below)
@@ -207,7 +236,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void attention_bf16_v3_kernel(const b
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
                 va[db] = (unsigned)(size_t)(lptr_t)(a3_lds) + (unsigned)((kt & 1) * (KT * 256) + v_db[db]);
-                if (HOLD) asm volatile("" : "+v"(va[db]));
+                asm volatile("" : "+v"(va[db]));
             }
             a3_static_for<NB>([&](auto blk_c) {
                 constexpr int blk = decltype(blk_c)::value;
@@ -270,13 +299,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void attention_bf16_v3_kernel(const b
                             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) s[kb][qs][r] -= delta;
-                            if (HOLD) {
 #pragma unroll
-                                for (int r = 0; r < 4; ++r) negm[qs][r] -= delta;
-                            } else {
-                                m_ref[qs] += delta;
-                                negm[qs] = (f32x4){-m_ref[qs], -m_ref[qs], -m_ref[qs], -m_ref[qs]};
-                            }
+                            for (int r = 0; r < 4; ++r) negm[qs][r] -= delta;
                         }
                     }
                     // ---- p = 2^(s - m_ref), row sums, P^T[qs] as the B operand (slot (fq, j) = key 16 (j >> 2) + 4 fq + (j & 3)) ----
@@ -291,7 +315,11 @@ __global__ __launch_bounds__(64 * NW, OCC) void attention_bf16_v3_kernel(const b
                         lsum[qs] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones_f, pf[qs], lsum[qs], 0, 0, 0);
                     }
                     // ---- O^T[db][qs] += V^T[db] P^T[qs] ----
-                    if (ASMV) {   // two d blocks' reads in flight ahead of the MFMAs that consume them
+                    {   // two d blocks' reads in flight ahead of the MFMAs that consume them
+                        // (names v_db so that the closure keeps its reference to it, as it did while the builtin-read form lived in this lambda: without
+                        // the capture hipcc numbers the kernel's registers differently - same instructions, other names - and the kernel as
+                        // measured is the one that ships)
+                        (void)v_db;
                         bf16x4 vlo[4], vhi[4];
                         a3_tr_pair<blk * 4096>(vlo[0], vhi[0], va[0]);
                         a3_tr_pair<blk * 4096>(vlo[1], vhi[1], va[1]);
@@ -304,21 +332,6 @@ __global__ __launch_bounds__(64 * NW, OCC) void attention_bf16_v3_kernel(const b
                             for (int qs = 0; qs < QS; ++qs) o[db][qs] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qs], o[db][qs], 0, 0, 0);
                             if (db == 0) a3_tr_pair<blk * 4096>(vlo[2], vhi[2], va[2]);
                             if (db == 1) a3_tr_pair<blk * 4096>(vlo[3], vhi[3], va[3]);
-                        }
-                    } else {
-                        const char* vp = B0 + blk * 4096;
-#pragma unroll
-                        for (int db = 0; db < 4; ++db) {
-                            const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(vp + v_db[db]));
-                            const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(vp + 2048 + v_db[db]));
-                            bf16x8 vf;
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                vf[j] = v0[j];
-                                vf[4 + j] = v1[j];
-                            }
-#pragma unroll
-                            for (int qs = 0; qs < QS; ++qs) o[db][qs] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qs], o[db][qs], 0, 0, 0);
                         }
                     }
                 }
@@ -340,26 +353,26 @@ __global__ __launch_bounds__(64 * NW, OCC) void attention_bf16_v3_kernel(const b
     }
 }
 
-// Items item0 .. item0 + nitems - 1 of a batch cut into query blocks of 16 QS NW queries, nqblk per clip-head (nqblk may exceed
+// Items item0 .. item0 + nitems - 1 of a batch cut into query blocks of 32 NW queries, nqblk per clip-head (nqblk may exceed
 // ceil(T / (16 QS NW)): blocks past the clip's end return at once).
-template <int NW, int KT, int OCC, int QS = 2, bool ASMV = true, bool HOLD = true>
+template <int NW, int KT, int OCC>
 inline hipError_t launch_attention_bf16_v3_items(const bf16_t* qkv, bf16_t* out, int T, int nqblk, const int* tpref, hipStream_t s, int item0,
                                                  int nitems) {
     static LdsAttrOnce configured;
-    auto kern = attention_bf16_v3_kernel<NW, KT, OCC, QS, ASMV, HOLD>;
-    constexpr int lds = attn_bf16_v2_lds(KT);
+    auto kern = attention_bf16_v3_kernel<NW, KT, OCC>;
+    constexpr int lds = attn_bf16_lds(KT);
     if (hipError_t e = configured.ensure(reinterpret_cast<const void*>(kern), lds); e != hipSuccess) return e;
     if (nitems <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3(nitems), dim3(64 * NW), lds, s, qkv, out, T, nqblk, tpref, item0);
     return hipGetLastError();
 }
 
-template <int NW, int KT, int OCC, int QS = 2, bool ASMV = true, bool HOLD = true>
+template <int NW, int KT, int OCC>
 inline hipError_t launch_attention_bf16_v3(const bf16_t* qkv, bf16_t* out, int B, int T, const int* tpref, hipStream_t s, int item0 = 0,
                                            int nitems = -1) {
-    const int nqblk = (T + 16 * QS * NW - 1) / (16 * QS * NW);
+    const int nqblk = (T + 32 * NW - 1) / (32 * NW);
     if (nitems < 0) nitems = nqblk * B * 12 - item0;
-    return launch_attention_bf16_v3_items<NW, KT, OCC, QS, ASMV, HOLD>(qkv, out, T, nqblk, tpref, s, item0, nitems);
+    return launch_attention_bf16_v3_items<NW, KT, OCC>(qkv, out, T, nqblk, tpref, s, item0, nitems);
 }
 
 }  // namespace nomad

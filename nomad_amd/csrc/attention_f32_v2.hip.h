@@ -1,6 +1,6 @@
 // fp32 self-attention, second generation (the reference's arithmetic: exact fp32 products, fp32 softmax):
 //   ctx[b,t,h*64:(h+1)*64] = softmax_j(q[b,t,h] . k[b,j,h]) v[b,j,h]        (fairseq MultiheadAttention)
-// on qkv[B*T][2304] = [q*64^-0.5 | k | v] fp32.  Same structure as attention_bf16_v2.hip.h.  Matrix shape: v_mfma_f32_16x16x4_f32
+// on qkv[B*T][2304] = [q*64^-0.5 | k | v] fp32.  Same structure as the bf16 kernel (attention_bf16_v3.hip.h, which also holds the helpers shared with it).  Matrix shape: v_mfma_f32_16x16x4_f32
 // since the end of round 4 (the operand maps of THAT shape are in the second comment block below; this first block describes the
 // structure, which the shape change kept):
 //   * 128 queries per workgroup, 32 per wave; both products TRANSPOSED (S^T = K Q^T, O^T += V^T P^T), so a lane owns its
@@ -18,7 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "attention_bf16_v2.hip.h"
+#include "attention_bf16_v3.hip.h"
 
 namespace nomad {
 
@@ -42,14 +42,6 @@ constexpr int attn_f32_v2_lds() { return 2 * kF2Buf; }
 // clip c's [12][T_c] block at 12 * tpref[c].
 // grid: 1-D, ceil(T / 128) * B * 12 workgroups of 256 threads; dynamic LDS attn_f32_v2_lds().
 // tpref (nullable): ragged batches - clip b owns rows tpref[b] .. tpref[b+1]-1; T is then the longest clip's.
-__device__ __forceinline__ float f2_max4(float x) {   // maximum over the four lanes fi, fi + 16, fi + 32, fi + 48, in all of them
-    const unsigned u = __float_as_uint(x);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const float y = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    float lo, hi;
-    a2_halves(y, lo, hi);
-    return fmaxf(lo, hi);
-}
 __device__ __forceinline__ float f2_sum4(float x) {   // sum over the same four lanes (fixed order: rows 0+1, 2+3, then the halves)
     const unsigned u = __float_as_uint(x);
     const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
@@ -59,9 +51,6 @@ __device__ __forceinline__ float f2_sum4(float x) {   // sum over the same four 
     return lo + hi;
 }
 
-// EXTV (true in every product launch): the K / V fragments as ext-vector loads; false = float4 struct copies, in front of which hipcc
-// waits for the next tile's LDS-DMA (A/B runs of libnomad_diag.so, NOMAD_F32_ATTN_STRUCT_LOADS=1).
-template <bool EXTV = true, bool VT4 = true>
 __global__ __launch_bounds__(256, 3) void attention_f32_v2_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                   float* __restrict__ lse, int T, int nqblk,
                                                                   const int* __restrict__ tpref, int t_min) {
@@ -132,27 +121,17 @@ __global__ __launch_bounds__(256, 3) void attention_f32_v2_kernel(const float* _
         for (int i = 0; i < 2; ++i) {
             // V[key = row][d = 4*c16 + c] -> V^T[d][key]: row d is 128 B, chunk (key >> 2) ^ ((d >> 1) & 7), element key & 3
             const int cid = tid + i * 256, row = cid >> 4, c16 = cid & 15;
-            if (VT4) {
-                // Round 6: lanes l, l + 16, l + 32, l + 48 of a wave hold keys 4 kq .. 4 kq + 3 of the same four d: a 4 x 4 transpose across
-                // them (two v_permlane16_swap, two v_permlane32_swap) leaves lane group k with the four KEYS of d = 4 c16 + k - one chunk
-                // of V^T, one ds_write_b128 instead of four ds_write_b32 whose 16 lanes of a key hit 4 banks (PMC: 3.9 % of the kernel's
-                // cycles were LDS bank conflicts, all from these stores).  Data movement only: the same bytes land in the same places.
-                const auto ab = __builtin_amdgcn_permlane16_swap(__float_as_uint(vreg[i].x), __float_as_uint(vreg[i].y), false, false);
-                const auto cd = __builtin_amdgcn_permlane16_swap(__float_as_uint(vreg[i].z), __float_as_uint(vreg[i].w), false, false);
-                const auto ac = __builtin_amdgcn_permlane32_swap(ab[0], cd[0], false, false);
-                const auto bd = __builtin_amdgcn_permlane32_swap(ab[1], cd[1], false, false);
-                const int kq = row >> 2, k = row & 3, d = 4 * c16 + k;
-                f32x4 v4 = {__uint_as_float(ac[0]), __uint_as_float(bd[0]), __uint_as_float(ac[1]), __uint_as_float(bd[1])};
-                *reinterpret_cast<f32x4*>(B0 + kF2KT * 256 + d * 128 + 16 * (kq ^ ((d >> 1) & 7))) = v4;
-                continue;
-            }
-            const int kq = row >> 2, ke = row & 3;
-            char* vt = B0 + kF2KT * 256 + 4 * ke;
-            const int d0 = 4 * c16, x0 = (d0 >> 1) & 7, x1 = x0 + 1;  // d0, d0+1 share x0; d0+2, d0+3 share x0 + 1 (d0 % 4 == 0)
-            *reinterpret_cast<float*>(vt + (d0 + 0) * 128 + 16 * (kq ^ x0)) = vreg[i].x;
-            *reinterpret_cast<float*>(vt + (d0 + 1) * 128 + 16 * (kq ^ x0)) = vreg[i].y;
-            *reinterpret_cast<float*>(vt + (d0 + 2) * 128 + 16 * (kq ^ x1)) = vreg[i].z;
-            *reinterpret_cast<float*>(vt + (d0 + 3) * 128 + 16 * (kq ^ x1)) = vreg[i].w;
+            // Round 6: lanes l, l + 16, l + 32, l + 48 of a wave hold keys 4 kq .. 4 kq + 3 of the same four d: a 4 x 4 transpose across
+            // them (two v_permlane16_swap, two v_permlane32_swap) leaves lane group k with the four KEYS of d = 4 c16 + k - one chunk
+            // of V^T, one ds_write_b128 instead of four ds_write_b32 whose 16 lanes of a key hit 4 banks (PMC: 3.9 % of the kernel's
+            // cycles were LDS bank conflicts, all from these stores).  Data movement only: the same bytes land in the same places.
+            const auto ab = __builtin_amdgcn_permlane16_swap(__float_as_uint(vreg[i].x), __float_as_uint(vreg[i].y), false, false);
+            const auto cd = __builtin_amdgcn_permlane16_swap(__float_as_uint(vreg[i].z), __float_as_uint(vreg[i].w), false, false);
+            const auto ac = __builtin_amdgcn_permlane32_swap(ab[0], cd[0], false, false);
+            const auto bd = __builtin_amdgcn_permlane32_swap(ab[1], cd[1], false, false);
+            const int kq = row >> 2, k = row & 3, d = 4 * c16 + k;
+            f32x4 v4 = {__uint_as_float(ac[0]), __uint_as_float(bd[0]), __uint_as_float(ac[1]), __uint_as_float(bd[1])};
+            *reinterpret_cast<f32x4*>(B0 + kF2KT * 256 + d * 128 + 16 * (kq ^ ((d >> 1) & 7))) = v4;
         }
     };
     // ---- fragment addresses inside a buffer ----
@@ -183,13 +162,8 @@ __global__ __launch_bounds__(256, 3) void attention_f32_v2_kernel(const float* _
                         // (an ext-vector load, not a float4 struct copy: the struct's load carries no alias information and hipcc then
                         // puts s_waitcnt vmcnt(0) in front of it - "the LDS-DMA issued above may alias" - which serialises the next
                         // tile's fetch with this tile's products; profiles/NOTEBOOK.md, round 5)
-                        float4 kf;
-                        if (EXTV) {
-                            const f32x4 kv = *reinterpret_cast<const f32x4*>(B0 + k_base + sk * 4096 + 16 * ((4 * j + g) ^ fi));
-                            kf = make_float4(kv[0], kv[1], kv[2], kv[3]);
-                        } else {
-                            kf = *reinterpret_cast<const float4*>(B0 + k_base + sk * 4096 + 16 * ((4 * j + g) ^ fi));
-                        }
+                        const f32x4 kv = *reinterpret_cast<const f32x4*>(B0 + k_base + sk * 4096 + 16 * ((4 * j + g) ^ fi));
+                        const float4 kf = make_float4(kv[0], kv[1], kv[2], kv[3]);
 #pragma unroll
                         for (int sq = 0; sq < 2; ++sq) {
                             if (sq < nsq) {
@@ -254,13 +228,8 @@ __global__ __launch_bounds__(256, 3) void attention_f32_v2_kernel(const float* _
                 if (sk < nsk) {
 #pragma unroll
                     for (int sd = 0; sd < 4; ++sd) {
-                        float4 vf;
-                        if (EXTV) {
-                            const f32x4 vv = *reinterpret_cast<const f32x4*>(B0 + v_base + sd * 2048 + 16 * ((4 * sk + g) ^ v_x));
-                            vf = make_float4(vv[0], vv[1], vv[2], vv[3]);
-                        } else {
-                            vf = *reinterpret_cast<const float4*>(B0 + v_base + sd * 2048 + 16 * ((4 * sk + g) ^ v_x));
-                        }
+                        const f32x4 vv = *reinterpret_cast<const f32x4*>(B0 + v_base + sd * 2048 + 16 * ((4 * sk + g) ^ v_x));   // (ext-vector load: as for K)
+                        const float4 vf = make_float4(vv[0], vv[1], vv[2], vv[3]);
 #pragma unroll
                         for (int sq = 0; sq < 2; ++sq) {
                             if (sq < nsq) {
@@ -293,11 +262,10 @@ __global__ __launch_bounds__(256, 3) void attention_f32_v2_kernel(const float* _
     }
 }
 
-template <bool EXTV = true, bool VT4 = true>
 inline hipError_t launch_attention_f32_v2(const float* qkv, float* out, float* lse, int B, int T, const int* tpref, hipStream_t s,
                                           int t_min = 0) {
     const int nqblk = (T + 127) / 128;
-    hipLaunchKernelGGL((attention_f32_v2_kernel<EXTV, VT4>), dim3(nqblk * B * 12), dim3(256), attn_f32_v2_lds(), s, qkv, out, lse, T, nqblk, tpref, t_min);
+    hipLaunchKernelGGL(attention_f32_v2_kernel, dim3(nqblk * B * 12), dim3(256), attn_f32_v2_lds(), s, qkv, out, lse, T, nqblk, tpref, t_min);
     return hipGetLastError();
 }
 

@@ -14,8 +14,8 @@
 // A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; D[i][j] lands at column j = l & 15, rows i = 4 (l >> 4) + reg.  A 32 x 32
 // accumulator block is 2 x 2 such sub-blocks.  The contraction index may be visited in any order, so one ds_read_b128 per lane feeds
 // four consecutive k-steps: lane (fi, g) reads logical chunk 4 kh + g of its row and element c of it feeds k-step c, which contracts
-// k = 16 kh + c + {0, 4, 8, 12} (gemm_f32_glds_body, M16).  The legacy register-staged kernel gemm_f32_kernel (diag tiles 0-19) and the
-// persistent experiment gemm_f32_pers_kernel are still on 32x32x2: they are NOT bit-identical to the production tiles any more.
+// k = 16 kh + c + {0, 4, 8, 12} (gemm_f32_glds_body, M16).  The legacy register-staged kernel gemm_f32_kernel (diag tiles 0-19)
+// is still on 32x32x2: it is NOT bit-identical to the production tiles any more.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -95,7 +95,7 @@ struct GemmParams {
     // local_row * c_blk_step + b, stored only while that is < the clip's frame count (c_clip_frames for uniform
     // batches, cmap.base[c + 1] - cmap.base[c] for ragged ones).
     int c_blk_step, c_clip_frames;
-    // persistent kernel (gemm_f32_pers_kernel): exact division by amap.clip_rows and by tiles_n as mulhi + shift
+    // lean set-up (gemm_f32_glds_body, OPT bit 16384): exact division by amap.clip_rows and by tiles_n as mulhi + shift
     // (fast_div_magic; magic 0 = quotient 0 / divisor 1)
     unsigned a_clip_magic, tn_magic;
     int a_clip_shift, tn_shift;
@@ -1166,238 +1166,6 @@ inline hipError_t launch_gemm_mixed(GemmParams p, int M1, hipStream_t s) {
     if (hipError_t e = attr_set.ensure(reinterpret_cast<const void*>(gemm_f32_mixed_kernel<OPTB, OPTS>), 160 * 1024); e != hipSuccess) return e;
     const int n_big = pb.tiles_m * pb.tiles_n, n_small = ps.tiles_m * ps.tiles_n;
     hipLaunchKernelGGL((gemm_f32_mixed_kernel<OPTB, OPTS>), dim3(n_big + n_small), dim3(512), CfgB::LDS_BYTES, s, pb, ps, n_big);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Persistent 256 x 128 kernel (round 4).  The per-workgroup timeline of the kernel above (tools/gemm_timeline_f32.py,
-// profiles/r04_gemm_timeline_f32.txt) shows a QKV tile spending 176 us in its K loop and 46 us around it - 13 us of address
-// set-up that crawls next to a peer workgroup's MFMA stream, 9 us until the first K tile has landed and the first barrier is
-// passed, 19 us of LDS-staged epilogue, 5 us until the slot is taken again - and the lone peer fills only ~3/4 of the matrix
-// pipe meanwhile: two workgroups are inside their K loops for 58 % of a CU's time.  Here a workgroup stays resident and walks
-// tiles blockIdx.x, + gridDim.x, ... (two workgroups per CU):
-//  * the LDS-DMA stream never drains: while K tiles nk-2 and nk-1 of an output tile are multiplied, K tiles 0 and 1 of the NEXT
-//    output tile are staged (its three per-lane offsets overwrite the current tile's after their last use, its bases are a few
-//    scalar instructions with precomputed division magic), so the next K loop starts on data that is already in LDS;
-//  * the epilogue is the direct one from transposed accumulators (OPT bit 1024 above): no LDS, so it cannot collide with the
-//    staged K tiles, no barrier, and its vector-memory operations are accounted for in the counted vmcnt of the next two K tiles;
-//  * nothing is recomputed per tile but ~40 scalar and ~20 vector instructions.
-// Same tile, same K loop, same contraction order: bit-identical to every other fp32 instantiation.  Plain C / R matrices,
-// one group, contiguous K (the caller checks); A may be a per-clip RowMap (the conv stack).
-template <bool NOEPI = false, int OPT = 0>
-__global__ __launch_bounds__(512, 4) void gemm_f32_pers_kernel(const GemmParams p) {
-    constexpr int BM = 256, BN = 128, BK = 16, WN = 2, ST = 3, NT = 512, KC = 4, RB = 4, WTM = 64, WTN = 64, TM = 2, TN = 2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                  // [ST][BM][BK]
-    float* Bs = smem + ST * BM * BK;   // [ST][BN][BK]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave - wm * WN;
-    const int nwg = p.tiles_m * p.tiles_n, nk = p.K / BK;
-
-    // tile-independent per-lane DMA geometry: LDS chunk id = tid + i * NT, source chunk swizzled (see the kernel above)
-    int a_rowl[2], a_sw[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int id = tid + i * NT, row = id / KC, pc = id - row * KC;
-        a_rowl[i] = row;
-        a_sw[i] = (pc ^ ((row / RB) % KC)) * 4;
-    }
-    const int b_voff = [&] {
-        const int row = tid / KC, pc = tid - row * KC;
-        return (int)(((long long)row * p.ldw + ((pc ^ ((row / RB) % KC)) * 4)) * 4);
-    }();
-    // fragment read offsets
-    const int frag_row = lane & 31, h = lane >> 5;
-    const int swz = (frag_row / RB) % KC;
-    int koff[2];
-#pragma unroll
-    for (int kq = 0; kq < 2; ++kq) koff[kq] = ((kq * 2 + h) ^ swz) * 4;
-    const int a_row_off = (wm * WTM + frag_row) * BK, b_row_off = (wn * WTN + frag_row) * BK;
-
-    auto row_addr_fast = [&](int m) -> long long {
-        const int c = p.a_clip_magic ? fast_div(m, p.a_clip_magic, p.a_clip_shift) : 0;
-        return p.amap.off + (long long)c * p.amap.clip_stride + (long long)(m - c * p.amap.clip_rows) * p.amap.ld;
-    };
-    // tile t -> (m0, n0), scalar tile bases, per-lane A offsets
-    auto setup = [&](int t, int& m0_, int& n0_, const float*& at, const float*& bt, int (&av)[2]) {
-        const int wg = xcd_remap(t, nwg);
-        const int tm = p.tn_magic ? fast_div(wg, p.tn_magic, p.tn_shift) : wg;
-        m0_ = tm * BM;
-        n0_ = (wg - tm * p.tiles_n) * BN;
-        const long long row0 = row_addr_fast(m0_);
-        at = uniform_ptr(p.A + row0);
-        bt = uniform_ptr(p.W + (long long)n0_ * p.ldw);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int m = m0_ + a_rowl[i];
-            m = m < p.M ? m : p.M - 1;
-            av[i] = (int)((row_addr_fast(m) - row0 + a_sw[i]) * 4);
-        }
-    };
-    auto issue = [&](const float* at, const float* bt, const int (&av)[2], int k_off_bytes, int stage) {
-        float* as_ = As + stage * BM * BK + wave * 256;
-        float* bs_ = Bs + stage * BN * BK + wave * 256;
-        dma16_buffer(at, (lptr_t)(as_), av[0], k_off_bytes);
-        dma16_buffer(at, (lptr_t)(as_ + NT * 4), av[1], k_off_bytes);
-        dma16_buffer(bt, (lptr_t)(bs_), b_voff, k_off_bytes);
-    };
-
-    // Two cursors walk the same sequence of (output tile, K tile): the LOAD side (a_tile / b_tile / a_voff / k_ld) runs two K
-    // tiles ahead of the multiply side and crosses into the next output tile first - its bases and per-lane offsets are
-    // recomputed in place right after the current tile's last K tile has been issued.  The last output tile of a workgroup
-    // "crosses" into itself: two K tiles are staged that nobody reads (no has-next special case anywhere in the loop).
-    // OPT bit 1 (experiment): the second workgroup of every CU starts half a tile late, so that the two do not reach their
-    // epilogues together for the rest of the launch (they process equal tiles at equal speed from a common start otherwise)
-    if ((OPT & 1) && blockIdx.x >= gridDim.x / 2) {
-        const int naps = nk / 4;   // ~ half a K loop: a K tile takes ~3.5 us when two workgroups share the CU, s_sleep 127 ~ 3.4 us
-        for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-    int tile = blockIdx.x;
-    int m0, n0, m0_ld, n0_ld, a_voff[2];
-    const float *a_tile, *b_tile;
-    setup(tile, m0_ld, n0_ld, a_tile, b_tile, a_voff);
-    m0 = m0_ld;
-    n0 = n0_ld;
-    int k_ld = 0;         // byte offset of the next K tile to stage, within the load side's output tile
-    const int k_bytes = p.K * 4;
-    issue(a_tile, b_tile, a_voff, k_ld, 0);
-    k_ld += BK * 4;
-    issue(a_tile, b_tile, a_voff, k_ld, 1);
-    k_ld += BK * 4;
-    int cur = 0;          // LDS stage of the K tile being multiplied
-    int fresh = 2;        // K tiles to go before an epilogue's vector-memory operations no longer sit between the DMA groups
-    const bool has_r = p.R != nullptr;
-    while (true) {
-        const bool has_next = tile + (int)gridDim.x < nwg;
-        f32x16 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        for (int kt = 0; kt < nk; ++kt) {
-            // this wave's share of K tile kt has landed once only NEWER vector-memory operations are outstanding: the next K
-            // tile's three DMA instructions and, for the first two K tiles after an epilogue, that epilogue's 8 bias loads, 16
-            // stores and (with a residual) 16 residual loads, which were issued between the two DMA groups
-            if (fresh < 2) {
-                if (NOEPI) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-                else if (has_r) asm volatile("s_waitcnt vmcnt(43)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(27)" ::: "memory");
-                ++fresh;
-            } else {
-                asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            }
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            int nb = cur + 2;
-            nb = nb >= ST ? nb - ST : nb;
-            const float* as = As + cur * BM * BK + a_row_off;
-            const float* bs = Bs + cur * BN * BK + b_row_off;
-#pragma unroll
-            for (int kq = 0; kq < 2; ++kq) {
-                if (kq == 1) {   // stage the K tile two ahead in the stream, behind the first k-step's MFMAs
-                    __builtin_amdgcn_sched_barrier(0);   // (unconditional here: without the fence the compiler hoists the DMA to the barrier)
-                    issue(a_tile, b_tile, a_voff, k_ld, nb);
-                    __builtin_amdgcn_sched_barrier(0);
-                    k_ld += BK * 4;
-                    if (k_ld == k_bytes) {   // the load side crosses into the next output tile
-                        k_ld = 0;
-                        setup(has_next ? tile + (int)gridDim.x : tile, m0_ld, n0_ld, a_tile, b_tile, a_voff);
-                    }
-                }
-                f32x4 af[TM], bf[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(as + i * 32 * BK + koff[kq]);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(bs + j * 32 * BK + koff[kq]);
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[j][c], af[i][c], acc[i][j], 0, 0, 0);   // transposed: D^T
-            }
-            cur = cur + 1 == ST ? 0 : cur + 1;
-        }
-        fresh = 0;
-        // ---- direct epilogue from transposed accumulators (as OPT bit 1024 of the kernel above) ----
-        {
-            int lane_e = lane;
-            asm volatile("" : "+v"(lane_e));
-            const int mw = m0 + wm * WTM, nw = n0 + wn * WTN;
-            const int mrow = lane_e & 31, hh = lane_e >> 5;
-            auto clamp_bytes = [](long long v) { return (unsigned)(v < 0 ? 0 : (v > (1ll << 30) ? (1ll << 30) : v)); };
-            const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>(uniform_ptr(p.C + p.cmap.off + (long long)mw * p.cmap.ld + nw)), 0, clamp_bytes((long long)(p.M - mw) * p.cmap.ld * 4), 0x00020000);
-            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>(uniform_ptr(has_r ? p.R + p.rmap.off + (long long)mw * p.rmap.ld + nw : p.C)), 0,
-                has_r ? clamp_bytes((long long)(p.M - mw) * p.rmap.ld * 4) : 0u, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>(uniform_ptr(p.bias ? p.bias + nw : p.C)), 0, p.bias ? (unsigned)(WTN * 4) : 0u, 0x00020000);
-            const int c_voff = (mrow * p.cmap.ld + 4 * hh) * 4, r_voff = (mrow * p.rmap.ld + 4 * hh) * 4, b_off = 16 * hh;
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                f32x4 rres[TM][4], b4[4];
-                if (has_r) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int g = 0; g < 4; ++g)
-                            rres[i][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, r_voff + i * 32 * p.rmap.ld * 4 + (j * 32 + 8 * g) * 4, 0, 0));
-                }
-#pragma unroll
-                for (int g = 0; g < 4; ++g) b4[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, b_off + (j * 32 + 8 * g) * 4, 0, 0));
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * g + e] + b4[g][e];
-                        if (p.gelu) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-                        }
-                        if (has_r) v += rres[i][g];
-                        // (VGPR offset only - see the store-data hazard note at OPT bit 1024)
-                        if (!NOEPI || p.M < 0)   // (NOEPI, a timing probe: the never-true condition keeps the arithmetic alive)
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rc, c_voff + i * 32 * p.cmap.ld * 4 + (j * 32 + 8 * g) * 4, 0, 0);
-                    }
-            }
-        }
-        if (!has_next) break;
-        tile += (int)gridDim.x;
-        m0 = m0_ld;
-        n0 = n0_ld;
-    }
-}
-
-// workgroups: two per CU (the kernel's residency), never more than there are tiles
-inline hipError_t launch_gemm_pers(GemmParams p, hipStream_t s, int num_cus, bool noepi = false, bool one_tile_each = false, bool stagger = false) {
-    p.tiles_m = (p.M + 255) / 256;
-    p.tiles_n = p.N / 128;
-    p.a_clip_magic = p.tn_magic = 0;
-    p.a_clip_shift = p.tn_shift = 0;
-    if (p.amap.clip_rows < p.M) fast_div_magic((unsigned)p.amap.clip_rows, &p.a_clip_magic, &p.a_clip_shift);
-    if (p.tiles_n > 1) fast_div_magic((unsigned)p.tiles_n, &p.tn_magic, &p.tn_shift);
-    static LdsAttrOnce attr_set;
-    if (hipError_t e = attr_set.ensure(reinterpret_cast<const void*>(gemm_f32_pers_kernel<false>), 160 * 1024); e != hipSuccess) return e;
-    static LdsAttrOnce attr_set_2;
-    if (hipError_t e = attr_set_2.ensure(reinterpret_cast<const void*>(gemm_f32_pers_kernel<true>), 160 * 1024); e != hipSuccess) return e;
-    const long long nwg = (long long)p.tiles_m * p.tiles_n;
-    // one_tile_each: the same kernel launched with one workgroup per tile - no tile loop, only its lean set-up and direct epilogue
-    const int grid = (int)((one_tile_each || nwg < 2ll * num_cus) ? nwg : 2ll * num_cus);
-    constexpr int lds = 3 * (256 + 128) * 16 * 4;
-    if (stagger) {
-        static LdsAttrOnce attr2;
-        if (hipError_t e = attr2.ensure(reinterpret_cast<const void*>(gemm_f32_pers_kernel<false, 1>), 160 * 1024); e != hipSuccess) return e;
-        hipLaunchKernelGGL((gemm_f32_pers_kernel<false, 1>), dim3(grid), dim3(512), lds, s, p);
-    } else if (noepi) hipLaunchKernelGGL(gemm_f32_pers_kernel<true>, dim3(grid), dim3(512), lds, s, p);
-    else hipLaunchKernelGGL(gemm_f32_pers_kernel<false>, dim3(grid), dim3(512), lds, s, p);
     return hipGetLastError();
 }
 

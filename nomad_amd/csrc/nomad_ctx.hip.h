@@ -63,47 +63,16 @@ struct LayerDev {
 
 // Kernel-choice switches.  Every default below is the shipped configuration, and the product library (libnomad_hip.so) never
 // reads the environment: "nothing but the arguments" decides what a call does.  Only libnomad_diag.so (-DNOMAD_DIAG) fills a
-// context's copy from NOMAD_* environment variables, once, in nomad_create (tuning_from_env) - the A/B runs of tools/ and profiles/.
+// context's copy from NOMAD_* environment variables, once, in nomad_create (tuning_from_env).  What is left here is what a test
+// flips (the other side stays as that test's reference) and the run-time modes of the persistent bf16 kernel; a switch whose A/B
+// run is settled goes, with the losing kernel (DESIGN.md 4a-4c and profiles/NOTEBOOK.md keep the measurements).
 struct Tuning {
     bool splitk_lnb_fuse = true;   // NOMAD_SPLITK_LNB: a split-K dX GEMM in front of a LayerNorm backward has that kernel form its output (no epilogue launch)
     bool splitk_ln_fuse = true;    // NOMAD_SPLITK_LN: a split-K out_proj / fc2 normalises its rows in its own epilogue (splitk_epilogue_ln_kernel)
-    bool splitk_posconv = true;    // NOMAD_SPLITK_POSCONV: the grouped pos-conv of the loss path splits K four ways
-    bool splitk_layers = true;     // NOMAD_SPLITK_LAYERS: so do the dense GEMMs of a small layer-output forward
-    bool f32_plain_epi = true;     // NOMAD_F32_PLAIN_EPI: small epilogue for plain C / R matrices
-    bool f32_lean = true, f32_direct_epi = true, f32_skew = true, f32_res_ahead = true;   // NOMAD_F32_LEAN / _DIRECT_EPI / _SKEW / _RES_AHEAD
-    int f32_mixed = 1;             // NOMAD_F32_MIXED: two tile shapes in one launch
-    int f32_mixed_m1 = 0;          // NOMAD_F32_MIXED_M1: forced row split (diagnostics)
-    int f32_mixed_slots = 0;       // NOMAD_F32_MIXED_SLOTS: 0 = two workgroup slots per CU
-    double f32_mixed_min = 0.05, f32_mixed_max = 0.70;   // NOMAD_F32_MIXED_MIN / _MAX: fill of the last round that takes the split
-    bool f32_mixed_prefer = false; // NOMAD_F32_MIXED_PREFER
-    bool f32_quant_tile = true;    // NOMAD_F32_QUANT_TILE: tile choice by the largest tile count any CU gets
     bool f32_conv_wino = true;     // NOMAD_F32_CONV_WINO: conv1 .. conv4 of every fp32-product forward in polyphase Winograd form (conv_s2_f32.hip.h; 0: the implicit GEMM)
-    double f32_quant_penalty = 0.0;  // NOMAD_F32_QUANT_PENALTY (percent): 0 = 8 % with two concurrent parts, 3 % alone
-    bool f32_longk_33 = false;     // NOMAD_F32_LONGK_33
-    int f32_mid_tile = 31;         // NOMAD_F32_MID_TILE
-    bool f32_attn_vt4 = true;      // NOMAD_F32_ATTN_VT4 (diag): the fp32 attention transposes V across lanes and stores 16-byte chunks (0: four ds_write_b32, A/B)
-    bool f32_attn_struct_loads = false;  // NOMAD_F32_ATTN_STRUCT_LOADS (diag): the fp32 attention's LDS fragments as float4 struct copies (A/B)
-    bool bf16_posconv_slab = true;  // NOMAD_BF16_POSCONV_SLAB: the bf16 pos-conv with its input slab resident in LDS (posconv_bf16_slab.hip.h);
-                                    // false: the grouped GEMM on 128 x 64 tiles it replaces (A/B)
-    int bf16_attn_dma = 2;         // NOMAD_BF16_ATTN_DMA: K / V of the bf16 attention by LDS-DMA in 128-key tiles
-    int bf16_attn_v3 = 2;          // NOMAD_BF16_ATTN_V3: the bf16 attention on v_mfma_f32_16x16x32_bf16 with 32 queries per wave (2, shipped);
-                                   // 3: its V reads through the builtin; 5: round 5's register use; 4 / 8: 64 queries per wave, 4 / 8 waves per workgroup (A/B: no faster); 0: the 32x32x16 kernel
     int bf16_attn_tail = 0;        // NOMAD_BF16_ATTN_TAIL (diag): a last round of 256-query workgroups that is at most this many eighths full runs
                                    // as 128-query workgroups in a second launch (0: never; run_attention_bf16 - measured slower, A/B only)
     int bf16_ln_rows = 4;          // NOMAD_BF16_LN_ROWS: rows per wave of the bf16 forward's LayerNorm (4: one gamma / beta fetch per 4 rows; 1: A/B)
-    bool bf16_conv0_mfma = true;   // NOMAD_BF16_CONV0_MFMA
-    bool bf16_conv0_gelu_erf = false;   // NOMAD_BF16_CONV0_GELU_ERF (diag): the matrix-core conv0 with the erf GELU instead of the bf16-output one (A/B)
-    int p8_min_tiles = 256;        // NOMAD_BF16_8PHASE_MIN_TILES: smallest grid (256 x 256 tiles) for the deep-pipelined bf16 kernels
-    bool p8_nt_stores = true;      // NOMAD_BF16_NT_STORES
-    int p8_rpre = 3;               // NOMAD_BF16_RPRE
-    bool x3_plain_epi = true;      // NOMAD_X3_PLAIN_EPI
-    bool p8_three_b = true;        // NOMAD_BF16_B3
-    int p8_n192 = 0;               // NOMAD_BF16_N192
-    bool p9 = true;                // NOMAD_BF16_P9: the persistent 256 x 256 bf16 kernel wherever it applies
-    bool p9_res = true;            // NOMAD_BF16_P9_RES: residual GEMMs on the persistent kernel too (0: the one-tile-per-workgroup kernel, A/B)
-    bool p9_share = false;         // NOMAD_BF16_P9_SHARE: persistent launches of concurrent batch parts share the CUs (1 / parts each)
-    bool p9_tail_split = false;    // NOMAD_BF16_P9_TAIL: rows of a sparse last round of its tiles go to the 128 x 128 kernel (+4-17 % on the
-                                   // N = 768 GEMMs alone, -3 % in the two-stream forward, where the other half's kernels fill that round)
     int p9_short = 1;              // NOMAD_BF16_P9_SHORT: 192-row tiles of the persistent kernel (a run-time mode of the same instantiation) where they
                                    // save more than they cost: 1 = by the round count, batches that run alone only (the N = 768 GEMMs of config C5 on one
                                    // stream), 2 = every problem, 0 = never
@@ -119,50 +88,15 @@ struct Tuning {
 static void tuning_from_env(Tuning& t) {
     auto geti = [](const char* n, int d) { const char* e = getenv(n); return e ? atoi(e) : d; };
     auto getb = [](const char* n, bool d) { const char* e = getenv(n); return e ? atoi(e) != 0 : d; };
-    auto getd = [](const char* n, double d) { const char* e = getenv(n); return e ? atof(e) : d; };
     t.splitk_ln_fuse = getb("NOMAD_SPLITK_LN", t.splitk_ln_fuse);
-    t.splitk_posconv = getb("NOMAD_SPLITK_POSCONV", t.splitk_posconv);
-    t.splitk_layers = getb("NOMAD_SPLITK_LAYERS", t.splitk_layers);
-    t.f32_plain_epi = getb("NOMAD_F32_PLAIN_EPI", t.f32_plain_epi);
-    t.f32_lean = getb("NOMAD_F32_LEAN", t.f32_lean);
-    t.f32_direct_epi = getb("NOMAD_F32_DIRECT_EPI", t.f32_direct_epi);
-    t.f32_skew = getb("NOMAD_F32_SKEW", t.f32_skew);
-    t.f32_res_ahead = getb("NOMAD_F32_RES_AHEAD", t.f32_res_ahead);
-    t.f32_mixed = geti("NOMAD_F32_MIXED", t.f32_mixed);
-    t.f32_mixed_m1 = geti("NOMAD_F32_MIXED_M1", t.f32_mixed_m1);
-    t.f32_mixed_slots = geti("NOMAD_F32_MIXED_SLOTS", t.f32_mixed_slots);
-    t.f32_mixed_min = getd("NOMAD_F32_MIXED_MIN", t.f32_mixed_min);
-    t.f32_mixed_max = getd("NOMAD_F32_MIXED_MAX", t.f32_mixed_max);
-    t.f32_mixed_prefer = getb("NOMAD_F32_MIXED_PREFER", t.f32_mixed_prefer);
-    t.f32_quant_tile = getb("NOMAD_F32_QUANT_TILE", t.f32_quant_tile);
+    t.splitk_lnb_fuse = getb("NOMAD_SPLITK_LNB", t.splitk_lnb_fuse);
     t.f32_conv_wino = getb("NOMAD_F32_CONV_WINO", t.f32_conv_wino);
-    t.f32_quant_penalty = getd("NOMAD_F32_QUANT_PENALTY", t.f32_quant_penalty);
-    t.f32_longk_33 = getb("NOMAD_F32_LONGK_33", t.f32_longk_33);
-    t.f32_mid_tile = geti("NOMAD_F32_MID_TILE", t.f32_mid_tile);
-    t.bf16_attn_dma = geti("NOMAD_BF16_ATTN_DMA", t.bf16_attn_dma);
-    t.f32_attn_struct_loads = geti("NOMAD_F32_ATTN_STRUCT_LOADS", t.f32_attn_struct_loads) != 0;
-    t.bf16_posconv_slab = geti("NOMAD_BF16_POSCONV_SLAB", t.bf16_posconv_slab) != 0;
-    t.bf16_attn_v3 = geti("NOMAD_BF16_ATTN_V3", t.bf16_attn_v3);
     t.bf16_attn_tail = geti("NOMAD_BF16_ATTN_TAIL", t.bf16_attn_tail);
     t.bf16_ln_rows = geti("NOMAD_BF16_LN_ROWS", t.bf16_ln_rows);
-    t.bf16_conv0_mfma = getb("NOMAD_BF16_CONV0_MFMA", t.bf16_conv0_mfma);
-    t.p8_min_tiles = geti("NOMAD_BF16_8PHASE_MIN_TILES", t.p8_min_tiles);
-    t.p8_nt_stores = getb("NOMAD_BF16_NT_STORES", t.p8_nt_stores);
-    t.p8_rpre = geti("NOMAD_BF16_RPRE", t.p8_rpre);
-    t.x3_plain_epi = getb("NOMAD_X3_PLAIN_EPI", t.x3_plain_epi);
-    t.p8_three_b = getb("NOMAD_BF16_B3", t.p8_three_b);
-    t.p8_n192 = geti("NOMAD_BF16_N192", t.p8_n192);
-    t.p9 = getb("NOMAD_BF16_P9", t.p9);
-    t.p9_tail_split = getb("NOMAD_BF16_P9_TAIL", t.p9_tail_split);
-    t.p9_share = getb("NOMAD_BF16_P9_SHARE", t.p9_share);
-    t.p9_res = getb("NOMAD_BF16_P9_RES", t.p9_res);
     t.p9_short = geti("NOMAD_BF16_P9_SHORT", t.p9_short);
     t.p9_skew = geti("NOMAD_BF16_P9_SKEW", t.p9_skew);
     t.p9_late = getb("NOMAD_BF16_P9_LATE", t.p9_late);
     t.p9_wl = getb("NOMAD_BF16_P9_WL", t.p9_wl);
-    t.splitk_lnb_fuse = getb("NOMAD_SPLITK_LNB", t.splitk_lnb_fuse);
-    t.f32_attn_vt4 = getb("NOMAD_F32_ATTN_VT4", t.f32_attn_vt4);
-    t.bf16_conv0_gelu_erf = getb("NOMAD_BF16_CONV0_GELU_ERF", t.bf16_conv0_gelu_erf);
     t.attn_bwd_small = getb("NOMAD_ATTN_BWD_SMALL", t.attn_bwd_small);
 }
 #endif
@@ -233,7 +167,7 @@ struct nomad_ctx {
     bf16_t *qkv_w16[NOMAD_NUM_LAYERS] = {}, *o_w16[NOMAD_NUM_LAYERS] = {}, *fc1_w16[NOMAD_NUM_LAYERS] = {},
            *fc2_w16[NOMAD_NUM_LAYERS] = {};
     // the bf16 path's q rows of the fused QKV weight and bias also carry log2(e): its attention kernel works in log2
-    // units (p = 2^(s - m), attention_bf16_v2.hip.h); qkv_b16 is the matching fp32 bias
+    // units (p = 2^(s - m), attention_bf16_v3.hip.h); qkv_b16 is the matching fp32 bias
     float* qkv_b16[NOMAD_NUM_LAYERS] = {};
     // split (hi | lo bf16 planes) weight copies for the bf16x3 path (built by nomad_enable_bf16x3)
     bool x3_ready = false;

@@ -22,46 +22,30 @@ static bool p9_applies(const GemmParams& p, int groups) {
            !(p.gelu && p.R);   // (GELU and a residual in one epilogue: no GEMM of the model has both, and the shipped instantiation has no copy for it)
 }
 
-// 256 x 192 instead of 256 x 256 tiles in the deep-pipelined bf16 kernel (gemm_bf16_8phase.hip.h, NJ = 3) for the N = 768 GEMMs
-// of config C5 (out_proj, fc2: 188 row tiles x 3 = 2.2 rounds of the 256 CUs, 2.94 with 192-column tiles).  Bit-identical
-// results.  OFF by default: in isolation fc2 runs 19 % and out_proj 12 % faster (hipBLASLt picks MT256x192 there too), but inside
-// the C5 forward the other GEMMs slow down by more than that - the chip holds 2130 instead of 2157 MHz (2400 nominal) with
-// them, 19.25 vs 18.98 ms per forward (profiles/r03_n192_null.txt).  NOMAD_BF16_N192=1 takes them wherever they save a round
-// (a 192-column tile costs ~0.78 of a 256-column one), =2 wherever N % 192 == 0.
-static bool p8_use_n192(const nomad_ctx* c, int M, int N, int K) {
-    const int mode = c->tune.p8_n192;
-    if (N % 192 != 0 || mode <= 0) return false;
-    if (mode == 2) return true;
-    if (mode == 3 && K < 2048) return false;   // A/B: the long-K problems only (fc2)
-    if (mode == 4 && K >= 2048) return false;  // A/B: the short-K problems only (out_proj, proj)
-    const long long tm = (M + 255) / 256;
-    const long long r256 = (tm * (N / 256) + 255) / 256, r192 = (tm * (N / 192) + 255) / 256;
-    return 0.80 * (double)r192 < 0.95 * (double)r256;
-}
+// Smallest grid, in 256 x 256 tiles, that takes the deep-pipelined kernels: one round of the 256 CUs (profiles/r01_gemm_sweep_bf16_8phase.json)
+constexpr int kP8MinTiles = 256;
 
+// Settled A/B runs behind this dispatch (profiles/NOTEBOOK.md); the losing kernels were removed from the product:
+// the deep-pipelined kernels store with the non-temporal hint, stage B in three buffers (160 KB of LDS) and prefetch the residual in
+// their epilogue, with the small epilogue for plain C / R; bf16x3 has one plain instantiation with a run-time output format; the
+// persistent kernel runs wherever it applies, residual GEMMs included, on all CUs.  256 x 192 tiles (tile 55) are never picked: in
+// isolation fc2 runs 19 % and out_proj 12 % faster on them, but inside the C5 forward the other GEMMs slow down by more than that - the
+// chip holds 2130 instead of 2157 MHz, 19.25 vs 18.98 ms per forward (profiles/r03_n192_null.txt).  Handing the rows of a sparse last
+// round of persistent tiles to the 128 x 128 kernel was +4-17 % on the N = 768 GEMMs alone and -3 % in the two-stream forward.
 int run_gemm_bf16(nomad_ctx* c, GemmParams p, int groups, hipStream_t s, int tile) {
-    // Tuning (A/B switches of the diag library; defaults = shipped): p8_min_tiles - smallest grid in 256 x 256 tiles that takes the
-    // deep-pipelined kernels; p8_nt_stores - their output stores carry the non-temporal hint; p8_rpre - residual prefetch in p8_epilogue
-    // (0 off, 1 residual GEMMs only, 2 every GEMM, 3 = 2 + the small epilogue for plain C / R); x3_plain_epi - one bf16x3 instantiation
-    // with a run-time output format; p8_three_b - three B buffers (160 KB of LDS); p9 - the persistent kernel wherever it applies
     const Tuning& tu = c->tune;
-    auto p8_min_tiles = [&] { return tu.p8_min_tiles; };
-    auto p8_nt_stores = [&] { return tu.p8_nt_stores; };
-    auto p8_residual_prefetch = [&] { return tu.p8_rpre; };
-    auto x3_plain_epilogue = [&] { return tu.x3_plain_epi; };
-    auto p8_three_b = [&] { return tu.p8_three_b; };
-    auto p9_on = [&] { return tu.p9; };
     const double flops = 2.0 * p.M * (double)p.n_valid * p.K * groups;  // bf16x3: the fp32-equivalent count, not 3x
     if (tile < 0) {
         // measured (profiles/r01_gemm_sweep_bf16.json): 256x256 tiles (wave tile 64x128) win on wide (N >= 1024)
         // and very tall problems, 128x128 (8 waves) on the N = 768 / 512 transformer shapes
         if (p.N % 128 != 0) tile = p.M < 512 ? 4 : 2;
         else if (p.M < 512) tile = 4;
-        else if (p.N % 256 == 0 && p.K % 128 == 0 && groups == 1 && (long long)((p.M + 255) / 256) * (p.N / 256) >= p8_min_tiles())
-            tile = (p9_on() && p9_applies(p, groups) && (tu.p9_res || !p.R)) ? 60 : (p8_three_b() && p8_nt_stores() && p8_use_n192(c, p.M, p.N, p.K)) ? 55 : 16;  // deep-pipelined 256x256 / 256x192 kernel once there are >= 2 rounds of tiles (profiles/r01_gemm_sweep_bf16_8phase.json)
+        else if (p.N % 256 == 0 && p.K % 128 == 0 && groups == 1 && (long long)((p.M + 255) / 256) * (p.N / 256) >= kP8MinTiles)
+            tile = p9_applies(p, groups) ? 60 : 16;  // persistent / one-tile-per-workgroup form of the deep-pipelined 256x256 kernel
         else tile = (p.N % 256 == 0 && (p.N >= 1024 || p.M >= 100000)) ? 3 : 1;
     }
-    Scope sc(c, s, NOMAD_K_GEMM, flops, (tile == 1 || tile == 3 || tile == 16 || tile == 60 || tile == 61 || tile == 62 || tile == 63 || tile == 64 || tile == 68 || tile == 65 || tile == 66 || tile == 67 || tile == 55 || tile == 56 || tile == 57 || tile == 58 || tile == 42 || tile == 43 || tile == 44 || tile == 45 || tile == 46 || tile == 47 || tile == 48 || tile == 49 || tile == 50 || tile == 51 || tile == 52 || tile == 53 || tile == 54 || tile == 20 || tile == 21 || tile == 27 || tile == 28 || tile == 32 || tile == 33) ? NOMAD_K_GEMM_BIG : (tile == 2 ? NOMAD_K_GEMM_FINE : -1));
+    const bool big = tile == 1 || tile == 3 || tile == 16 || tile == 20 || tile == 21 || tile == 27 || tile == 28 || tile == 32 || tile == 33 || (tile >= 42 && tile <= 58) || (tile >= 60 && tile <= 68);
+    Scope sc(c, s, NOMAD_K_GEMM, flops, big ? NOMAD_K_GEMM_BIG : (tile == 2 ? NOMAD_K_GEMM_FINE : -1));
     hipError_t e;
     switch (tile) {
         // the instantiations the bf16 / bf16x3 forwards select
@@ -69,60 +53,27 @@ int run_gemm_bf16(nomad_ctx* c, GemmParams p, int groups, hipStream_t s, int til
         case 2: e = launch_gemm_bf16<128, 64, 4, 2>(p, groups, s); break;
         case 3: e = launch_gemm_bf16<256, 256, 4, 2>(p, groups, s); break;
         case 4: e = launch_gemm_bf16<64, 64, 2, 2>(p, groups, s); break;
-        case 16:  // 256x256 deep-pipelined schedule (gemm_bf16_8phase.hip.h)
+        case 16:  // 256x256 deep-pipelined schedule (gemm_bf16_8phase.hip.h): the small epilogue for plain C / R, else the general one
             if (p.N % 256 != 0 || p.K % 128 != 0) return fail(NOMAD_ERR_INVALID, "bf16 8-phase gemm: N %% 256, K %% 128");
-            e = !p8_nt_stores() ? launch_gemm_bf16_8phase<0>(p, groups, s)
-                : !p8_three_b() ? launch_gemm_bf16_8phase<8>(p, groups, s)
-                : (p8_residual_prefetch() == 3 && p8_plain_cr(p)) ? launch_gemm_bf16_8phase<8, false, 0, 3, 4, true, true>(p, groups, s)
-                : ((p.R && p8_residual_prefetch() == 1) || p8_residual_prefetch() >= 2) ? launch_gemm_bf16_8phase<8, false, 0, 3, 4, true>(p, groups, s)
-                                                  : launch_gemm_bf16_8phase<8, false, 0, 3>(p, groups, s);
+            e = p8_plain_cr(p) ? launch_gemm_bf16_8phase<8, false, 0, 3, 4, true, true>(p, groups, s) : launch_gemm_bf16_8phase<8, false, 0, 3, 4, true>(p, groups, s);
             break;
         case 60:  // persistent form of the deep-pipelined kernel: one workgroup per CU walks tiles, direct epilogue (gemm_bf16_p9.hip.h)
-        case 64: {  // ... (64: never split by rows - A/B)
+        case 64: {  // ... (64: never short tiles - A/B)
             if (!p9_applies(p, groups)) return fail(NOMAD_ERR_INVALID, "bf16 persistent gemm: plain C / R, one group, N %% 256, K %% 128, contiguous K");
-            // Tile quantisation (round 5).  One workgroup per CU and tiles of 256 x 256: the N = 768 GEMMs of config C5 (out_proj, fc2) are
-            // 564 tiles = 2.2 rounds of the 256 CUs, i.e. three rounds' time.  The one-tile-per-workgroup kernel hid that behind the
-            // OTHER half of the batch on a second stream; persistent workgroups of two launches cannot share CUs.  Instead the rows of
-            // the whole rounds go to the persistent kernel and the rows of the sparse last round to the 128 x 128 kernel (tile 1,
-            // two workgroups per CU) right behind it on the same stream: every bf16 kernel contracts k in the same order, so which
-            // kernel computes a row changes no bit (tests/test_gpu_bf16.py).  Plain A matrices only (the conv stack's per-clip maps
-            // have thousands of tiles); Tuning::p9_tail_split = 0 switches it off.
-            // (Tuning::p9_share, A/B: with n concurrent parts of a batch on n streams each launch takes 1 / n of the CUs, so that the parts'
-            // persistent launches run side by side instead of queueing for each other's LDS)
-            const int cus = (tu.p9_share && tu.concurrent_parts > 1) ? std::max(8, c->num_cus / tu.concurrent_parts) : c->num_cus;
-            const int grid = 8 * std::max(1, cus / 8);
-            const long long tn = p.N / 256, tm = (p.M + 255) / 256, tiles = tm * tn;
-            const long long rounds = tiles / grid, rem = tiles - rounds * grid;
-            if (tile == 60 && tu.p9_tail_split && rounds >= 1 && rounds <= 4 && rem > 0 && rem * 10 < grid * 6 && p.amap.clip_rows >= p.M && p.N % 128 == 0) {
-                const int m_main = (int)(rounds * grid / tn) * 256;
-                if (m_main > 0 && m_main < p.M) {
-                    GemmParams a = p, b = p;
-                    a.M = m_main;
-                    a.amap = plain_map(a.M, p.amap.ld); a.amap.off = p.amap.off;
-                    a.cmap = plain_map(a.M, p.cmap.ld); a.cmap.off = p.cmap.off;
-                    a.rmap = plain_map(a.M, p.rmap.ld); a.rmap.off = p.rmap.off;
-                    b.M = p.M - m_main;
-                    b.amap = plain_map(b.M, p.amap.ld); b.amap.off = p.amap.off + (long long)m_main * p.amap.ld;
-                    b.cmap = plain_map(b.M, p.cmap.ld); b.cmap.off = p.cmap.off + (long long)m_main * p.cmap.ld;
-                    b.rmap = plain_map(b.M, p.rmap.ld); b.rmap.off = p.rmap.off + (long long)m_main * p.rmap.ld;
-                    e = launch_gemm_bf16_p9<0, true>(a, s, cus);
-                    if (e == hipSuccess) e = launch_gemm_bf16<128, 128, 4, 2>(b, groups, s);
-                    break;
-                }
-            }
             // Short (192-row) tiles, round 6: a run-time mode of the same instantiation.  A 192 x 256 tile costs ~0.80 of a 256 x 256 one (three
             // quarters of the MFMAs, 7 / 8 of the LDS-DMA bytes); it is taken where the largest tile count any CU gets, priced so, is smaller.
             // Only for a batch that runs ALONE (concurrent_parts == 1): next to the other half of a two-stream batch the CUs never idle - the
             // other half's workgroups take a CU the moment a workgroup leaves it - so what counts there is the total work, which short tiles
-            // raise (measured, gpurun_out/r6a: two streams 1888 -> 1877 clips/s with short tiles, one stream 1828-1845 -> 1876-1878).
+            // raise (measured: two streams 1888 -> 1877 clips/s with short tiles, one stream 1828-1845 -> 1876-1878).
             if (tile == 60 && (tu.p9_short == 2 || (tu.p9_short == 1 && tu.concurrent_parts <= 1))) {
-                const long long tm_s = (p.M + 191) / 192;
+                const int grid = 8 * std::max(1, c->num_cus / 8);
+                const long long tn = p.N / 256, tiles = (long long)((p.M + 255) / 256) * tn, tm_s = (p.M + 191) / 192;
                 const long long r_full = (tiles + grid - 1) / grid, r_short = (tm_s * tn + grid - 1) / grid;
                 p.p9_short = (tu.p9_short == 2 || 0.80 * (double)r_short < 0.95 * (double)r_full) ? 1 : 0;
             }
             p.p9_late = tu.p9_late ? 1 : 0;
             p.p9_wl = tu.p9_wl ? 1 : 0;
-            e = launch_gemm_bf16_p9<0, true>(p, s, cus);
+            e = launch_gemm_bf16_p9<0, true>(p, s, c->num_cus);
             break;
         }
         case 57:  // the deep-pipelined kernel with the residual prefetch in the epilogue, general C / R addressing
@@ -133,16 +84,13 @@ int run_gemm_bf16(nomad_ctx* c, GemmParams p, int groups, hipStream_t s, int til
             break;
         case 55:  // 256x192 tiles of the same schedule (three B buffers, nt stores)
             if (p.N % 192 != 0 || p.K % 128 != 0) return fail(NOMAD_ERR_INVALID, "bf16 8-phase gemm, 192-column tiles: N %% 192, K %% 128");
-            e = (p8_residual_prefetch() == 3 && p8_plain_cr(p)) ? launch_gemm_bf16_8phase<8, false, 0, 3, 3, true, true>(p, groups, s)
-                                                                : launch_gemm_bf16_8phase<8, false, 0, 3, 3>(p, groups, s);
+            e = p8_plain_cr(p) ? launch_gemm_bf16_8phase<8, false, 0, 3, 3, true, true>(p, groups, s) : launch_gemm_bf16_8phase<8, false, 0, 3, 3>(p, groups, s);
             break;
         case 27:  // bf16x3, every plane staged once (gemm_bf16x3.hip.h): split output
         case 28:  // ... fp32 output
             if (p.N % 256 != 0 || p.K % 64 != 0) return fail(NOMAD_ERR_INVALID, "bf16x3 gemm: N %% 256, K %% 64");
-            if (p8_nt_stores() && x3_plain_epilogue() && p8_plain_cr(p) && (tile == 27) == (p.c_plane != 0))
-                e = launch_gemm_bf16x3<8, 3, 2, true>(p, groups, s);   // one instantiation for both output formats, small epilogue
-            else if (p8_nt_stores()) e = tile == 27 ? launch_gemm_bf16x3<8, 1>(p, groups, s) : launch_gemm_bf16x3<8, 2>(p, groups, s);
-            else e = tile == 27 ? launch_gemm_bf16x3<0, 1>(p, groups, s) : launch_gemm_bf16x3<0, 2>(p, groups, s);
+            if (p8_plain_cr(p) && (tile == 27) == (p.c_plane != 0)) e = launch_gemm_bf16x3<8, 3, 2, true>(p, groups, s);   // one instantiation for both output formats, small epilogue
+            else e = tile == 27 ? launch_gemm_bf16x3<8, 1>(p, groups, s) : launch_gemm_bf16x3<8, 2>(p, groups, s);
             break;
 #ifdef NOMAD_DIAG
         // experimental instantiations, cross-check kernels and timing probes (libnomad_diag.so)

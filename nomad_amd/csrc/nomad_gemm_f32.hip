@@ -16,9 +16,8 @@ int gemm_f32_dispatch(nomad_ctx* c, GemmParams p, int groups, int tile, hipStrea
         tile = 20;  // bf16x3 products: a 64 x 64 wave tile (128 x 128, 4 waves) does 12 MFMAs per 4 fragment splits where the
                     // 32 x 32 one does 3 per 2 - the split is VALU work - so it is taken as soon as it fills two rounds of CUs
     // plain C / R (/ Upre / DG) matrices: the instantiations with the small, residual-prefetching epilogue (gemm_f32.hip.h, OPT bits
-    // 16 / 32) - every GEMM of the uniform scoring forward but the pos-conv's neighbours.  NOMAD_F32_PLAIN_EPI=0: the general
-    // epilogue (A/B runs)
-    const bool plain_cr = c->tune.f32_plain_epi && p.c_colblk == 0 && p.cmap.clip_rows >= p.M && !p.cmap.pref &&
+    // 16 / 32) - every GEMM of the uniform scoring forward but the pos-conv's neighbours
+    const bool plain_cr = p.c_colblk == 0 && p.cmap.clip_rows >= p.M && !p.cmap.pref &&
                           (!p.R || (p.rmap.clip_rows >= p.M && !p.rmap.pref)) && (!p.DG || (p.dgmap.clip_rows >= p.M && !p.dgmap.pref));
     if (c->gemm_x3 && plain_cr && (tile == 20 || tile == 31 || tile == 34 || tile == 37)) {   // (not 33: its X3 form needs 146 VGPRs)
         constexpr int T = 16 | 32;   // one plain instantiation per tile for scoring and training alike (this mode is the small-batch / training one)
@@ -49,68 +48,45 @@ int gemm_f32_dispatch(nomad_ctx* c, GemmParams p, int groups, int tile, hipStrea
         // Round 4 (gemm_f32.hip.h OPT bits 16384 / 64 / 1024; profiles/r04_gemm_f32_variants.txt): the scoring GEMMs on uniform
         // clip maps take the lean set-up (magic-number divisions on the scalar unit), the 256 x 128 tile also the skewed K
         // loop, and GEMMs without a residual the direct epilogue from transposed accumulators.  All bit-identical to the plain
-        // instantiations.  NOMAD_F32_LEAN=0 / NOMAD_F32_DIRECT_EPI=0 / NOMAD_F32_SKEW=0 switch them off (A/B runs).
-        const int variants = (c->tune.f32_lean ? 1 : 0) | (c->tune.f32_direct_epi ? 2 : 0) | (c->tune.f32_skew ? 4 : 0) | (c->tune.f32_res_ahead ? 8 : 0);
+        // instantiations, each measured faster than what it replaced; the forms without them were removed.
         // (a divisor of 1 - clips of ONE row, the shortest legal input - has no 32-bit magic number: those stay on the general set-up)
-        const bool lean = (variants & 1) && !tr && !p.amap.pref && p.group_m == 0 && p.kchunk >= p.K &&
-                          (p.amap.clip_rows >= p.M || p.amap.clip_rows >= 2);
-        const bool direct = lean && (variants & 2) && !p.R && p.n_valid == p.N;
-        const bool skew = lean && (variants & 4);
+        const bool lean = !tr && !p.amap.pref && p.group_m == 0 && p.kchunk >= p.K && (p.amap.clip_rows >= p.M || p.amap.clip_rows >= 2);
+        const bool direct = lean && !p.R && p.n_valid == p.N;
         // residual GEMMs (out_proj, fc2; no GELU): the residual of the next slab loaded ahead of the current slab's stores (OPT bit 32768)
-        const bool ahead = lean && (variants & 8) && p.R && !p.gelu && p.n_valid == p.N && p.rmap.clip_rows >= p.M;
+        const bool ahead = lean && p.R && !p.gelu && p.n_valid == p.N && p.rmap.clip_rows >= p.M;
         constexpr int L = 16384, D = 1024, S = 64, RA = 32768;
-        // two tile shapes in one launch when the last round of 256 x 128 tiles would be sparsely filled
-        if (lean && skew && tile == 33 && groups == 1 && (p.R ? ahead : direct)) {
+        const int pad31 = occ_pad(occ, GldsCfg<128, 128, 32, 4, 2>::LDS_BYTES), pad20 = occ_pad(occ, GldsCfg<128, 128, 32, 2, 2>::LDS_BYTES);
+        if (lean && tile == 33) {   // the 256 x 128 tile: lean + skewed
+            // two tile shapes in one launch when the last round of 256 x 128 tiles would be sparsely filled
             // (sending the launches that need no split through the same kernel as well - one instantiation less alternating between
             // the launches of a transformer layer - changes nothing: 2405 vs 2408 clips/s)
-            const int m1 = mixed_split_rows(c, p.M, p.N);
-            if (m1 > 0) {
+            const int m1 = groups == 1 && (p.R ? ahead : direct) ? mixed_split_rows(c, p.M, p.N) : 0;
+            if (m1 > 0)
                 e = p.R ? launch_gemm_mixed<13 | P | L | S | RA, 13 | P | L | S | RA>(p, m1, s)
                         : launch_gemm_mixed<13 | P | L | S | D, 13 | P | L | S | D>(p, m1, s);
-                if (e != hipSuccess) return fail(NOMAD_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
-                return 0;
-            }
-        }
-        if (ahead && tile == 33 && skew) {
-            e = launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P | L | S | RA>(p, groups, s);
-            if (e != hipSuccess) return fail(NOMAD_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
-            return 0;
-        }
-        if (ahead && tile == 31) {
-            e = launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | P | L | RA>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 4, 2>::LDS_BYTES));
-            if (e != hipSuccess) return fail(NOMAD_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
-            return 0;
-        }
-        if (lean && tile == 33) {
-            e = direct ? (skew ? launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P | L | S | D>(p, groups, s) : launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P | L | D>(p, groups, s))
-                       : (skew ? launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P | L | S>(p, groups, s) : launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P | L>(p, groups, s));
-            if (e != hipSuccess) return fail(NOMAD_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
-            return 0;
-        }
-        if (lean && tile == 31) {
-            e = direct ? launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | P | L | D>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 4, 2>::LDS_BYTES))
-                       : launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | P | L>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 4, 2>::LDS_BYTES));
-            if (e != hipSuccess) return fail(NOMAD_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
-            return 0;
-        }
-        if (lean && (tile == 37 || tile == 34 || tile == 20)) {   // the small-problem tiles (batch 1 .. config C4): one round of workgroups, the set-up is a visible part of each
+            else
+                e = ahead    ? launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P | L | S | RA>(p, groups, s)
+                    : direct ? launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P | L | S | D>(p, groups, s)
+                             : launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P | L | S>(p, groups, s);
+        } else if (lean && tile == 31) {
+            e = ahead    ? launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | P | L | RA>(p, groups, s, pad31)
+                : direct ? launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | P | L | D>(p, groups, s, pad31)
+                         : launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | P | L>(p, groups, s, pad31);
+        } else if (lean) {   // the small-problem tiles (batch 1 .. config C4): one round of workgroups, the set-up is a visible part of each
             switch (tile) {
                 case 37: e = direct ? launch_gemm_glds<64, 64, 32, 2, 2, 3, false, 12 | P | L | D>(p, groups, s) : launch_gemm_glds<64, 64, 32, 2, 2, 3, false, 12 | P | L>(p, groups, s); break;
                 case 34: e = direct ? launch_gemm_glds<128, 64, 32, 4, 2, 3, false, 12 | P | L | D>(p, groups, s) : launch_gemm_glds<128, 64, 32, 4, 2, 3, false, 12 | P | L>(p, groups, s); break;
-                default: e = direct ? launch_gemm_glds<128, 128, 32, 2, 2, 2, false, 12 | P | L | D>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 2, 2>::LDS_BYTES))
-                                    : launch_gemm_glds<128, 128, 32, 2, 2, 2, false, 12 | P | L>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 2, 2>::LDS_BYTES)); break;
+                default: e = direct ? launch_gemm_glds<128, 128, 32, 2, 2, 2, false, 12 | P | L | D>(p, groups, s, pad20)
+                                    : launch_gemm_glds<128, 128, 32, 2, 2, 2, false, 12 | P | L>(p, groups, s, pad20); break;
             }
-            if (e != hipSuccess) return fail(NOMAD_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
-            return 0;
-        }
-        switch (tile) {
-            case 33: e = tr ? launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | T>(p, groups, s) : launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P>(p, groups, s); break;
-            case 31: e = tr ? launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | T>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 4, 2>::LDS_BYTES))
-                            : launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | P>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 4, 2>::LDS_BYTES)); break;
-            case 20: e = tr ? launch_gemm_glds<128, 128, 32, 2, 2, 2, false, 12 | T>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 2, 2>::LDS_BYTES))
-                            : launch_gemm_glds<128, 128, 32, 2, 2, 2, false, 12 | P>(p, groups, s, occ_pad(occ, GldsCfg<128, 128, 32, 2, 2>::LDS_BYTES)); break;
-            case 34: e = tr ? launch_gemm_glds<128, 64, 32, 4, 2, 3, false, 12 | T>(p, groups, s) : launch_gemm_glds<128, 64, 32, 4, 2, 3, false, 12 | P>(p, groups, s); break;
-            default: e = tr ? launch_gemm_glds<64, 64, 32, 2, 2, 3, false, 12 | T>(p, groups, s) : launch_gemm_glds<64, 64, 32, 2, 2, 3, false, 12 | P>(p, groups, s); break;
+        } else {
+            switch (tile) {
+                case 33: e = tr ? launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | T>(p, groups, s) : launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | P>(p, groups, s); break;
+                case 31: e = tr ? launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | T>(p, groups, s, pad31) : launch_gemm_glds<128, 128, 32, 4, 2, 2, false, 12 | P>(p, groups, s, pad31); break;
+                case 20: e = tr ? launch_gemm_glds<128, 128, 32, 2, 2, 2, false, 12 | T>(p, groups, s, pad20) : launch_gemm_glds<128, 128, 32, 2, 2, 2, false, 12 | P>(p, groups, s, pad20); break;
+                case 34: e = tr ? launch_gemm_glds<128, 64, 32, 4, 2, 3, false, 12 | T>(p, groups, s) : launch_gemm_glds<128, 64, 32, 4, 2, 3, false, 12 | P>(p, groups, s); break;
+                default: e = tr ? launch_gemm_glds<64, 64, 32, 2, 2, 3, false, 12 | T>(p, groups, s) : launch_gemm_glds<64, 64, 32, 2, 2, 3, false, 12 | P>(p, groups, s); break;
+            }
         }
         if (e != hipSuccess) return fail(NOMAD_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
         return 0;
@@ -214,59 +190,53 @@ hipError_t gemm_f32_n48_split(const GemmParams& q, int groups, hipStream_t s, in
 // (all production instantiations (v_mfma_f32_16x16x4_f32, gemm_f32_glds_body) contract k in the same order, so the choice never changes a result bit)
 // Rows of the 256 x 128 part of a two-shape launch (gemm_f32_mixed_kernel), or 0: whole rounds of the 2-per-CU workgroup slots go to
 // 256 x 128 tiles, the rows of the last, partial round to 128 x 128 tiles - when that round is between 5 % and 70 % full.
-// Tuning::f32_mixed = 0 switches it off; f32_mixed_m1 = <rows> (diagnostics) forces a split.
+constexpr double kMixedMinFill = 0.05, kMixedMaxFill = 0.70;   // fill of the last round that takes the split (swept in round 4: profiles/r04_gemm_f32_variants.txt)
 int mixed_split_rows(const nomad_ctx* c, int M, int N) {
-    const Tuning& t = c->tune;
-    if (!t.f32_mixed || N % 128) return 0;
-    if (t.f32_mixed_m1 > 0) return t.f32_mixed_m1 < M && t.f32_mixed_m1 % 256 == 0 ? t.f32_mixed_m1 : 0;
-    const int tn = N / 128, slots = t.f32_mixed_slots > 0 ? t.f32_mixed_slots : 2 * c->num_cus;
+    if (N % 128) return 0;
+    const int tn = N / 128, slots = 2 * c->num_cus;   // two workgroup slots per CU
     const long long tiles = (long long)((M + 255) / 256) * tn;
     const long long rounds = tiles / slots;
     const double frac = (double)(tiles - rounds * slots) / slots;
-    if (rounds < 1 || frac < t.f32_mixed_min || frac > t.f32_mixed_max) return 0;
+    if (rounds < 1 || frac < kMixedMinFill || frac > kMixedMaxFill) return 0;
     const long long m1 = rounds * slots / tn * 256;
     return m1 > 0 && m1 < M ? (int)m1 : 0;
 }
 
+// out_proj, conv5/6 at full batch (K = 768 / 1024, N = 768 / 512): 128x128x32 tiles, 8 waves, 2 stages: +2..5 % over 128x64
+// (profiles/r01_gemm_sweep_n768_128x128.json; the 256x128 kernel there too - ONE GEMM instantiation per transformer layer - was no gain)
+constexpr int kMidTile = 31;
+
 int pick_tile(const nomad_ctx* c, int M, int N, int K) {
-    const Tuning& tu = c->tune;
     const int cus = c->num_cus;
     const long long tiles256 = (long long)((M + 255) / 256) * (N / 128);
-    // (NOMAD_F32_MIXED_PREFER=1, A/B: wherever the two-shape launch applies - run_gemm turns tile 33 into it - take it over the
-    // 128 x 128 choice below.  Was +0.3 % of the bench step with the 32x32x2 products, is -0.4 % with 16x16x4: off.)
-    if (tu.f32_mixed_prefer && N % 128 == 0 && mixed_split_rows(c, M, N) > 0) return 33;
-    // 1500, not 2048: a half of the bench batch (Engine.embed runs the batch as two halves on two streams) has 1800 tiles in
-    // QKV and 1600 in conv4 - the 256x128 kernel there is worth +0.5 % of the step (2230-2235 vs 2219-2222 clips/s, alternating)
+    // (taking the two-shape launch wherever it applies over the 128 x 128 choice below was +0.3 % of the bench step with the 32x32x2
+    // products and is -0.4 % with 16x16x4: removed)
     // 256 x 128 or 128 x 128 (round 4)?  Two workgroups share a CU and a lone one runs about twice as fast, so what a launch costs
     // is the largest number of tiles any CU gets: ceil(tiles / CUs) big tiles against ceil(2 tiles / CUs) half-size ones, the latter
     // ~8 % dearer per flop (more operand traffic per MFMA; 3 % before the 16x16x4 products).  conv5 at the bench batch is 1596 big tiles = 6.2 per CU -> 7, or 3192
-    // small ones = 12.5 -> 13 halves = 6.5: 135 vs 127 TFLOP/s measured (profiles/r04_gemm_f32_variants.txt).  NOMAD_F32_QUANT_TILE=0:
-    // the round-3 rule.
-    if (tu.f32_quant_tile && N % 128 == 0 && tiles256 >= 4LL * cus) {
+    // small ones = 12.5 -> 13 halves = 6.5: 135 vs 127 TFLOP/s measured (profiles/r04_gemm_f32_variants.txt).
+    if (N % 128 == 0 && tiles256 >= 4LL * cus) {
         const long long per_cu_256 = (tiles256 + cus - 1) / cus;
         const long long tiles128 = (long long)((M + 127) / 128) * (N / 128);
         // what a flop costs more on 128 x 128 tiles: 8 % when the host layer runs two parts of a batch concurrently (swept with the
         // 16x16x4 products: 3 / 6 / 8 / 10 / 15 % -> 2411 / 2418 / 2419 / 2418 / 2415 clips/s), 3 % for one forward at a time
-        // (NOMAD_F32_QUANT_PENALTY, percent: both, A/B runs)
-        const double penalty = tu.f32_quant_penalty != 0.0 ? 1.0 + tu.f32_quant_penalty / 100.0 : (tu.concurrent_parts >= 2 ? 1.08 : 1.03);
+        const double penalty = c->tune.concurrent_parts >= 2 ? 1.08 : 1.03;
         const double cost128 = (double)((tiles128 + cus - 1) / cus) * 0.5 * penalty;
         return cost128 < (double)per_cu_256 ? 31 : 33;
     }
+    // 1500, not 2048: a half of the bench batch (Engine.embed runs the batch as two halves on two streams) has 1800 tiles in
+    // QKV and 1600 in conv4 - the 256x128 kernel there is worth +0.5 % of the step (2230-2235 vs 2219-2222 clips/s, alternating)
     if (N % 128 == 0 && tiles256 >= 1500) return 33;
-    // (NOMAD_F32_LONGK_33=1, A/B: one to two rounds of 256 x 128 tiles with a long or short K - fc2 / proj of HALF a bench batch - on
-    // the 256 x 128 kernel, as up to round 4; with the 16x16x4 products the 128 x 128 x 32 kernel is faster and steadier there:
-    // fc2 of half a batch 133.1 against 125 TFLOP/s median, out_proj 127 against 114)
-    if (tu.f32_longk_33 && N % 128 == 0 && tiles256 >= 512 && (K >= 2048 || K <= 512)) return 33;
+    // (one to two rounds of 256 x 128 tiles with a long or short K - fc2 / proj of HALF a bench batch - ran on the 256 x 128 kernel up
+    // to round 4; with the 16x16x4 products the 128 x 128 x 32 kernel is faster and steadier there: fc2 of half a batch 133.1
+    // against 125 TFLOP/s median, out_proj 127 against 114)
     // less than one round of 256x128 tiles (batch 1 .. a few dozen short clips, config C4): 64x64 tiles keep the
     // most CUs busy; one wave's K loop is the latency floor there (profiles/r01_gemm_sweep_small_m.json)
     if (tiles256 < 512) return 37;
     // a few rounds of tiles with wide N (the merged training batch, M ~ 12k): 128x128 tiles, 4 waves
     // (profiles/r01_gemm_sweep_train_m.json)
     if (N >= 2048 && N % 128 == 0 && tiles256 < 2048) return 20;
-    // out_proj, conv5/6 at full batch (K = 768 / 1024, N = 768 / 512): 128x128x32 tiles, 8 waves, 2 stages: +2..5 % over
-    // 128x64 (profiles/r01_gemm_sweep_n768_128x128.json).  NOMAD_F32_MID_TILE=33 (A/B): the 256x128 kernel there too, so that the
-    // transformer layers run ONE GEMM instantiation (no alternation)
-    return N % 128 == 0 ? tu.f32_mid_tile : 34;
+    return N % 128 == 0 ? kMidTile : 34;
 }
 
 #ifdef NOMAD_DIAG
@@ -302,6 +272,7 @@ int nomad_diag_gemm(nomad_ctx* c, const float* A, const float* W, const float* b
         GemmParams p48 = dense(A, K, W, bias, R, C, M, N, K, gelu);
         return run_gemm(c, p48, 1, tile, static_cast<hipStream_t>(stream));
     }
+#ifdef NOMAD_DIAG   // probe instantiations launched directly (not through gemm_f32_dispatch)
     if (tile == 94 || tile == 95) {   // the shipped lean + skewed + direct-epilogue instantiation with timeline stamps (94) / set-up detail stamps (95)
         if (N % 128 || K % 32) return fail(NOMAD_ERR_INVALID, "nomad_diag_gemm: N %% 128 or K %% 32 != 0");
         GemmParams pp = dense(A, K, W, bias, R, C, M, N, K, gelu);
@@ -310,7 +281,7 @@ int nomad_diag_gemm(nomad_ctx* c, const float* A, const float* W, const float* b
         else HIP_TRY((launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | 16 | 64 | 1024 | 16384 | 128 | 8192>(pp, 1, st)));
         return 0;
     }
-    if (tile == 99) {   // two tile shapes in one launch (gemm_f32_mixed_kernel): the split by mixed_split_rows (NOMAD_F32_MIXED_M1 forces one)
+    if (tile == 99) {   // two tile shapes in one launch (gemm_f32_mixed_kernel): the split by mixed_split_rows
         if (N % 128 || K % 32 || (R && gelu)) return fail(NOMAD_ERR_INVALID, "nomad_diag_gemm: tile 99 needs N %% 128 == 0, K %% 32 == 0, no GELU with a residual");
         GemmParams pp = dense(A, K, W, bias, R, C, M, N, K, gelu);
         hipStream_t st = static_cast<hipStream_t>(stream);
@@ -355,14 +326,10 @@ int nomad_diag_gemm(nomad_ctx* c, const float* A, const float* W, const float* b
         HIP_TRY((launch_gemm_glds<256, 128, 16, 4, 2, 3, false, 13 | 16 | 64 | 1024>(pp, 1, static_cast<hipStream_t>(stream))));
         return 0;
     }
-    if (tile == 82 || tile == 83 || tile == 87 || tile == 96) {   // (96: persistent, second workgroup of a CU starts half a tile late)
-   // the persistent 256 x 128 kernel (83: without its output stores; 87: one workgroup per tile)
-        if (N % 128 || K % 16 || K < 64) return fail(NOMAD_ERR_INVALID, "nomad_diag_gemm: persistent kernel needs N %% 128 == 0, K %% 16 == 0, K >= 64");
-        GemmParams pp = dense(A, K, W, bias, R, C, M, N, K, gelu);
-        Scope sc(c, static_cast<hipStream_t>(stream), NOMAD_K_GEMM, 2.0 * M * (double)N * K, NOMAD_K_GEMM_BIG);
-        HIP_TRY(launch_gemm_pers(pp, static_cast<hipStream_t>(stream), c->num_cus, tile == 83, tile == 87, tile == 96));
-        return 0;
-    }
+#else
+    if (tile == 84 || tile == 85 || (tile >= 88 && tile <= 95) || (tile >= 97 && tile <= 99))
+        return fail(NOMAD_ERR_INVALID, "gemm tile id %d is not in this library (experimental instantiations live in libnomad_diag.so)", tile);
+#endif
     if (tile < 0 || (tile > 47 && (tile < 60 || tile > 81) && tile != 86)) return fail(NOMAD_ERR_INVALID, "nomad_diag_gemm: tile id %d", tile);
     const int bn = (tile == 46 || tile == 47) ? 64 : tile >= 60 ? (tile == 67 ? 256 : 128) : kBN[tile], bk = tile == 46 ? 32 : tile == 47 ? 16 : tile >= 60 ? (tile == 73 ? 32 : 16) : kBK[tile];
     if (N % bn || K % bk) return fail(NOMAD_ERR_INVALID, "nomad_diag_gemm: N %% %d or K %% %d != 0", bn, bk);

@@ -20,7 +20,6 @@
 // "bf16 nondeterminism".  Those instructions are the compiler's choice (SLP vectorisation of scalar source), so the
 // target feature is off for every kernel rather than relying on kernels never being co-scheduled.
 #include "attention.hip.h"
-#include "attention_bf16_v2.hip.h"
 #include "attention_bf16_v3.hip.h"
 #include "posconv_bf16_slab.hip.h"
 #include "attention_f32_v2.hip.h"
@@ -609,9 +608,9 @@ static int run_gemm_splitk(nomad_ctx* c, const GemmParams& p, int S, hipStream_t
 // The grouped pos-conv (16 groups x [M x 48 x 6144]) at the loss path's M = 1600 is 7 row tiles x 16 groups = 112 workgroups with a
 // serial K loop of 384 tiles: 331 us per launch on fewer than half of the CUs (three launches per configs[3] step).  K in 4 fixed
 // slices over blockIdx.z (448 workgroups), partial products added in slice order by posconv_splitk_epilogue_kernel.  Where the
-// dense GEMMs of the same call split (splitk_applies): never on a scoring entry point.  Tuning::splitk_posconv = 0 switches it off.
+// dense GEMMs of the same call split (splitk_applies): never on a scoring entry point.
 static bool posconv_splitk_applies(const nomad_ctx* c, const GemmParams& p, int groups, int tile) {
-    if (!c->tune.splitk_posconv || !c->splitk_ok || !c->splitk_cur || groups != 16 || tile != 48) return false;
+    if (!c->splitk_ok || !c->splitk_cur || groups != 16 || tile != 48) return false;
     if (p.DG || p.K != 6144 || p.kchunk != p.K || p.n_valid != 48 || p.c_goff != 48) return false;
     const bool c_plain = p.cmap.clip_rows >= p.M && p.cmap.off == 0 && p.cmap.ld == 768;
     return c_plain && (long long)((p.M + 255) / 256) * 16 < 256 && (size_t)4 * p.M * 768 <= c->splitk_cur_floats;
@@ -727,14 +726,7 @@ int run_attention(nomad_ctx* c, const BatchGeom& g, const float* qkv, float* out
     if (dc && dc->threshold)
         hipLaunchKernelGGL((attention_f32_kernel<float, true>), grid, dim3(256), 0, s, qkv, out, lse, T, kNoInts, *dc, site, bh0);
     else if (T >= kAttnV2MinT)  // by the clip's length only: the same clip takes the same kernel in every batch
-    {
-#ifdef NOMAD_DIAG
-        if (c->tune.f32_attn_struct_loads) HIP_TRY(launch_attention_f32_v2<false>(qkv, out, lse, B, T, kNoInts, s));
-        else if (!c->tune.f32_attn_vt4) HIP_TRY((launch_attention_f32_v2<true, false>(qkv, out, lse, B, T, kNoInts, s)));
-        else
-#endif
-            HIP_TRY(launch_attention_f32_v2(qkv, out, lse, B, T, kNoInts, s));
-    }
+        HIP_TRY(launch_attention_f32_v2(qkv, out, lse, B, T, kNoInts, s));
     else
         hipLaunchKernelGGL((attention_f32_kernel<float, false>), grid, dim3(256), 0, s, qkv, out, lse, T, kNoInts, DropCfg{}, 0u, 0);
     HIP_TRY(hipGetLastError());
@@ -1015,8 +1007,8 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
     // results are deterministic, but they are the loss path's bits, not the scoring path's - nomad_embed WITHOUT layer outputs
     // (TripletModel / predict) never splits, whatever the batch.  The partial sums live in the call's own workspace (round 5; they
     // were two context-wide blocks handed to launch streams by hipEventQuery: whether a third stream's forward split depended on
-    // timing).  Tuning::splitk_layers = 0 switches the case off (A/B, diag library).
-    float* const loss_block = (sv == nullptr && layers_out != nullptr && splitk_block != nullptr && c->tune.splitk_layers) ? splitk_block : nullptr;
+    // timing).
+    float* const loss_block = (sv == nullptr && layers_out != nullptr && splitk_block != nullptr) ? splitk_block : nullptr;
     const SplitKScope splitk(c, (sv != nullptr || loss_block != nullptr) && !c->train_ready && !g.ragged());
     float* const prev_cur = c->splitk_cur;
     const size_t prev_cur_floats = c->splitk_cur_floats;
@@ -1299,60 +1291,26 @@ static int run_ln_bwd(nomad_ctx* c, const float* x, const float* g, const float*
 }
 
 // ---- bf16 path (config C5) -----------------------------------------------------------------------------
-// bf16 attention (attention_bf16_v2.hip.h).  T = frames per clip (the longest clip's with tpref).  256-query workgroups
-// when that still gives the chip >= 2 rounds of them, 128-query ones for small batches.  log2e: q carries log2(e).
-// The forward's (log2e) kernels stage K / V by LDS-DMA, 128-key tiles for the 256-query workgroups: attention 3.33 -> 3.05 ms per
-// C5 step, 1637-1646 -> 1676-1679 clips/s, bit-identical (gpurun_out/attndma).  NOMAD_BF16_ATTN_DMA = 0: staging through registers,
-// 1: LDS-DMA with 64-key tiles (A/B runs).
-static hipError_t run_attention_bf16(const nomad_ctx* c, const bf16_t* qkv, bf16_t* out, int B, int T, const int* tpref, bool log2e, hipStream_t s) {
-    const int dma = c->tune.bf16_attn_dma;
+// bf16 attention (attention_bf16_v3.hip.h: the 16-wide matrix shape, K / V staged by LDS-DMA; q carries log2(e)).  T = frames per clip
+// (the longest clip's with tpref).  256-query workgroups with 128-key tiles when that still gives the chip >= 2 rounds of them,
+// 128-query ones with 64-key tiles for small batches - a clip's bits do not depend on its batch (the wave composition - 32
+// consecutive queries - is the same in both workgroup shapes, so the deferred-rescale decisions and every bit are too).
+static hipError_t run_attention_bf16(const nomad_ctx* c, const bf16_t* qkv, bf16_t* out, int B, int T, const int* tpref, hipStream_t s) {
     const bool big = (long long)((T + 255) / 256) * B * 12 >= 1024;
-    // round 5: the 16-wide matrix shape (attention_bf16_v3.hip.h) for every batch size - a clip's bits do not depend on its batch
-    // (the wave composition - 32 consecutive queries - is the same in both workgroup shapes, so the deferred-rescale decisions and
-    // every bit are too)
-    if (log2e && c->tune.bf16_attn_v3 == 2) {
 #ifdef NOMAD_DIAG
-        // Round 6 probe, measured slower and kept out of the product (profiles/NOTEBOOK.md "the last round of the bf16 attention"): two
-        // 256-query workgroups fit a CU, so the launch runs in rounds of 2 x CUs items (configs[4]: 2304 items = 4.5 rounds of 512); here
-        // the items of a last round at most `bf16_attn_tail` / 8 full run as twice as many 128-query workgroups in a second launch (the
-        // same 32-query waves and 32-key blocks: every bit the same).  227 -> 240 us: a CU with ONE 256-query workgroup in the last round
-        // already runs it faster (2 waves per SIMD), and the 128-query workgroups stage 64-key tiles.
-        const int nq = (T + 255) / 256, items = nq * B * 12, slots = 2 * c->num_cus, tail = items % slots;
-        if (big && tail != 0 && tail * 8 <= slots * c->tune.bf16_attn_tail) {
-            if (hipError_t e = launch_attention_bf16_v3<8, 128, 4>(qkv, out, B, T, tpref, s, 0, items - tail); e != hipSuccess) return e;
-            // (128-query items: clip-head bh, query block 2 qb + {0, 1} - item numbers double; a second half past the clip's end returns at once)
-            return launch_attention_bf16_v3_items<4, 64, 4>(qkv, out, T, 2 * nq, tpref, s, 2 * (items - tail), 2 * tail);
-        }
-#endif
-        return big ? launch_attention_bf16_v3<8, 128, 4>(qkv, out, B, T, tpref, s) : launch_attention_bf16_v3<4, 64, 4>(qkv, out, B, T, tpref, s);
+    // Round 6 probe, measured slower and kept out of the product (profiles/NOTEBOOK.md "the last round of the bf16 attention"): two
+    // 256-query workgroups fit a CU, so the launch runs in rounds of 2 x CUs items (configs[4]: 2304 items = 4.5 rounds of 512); here
+    // the items of a last round at most `bf16_attn_tail` / 8 full run as twice as many 128-query workgroups in a second launch (the
+    // same 32-query waves and 32-key blocks: every bit the same).  227 -> 240 us: a CU with ONE 256-query workgroup in the last round
+    // already runs it faster (2 waves per SIMD), and the 128-query workgroups stage 64-key tiles.
+    const int nq = (T + 255) / 256, items = nq * B * 12, slots = 2 * c->num_cus, tail = items % slots;
+    if (big && tail != 0 && tail * 8 <= slots * c->tune.bf16_attn_tail) {
+        if (hipError_t e = launch_attention_bf16_v3<8, 128, 4>(qkv, out, B, T, tpref, s, 0, items - tail); e != hipSuccess) return e;
+        // (128-query items: clip-head bh, query block 2 qb + {0, 1} - item numbers double; a second half past the clip's end returns at once)
+        return launch_attention_bf16_v3_items<4, 64, 4>(qkv, out, T, 2 * nq, tpref, s, 2 * (items - tail), 2 * tail);
     }
-#ifdef NOMAD_DIAG
-    // the V reads through the compiler's builtin (it waits for the next tile's LDS-DMA in front of them: attention_bf16_v3.hip.h): A/B
-    if (log2e && c->tune.bf16_attn_v3 == 3)
-        return big ? launch_attention_bf16_v3<8, 128, 4, 2, false>(qkv, out, B, T, tpref, s) : launch_attention_bf16_v3<4, 64, 4, 2, false>(qkv, out, B, T, tpref, s);
-    // round 5's register use (a second copy of the -m_ref quads, the ones operand and the V addresses re-made per block): A/B
-    if (log2e && c->tune.bf16_attn_v3 == 5)
-        return big ? launch_attention_bf16_v3<8, 128, 4, 2, true, false>(qkv, out, B, T, tpref, s) : launch_attention_bf16_v3<4, 64, 4, 2, true, false>(qkv, out, B, T, tpref, s);
-    // 16 waves per workgroup (512 queries share a staged K / V tile: half the LDS-DMA pieces per wave): A/B
-    if (log2e && c->tune.bf16_attn_v3 == 16)
-        return big ? launch_attention_bf16_v3<16, 128, 4, 2>(qkv, out, B, T, tpref, s) : launch_attention_bf16_v3<4, 64, 4>(qkv, out, B, T, tpref, s);
-    // 64 queries per wave (half the LDS bytes per MFMA, 2 waves per SIMD): measured no faster - 262 / 271 / 310 us best launch at C5's
-    // shape for 32 queries, 64 queries x 4 waves, 64 queries x 8 waves (profiles/r05_attention_bf16_variants.txt)
-    if (log2e && c->tune.bf16_attn_v3 == 8)
-        return big ? launch_attention_bf16_v3<8, 128, 2, 4>(qkv, out, B, T, tpref, s) : launch_attention_bf16_v3<4, 64, 2, 4>(qkv, out, B, T, tpref, s);
-    if (log2e && c->tune.bf16_attn_v3 == 4)
-        return big ? launch_attention_bf16_v3<4, 128, 2, 4>(qkv, out, B, T, tpref, s) : launch_attention_bf16_v3<4, 64, 2, 4>(qkv, out, B, T, tpref, s);
 #endif
-    if (log2e && dma == 1)
-        return big ? launch_attention_bf16_v2<8, 64, 4, true, true>(qkv, out, B, T, tpref, s)
-                   : launch_attention_bf16_v2<4, 64, 4, true, true>(qkv, out, B, T, tpref, s);
-    if (log2e && dma == 2)
-        return big ? launch_attention_bf16_v2<8, 128, 4, true, true>(qkv, out, B, T, tpref, s)
-                   : launch_attention_bf16_v2<4, 64, 4, true, true>(qkv, out, B, T, tpref, s);
-    if (log2e) return big ? launch_attention_bf16_v2<8, 64, 4, true>(qkv, out, B, T, tpref, s)
-                          : launch_attention_bf16_v2<4, 64, 4, true>(qkv, out, B, T, tpref, s);
-    return big ? launch_attention_bf16_v2<8, 64, 4, false>(qkv, out, B, T, tpref, s)
-               : launch_attention_bf16_v2<4, 64, 4, false>(qkv, out, B, T, tpref, s);
+    return big ? launch_attention_bf16_v3<8, 128, 4>(qkv, out, B, T, tpref, s) : launch_attention_bf16_v3<4, 64, 4>(qkv, out, B, T, tpref, s);
 }
 
 // x + gelu(pos_conv(x) + bias) of the bf16 forward from the padded group-major buffer: y[M][768] (posconv_bf16_slab.hip.h).  max_t: the
@@ -1372,19 +1330,10 @@ static int run_posconv_bf16_slab(nomad_ctx* c, const bf16_t* xpad, bf16_t* y, in
 // wav rows `stride` apart; lens == nullptr: every clip has l0 frames, else ragged (max_l0 = the longest clip's, pref0 = packed rows)
 static void launch_conv0_bf16(nomad_ctx* c, const float* wav, int stride, int l0, int max_l0, int B, const float* scale,
                               const float* shift, bf16_t* out, const int* lens, const int* pref0, hipStream_t s) {
-#ifdef NOMAD_DIAG
-    if (c->tune.bf16_conv0_mfma && c->conv0_wfrag && c->tune.bf16_conv0_gelu_erf) {   // A/B: the erf GELU (what shipped up to round 5)
-        hipLaunchKernelGGL((conv0_mfma_gn_gelu_kernel<kConv0MfmaOcc, kConv0MfmaUf, 3>), dim3((max_l0 + kConv0MfmaFrames - 1) / kConv0MfmaFrames, B), dim3(256), 0, s, wav,
-                           stride, l0, c->conv0_wfrag, scale, shift, out, lens, pref0);
-        return;
-    }
-#endif
-    if (c->tune.bf16_conv0_mfma && c->conv0_wfrag)   // (Tuning::bf16_conv0_mfma = 0: the VALU kernel, A/B runs)
-        hipLaunchKernelGGL((conv0_mfma_gn_gelu_kernel<kConv0MfmaOcc, kConv0MfmaUf>), dim3((max_l0 + kConv0MfmaFrames - 1) / kConv0MfmaFrames, B), dim3(256), 0, s, wav,
-                           stride, l0, c->conv0_wfrag, scale, shift, out, lens, pref0);
-    else
-        hipLaunchKernelGGL(conv0_gn_gelu_kernel<bf16_t>, dim3((max_l0 + kConv0Frames - 1) / kConv0Frames, B), dim3(256), 0, s, wav,
-                           stride, l0, c->conv0_w, scale, shift, out, lens, pref0, 0LL);
+    // the matrix-core kernel (conv0_wfrag: nomad_enable_bf16); the VALU kernel it replaced (1.02-1.13 against 0.88 ms at 32 x 30 s) stays
+    // in libnomad_diag.so as a test reference (nomad_diag_conv0_bf16)
+    hipLaunchKernelGGL((conv0_mfma_gn_gelu_kernel<kConv0MfmaOcc, kConv0MfmaUf>), dim3((max_l0 + kConv0MfmaFrames - 1) / kConv0MfmaFrames, B), dim3(256), 0, s, wav,
+                       stride, l0, c->conv0_wfrag, scale, shift, out, lens, pref0);
 }
 
 // plain C / R matrices AND an A map whose divisions have magic numbers (uniform clips of at least two rows, n-fastest tile walk):
@@ -1523,32 +1472,8 @@ static int forward_bf16_run(nomad_ctx* c, const float* wav, const BatchGeom& g, 
     }
     CK(xpad, 16 * B, sizeof(bf16_t) * 48 * (size_t)(T + 128));
     bf16_t *x = H(lay.x), *x2 = H(lay.x2), *y = H(lay.y), *qkv = H(lay.qkv), *ctxb = H(lay.ctxb), *hb = H(lay.h);
-    if (c->tune.bf16_posconv_slab) {
-        if ((rc = run_posconv_bf16_slab(c, xpad, y, g.max_t, B, M, g.pref[6], g.ppref, s))) return rc;
-    } else {
-        GemmParams p{};
-        p.A = asf(xpad);
-        p.amap = g.pos_amap;
-        p.a_goff = g.grp_stride;
-        p.K = 6144;
-        p.kchunk = 6144;
-        p.W = asf(c->pos_w16);
-        p.ldw = 6144;
-        p.w_goff = 64LL * 6144;
-        p.bias = c->pos_b;
-        p.bias_goff = 48;
-        p.C = asfm(y);
-        p.cmap = plain_map(M, 768);
-        p.c_goff = 48;
-        p.R = asf(xpad);
-        p.rmap = g.pad_map;
-        p.r_goff = g.grp_stride;
-        p.M = M;
-        p.N = 64;
-        p.n_valid = 48;
-        p.gelu = 1;
-        if ((rc = run_gemm_bf16(c, p, 16, s))) return rc;
-    }
+    // (posconv_bf16_slab.hip.h; the grouped GEMM on 128 x 64 tiles it replaced is the reference of its test: nomad_diag_posconv_bf16)
+    if ((rc = run_posconv_bf16_slab(c, xpad, y, g.max_t, B, M, g.pref[6], g.ppref, s))) return rc;
     const size_t clip768 = sizeof(bf16_t) * 768 * (size_t)T;
     CK(y, B, clip768);
     {
@@ -1563,7 +1488,7 @@ static int forward_bf16_run(nomad_ctx* c, const float* wav, const BatchGeom& g, 
         CK(qkv, B, clip768 * 3);
         {
             Scope sc(c, s, NOMAD_K_ATTN, g.attn_flops);
-            HIP_TRY(run_attention_bf16(c, qkv, ctxb, B, g.max_t, g.pref[6], true, s));
+            HIP_TRY(run_attention_bf16(c, qkv, ctxb, B, g.max_t, g.pref[6], s));
         }
         CK(ctxb, B, clip768);
         if ((rc = run_gemm_bf16(c, dense(asf(ctxb), 768, asf(c->o_w16[l]), d.o_b, asf(x), asfm(y), M, 768, 768, 0), 1, s)))
@@ -3696,9 +3621,11 @@ int nomad_diag_attention_bwd(nomad_ctx* c, const float* qkv, const float* dctx, 
 
 int nomad_diag_attention_bf16(nomad_ctx* c, const void* qkv, void* out, int B, int T, int q_has_log2e, nomad_stream_t stream) {
     if (!c || !qkv || !out || B <= 0 || T <= 0) return fail(NOMAD_ERR_INVALID, "nomad_diag_attention_bf16: bad argument");
+    if (!q_has_log2e)
+        return fail(NOMAD_ERR_INVALID, "nomad_diag_attention_bf16: q must carry log2(e) - the kernel that scaled q itself went with round 5's move to 16x16x32");
     hipStream_t s = static_cast<hipStream_t>(stream);
     Scope sc(c, s, NOMAD_K_ATTN, 4.0 * B * 12.0 * (double)T * T * 64);
-    HIP_TRY(run_attention_bf16(c, static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(out), B, T, nullptr, q_has_log2e != 0, s));
+    HIP_TRY(run_attention_bf16(c, static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(out), B, T, nullptr, s));
     return 0;
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Shader clock held during the config-C5 bf16 forward (32 x 30 s), by the one-wave probe of tools/clock_under_load.py on a side
-stream, with the time per forward next to it.  Run once per NOMAD_BF16_N192 setting (the switch is read once per process).
+stream, with the time per forward next to it.
 Usage: python3 tools/clock_c5.py [split|single]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,7 +16,7 @@ wav = (0.1 * torch.randn(32, 480000, generator=g)).clamp(-1, 1).cuda()
 for _ in range(3):
     eng.embed_bf16(wav)
 torch.cuda.synchronize()
-res = {"mode": sys.argv[1] if len(sys.argv) > 1 else "split", "n192": os.environ.get("NOMAD_BF16_N192", "auto")}
+res = {"mode": sys.argv[1] if len(sys.argv) > 1 else "split"}
 for rep in range(3):
     n = 60
     for _ in range(5):

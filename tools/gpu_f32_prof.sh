@@ -1,14 +1,13 @@
 #!/bin/bash
 # per-launch durations of the fp32 GEMMs inside the headline forward (rocprofv3 --kernel-trace), grouped by instantiation and
-# grid, for the round-4 variants on / off.  Usage: bash tools/gpu_f32_prof.sh <tag> [extra bench args, e.g. --single-stream]
+# grid.  Usage: bash tools/gpu_f32_prof.sh <tag> [extra bench args, e.g. --single-stream]
 TAG=${1:-f32prof}; shift
 ROOTDIR=$(pwd); OUT=$ROOTDIR/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-for m in 1 0; do
-  export NOMAD_F32_LEAN=$m NOMAD_F32_QUANT_TILE=$m
+for m in 1; do
   rm -rf $OUT/prof_$m
-  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_$m -o f32 -- python3 $ROOTDIR/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-profile --no-also --live-traffic off "$@" > $OUT/prof_$m.json 2> $OUT/prof_$m.err; echo "rocprof variants=$m exit $?"
+  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_$m -o f32 -- python3 $ROOTDIR/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-profile --no-also --live-traffic off "$@" > $OUT/prof_$m.json 2> $OUT/prof_$m.err; echo "rocprof exit $?"
   t=$(find $OUT/prof_$m -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python3 - "$t" > $OUT/per_launch_$m.txt <<'PY'
 import csv, sys, collections, re
 rows = list(csv.DictReader(open(sys.argv[1])))
@@ -28,5 +27,5 @@ for k, v in sorted(per.items(), key=lambda kv: -sum(kv[1])):
 print("total %.3f ms" % (tot / 1e3))
 PY
   find $OUT/prof_$m -type f -delete 2>/dev/null
-  echo "== variants=$m"; head -24 $OUT/per_launch_$m.txt
+  head -24 $OUT/per_launch_$m.txt
 done

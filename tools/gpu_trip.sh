@@ -15,7 +15,6 @@
 #   c4table:<name>[:VAR=val,..]   kernel trace of configs[3] -> c4_trace_table_<name>.txt
 #   pmc:<shape>:<tile>:<name>     PMC passes (matrix pipe, TA, waits) of one bf16 GEMM shape
 #   pmcpy:<script>:<kernel substr>:<name>   the same PMC passes (+ SALU / waves / LDS conflicts) over any tools/ script
-#   attnab:<VAR>:<v1,v2,..>  tools/attn_bf16_ab.py per value
 #   attnf32:<VAR>:<v1,v2,..> tools/attn_f32_time.py per value
 #   py:<script>[:args]       python3 tools/<script> args  (stdout -> <script>.log)
 TAG=${1:-trip}; shift
@@ -87,10 +86,6 @@ for step in "$@"; do
       done
       python3 tools/pmc_summary.py $OUT "pmc_${NAME}_p" "$SUB" > $OUT/pmc_$NAME.txt; cat $OUT/pmc_$NAME.txt | tee -a $SUM
       find $OUT -name "*.csv" -path "*pmc_${NAME}_p*" -delete ;;
-    attnab)
-      VAR=${S[1]}; IFS=',' read -r -a VALS <<< "${S[2]}"
-      for rep in 1 2; do for v in "${VALS[@]}"; do env NOMAD_DIAG_LIB=1 $VAR=$v timeout 300 python3 tools/attn_bf16_ab.py >> $OUT/attn_ab.jsonl 2>> $OUT/attn_ab.err; done; done
-      cat $OUT/attn_ab.jsonl | tee -a $SUM ;;
     attnf32)
       VAR=${S[1]}; IFS=',' read -r -a VALS <<< "${S[2]}"
       for rep in 1 2; do for v in "${VALS[@]}"; do env NOMAD_DIAG_LIB=1 $VAR=$v timeout 300 python3 tools/attn_f32_time.py >> $OUT/attn_f32.jsonl 2>> $OUT/attn_f32.err; done; done

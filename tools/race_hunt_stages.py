@@ -27,7 +27,7 @@ STAGES = (["gn_sums", "gn_scale", "gn_shift"] + [f"conv{i}" for i in range(7)] +
           + [f"L{l}.{n}" for l in range(12) for n in ("qkv", "attn", "out_proj+res", "ln1", "fc1", "fc2+res", "ln2")] + ["emb"])
 KERNEL = {"gn_sums": "wav_stats/fold", "gn_scale": "gn_fold", "gn_shift": "gn_fold", "conv0": "conv0_gn_gelu<bf16>", "feature_ln": "layernorm<2,bf16>",
           "proj(xpad)": "gemm_bf16 (+zero_pad_rows)", "posconv+res": "gemm_bf16<128,64> grouped", "encoder_ln": "layernorm<3,bf16>",
-          "qkv": "gemm_bf16", "attn": "attention_bf16_v2", "out_proj+res": "gemm_bf16", "ln1": "layernorm<3,bf16>", "fc1": "gemm_bf16",
+          "qkv": "gemm_bf16", "attn": "attention_bf16_v3", "out_proj+res": "gemm_bf16", "ln1": "layernorm<3,bf16>", "fc1": "gemm_bf16",
           "fc2+res": "gemm_bf16", "ln2": "layernorm<3,bf16>", "emb": "head_pool/head"}
 NST = len(STAGES)
 snap = cksum and os.environ.get("HUNT_SNAP", "0") == "1"      # keep copies of scale / shift / conv0 output of both halves
