@@ -70,6 +70,7 @@ struct Tuning {
     bool splitk_lnb_fuse = true;   // NOMAD_SPLITK_LNB: a split-K dX GEMM in front of a LayerNorm backward has that kernel form its output (no epilogue launch)
     bool splitk_ln_fuse = true;    // NOMAD_SPLITK_LN: a split-K out_proj / fc2 normalises its rows in its own epilogue (splitk_epilogue_ln_kernel)
     bool f32_conv_wino = true;     // NOMAD_F32_CONV_WINO: conv1 .. conv4 of every fp32-product forward in polyphase Winograd form (conv_s2_f32.hip.h; 0: the implicit GEMM)
+    bool f32_posconv_wino = true;  // NOMAD_F32_POSCONV_WINO: the pos-conv of every fp32-product forward in nested F(2,2) form (posconv_wino_f32.hip.h; 0: the direct 128-tap GEMM)
     int bf16_attn_tail = 0;        // NOMAD_BF16_ATTN_TAIL (diag): a last round of 256-query workgroups that is at most this many eighths full runs
                                    // as 128-query workgroups in a second launch (0: never; run_attention_bf16 - measured slower, A/B only)
     int bf16_ln_rows = 4;          // NOMAD_BF16_LN_ROWS: rows per wave of the bf16 forward's LayerNorm (4: one gamma / beta fetch per 4 rows; 1: A/B)
@@ -91,6 +92,7 @@ static void tuning_from_env(Tuning& t) {
     t.splitk_ln_fuse = getb("NOMAD_SPLITK_LN", t.splitk_ln_fuse);
     t.splitk_lnb_fuse = getb("NOMAD_SPLITK_LNB", t.splitk_lnb_fuse);
     t.f32_conv_wino = getb("NOMAD_F32_CONV_WINO", t.f32_conv_wino);
+    t.f32_posconv_wino = getb("NOMAD_F32_POSCONV_WINO", t.f32_posconv_wino);
     t.bf16_attn_tail = geti("NOMAD_BF16_ATTN_TAIL", t.bf16_attn_tail);
     t.bf16_ln_rows = geti("NOMAD_BF16_LN_ROWS", t.bf16_ln_rows);
     t.p9_short = geti("NOMAD_BF16_P9_SHORT", t.p9_short);
@@ -112,6 +114,7 @@ struct nomad_ctx {
     float *gn_w = nullptr, *gn_b = nullptr, *fln_w = nullptr, *fln_b = nullptr;
     float *proj_w = nullptr, *proj_b = nullptr;
     float *pos_w = nullptr, *pos_b = nullptr;  // [16][64][6144] (rows 48..63 zero), k = tap*48 + cin
+    float* pos_wt = nullptr;                   // pos_w in nested F(2,2) form [16 * kPwOps][64][kPwK] (posconv_wino_f32.hip.h): rebuilt wherever pos_w is
     float *eln_w = nullptr, *eln_b = nullptr;
     LayerDev layers[NOMAD_NUM_LAYERS] = {};
     float *emb_w = nullptr, *emb_b = nullptr;

@@ -34,6 +34,7 @@
 #ifdef NOMAD_DIAG  // libnomad_diag.so only: experiments kept for A/B measurements (tools/, tests of the experimental tiles)
 #endif
 #include "pairwise.hip.h"
+#include "posconv_wino_f32.hip.h"
 #include "rowops.hip.h"
 #include "train.hip.h"
 #include "wav_reader.h"
@@ -73,6 +74,11 @@ void launch_wav_stats(const float* wav, int ld, int L0, int max_l0, int B, doubl
     hipLaunchKernelGGL(wav_stats_fold_kernel, dim3(B), dim3(128), 0, s, part, nchunk, L0, stats, lens);
 }
 
+// bytes of the operand / product buffers of the pos-conv in nested F(2,2) form (posconv_wino_f32.hip.h) over that many operand
+// frames / rows of one operand
+size_t pos_wino_q_bytes(long long q_frames) { return sizeof(float) * 16 * kPwOps * 48 * (size_t)q_frames; }
+size_t pos_wino_s_bytes(long long q_rows) { return sizeof(float) * 16 * kPwOps * 48 * (size_t)q_rows; }
+
 // floats in the split-K block of a small layer-output forward (Layout::splitk), 0 where that forward does not split: S x M x N
 // for the largest transformer problem splitk_applies / posconv_splitk_applies let through at M = s.M frames (S x N <= 6144: fc1
 // 2 x 3072, qkv 2 x 2304, fc2 / pos-conv 4 x 768), never more than the fixed cap those checks use.  The conv GEMMs of one clip
@@ -82,10 +88,10 @@ size_t layers_splitk_floats(const Shapes& s) {
 }
 
 struct Layout {
-    size_t stats, scale, shift, conv[7], featln, xpad, x, x2, y, qkv, ctxb, h, splitk, total;
+    size_t stats, scale, shift, conv[7], featln, xpad, x, x2, y, qkv, ctxb, h, splitk, pwq, pws, total;
 };
 
-Layout make_layout(const Shapes& s, bool keep) {
+Layout make_layout(const Shapes& s, bool keep, bool pos_wino) {
     Layout l{};
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -117,6 +123,11 @@ Layout make_layout(const Shapes& s, bool keep) {
     // whether such a forward splits depends on its shape alone - not on which streams other calls are running on
     const size_t sk = layers_splitk_floats(s);
     l.splitk = sk ? take(sk * sizeof(float)) : 0;
+    if (pos_wino) {   // operands and products of the pos-conv in nested F(2,2) form
+        const size_t q = (size_t)(s.T + kPwRate - 1) / kPwRate;
+        l.pwq = take(pos_wino_q_bytes((long long)s.B * (q + kPwTaps - 1)));
+        l.pws = take(pos_wino_s_bytes((long long)s.B * q));
+    }
     l.total = off;
     return l;
 }
@@ -134,6 +145,8 @@ struct RaggedShapes {
     long long P = 0;          // total padded pos-conv frames, sum (T_c + 128)
     long long blocks = 0;     // total pos-conv frame blocks, sum ceil(T_c / kPosBlk) (bf16x3 path)
     long long pairs[5] = {};  // total output pairs of conv1 .. conv4 (Winograd form), sum ceil(L_i / 2)
+    long long q_rows = 0, q_frames = 0;    // pos-conv in nested F(2,2) form: total operand rows, sum ceil(T_c / kPwRate), and frames, + kPwTaps - 1 each
+                                           // (their prefix sums are formed on the device, in the call's workspace: posconv_wino_prefix_kernel)
     long long even[4] = {}, odd[4] = {};   // backward: total even / odd frames of conv levels 0 .. 3, sum ceil(L_i / 2) / sum floor(L_i / 2)
     // [lens(B) | pref_0 (B+1) | ... | pref_6 (B+1) | ppref (B+1) | bpref (B+1) | pairpref_1 .. pairpref_4 (B+1) |
     //  upref_0 .. upref_6 | epref_0 .. epref_3 | opref_0 .. opref_3 (B+1 each)]: the last three groups are the backward's -
@@ -176,6 +189,9 @@ bool make_ragged(int B, const int* lens, RaggedShapes* r) {
         }
         r->meta[r->off_ppref() + c + 1] = r->meta[r->off_ppref() + c] + sh.T + 128;
         r->P += sh.T + 128;
+        const int q = (sh.T + kPwRate - 1) / kPwRate;
+        r->q_rows += q;
+        r->q_frames += q + kPwTaps - 1;
         const int nb = (sh.T + kPosBlk - 1) / kPosBlk;
         r->meta[r->off_bpref() + c + 1] = r->meta[r->off_bpref() + c] + nb;
         r->blocks += nb;
@@ -209,6 +225,7 @@ struct BatchGeom {
     // bf16x3 pos-conv as a GEMM over blocks of kPosBlk frames: input rows, output rows (in y), residual rows
     long long pos_blocks = 0;
     RowMap blk_amap{}, blk_cmap{}, blk_rmap{};
+    PosWinoGeom pos_wino{};        // the fp32 pos-conv in nested F(2,2) form (posconv_wino_f32.hip.h)
     double attn_flops = 0.0;
     // the backward's: padded dU rows, even / odd frames of conv levels 0 .. 3 and their prefix sums (ragged), and the HOST copy of
     // the encoder's frame prefix sums (ragged; LayerDrop branches are clip ranges) - valid as long as the RaggedShapes it came from
@@ -245,6 +262,8 @@ BatchGeom geom_uniform(const Shapes& sh) {
     g.blk_rmap = RowMap{64LL * 48, pad_ld, nb, kPosBlk * 48};
     g.blk_cmap = RowMap{0, (long long)sh.T * 768, nb, kPosBlk * 768};
     g.attn_flops = 4.0 * sh.B * 12.0 * (double)sh.T * sh.T * 64;
+    const int q = (sh.T + kPwRate - 1) / kPwRate;
+    g.pos_wino = PosWinoGeom{sh.B, sh.T, nullptr, nullptr, nullptr, nullptr, g.pad_rows, (long long)sh.B * q, (long long)sh.B * (q + kPwTaps - 1), q};
     for (int i = 0; i < 4; ++i) {
         g.even[i] = (long long)sh.B * ((sh.L[i] + 1) / 2);
         g.odd[i] = (long long)sh.B * (sh.L[i] / 2);
@@ -287,6 +306,8 @@ BatchGeom geom_ragged(const RaggedShapes& rs, int stride, const int* meta) {
         g.even[i] = rs.even[i];
         g.odd[i] = rs.odd[i];
     }
+    g.pos_wino = PosWinoGeom{rs.B, 0, g.pref[6], g.ppref, nullptr, nullptr, rs.P, rs.q_rows, rs.q_frames,
+                             (rs.max_t + kPwRate - 1) / kPwRate};
     g.host_tpref = rs.meta.data() + rs.off_pref(6);
     for (int i = 0; i < rs.B; ++i) {
         const double t = rs.meta[rs.off_pref(6) + i + 1] - rs.meta[rs.off_pref(6) + i];
@@ -298,12 +319,13 @@ BatchGeom geom_ragged(const RaggedShapes& rs, int stride, const int* meta) {
 // Workspace of every forward except the fp32 equal-length one (Layout): the ragged metadata, the front end's statistics, two
 // ping-pong conv buffers and the activations, elem_bytes per element (bf16: 2; fp32 or two bf16 planes: 4).
 struct ActLayout {
-    size_t meta, stats, scale, shift, conva, convb, xpad, x, x2, y, qkv, ctxb, h, total;
+    size_t meta, stats, scale, shift, conva, convb, xpad, x, x2, y, qkv, ctxb, h, pwq, pws, pwmeta, total;
     long long capa, capb;  // elements per plane of the two conv ping-pong buffers
     long long xpad_plane;  // elements per plane of the padded pos-conv buffer, + xpad_slack zeroed elements (bf16x3)
 };
 
-ActLayout make_act_layout(const BatchGeom& g, size_t elem_bytes, size_t xpad_slack) {
+// pos_wino: the fp32 forward with its pos-conv in nested F(2,2) form - the operand and product buffers of that form.
+ActLayout make_act_layout(const BatchGeom& g, size_t elem_bytes, size_t xpad_slack, bool pos_wino = false) {
     ActLayout l{};
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -328,6 +350,11 @@ ActLayout make_act_layout(const BatchGeom& g, size_t elem_bytes, size_t xpad_sla
     l.qkv = take(e * 2304 * M);
     l.ctxb = take(e * 768 * M);
     l.h = take(e * 3072 * M);
+    if (pos_wino) {
+        l.pwq = take(pos_wino_q_bytes(g.pos_wino.q_frames));
+        l.pws = take(pos_wino_s_bytes(g.pos_wino.q_rows));
+        l.pwmeta = take(sizeof(int) * 2 * (size_t)(g.B + 1));   // ragged: operand row / frame prefix sums
+    }
     l.total = off;
     return l;
 }
@@ -365,10 +392,11 @@ int ragged_upload(nomad_ctx* c, const RaggedShapes& rs, int stride, int* meta, h
 
 // The scoring forwards' prologue: the three steps over the ActLayout.  c == nullptr: nomad_workspace_bytes_ragged*, sizing only.
 int ragged_prologue(const char* who, nomad_ctx* c, bool ok, int B, int stride, const int* lens_host, size_t elem_bytes,
-                    size_t xpad_slack, RaggedBatch* r, void* workspace = nullptr, size_t workspace_bytes = 0, hipStream_t s = nullptr) {
+                    size_t xpad_slack, RaggedBatch* r, void* workspace = nullptr, size_t workspace_bytes = 0, hipStream_t s = nullptr,
+                    bool pos_wino = false) {
     if (int rc = ragged_shapes(who, ok, B, c ? stride : -1, lens_host, &r->rs)) return rc;
     r->g = geom_ragged(r->rs, stride, nullptr);
-    r->lay = make_act_layout(r->g, elem_bytes, xpad_slack);
+    r->lay = make_act_layout(r->g, elem_bytes, xpad_slack, pos_wino);
     if (!c) return 0;
     if (workspace_bytes < r->lay.total)
         return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, r->lay.total);
@@ -660,6 +688,63 @@ namespace {
 // fp32 forward sequence (forward_run) asks here, so embed, embed_train, layer outputs and the ragged forward switch together.
 bool conv_wino(const nomad_ctx* c, int i) { return c->tune.f32_conv_wino && !c->gemm_x3 && kConvK[i] == 3 && kConvS[i] == 2; }
 
+// The pos-conv of an fp32-product forward runs in nested F(2,2) form (posconv_wino_f32.hip.h): fp32 products only, as above;
+// NOMAD_F32_POSCONV_WINO.  Asked by forward_run alone, so every fp32 entry point, uniform or ragged, switches together.
+bool posconv_wino(const nomad_ctx* c) { return c->tune.f32_posconv_wino && !c->gemm_x3; }
+
+// pos_w -> pos_wt, queued on s: behind everything that writes pos_w (nomad_create, refresh_weights), never anywhere else - a
+// forward cannot see transformed weights older than pos_w.
+int rebuild_posconv_wino_weights(nomad_ctx* c, hipStream_t s) {
+    hipLaunchKernelGGL(posconv_wino_weight_kernel, dim3(16 * kPwOps * 64), dim3(256), 0, s, c->pos_w, c->pos_wt);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// x + gelu(pos_conv(x) + bias) in nested F(2,2) form.  xpad: the padded group-major input; wt: the transformed weights
+// [16 * kPwOps][64][kPwK]; y / upre (nullable): [sum T][768]; wq / ws: the operand and product buffers (pos_wino_q_bytes /
+// pos_wino_s_bytes of geo); qmeta: 2 (B + 1) ints for a ragged batch's operand prefix sums, formed here.  One launch of the
+// N = 48 GEMM kernel over 16 * kPwOps groups, a plain store; the same instantiation for every batch, so a clip's values do not
+// depend on its batch.
+int run_posconv_wino(nomad_ctx* c, const float* xpad, const float* wt, const float* bias, float* y, float* upre,
+                     const PosWinoGeom& geo_in, float* wq, float* ws, int* qmeta, hipStream_t s) {
+    PosWinoGeom geo = geo_in;
+    if (geo.q_rows >= (1LL << 31) / 48) return fail(NOMAD_ERR_INVALID, "pos-conv: %lld operand rows", geo.q_rows);
+    if (geo.tpref && !qmeta) return fail(NOMAD_ERR_INVALID, "pos-conv: a ragged batch without its operand prefix sums");
+    {
+        Scope sc(c, s, NOMAD_K_ROW, 0.0);
+        if (geo.tpref) {
+            hipLaunchKernelGGL(posconv_wino_prefix_kernel, dim3(1), dim3(64), 0, s, geo.tpref, geo.B, qmeta);
+            geo.qpref = qmeta;
+            geo.qbase = qmeta + geo.B + 1;
+        }
+        hipLaunchKernelGGL(posconv_wino_input_kernel, dim3((geo.max_q + kPwTaps - 1 + 15) / 16, 16 * geo.B), dim3(192), 0, s, xpad, wq, geo);
+        HIP_TRY(hipGetLastError());
+    }
+    GemmParams p{};
+    p.A = wq;
+    if (geo.tpref) p.amap = RowMap{0, 0, 0, 48, geo.qpref, geo.qbase, geo.B, 48};
+    else p.amap = RowMap{0, (long long)(geo.max_q + kPwTaps - 1) * 48, geo.max_q, 48};
+    p.a_goff = geo.q_frames * 48;
+    p.K = kPwK;
+    p.kchunk = kPwK;
+    p.W = wt;
+    p.ldw = kPwK;
+    p.w_goff = 64LL * kPwK;
+    p.C = ws;
+    p.M = (int)geo.q_rows;
+    p.cmap = plain_map(p.M, 48);
+    p.rmap = p.cmap;
+    p.c_goff = geo.q_rows * 48;
+    p.N = 64;
+    p.n_valid = 48;
+    int rc;
+    if ((rc = run_gemm(c, p, 16 * kPwOps, 48, s))) return rc;   // (counted with its executed FLOPs: 2 M' 48 kPwK per group)
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(posconv_wino_output_kernel, dim3((geo.max_q + 15) / 16, 16 * geo.B), dim3(192), 0, s, ws, bias, xpad, y, upre, geo);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 
 int run_layernorm(nomad_ctx* c, const float* in, const float* g, const float* b, float* out, float* out2, int M, int N,
                   hipStream_t s) {
@@ -882,6 +967,17 @@ int nomad_create(nomad_ctx** out, int device, const nomad_weights* w) {
                     for (size_t t = 0; t < 128; ++t)
                         r[(g * 64 + n) * 6144 + t * 48 + ci] = w->pos_v[((g * 48 + n) * 48 + ci) * 128 + t] * sc[t];
         up(r.data(), r.size(), &c->pos_w);
+        if (rc == 0 && c->tune.f32_posconv_wino) {
+            void* d = nullptr;
+            const hipError_t e = hipMalloc(&d, sizeof(float) * 16 * kPwOps * 64 * kPwK);
+            if (e != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_create: pos-conv weights: %s", hipGetErrorString(e));
+            else {
+                c->allocs.push_back(d);
+                c->pos_wt = static_cast<float*>(d);
+                rc = rebuild_posconv_wino_weights(c, nullptr);
+                if (rc == 0 && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_create: pos-conv weights: kernel");
+            }
+        }
     }
     up(w->pos_b, 768, &c->pos_b);
     up(w->enc_ln_w, 768, &c->eln_w);
@@ -950,7 +1046,7 @@ int nomad_workspace_bytes(const nomad_ctx* c, int B, int n_samples, size_t* byte
     Shapes s;
     if (!c || !bytes || B <= 0 || !make_shapes(B, n_samples, &s))
         return fail(NOMAD_ERR_INVALID, "nomad_workspace_bytes: bad shape B=%d N=%d", B, n_samples);
-    *bytes = make_layout(s, c->keep).total;
+    *bytes = make_layout(s, c->keep, c->tune.f32_posconv_wino).total;
     return 0;
 }
 
@@ -959,7 +1055,7 @@ int nomad_diag_workspace_region(const nomad_ctx* c, int B, int n_samples, const 
     Shapes s;
     if (!c || !name || !offset || !bytes || !make_shapes(B, n_samples, &s))
         return fail(NOMAD_ERR_INVALID, "nomad_diag_workspace_region: bad argument");
-    const Layout l = make_layout(s, c->keep);
+    const Layout l = make_layout(s, c->keep, c->tune.f32_posconv_wino);
     if (strncmp(name, "conv", 4) == 0 && name[4] >= '0' && name[4] <= '6' && name[5] == 0) {
         const int i = name[4] - '0';
         *offset = l.conv[i];
@@ -986,6 +1082,8 @@ int nomad_diag_workspace_region(const nomad_ctx* c, int B, int n_samples, const 
 struct F32Bufs {
     double* stats;
     float *scale, *shift, *conv[7], *featln, *xpad, *x, *x2, *y, *qkv, *ctxb, *h;
+    float *pwq = nullptr, *pws = nullptr;   // operands / products of the pos-conv in nested F(2,2) form (nullptr: the layout has none)
+    int* pwmeta = nullptr;                  // ... and, for a ragged batch, the operands' 2 (B + 1) prefix sums
 };
 
 // The fp32 forward, over an equal-length or a ragged batch.  sv == nullptr: scoring mode (intermediates alias inside the
@@ -1098,7 +1196,11 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
         hipLaunchKernelGGL(dropout_groups_kernel, dim3(M), dim3(192), 0, s, xpad, T, g.grp_stride, d_in, kSiteInput, g.pref[6], g.ppref, B);
     }
     // ---- pos-conv: 16 groups x (M x 48 x 6144), x + gelu(conv + bias) -------------------------
-    {
+    if (posconv_wino(c)) {   // 9 / 16 of the products (posconv_wino_f32.hip.h)
+        if (!bf.pwq || !bf.pws) return fail(NOMAD_ERR_INVALID, "fp32 forward: no workspace for the pos-conv operands");
+        if ((rc = run_posconv_wino(c, xpad, c->pos_wt, c->pos_b, sv ? sv->y0 : bf.y, sv ? sv->upc : nullptr, g.pos_wino, bf.pwq, bf.pws, bf.pwmeta, s)))
+            return rc;
+    } else {
         GemmParams p{};
         p.A = xpad;
         p.amap = g.pos_amap;
@@ -1232,13 +1334,14 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
     Shapes sh;
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d, n_samples=%d)", who, B, n_samples);
-    const Layout lay = make_layout(sh, c->keep);
+    const Layout lay = make_layout(sh, c->keep, c->tune.f32_posconv_wino);
     if (workspace_bytes < lay.total)
         return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, lay.total);
     char* ws = static_cast<char*>(workspace);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.featln), F(lay.xpad), F(lay.x),
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
+    if (c->tune.f32_posconv_wino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws);
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(lay.conv[i]);
     return forward_run(c, wav, geom_uniform(sh), bf, head_w, head_b, emb, layers_out, lay.splitk != 0 ? F(lay.splitk) : nullptr,
                        layers_splitk_floats(sh), static_cast<hipStream_t>(stream), sv, features);
@@ -1253,7 +1356,7 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
     RaggedBatch r;
     if (int rc = ragged_shapes(who, c && wav && emb && workspace, B, stride, lens_host, &r.rs)) return rc;
     r.g = geom_ragged(r.rs, stride, nullptr);
-    r.lay = make_act_layout(r.g, sizeof(float), 0);
+    r.lay = make_act_layout(r.g, sizeof(float), 0, c->tune.f32_posconv_wino);
     if (workspace_bytes < r.lay.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, r.lay.total);
     Saved sv{};
     if (saved) {   // every check before the first byte is queued
@@ -1267,6 +1370,7 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
     const ActLayout& lay = r.lay;
     F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.convb), F(lay.xpad), F(lay.x),
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
+    if (c->tune.f32_posconv_wino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws), bf.pwmeta = reinterpret_cast<int*>(ws + lay.pwmeta);
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(i % 2 ? lay.convb : lay.conva);   // conv6 lands in conva, LN(512) writes to convb
     return forward_run(c, wav, r.g, bf, head_w, head_b, emb, layers_out, nullptr, 0, s, saved ? &sv : nullptr, features);
 }
@@ -2086,6 +2190,77 @@ int nomad_diag_timeline(unsigned long long* out_host, int n) {
     std::memcpy(out_host, (ma >= mb ? a : b).data(), sizeof(unsigned long long) * 6 * (size_t)n);
     return 0;
 }
+
+/* Test hook: the fp32 pos-conv alone on the caller's operands, in the form this context's forwards run it in - nested F(2,2)
+ * (posconv_wino_f32.hip.h) or, with NOMAD_F32_POSCONV_WINO=0 or bf16x3 products, the direct 128-tap GEMM.  x: the padded
+ * group-major input [16][sum_c (T_c + 128)][48] (zero frames 0..63 and T_c + 64.. of every clip); v: weights as pos_w,
+ * [16][64][6144]; bias: [768] or null; y = x + gelu(u), u (nullable) = pos_conv(x) + bias: [sum_c T_c][768].  lens_host: the
+ * clips' frame counts T_c.  ragged = 0: the uniform launch (every T_c equal), 1: the ragged one.  Synchronous. */
+int nomad_diag_posconv(nomad_ctx* c, const float* x, const float* v, const float* bias, float* y, float* u, int B,
+                       const int* lens_host, int ragged, nomad_stream_t stream) {
+    if (!c || !x || !v || !y || !lens_host || B <= 0) return fail(NOMAD_ERR_INVALID, "nomad_diag_posconv: bad argument");
+    std::vector<int> meta(4 * (size_t)(B + 1), 0);   // frame / padded frame prefix sums; room for the operands' (run_posconv_wino)
+    int max_t = 0;
+    long long q_rows = 0;
+    for (int b = 0; b < B; ++b) {
+        const int T = lens_host[b], q = (T + kPwRate - 1) / kPwRate;
+        if (T <= 0 || (!ragged && T != lens_host[0])) return fail(NOMAD_ERR_INVALID, "nomad_diag_posconv: clip %d of %d frames", b, T);
+        meta[b + 1] = meta[b] + T;
+        meta[(B + 1) + b + 1] = meta[(B + 1) + b] + T + 128;
+        q_rows += q;
+        max_t = std::max(max_t, T);
+    }
+    PosWinoGeom geo{B, ragged ? 0 : lens_host[0], nullptr, nullptr, nullptr, nullptr, meta[(B + 1) + B], q_rows,
+                    q_rows + (long long)B * (kPwTaps - 1), (max_t + kPwRate - 1) / kPwRate};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t meta_bytes = (sizeof(int) * meta.size() + 255) & ~size_t(255), wt_bytes = sizeof(float) * 16 * kPwOps * 64 * kPwK;
+    const size_t q_bytes = (pos_wino_q_bytes(geo.q_frames) + 255) & ~size_t(255);
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), meta_bytes + wt_bytes + q_bytes + pos_wino_s_bytes(geo.q_rows)));
+    int* dm = reinterpret_cast<int*>(d);
+    float* wt = reinterpret_cast<float*>(d + meta_bytes);
+    float* wq = reinterpret_cast<float*>(d + meta_bytes + wt_bytes);
+    float* ws = reinterpret_cast<float*>(d + meta_bytes + wt_bytes + q_bytes);
+    int rc = 0;
+    if (hipMemcpy(dm, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_diag_posconv: copy");
+    if (ragged) {
+        geo.tpref = dm;
+        geo.ppref = dm + (B + 1);
+    }
+    if (rc == 0 && posconv_wino(c)) {
+        hipLaunchKernelGGL(posconv_wino_weight_kernel, dim3(16 * kPwOps * 64), dim3(256), 0, s, v, wt);
+        rc = run_posconv_wino(c, x, wt, bias, y, u, geo, wq, ws, dm + 2 * (B + 1), s);
+    } else if (rc == 0) {
+        const int T = lens_host[0], M = meta[B];
+        GemmParams p{};
+        p.A = x;
+        p.amap = ragged ? RowMap{0, 0, 0, 48, dm, dm + (B + 1), B, 48} : RowMap{0, (long long)(T + 128) * 48, T, 48};
+        p.a_goff = geo.pad_rows * 48;
+        p.K = 6144;
+        p.kchunk = 6144;
+        p.W = v;
+        p.ldw = 6144;
+        p.w_goff = 64LL * 6144;
+        p.bias = bias;
+        p.bias_goff = 48;
+        p.C = y;
+        p.Upre = u;
+        p.cmap = plain_map(M, 768);
+        p.c_goff = 48;
+        p.R = x;
+        p.rmap = p.amap;
+        p.rmap.off = 64LL * 48;
+        p.r_goff = p.a_goff;
+        p.M = M;
+        p.N = 64;
+        p.n_valid = 48;
+        p.gelu = 1;
+        rc = run_gemm(c, p, 16, 48, s);
+    }
+    if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_diag_posconv: kernel");
+    (void)hipFree(d);
+    return rc;
+}
 #endif
 
 int nomad_diag_gemm_bf16(nomad_ctx* c, const void* A, const void* W, const float* bias, const void* R, void* C, int M,
@@ -2115,7 +2290,9 @@ int nomad_embed(nomad_ctx* c, const float* wav, int B, int n_samples, const floa
 
 int nomad_workspace_bytes_ragged(const nomad_ctx* c, int B, const int* lengths_host, size_t* bytes) {
     RaggedBatch r;
-    if (int rc = ragged_prologue("nomad_workspace_bytes_ragged", nullptr, c && bytes, B, 0, lengths_host, sizeof(float), 0, &r)) return rc;
+    if (int rc = ragged_prologue("nomad_workspace_bytes_ragged", nullptr, c && bytes, B, 0, lengths_host, sizeof(float), 0, &r, nullptr, 0, nullptr,
+                                 c && c->tune.f32_posconv_wino))
+        return rc;
     *bytes = r.lay.total;
     return 0;
 }
@@ -2929,6 +3106,8 @@ int refresh_weights(nomad_ctx* c, hipStream_t s) {
     hipLaunchKernelGGL(posconv_fold_kernel, dim3(768), dim3(256), 0, s, c->theta + po.pos_v, c->theta + po.pos_g,
                        c->pos_nrm2, c->pos_w);
     hipLaunchKernelGGL(posconv_bwd_weight_kernel, dim3(16 * 64), dim3(256), 0, s, c->pos_w, c->pos_wb);
+    if (c->pos_wt)
+        if (int rc = rebuild_posconv_wino_weights(c, s)) return rc;
     transpose(c->proj_w, 512, c->proj_wT, 768, 768, 512);
     for (int i = 1; i < 7; ++i) {  // conv feature extractor: kernel layout [co][tap * 512 + ci] and the dX GEMMs' copies
         const long long n = 512LL * 512 * kConvK[i];
