@@ -14,6 +14,12 @@ from . import _lib
 from .weights import check_state_dict, num_frames
 
 P = "ssl_model."
+_SUFFIX = {"fp32": "", "bf16": "_bf16", "bf16x3": "_bf16x3"}   # of the C ABI's per-precision entry points
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    """An optional tensor's device pointer: None (a NULL argument) where the tensor is left out."""
+    return None if t is None else t.data_ptr()
 
 
 def _weights_struct(sd: Dict[str, torch.Tensor]):
@@ -115,10 +121,27 @@ class Engine:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def workspace_bytes(self, B: int, n_samples: int) -> int:
+    def _size(self, fn, B, n_samples, what):
         n = C.c_size_t()
-        _lib.check(self.lib.nomad_workspace_bytes(self.ctx, B, n_samples, C.byref(n)), "nomad_workspace_bytes")
+        _lib.check(fn(self.ctx, B, n_samples, C.byref(n)), what)
         return n.value
+
+    def _size_ragged(self, fn, lens, what):
+        n = C.c_size_t()
+        _lib.check(fn(self.ctx, len(lens), (C.c_int * len(lens))(*lens), C.byref(n)), what)
+        return n.value
+
+    def _forward_size(self, precision: str, B: int, n_samples: int) -> int:
+        """Workspace bytes of the forward of ``precision`` over B clips of n_samples."""
+        name = "nomad_workspace_bytes" + _SUFFIX[precision]
+        return self._size(getattr(self.lib, name), B, n_samples, name)
+
+    def _forward_size_ragged(self, precision: str, lens) -> int:
+        name = "nomad_workspace_bytes_ragged" + _SUFFIX[precision]
+        return self._size_ragged(getattr(self.lib, name), lens, name)
+
+    def workspace_bytes(self, B: int, n_samples: int) -> int:
+        return self._forward_size("fp32", B, n_samples)
 
     def _workspace(self, nbytes: int, side=False) -> torch.Tensor:
         """side: False / 0 = the main workspace, True / k >= 1 = the workspace of side stream k."""
@@ -148,12 +171,8 @@ class Engine:
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
             raise ValueError(f"{name} must be a contiguous fp32 tensor on {self.device}")
 
-    # ---- hot path ------------------------------------------------------------------------------
-    def embed(self, wav: torch.Tensor, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-              want_layers: bool = False, side: bool = False):
-        """wav (B,N) or (B,1,N) fp32 on the GPU -> emb (B,256) [, layers (12,B,T,768)].
-        side=True uses a second workspace so the call may run concurrently with another forward on a
-        different stream (the launch stream is always torch's current stream)."""
+    def _check_wav(self, wav: torch.Tensor):
+        """Equal-length waveforms (B,N) or (B,1,N) -> ((B,N) tensor, B, N, frames per clip)."""
         if wav.dim() == 3:
             wav = wav.squeeze(1)
         self._check_dev(wav, "wav")
@@ -161,55 +180,103 @@ class Engine:
         T = num_frames(N)
         if T < 1:
             raise ValueError(f"clip of {N} samples is shorter than the conv stack's receptive field")
+        return wav, B, N, T
+
+    def _check_head(self, head):
+        hw, hb = head if head is not None else (None, None)
+        for t, name in ((hw, "head weight"), (hb, "head bias")):
+            if t is not None:
+                self._check_dev(t, name)
+        return hw, hb
+
+    def enable(self, precision: str) -> int:
+        """Have the context allocate what the forward of ``precision`` needs ("fp32": nothing) -> the precision's code in the C ABI."""
+        if precision not in _lib.PRECISION:
+            raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
+        if precision != "fp32":
+            _lib.check(getattr(self.lib, "nomad_enable_" + precision)(self.ctx), "nomad_enable_" + precision)
+        return _lib.PRECISION[precision]
+
+    # ---- two-stream batch splits -------------------------------------------------------------------------------------------------
+    # A scoring batch with at least *_SPLIT_ROWS frames (rows of the encoder GEMMs) runs as two parts on two streams, each with
+    # its own workspace: one part's kernels fill the CUs that the partial last round of the other's tiles leaves idle.  Every
+    # GEMM instantiation contracts k in the same order and a clip's bits do not depend on the batch it is in, so the split
+    # changes no result (tests/test_gpu_race_screen.py holds every precision to bit-identical results with the split on).
+    # Equal-length batches are cut at B // 2, ragged ones where half of the audio is reached; two parts and equal halves are
+    # what the measurements left (profiles/r01_f32_two_streams.txt, profiles/r02_c5_split_and_threshold_ab.txt).  The three
+    # thresholds are read from the instance at call time: bench.py zeroes them for its per-kernel (roofline) pass, where kernels
+    # have to run alone, and the constructor does for a packed-FP32 build.  NOMAD_*_SPLIT_ROWS override; 0 disables.
+    #
+    # fp32: +7.6 % at 32 clips of 4 s, +4 % at 64, +5 % at 128 (profiles/r01_f32_two_streams.txt), +0.7 % at 256 (the bench
+    # workload, 50 944 frames: 2253-2260 vs 2238-2245 clips/s alternating in one run).
+    F32_SPLIT_ROWS = int(os.environ.get("NOMAD_F32_SPLIT_ROWS", 4000))
+    # bf16 (long-form clips, config C5): every GEMM of the path runs one 256 x 256 workgroup per CU, so the partial last round of
+    # one half's tiles (the N = 768 GEMMs of 32 clips x 30 s are 2.2 rounds) and its per-tile prologue / epilogue are filled by
+    # the other half's kernels.  (Round 2 switched this off because embed_bf16 then differed run to run in ~1 % of the calls.
+    # Round 3 found the cause - not the split: v_pk_fma_f32 in conv0 lost products while the other half's 128 x 128 bf16 GEMM
+    # shared its SIMD, DESIGN.md "The packed-FP32 hazard" - and the library is now built without packed-FP32 instructions.)
+    BF16_SPLIT_ROWS = int(os.environ.get("NOMAD_BF16_SPLIT_ROWS", 4000))
+    # bf16x3: one 256 x 256 workgroup per CU as well; e.g. the N = 768 GEMMs of a 256-clip batch are 2.33 rounds of the 256 CUs
+    # and the other half's kernels fill the idle third round: +4 % at 256 clips of 4 s, +14 % at 128, break-even at 16
+    # (profiles/r01_bf16x3_two_streams.txt).
+    X3_SPLIT_ROWS = int(os.environ.get("NOMAD_X3_SPLIT_ROWS", 4000))
+
+    def _split_rows(self, precision: str) -> int:
+        return {"fp32": self.F32_SPLIT_ROWS, "bf16": self.BF16_SPLIT_ROWS, "bf16x3": self.X3_SPLIT_ROWS}[precision]
+
+    def _splits(self, precision: str, B: int, rows: int) -> bool:
+        threshold = self._split_rows(precision)
+        return B >= 2 and bool(threshold) and rows >= threshold
+
+    @staticmethod
+    def _audio_cut(lens) -> int:
+        """Where a ragged batch of at least two clips is cut: behind the clip in which half of the audio is reached, never behind
+        the last one."""
+        acc = 0
+        for i, n in enumerate(lens[:-1]):
+            acc += n
+            if 2 * acc >= sum(lens):
+                return i + 1
+        return len(lens) - 1
+
+    def _dispatch(self, B: int, cut: int, run, hint: bool = False):
+        """``run(lo, hi, side)`` over clips 0 .. B-1: in one call (cut 0), or clips cut .. B-1 on the side stream with the side
+        workspace and clips 0 .. cut-1 on the current stream, which then waits for the side stream.  hint: tell the library how
+        many parts run concurrently (``nomad_set_concurrent_parts``: it selects tile shapes, results never depend on it).  Which
+        entry points announce their parts is historical - DESIGN.md, "Known wart: the concurrent-parts hint"."""
+        if hint:
+            self.lib.nomad_set_concurrent_parts(self.ctx, 2 if cut else 1)
+        if not cut:
+            run(0, B, False)
+            return
+        cur, ss = torch.cuda.current_stream(self.device), self.side_stream()
+        ss.wait_stream(cur)                        # the waveform (and anything queued before) is ready
+        with torch.cuda.stream(ss):                # _workspace records the side workspace on the stream current inside run
+            run(cut, B, True)
+        run(0, cut, False)
+        cur.wait_stream(ss)
+
+    # ---- hot path ------------------------------------------------------------------------------
+    def embed(self, wav: torch.Tensor, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+              want_layers: bool = False, side: bool = False):
+        """wav (B,N) or (B,1,N) fp32 on the GPU -> emb (B,256) [, layers (12,B,T,768)].
+        side=True uses a second workspace so the call may run concurrently with another forward on a
+        different stream (the launch stream is always torch's current stream)."""
+        wav, B, N, T = self._check_wav(wav)
         emb = torch.empty(B, 256, dtype=torch.float32, device=self.device)
         layers = torch.empty(12, B, T, 768, dtype=torch.float32, device=self.device) if want_layers else None
-        hw = hb = None
-        if head is not None:
-            hw, hb = head
-            self._check_dev(hw, "head weight")
-            self._check_dev(hb, "head bias")
+        hw, hb = self._check_head(head)
 
-        def run(w, e, use_side):
-            b = w.shape[0]
-            ws = self._workspace(self.workspace_bytes(b, N), use_side)
-            _lib.check(self.lib.nomad_embed(self.ctx, w.data_ptr(), b, N,
-                                            hw.data_ptr() if hw is not None else None,
-                                            hb.data_ptr() if hb is not None else None,
-                                            e.data_ptr(), layers.data_ptr() if layers is not None else None,
-                                            ws.data_ptr(), ws.numel(), self._stream()), "nomad_embed")
+        def run(lo, hi, use_side):
+            ws = self._workspace(self.workspace_bytes(hi - lo, N), use_side)
+            _lib.check(self.lib.nomad_embed(self.ctx, wav[lo:hi].data_ptr(), hi - lo, N, _ptr(hw), _ptr(hb), emb[lo:hi].data_ptr(),
+                                            _ptr(layers), ws.data_ptr(), ws.numel(), self._stream()), "nomad_embed")
 
-        ways = min(self.F32_SPLIT_WAYS, B)
-        if side or want_layers or ways < 2 or not self.F32_SPLIT_ROWS or not (self.F32_SPLIT_ROWS <= B * T < self.F32_SPLIT_MAX_ROWS):
-            if not side:
-                self.lib.nomad_set_concurrent_parts(self.ctx, 1)   # tile-shape hint only: results never depend on it (include/nomad_hip.h)
-            run(wav, emb, side)
+        if side:
+            run(0, B, side)   # the caller's own concurrency: its stream, the side workspace it names, no split
         else:
-            self.lib.nomad_set_concurrent_parts(self.ctx, ways)
-            # parts of the batch on separate streams: each part's kernels fill the CUs the others' partial last rounds of tiles
-            # leave idle (every instantiation contracts k in the same order, so the parts' bits equal the whole batch's)
-            cur = torch.cuda.current_stream(self.device)
-            cuts = [B * i // ways for i in range(ways + 1)]
-            if ways == 2 and self.F32_SPLIT_FRAC != 0.5:   # (experiment: unequal halves, so that the two parts' launches do not end together)
-                cuts[1] = max(1, min(B - 1, int(round(B * self.F32_SPLIT_FRAC))))
-            for k in range(1, ways):
-                st = self.side_stream(k)
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    run(wav[cuts[k]:cuts[k + 1]], emb[cuts[k]:cuts[k + 1]], k)
-            run(wav[:cuts[1]], emb[:cuts[1]], False)
-            for k in range(1, ways):
-                cur.wait_stream(self.side_stream(k))
+            self._dispatch(B, B // 2 if not want_layers and self._splits("fp32", B, B * T) else 0, run, hint=True)
         return (emb, layers) if want_layers else emb
-
-    # Plain scoring batches of at least F32_SPLIT_ROWS frames run as two halves on two streams: each half's kernels fill the
-    # CUs the other's partial last round of tiles leaves idle: +7.6 % at 32 clips of 4 s, +4 % at 64, +5 % at 128
-    # (profiles/r01_f32_two_streams.txt), +0.7 % at 256 (the bench workload, 50 944 frames: 2253-2260 vs 2238-2245 clips/s
-    # alternating in one run).  bench.py takes its per-kernel timings (roofline) from a second pass with the split off
-    # (F32_SPLIT_ROWS = 0), where kernels run alone.  NOMAD_F32_SPLIT_ROWS / _MAX_ROWS override.
-    F32_SPLIT_ROWS = int(os.environ.get("NOMAD_F32_SPLIT_ROWS", 4000))
-    F32_SPLIT_MAX_ROWS = int(os.environ.get("NOMAD_F32_SPLIT_MAX_ROWS", 1 << 30))
-    F32_SPLIT_WAYS = int(os.environ.get("NOMAD_F32_SPLIT_WAYS", 2))
-    F32_SPLIT_FRAC = float(os.environ.get("NOMAD_F32_SPLIT_FRAC", 0.5))
 
     def fetch_async(self, dev: torch.Tensor) -> _AsyncFetch:
         """Start copying a result to the host; ``.result()`` (numpy) later waits for this copy alone."""
@@ -227,6 +294,38 @@ class Engine:
             host[i, :lens[i]] = w
         return host, lens
 
+    def _pack(self, waves, packed=None):
+        """Clips -> (device (B, stride) fp32 buffer, lengths), stride a multiple of 4.  Rows are only read up to their length, so the
+        buffer needs no zero fill; device clips are packed on the device, host clips in one pinned staging buffer
+        (``pack_ragged_host``; packed: its result, made ahead) and ONE asynchronous copy."""
+        if packed is None:
+            flat = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in waves]
+            if all(w.is_cuda for w in flat):
+                lens = [int(w.numel()) for w in flat]
+                buf = torch.empty(len(flat), (max(lens) + 3) // 4 * 4, dtype=torch.float32, device=self.device)
+                for i, w in enumerate(flat):
+                    buf[i, :lens[i]] = w
+                return buf, lens
+            packed = self.pack_ragged_host(flat)
+        host, lens = packed
+        return host.to(self.device, non_blocking=True), lens
+
+    def _forward_ragged(self, waves, packed, precision: str, width: int, launch) -> torch.Tensor:
+        """The ragged forwards: pack, then ``launch(source, clips, stride, lengths array, destination, workspace)`` over the whole
+        batch or, where that pays, over two halves by audio length on two streams, each with its own length array and workspace
+        size -> the (B, width) result."""
+        buf, lens = self._pack(waves, packed)
+        B, stride = buf.shape
+        out = torch.empty(B, width, dtype=torch.float32, device=self.device)
+
+        def run(lo, hi, side):
+            ws = self._workspace(self._forward_size_ragged(precision, lens[lo:hi]), side)
+            launch(buf[lo:hi].data_ptr(), hi - lo, stride, (C.c_int * (hi - lo))(*lens[lo:hi]), out[lo:hi].data_ptr(), ws)
+
+        split = self._splits(precision, B, sum(num_frames(n) for n in lens))
+        self._dispatch(B, self._audio_cut(lens) if split else 0, run)
+        return out
+
     def embed_ragged(self, waves, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, bf16: bool = False,
                      precision: Optional[str] = None, packed: Optional[Tuple[torch.Tensor, list]] = None) -> torch.Tensor:
         """Embed clips of different lengths in ONE launch sequence (no padding in the arithmetic).
@@ -240,176 +339,47 @@ class Engine:
             raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
         if precision != "fp32" and head is not None:
             raise ValueError(f"the {precision} path has no head override")
-        if packed is not None:
-            host, lens = packed
-            B, stride = host.shape
-            buf = host.to(self.device, non_blocking=True)
-        else:
-            flat = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in waves]
-            lens = [int(w.numel()) for w in flat]
-            B, stride = len(flat), max(lens)
-            stride = (stride + 3) // 4 * 4
-            # rows are only read up to lens[i], so the buffer needs no zero fill; device inputs are packed on the device,
-            # host inputs in one pinned staging buffer and ONE asynchronous copy
-            if all(w.is_cuda for w in flat):
-                buf = torch.empty(B, stride, dtype=torch.float32, device=self.device)
-                for i, w in enumerate(flat):
-                    buf[i, :lens[i]] = w
-            else:
-                host, lens = self.pack_ragged_host(flat)
-                buf = host.to(self.device, non_blocking=True)
-        emb = torch.empty(B, 256, dtype=torch.float32, device=self.device)
         hw, hb = head if head is not None else (None, None)
-        if precision != "fp32":
-            enable = self.lib.nomad_enable_bf16 if precision == "bf16" else self.lib.nomad_enable_bf16x3
-            _lib.check(enable(self.ctx), f"nomad_enable_{precision}")
+        self.enable(precision)
 
-        def run(lo, hi, side):
-            n = hi - lo
-            arr = (C.c_int * n)(*lens[lo:hi])
-            nb = C.c_size_t()
-            src, dst = buf[lo:hi], emb[lo:hi]
+        def launch(src, n, stride, arr, dst, ws):
             if precision == "fp32":
-                _lib.check(self.lib.nomad_workspace_bytes_ragged(self.ctx, n, arr, C.byref(nb)), "nomad_workspace_bytes_ragged")
-                ws = self._workspace(nb.value, side)
-                _lib.check(self.lib.nomad_embed_ragged(self.ctx, src.data_ptr(), n, stride, arr,
-                                                       hw.data_ptr() if hw is not None else None,
-                                                       hb.data_ptr() if hb is not None else None,
-                                                       dst.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                           "nomad_embed_ragged")
+                _lib.check(self.lib.nomad_embed_ragged(self.ctx, src, n, stride, arr, _ptr(hw), _ptr(hb), dst, ws.data_ptr(), ws.numel(),
+                                                       self._stream()), "nomad_embed_ragged")
                 return
-            size, fwd = ((self.lib.nomad_workspace_bytes_ragged_bf16, self.lib.nomad_embed_ragged_bf16) if precision == "bf16" else
-                         (self.lib.nomad_workspace_bytes_ragged_bf16x3, self.lib.nomad_embed_ragged_bf16x3))
-            _lib.check(size(self.ctx, n, arr, C.byref(nb)), f"nomad_workspace_bytes_ragged_{precision}")
-            ws = self._workspace(nb.value, side)
-            _lib.check(fwd(self.ctx, src.data_ptr(), n, stride, arr, dst.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                       f"nomad_embed_ragged_{precision}")
+            fwd = self.lib.nomad_embed_ragged_bf16 if precision == "bf16" else self.lib.nomad_embed_ragged_bf16x3
+            _lib.check(fwd(self.ctx, src, n, stride, arr, dst, ws.data_ptr(), ws.numel(), self._stream()), f"nomad_embed_ragged_{precision}")
 
-        # two halves (by audio length) on two streams where that pays, as in embed / embed_bf16x3; a clip's result does not
-        # depend on the batch it is in, so the split changes no bit
-        rows = sum(num_frames(n) for n in lens)
-        split = B >= 2 and ((precision == "bf16x3" and self.X3_SPLIT_ROWS and rows >= self.X3_SPLIT_ROWS) or
-                            (precision == "bf16" and self.BF16_SPLIT_ROWS and rows >= self.BF16_SPLIT_ROWS) or
-                            (precision == "fp32" and self.F32_SPLIT_ROWS and self.F32_SPLIT_ROWS <= rows < self.F32_SPLIT_MAX_ROWS))
-        if not split:
-            run(0, B, False)
-            return emb
-        acc, h = 0, 1
-        for i, n in enumerate(lens[:-1]):
-            acc += n
-            h = i + 1
-            if 2 * acc >= sum(lens):
-                break
-        cur, ss = torch.cuda.current_stream(self.device), self.side_stream()
-        ss.wait_stream(cur)
-        with torch.cuda.stream(ss):
-            run(h, B, True)
-        run(0, h, False)
-        cur.wait_stream(ss)
-        return emb
+        return self._forward_ragged(waves, packed, precision, 256, launch)
 
     # ---- pooled backbone features (the raw wav2vec 2.0 baseline, Origw2v) ----------------------------------------------
-    def _feature_precision(self, precision: str) -> int:
-        if precision not in _lib.PRECISION:
-            raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
-        if precision != "fp32":
-            enable = self.lib.nomad_enable_bf16 if precision == "bf16" else self.lib.nomad_enable_bf16x3
-            _lib.check(enable(self.ctx), f"nomad_enable_{precision}")
-        return _lib.PRECISION[precision]
-
     def embed_features(self, wav: torch.Tensor, precision: str = "fp32") -> torch.Tensor:
         """wav (B,N) or (B,1,N) fp32 on the GPU -> (B,768) fp32: the backbone's output averaged over time
         (``Origw2v.forward``), by the forward of ``precision``.  Batches split over two streams by the rule of that
         precision's ``embed*``; a clip's values do not depend on the batch it is in, so the split changes no bit."""
-        if wav.dim() == 3:
-            wav = wav.squeeze(1)
-        self._check_dev(wav, "wav")
-        B, N = wav.shape
-        T = num_frames(N)
-        if T < 1:
-            raise ValueError(f"clip of {N} samples is shorter than the conv stack's receptive field")
-        prec = self._feature_precision(precision)
-        size = {"fp32": self.lib.nomad_workspace_bytes, "bf16": self.lib.nomad_workspace_bytes_bf16,
-                "bf16x3": self.lib.nomad_workspace_bytes_bf16x3}[precision]
+        wav, B, N, T = self._check_wav(wav)
+        prec = self.enable(precision)
         feat = torch.empty(B, 768, dtype=torch.float32, device=self.device)
 
-        def run(w, f, side):
-            b = w.shape[0]
-            ws = self._workspace(self._size(size, b, N, "nomad_workspace_bytes"), side)
-            _lib.check(self.lib.nomad_embed_features(self.ctx, w.data_ptr(), b, N, prec, f.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     self._stream()), "nomad_embed_features")
+        def run(lo, hi, side):
+            ws = self._workspace(self._forward_size(precision, hi - lo, N), side)
+            _lib.check(self.lib.nomad_embed_features(self.ctx, wav[lo:hi].data_ptr(), hi - lo, N, prec, feat[lo:hi].data_ptr(),
+                                                     ws.data_ptr(), ws.numel(), self._stream()), "nomad_embed_features")
 
-        rows = B * T
-        split = B >= 2 and ((precision == "bf16x3" and self.X3_SPLIT_ROWS and rows >= self.X3_SPLIT_ROWS) or
-                            (precision == "bf16" and self.BF16_SPLIT_ROWS and rows >= self.BF16_SPLIT_ROWS) or
-                            (precision == "fp32" and self.F32_SPLIT_ROWS and self.F32_SPLIT_ROWS <= rows < self.F32_SPLIT_MAX_ROWS))
-        self.lib.nomad_set_concurrent_parts(self.ctx, 2 if split else 1)   # tile-shape hint only: results never depend on it
-        if not split:
-            run(wav, feat, False)
-            return feat
-        h = B // 2
-        cur, ss = torch.cuda.current_stream(self.device), self.side_stream()
-        ss.wait_stream(cur)
-        with torch.cuda.stream(ss):
-            run(wav[h:], feat[h:], True)
-        run(wav[:h], feat[:h], False)
-        cur.wait_stream(ss)
+        self._dispatch(B, B // 2 if self._splits(precision, B, B * T) else 0, run, hint=True)
         return feat
 
     def embed_features_ragged(self, waves=None, precision: str = "fp32",
                               packed: Optional[Tuple[torch.Tensor, list]] = None) -> torch.Tensor:
         """``embed_features`` for clips of different lengths in ONE launch sequence: (B,768) fp32, bit-identical to one
         ``embed_features`` call per clip.  waves / packed, the staging and the two-stream split: as in ``embed_ragged``."""
-        prec = self._feature_precision(precision)
-        if packed is not None:
-            host, lens = packed
-            B, stride = host.shape
-            buf = host.to(self.device, non_blocking=True)
-        else:
-            flat = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in waves]
-            lens = [int(w.numel()) for w in flat]
-            B, stride = len(flat), (max(lens) + 3) // 4 * 4
-            if all(w.is_cuda for w in flat):
-                buf = torch.empty(B, stride, dtype=torch.float32, device=self.device)
-                for i, w in enumerate(flat):
-                    buf[i, :lens[i]] = w
-            else:
-                host, lens = self.pack_ragged_host(flat)
-                buf = host.to(self.device, non_blocking=True)
-        feat = torch.empty(B, 768, dtype=torch.float32, device=self.device)
-        size = {"fp32": self.lib.nomad_workspace_bytes_ragged, "bf16": self.lib.nomad_workspace_bytes_ragged_bf16,
-                "bf16x3": self.lib.nomad_workspace_bytes_ragged_bf16x3}[precision]
+        prec = self.enable(precision)
 
-        def run(lo, hi, side):
-            n = hi - lo
-            arr = (C.c_int * n)(*lens[lo:hi])
-            nb = C.c_size_t()
-            _lib.check(size(self.ctx, n, arr, C.byref(nb)), "nomad_workspace_bytes_ragged")
-            ws = self._workspace(nb.value, side)
-            _lib.check(self.lib.nomad_embed_features_ragged(self.ctx, buf[lo:hi].data_ptr(), n, stride, arr, prec,
-                                                            feat[lo:hi].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                       "nomad_embed_features_ragged")
+        def launch(src, n, stride, arr, dst, ws):
+            _lib.check(self.lib.nomad_embed_features_ragged(self.ctx, src, n, stride, arr, prec, dst, ws.data_ptr(), ws.numel(),
+                                                            self._stream()), "nomad_embed_features_ragged")
 
-        rows = sum(num_frames(n) for n in lens)
-        split = B >= 2 and ((precision == "bf16x3" and self.X3_SPLIT_ROWS and rows >= self.X3_SPLIT_ROWS) or
-                            (precision == "bf16" and self.BF16_SPLIT_ROWS and rows >= self.BF16_SPLIT_ROWS) or
-                            (precision == "fp32" and self.F32_SPLIT_ROWS and self.F32_SPLIT_ROWS <= rows < self.F32_SPLIT_MAX_ROWS))
-        if not split:
-            run(0, B, False)
-            return feat
-        acc, h = 0, 1
-        for i, n in enumerate(lens[:-1]):   # two halves by audio length, as in embed_ragged
-            acc += n
-            h = i + 1
-            if 2 * acc >= sum(lens):
-                break
-        cur, ss = torch.cuda.current_stream(self.device), self.side_stream()
-        ss.wait_stream(cur)
-        with torch.cuda.stream(ss):
-            run(h, B, True)
-        run(0, h, False)
-        cur.wait_stream(ss)
-        return feat
+        return self._forward_ragged(waves, packed, precision, 768, launch)
 
     def cdist(self, a: torch.Tensor, b: torch.Tensor, want_matrix: bool = True):
         """a (Na,D), b (Nb,D) fp32 on the GPU, D a multiple of 4 up to 4096 -> (dist (Na,Nb) float64 or None, mean (Na,)
@@ -422,7 +392,7 @@ class Engine:
         dist = torch.empty(Na, Nb, dtype=torch.float64, device=self.device) if want_matrix else None
         mean = torch.empty(Na, dtype=torch.float64, device=self.device)
         _lib.check(self.lib.nomad_cdist(self.ctx, a.data_ptr(), Na, b.data_ptr(), Nb, D,
-                                        dist.data_ptr() if dist is not None else None, mean.data_ptr(), self._stream()),
+                                        _ptr(dist), mean.data_ptr(), self._stream()),
                    "nomad_cdist")
         return dist, mean
 
@@ -448,7 +418,7 @@ class Engine:
         dist = torch.empty(Nd, Nr, dtype=torch.float64, device=self.device) if want_matrix else None
         mean = torch.empty(Nd, dtype=torch.float64, device=self.device)
         _lib.check(self.lib.nomad_pairwise(self.ctx, deg.data_ptr(), Nd, ref.data_ptr(), Nr,
-                                           dist.data_ptr() if dist is not None else None, mean.data_ptr(),
+                                           _ptr(dist), mean.data_ptr(),
                                            self._stream()), "nomad_pairwise")
         return dist, mean
 
@@ -517,11 +487,9 @@ class Engine:
         M, B, arr, w, red, scratch = self._l1w_call(a_layers, b_layers, a_emb, b_emb, weights, reduction, frames)
         loss = torch.empty(B if reduction == "none" else 1, dtype=torch.float32, device=self.device)
         terms = torch.empty(13, B, dtype=torch.float64, device=self.device) if want_terms else None
-        _lib.check(self.lib.nomad_l1_loss_weighted(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(),
-                                                   a_emb.data_ptr() if a_emb is not None else None,
-                                                   b_emb.data_ptr() if b_emb is not None else None, M, B, arr, w, red,
-                                                   loss.data_ptr(), terms.data_ptr() if want_terms else None,
-                                                   scratch.data_ptr(), scratch.numel(), self._stream()), "nomad_l1_loss_weighted")
+        _lib.check(self.lib.nomad_l1_loss_weighted(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(), _ptr(a_emb), _ptr(b_emb), M,
+                                                   B, arr, w, red, loss.data_ptr(), _ptr(terms), scratch.data_ptr(),
+                                                   scratch.numel(), self._stream()), "nomad_l1_loss_weighted")
         return (loss if reduction == "none" else loss[0]), terms
 
     def l1_loss_weighted_backward(self, a_layers, b_layers, a_emb, b_emb, upstream: torch.Tensor, weights,
@@ -542,76 +510,32 @@ class Engine:
         up = upstream.to(self.device, torch.float32).reshape(-1).contiguous()
         if up.numel() != (B if reduction == "none" else 1):
             raise ValueError(f"upstream has {up.numel()} values for reduction={reduction!r} over {B} clips")
-        _lib.check(self.lib.nomad_l1_loss_weighted_backward(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(),
-                                                            a_emb.data_ptr() if a_emb is not None else None,
-                                                            b_emb.data_ptr() if b_emb is not None else None, M, B, arr, w, red, depth,
-                                                            up.data_ptr(), dl.data_ptr(), de.data_ptr() if de is not None else None,
-                                                            scratch.data_ptr(), scratch.numel(), self._stream()),
-                   "nomad_l1_loss_weighted_backward")
+        _lib.check(self.lib.nomad_l1_loss_weighted_backward(self.ctx, a_layers.data_ptr(), b_layers.data_ptr(), _ptr(a_emb),
+                                                            _ptr(b_emb), M, B, arr, w, red, depth, up.data_ptr(), dl.data_ptr(),
+                                                            _ptr(de), scratch.data_ptr(), scratch.numel(),
+                                                            self._stream()), "nomad_l1_loss_weighted_backward")
         return dl, de
 
-    # ---- bf16 path (long-form clips, config C5) -----------------------------------------------------
-    # Like the bf16x3 path below, bf16 batches with at least this many frames are embedded as two halves on two streams:
-    # every GEMM of the path runs one 256 x 256 workgroup per CU, so the partial last round of one half's tiles (the
-    # N = 768 GEMMs of 32 clips x 30 s are 2.2 rounds) and its per-tile prologue / epilogue are filled by the other
-    # half's kernels.  A clip's bits do not depend on the batch it is in, so the split changes no result.
-    # (Round 2 switched this off because embed_bf16 then differed run to run in ~1 % of the calls.  Round 3 found the cause -
-    # not the split: v_pk_fma_f32 in conv0 lost products while the other half's 128 x 128 bf16 GEMM shared its SIMD, DESIGN.md
-    # "The packed-FP32 hazard" - and the library is now built without packed-FP32 instructions; tests/test_gpu_race_screen.py
-    # holds every precision to bit-identical results with the split on.)  NOMAD_BF16_SPLIT_ROWS overrides; 0 disables.
-    BF16_SPLIT_ROWS = int(os.environ.get("NOMAD_BF16_SPLIT_ROWS", 4000))
-
-    def _embed_bf16_into(self, wav: torch.Tensor, emb: torch.Tensor, side: bool):
+    # ---- bf16 path (long-form clips, config C5) and bf16x3 path (fp32-class scores on the bf16 matrix cores) --------------------
+    def _embed_into(self, precision: str, wav: torch.Tensor, emb: torch.Tensor, side):
+        """``nomad_embed_bf16`` / ``nomad_embed_bf16x3`` over the whole of ``wav`` (B,N) into ``emb`` on the current stream."""
         B, N = wav.shape
-        ws = self._workspace(self._size(self.lib.nomad_workspace_bytes_bf16, B, N, "nomad_workspace_bytes_bf16"), side=side)
-        _lib.check(self.lib.nomad_embed_bf16(self.ctx, wav.data_ptr(), B, N, emb.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             self._stream()), "nomad_embed_bf16")
+        ws = self._workspace(self._forward_size(precision, B, N), side)
+        _lib.check(getattr(self.lib, "nomad_embed_" + precision)(self.ctx, wav.data_ptr(), B, N, emb.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                                 self._stream()), "nomad_embed_" + precision)
+
+    def _embed_bf16_into(self, wav: torch.Tensor, emb: torch.Tensor, side):
+        """(What the stage tests and the race-hunt tools drive directly: one bf16 forward, no split, on the workspace they name.)"""
+        self._embed_into("bf16", wav, emb, side)
 
     def embed_bf16(self, wav: torch.Tensor) -> torch.Tensor:
         """Scoring forward with bf16 activations/weights (fp32 accumulation and statistics)."""
-        if wav.dim() == 3:
-            wav = wav.squeeze(1)
-        self._check_dev(wav, "wav")
-        if not wav.is_contiguous():
-            wav = wav.contiguous()
-        B, N = wav.shape
-        if num_frames(N) < 1:
-            raise ValueError(f"clip of {N} samples is shorter than the conv stack's receptive field")
-        _lib.check(self.lib.nomad_enable_bf16(self.ctx), "nomad_enable_bf16")
+        wav, B, N, T = self._check_wav(wav)
+        self.enable("bf16")
         emb = torch.empty(B, 256, dtype=torch.float32, device=self.device)
-        rows = B * int(self.lib.nomad_num_frames(N))
-        ways = min(self.BF16_SPLIT_WAYS, B)
-        if ways < 2 or not self.BF16_SPLIT_ROWS or rows < self.BF16_SPLIT_ROWS:
-            self.lib.nomad_set_concurrent_parts(self.ctx, 1)   # scheduling hint only: results never depend on it (include/nomad_hip.h)
-            self._embed_bf16_into(wav, emb, side=False)
-            return emb
-        self.lib.nomad_set_concurrent_parts(self.ctx, ways)
-        cur = torch.cuda.current_stream(self.device)
-        cuts = [B * i // ways for i in range(ways + 1)]
-        for k in range(1, ways):
-            st = self.side_stream(k)
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                self._embed_bf16_into(wav[cuts[k]:cuts[k + 1]], emb[cuts[k]:cuts[k + 1]], side=k)
-        self._embed_bf16_into(wav[:cuts[1]], emb[:cuts[1]], side=False)
-        for k in range(1, ways):
-            cur.wait_stream(self.side_stream(k))
+        self._dispatch(B, B // 2 if self._splits("bf16", B, B * T) else 0,
+                       lambda lo, hi, side: self._embed_into("bf16", wav[lo:hi], emb[lo:hi], side), hint=True)
         return emb
-
-    BF16_SPLIT_WAYS = int(os.environ.get("NOMAD_BF16_SPLIT_WAYS", 2))
-
-    # ---- bf16x3 path: fp32-class scores on the bf16 matrix cores ---------------------------------------
-    # Batches with at least this many frames (rows of the encoder GEMMs) are embedded as two halves on two streams: the
-    # path's kernels run one 256 x 256 workgroup per CU, and e.g. the N = 768 GEMMs of a 256-clip batch are 2.33 rounds of
-    # the 256 CUs - the other half's kernels fill the idle third round (+4 % at 256 clips of 4 s, +14 % at 128, break-even at 16; bit-identical results:
-    # profiles/r01_bf16x3_two_streams.txt).  NOMAD_X3_SPLIT_ROWS overrides; 0 disables.
-    X3_SPLIT_ROWS = int(os.environ.get("NOMAD_X3_SPLIT_ROWS", 4000))
-
-    def _embed_bf16x3_into(self, wav: torch.Tensor, emb: torch.Tensor, side: bool):
-        B, N = wav.shape
-        ws = self._workspace(self._size(self.lib.nomad_workspace_bytes_bf16x3, B, N, "nomad_workspace_bytes_bf16x3"), side=side)
-        _lib.check(self.lib.nomad_embed_bf16x3(self.ctx, wav.data_ptr(), B, N, emb.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               self._stream()), "nomad_embed_bf16x3")
 
     def embed_bf16x3(self, wav: torch.Tensor, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                      want_layers: bool = False, side: bool = False):
@@ -619,44 +543,25 @@ class Engine:
         fp32 softmax / LayerNorm / head): NOMAD scores agree with the fp32 path to ~1e-6.
         want_layers / head: as in ``embed`` -> (emb, layers (12,B,T,768)), the LossNetLayers outputs (no gradient:
         the branch of ``forward()`` that needs one stays on ``embed_train``)."""
-        if wav.dim() == 3:
-            wav = wav.squeeze(1)
-        self._check_dev(wav, "wav")
-        if not wav.is_contiguous():
-            wav = wav.contiguous()
-        B, N = wav.shape
-        T = num_frames(N)
-        if T < 1:
-            raise ValueError(f"clip of {N} samples is shorter than the conv stack's receptive field")
-        _lib.check(self.lib.nomad_enable_bf16x3(self.ctx), "nomad_enable_bf16x3")
+        wav, B, N, T = self._check_wav(wav)
+        self.enable("bf16x3")
         emb = torch.empty(B, 256, dtype=torch.float32, device=self.device)
         if want_layers or head is not None:
-            hw, hb = head if head is not None else (None, None)
-            for t, name in ((hw, "head weight"), (hb, "head bias")):
-                if t is not None:
-                    self._check_dev(t, name)
+            hw, hb = self._check_head(head)
             layers = torch.empty(12, B, T, 768, dtype=torch.float32, device=self.device)
-            ws = self._workspace(self._size(self.lib.nomad_workspace_bytes_bf16x3, B, N, "nomad_workspace_bytes_bf16x3"), side=side)
-            _lib.check(self.lib.nomad_embed_layers_bf16x3(self.ctx, wav.data_ptr(), B, N,
-                                                          hw.data_ptr() if hw is not None else None,
-                                                          hb.data_ptr() if hb is not None else None,
-                                                          emb.data_ptr(), layers.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                          self._stream()), "nomad_embed_layers_bf16x3")
+            ws = self._workspace(self._forward_size("bf16x3", B, N), side)
+            _lib.check(self.lib.nomad_embed_layers_bf16x3(self.ctx, wav.data_ptr(), B, N, _ptr(hw), _ptr(hb), emb.data_ptr(),
+                                                          layers.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                       "nomad_embed_layers_bf16x3")
             return (emb, layers) if want_layers else emb
+
+        def run(lo, hi, use_side):
+            self._embed_into("bf16x3", wav[lo:hi], emb[lo:hi], use_side)
+
         if side:
-            self._embed_bf16x3_into(wav, emb, side=True)
-            return emb
-        rows = B * int(self.lib.nomad_num_frames(N))
-        if B < 2 or not self.X3_SPLIT_ROWS or rows < self.X3_SPLIT_ROWS:
-            self._embed_bf16x3_into(wav, emb, side=False)
-            return emb
-        h = B // 2
-        cur, side = torch.cuda.current_stream(self.device), self.side_stream()
-        side.wait_stream(cur)                      # the waveform (and anything queued before) is ready
-        with torch.cuda.stream(side):
-            self._embed_bf16x3_into(wav[h:], emb[h:], side=True)
-        self._embed_bf16x3_into(wav[:h], emb[:h], side=False)
-        cur.wait_stream(side)
+            run(0, B, side)   # the caller's own concurrency: its stream, the side workspace it names, no split
+        else:
+            self._dispatch(B, B // 2 if self._splits("bf16x3", B, B * T) else 0, run)
         return emb
 
     def diag_split_bf16(self, x: torch.Tensor) -> torch.Tensor:
@@ -686,10 +591,8 @@ class Engine:
         if out is None:
             out = (torch.zeros(M, N, dtype=torch.float32, device=self.device) if out_f32
                    else torch.zeros(2, M, N, dtype=torch.bfloat16, device=self.device))
-        _lib.check(self.lib.nomad_diag_gemm_bf16x3(self.ctx, A.data_ptr(), W.data_ptr(),
-                                                   bias.data_ptr() if bias is not None else None,
-                                                   R.data_ptr() if R is not None else None, out.data_ptr(),
-                                                   M, N, K, int(gelu), int(variant), self._stream()), "nomad_diag_gemm_bf16x3")
+        _lib.check(self.lib.nomad_diag_gemm_bf16x3(self.ctx, A.data_ptr(), W.data_ptr(), _ptr(bias), _ptr(R), out.data_ptr(), M, N,
+                                                   K, int(gelu), int(variant), self._stream()), "nomad_diag_gemm_bf16x3")
         return out
 
     def diag_attention_bf16x3(self, qkv_split, B, T, waves: int = -1):
@@ -713,10 +616,8 @@ class Engine:
         N = W.shape[0]
         if out is None:
             out = torch.zeros(M, N, dtype=torch.bfloat16, device=self.device)  # zeros: a kernel that writes nothing shows
-        _lib.check(self.lib.nomad_diag_gemm_bf16(self.ctx, A.data_ptr(), W.data_ptr(),
-                                                 bias.data_ptr() if bias is not None else None,
-                                                 R.data_ptr() if R is not None else None, out.data_ptr(),
-                                                 M, N, K, int(gelu), tile, self._stream()), "nomad_diag_gemm_bf16")
+        _lib.check(self.lib.nomad_diag_gemm_bf16(self.ctx, A.data_ptr(), W.data_ptr(), _ptr(bias), _ptr(R), out.data_ptr(), M, N, K,
+                                                 int(gelu), tile, self._stream()), "nomad_diag_gemm_bf16")
         return out
 
     # ---- training (differentiable forward) ---------------------------------------------------------
@@ -764,11 +665,6 @@ class Engine:
     def enable_backward(self):
         _lib.check(self.lib.nomad_enable_backward(self.ctx), "nomad_enable_backward")
 
-    def _size(self, fn, B, n_samples, what):
-        n = C.c_size_t()
-        _lib.check(fn(self.ctx, B, n_samples, C.byref(n)), what)
-        return n.value
-
     def embed_train(self, wav: torch.Tensor, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """Training-mode forward: -> (emb (B,256), layers (12,B,T,768), saved block for embed_backward)."""
         if wav.dim() == 3:
@@ -783,11 +679,9 @@ class Engine:
                             device=self.device)
         hw, hb = head if head is not None else (None, None)
         ws = self._workspace(self.workspace_bytes(B, N))
-        _lib.check(self.lib.nomad_embed_train(self.ctx, wav.data_ptr(), B, N,
-                                              hw.data_ptr() if hw is not None else None,
-                                              hb.data_ptr() if hb is not None else None,
-                                              emb.data_ptr(), layers.data_ptr(), saved.data_ptr(), saved.numel(),
-                                              ws.data_ptr(), ws.numel(), self._stream()), "nomad_embed_train")
+        _lib.check(self.lib.nomad_embed_train(self.ctx, wav.data_ptr(), B, N, _ptr(hw), _ptr(hb), emb.data_ptr(), layers.data_ptr(),
+                                              saved.data_ptr(), saved.numel(), ws.data_ptr(), ws.numel(),
+                                              self._stream()), "nomad_embed_train")
         return emb, layers, saved
 
     def embed_backward(self, wav, layers, saved, dlayers, demb, head=None) -> torch.Tensor:
@@ -801,14 +695,9 @@ class Engine:
         ws = self._workspace(nb)
         dwav = torch.empty(B, N, dtype=torch.float32, device=self.device)
         hw, hb = head if head is not None else (None, None)
-        _lib.check(self.lib.nomad_embed_backward(self.ctx, wav.data_ptr(), B, N,
-                                                 hw.data_ptr() if hw is not None else None,
-                                                 hb.data_ptr() if hb is not None else None,
-                                                 layers.data_ptr(), saved.data_ptr(), saved.numel(),
-                                                 dlayers.data_ptr() if dlayers is not None else None,
-                                                 demb.data_ptr() if demb is not None else None,
-                                                 dwav.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                   "nomad_embed_backward")
+        _lib.check(self.lib.nomad_embed_backward(self.ctx, wav.data_ptr(), B, N, _ptr(hw), _ptr(hb), layers.data_ptr(),
+                                                 saved.data_ptr(), saved.numel(), _ptr(dlayers), _ptr(demb), dwav.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), self._stream()), "nomad_embed_backward")
         return dwav
 
     def l1_loss_backward(self, a_layers, b_layers, a_emb, b_emb, upstream: torch.Tensor):
@@ -842,20 +731,7 @@ class Engine:
             if any(n > wav.shape[1] for n in lens):
                 raise ValueError("a length exceeds the padded waveform tensor")
             return wav, lens
-        flat = [torch.as_tensor(w, dtype=torch.float32).reshape(-1) for w in waves]
-        lens = [int(w.numel()) for w in flat]
-        if all(w.is_cuda for w in flat):
-            buf = torch.empty(len(flat), (max(lens) + 3) // 4 * 4, dtype=torch.float32, device=self.device)
-            for i, w in enumerate(flat):
-                buf[i, :lens[i]] = w
-            return buf, lens
-        host, lens = self.pack_ragged_host(flat)
-        return host.to(self.device, non_blocking=True), lens
-
-    def _size_ragged(self, fn, lens, what):
-        n = C.c_size_t()
-        _lib.check(fn(self.ctx, len(lens), (C.c_int * len(lens))(*lens), C.byref(n)), what)
-        return n.value
+        return self._pack(waves)
 
     def embed_train_ragged(self, waves, lengths=None, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                            save: bool = True, side: bool = False):
@@ -875,12 +751,9 @@ class Engine:
                             dtype=torch.uint8, device=self.device) if save else None
         hw, hb = head if head is not None else (None, None)
         ws = self._workspace(self._size_ragged(self.lib.nomad_workspace_bytes_ragged, lens, "nomad_workspace_bytes_ragged"), side)
-        _lib.check(self.lib.nomad_embed_train_ragged(self.ctx, buf.data_ptr(), B, stride, arr,
-                                                     hw.data_ptr() if hw is not None else None,
-                                                     hb.data_ptr() if hb is not None else None,
-                                                     emb.data_ptr(), layers.data_ptr(),
-                                                     saved.data_ptr() if save else None, saved.numel() if save else 0,
-                                                     ws.data_ptr(), ws.numel(), self._stream()), "nomad_embed_train_ragged")
+        _lib.check(self.lib.nomad_embed_train_ragged(self.ctx, buf.data_ptr(), B, stride, arr, _ptr(hw), _ptr(hb), emb.data_ptr(),
+                                                     layers.data_ptr(), _ptr(saved), saved.numel() if save else 0, ws.data_ptr(),
+                                                     ws.numel(), self._stream()), "nomad_embed_train_ragged")
         return emb, layers, saved, (buf, lens)
 
     def embed_backward_ragged(self, batch, layers, saved, dlayers, demb, head=None) -> torch.Tensor:
@@ -893,14 +766,10 @@ class Engine:
                                                "nomad_backward_workspace_bytes_ragged"))
         dwav = torch.empty(B, stride, dtype=torch.float32, device=self.device)
         hw, hb = head if head is not None else (None, None)
-        _lib.check(self.lib.nomad_embed_backward_ragged(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens),
-                                                        hw.data_ptr() if hw is not None else None,
-                                                        hb.data_ptr() if hb is not None else None,
-                                                        layers.data_ptr(), saved.data_ptr(), saved.numel(),
-                                                        dlayers.data_ptr() if dlayers is not None else None,
-                                                        demb.data_ptr() if demb is not None else None,
-                                                        dwav.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                   "nomad_embed_backward_ragged")
+        _lib.check(self.lib.nomad_embed_backward_ragged(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), _ptr(hw),
+                                                        _ptr(hb), layers.data_ptr(), saved.data_ptr(), saved.numel(), _ptr(dlayers),
+                                                        _ptr(demb), dwav.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                        self._stream()), "nomad_embed_backward_ragged")
         return dwav
 
     def train_backward_ragged(self, batch, layers: torch.Tensor, saved: torch.Tensor, demb: torch.Tensor):
@@ -970,10 +839,7 @@ class Engine:
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         da, dp, dn = (torch.empty_like(a), torch.empty_like(a), torch.empty_like(a)) if want_grad else (None, None, None)
         _lib.check(self.lib.nomad_triplet_loss(self.ctx, a.data_ptr(), p.data_ptr(), n.data_ptr(), B, float(margin),
-                                               loss.data_ptr(), da.data_ptr() if want_grad else None,
-                                               dp.data_ptr() if want_grad else None,
-                                               dn.data_ptr() if want_grad else None, self._stream()),
-                   "nomad_triplet_loss")
+                                               loss.data_ptr(), _ptr(da), _ptr(dp), _ptr(dn), self._stream()), "nomad_triplet_loss")
         return loss, da, dp, dn
 
     def adam_step(self, lr_body: float, lr_head: float, betas=(0.9, 0.999), eps: float = 1e-8):
@@ -1080,10 +946,8 @@ class Engine:
         M, K = A.shape
         N = W.shape[0]
         out = torch.empty(M, N, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.nomad_diag_gemm(self.ctx, A.data_ptr(), W.data_ptr(),
-                                            bias.data_ptr() if bias is not None else None,
-                                            R.data_ptr() if R is not None else None, out.data_ptr(),
-                                            M, N, K, int(gelu), tile, self._stream()), "nomad_diag_gemm")
+        _lib.check(self.lib.nomad_diag_gemm(self.ctx, A.data_ptr(), W.data_ptr(), _ptr(bias), _ptr(R), out.data_ptr(), M, N, K,
+                                            int(gelu), tile, self._stream()), "nomad_diag_gemm")
         return out
 
     def diag_layernorm(self, x, gamma, beta):

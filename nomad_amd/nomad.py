@@ -24,6 +24,7 @@ What differs, deliberately:
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from datetime import datetime
@@ -224,170 +225,81 @@ def _stack_layers(layers) -> torch.Tensor:
     return torch.stack([l.contiguous() for l in layers])
 
 
+@contextlib.contextmanager
+def _encoder_cut(eng: Engine, selection):
+    """The engine's ``encoder_depth`` set to the selection's around the engine calls of a pass and restored behind them: nothing else
+    that uses the engine ever sees a cut encoder.  The plain loss (selection None) neither reads nor sets it."""
+    if selection is None:
+        yield
+        return
+    prev = eng.encoder_depth
+    eng.encoder_depth = selection[1]
+    try:
+        yield
+    finally:
+        eng.encoder_depth = prev
+
+
 class _NomadLossFn(torch.autograd.Function):
     """loss = NomadLoss(LossNetLayers(clean), LossNetLayers(estimate)); backward = d loss / d estimate and, when ``clean`` requires a
-    gradient too, d loss / d clean - the reference's ``forward`` (nomad.py:142-146) is differentiable in both arguments."""
+    gradient too, d loss / d clean - the reference's ``forward`` (nomad.py:142-146) is differentiable in both arguments.
+
+    lens: None, or the clips' exact lengths (``Nomad.forward(estimate, clean, lengths)``) - both branches then run the ragged forward
+    on fp32 buffers (no padding in the arithmetic, packed layer outputs), the loss terms are means over the valid frames, and the
+    gradient is zero behind every length.  selection: None - the 13-term mean, ``l1_loss`` and its backward - or (13 weights,
+    encoder depth, reduction) from ``loss_selection``: a weight per term, a loss per clip (reduction "none") and the encoder cut
+    behind the deepest layer with a weight (``l1_loss_weighted``, whose kernels fold in another order: other bits than ``l1_loss``
+    where both apply)."""
 
     @staticmethod
-    def forward(ctx, estimate, clean, nomad):
+    def forward(ctx, estimate, clean, nomad, lens, selection):
         eng = nomad.engine
         head = (nomad.lossnet_layers.embedding_weight, nomad.lossnet_layers.embedding_bias)
         est = estimate.detach().to(eng.device, torch.float32).contiguous()
         cln = clean.detach().to(eng.device, torch.float32).contiguous()
         need_grad = estimate.requires_grad
         need_clean_grad = clean.requires_grad
-        # the two forwards are independent: at training batch sizes (32 x 1 s) one of them fills less than half
-        # of the chip, so the clean branch runs concurrently on a side stream with its own workspace
-        cur = torch.cuda.current_stream(eng.device)
+        frames = None if lens is None else [num_frames(n) for n in lens]
         # precision="bf16x3": the branches that carry no gradient (always `clean`; `estimate` too under no_grad) run
         # the split-bf16 forward (layer outputs within ~1e-5 of fp32); the branch that is differentiated stays on fp32 BUFFERS
         # (embed_train), its GEMM products in whatever Engine.gemm_precision says - "bf16x3" when the Nomad was made with
-        # precision="bf16x3", exact fp32 otherwise
-        fwd = eng.embed_bf16x3 if _takes_bf16x3(nomad.precision, cln) else eng.embed
-        saved_c = None
-        if need_clean_grad:
-            # the uncommon case (the speech-enhancement example differentiates `estimate` only, nomad_loss_test.py:69): the clean branch
-            # keeps its activations too, on the caller's stream - the training-mode forward has one workspace per context
-            c_emb, c_layers, saved_c = eng.embed_train(cln, head)
-        else:
-            side = eng.side_stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                c_emb, c_layers = fwd(cln, head=head, want_layers=True, side=True)
-        if need_grad:
-            e_emb, e_layers, saved = eng.embed_train(est, head)
-        else:
-            e_emb, e_layers = fwd(est, head=head, want_layers=True)
-            saved = None
-        if not need_clean_grad:
-            cur.wait_stream(side)
-            for t in (c_emb, c_layers, cln):
-                t.record_stream(cur)
-        loss = eng.l1_loss(e_layers, c_layers, e_emb, c_emb)
-        if need_grad or need_clean_grad:
-            ctx.nomad = nomad
-            ctx.shapes = (estimate.shape, clean.shape)
-            ctx.save_for_backward(est, e_layers, e_emb, cln, c_layers, c_emb, saved, saved_c)
-        return loss
+        # precision="bf16x3", exact fp32 otherwise.  A cut encoder exists on fp32 buffers only: no embed_bf16x3 below depth 12
+        x3 = (selection is None or selection[1] == 12) and _takes_bf16x3(nomad.precision, cln)
 
-    @staticmethod
-    def backward(ctx, grad_out):
-        est, e_layers, e_emb, cln, c_layers, c_emb, saved, saved_c = ctx.saved_tensors
-        eng = ctx.nomad.engine
-        head = (ctx.nomad.lossnet_layers.embedding_weight, ctx.nomad.lossnet_layers.embedding_bias)
-        dwav = dcln = None
-        if saved is not None and ctx.needs_input_grad[0]:
-            dl, de = eng.l1_loss_backward(e_layers, c_layers, e_emb, c_emb, grad_out)
-            dwav = eng.embed_backward(est, e_layers, saved, dl, de, head).reshape(ctx.shapes[0])
-        if saved_c is not None and ctx.needs_input_grad[1]:
-            # |e - c| is symmetric: the gradient with respect to the clean side is the same kernel with the arguments swapped
-            dl, de = eng.l1_loss_backward(c_layers, e_layers, c_emb, e_emb, grad_out)
-            dcln = eng.embed_backward(cln, c_layers, saved_c, dl, de, head).reshape(ctx.shapes[1])
-        return dwav, dcln, None
+        def branch(wav, save, side):
+            """One LossNetLayers forward -> (emb, layers, saved block or None, the waveform buffer its backward takes)."""
+            if lens is not None:
+                emb, layers, saved, batch = eng.embed_train_ragged(wav, lens, head, save=save, side=side)
+                return emb, layers, saved, batch[0]
+            if save:
+                return (*eng.embed_train(wav, head), wav)
+            emb, layers = (eng.embed_bf16x3 if x3 else eng.embed)(wav, head=head, want_layers=True, side=side)
+            return emb, layers, None, wav
 
-
-class _NomadLossRaggedFn(torch.autograd.Function):
-    """``_NomadLossFn`` over clips at their exact lengths (``Nomad.forward(estimate, clean, lengths)``): both branches run the ragged
-    forward on fp32 buffers (no padding in the arithmetic, packed layer outputs), the loss terms are means over the valid frames, and
-    the gradient is zero behind every length."""
-
-    @staticmethod
-    def forward(ctx, estimate, clean, nomad, lens):
-        eng = nomad.engine
-        head = (nomad.lossnet_layers.embedding_weight, nomad.lossnet_layers.embedding_bias)
-        est = estimate.detach().to(eng.device, torch.float32).contiguous()
-        cln = clean.detach().to(eng.device, torch.float32).contiguous()
-        need_grad = estimate.requires_grad
-        need_clean_grad = clean.requires_grad
-        cur = torch.cuda.current_stream(eng.device)
-        if need_clean_grad:   # (one training-mode workspace per context: on the caller's stream, as in _NomadLossFn)
-            c_emb, c_layers, saved_c, c_batch = eng.embed_train_ragged(cln, lens, head)
-        else:
-            side = eng.side_stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                c_emb, c_layers, saved_c, c_batch = eng.embed_train_ragged(cln, lens, head, save=False, side=True)
-        e_emb, e_layers, saved, e_batch = eng.embed_train_ragged(est, lens, head, save=need_grad)
-        if not need_clean_grad:
-            cur.wait_stream(side)
-            for t in (c_emb, c_layers, cln):
-                t.record_stream(cur)
-        loss = eng.l1_loss(e_layers, c_layers, e_emb, c_emb)
-        if need_grad or need_clean_grad:
-            ctx.nomad = nomad
-            ctx.lens = lens
-            ctx.shapes = (estimate.shape, clean.shape)
-            ctx.save_for_backward(e_batch[0], e_layers, e_emb, c_batch[0], c_layers, c_emb, saved, saved_c)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        est, e_layers, e_emb, cln, c_layers, c_emb, saved, saved_c = ctx.saved_tensors
-        eng = ctx.nomad.engine
-        head = (ctx.nomad.lossnet_layers.embedding_weight, ctx.nomad.lossnet_layers.embedding_bias)
-        dwav = dcln = None
-        if saved is not None and ctx.needs_input_grad[0]:
-            dl, de = eng.l1_loss_backward(e_layers, c_layers, e_emb, c_emb, grad_out)
-            dwav = eng.embed_backward_ragged((est, ctx.lens), e_layers, saved, dl, de, head).reshape(ctx.shapes[0])
-        if saved_c is not None and ctx.needs_input_grad[1]:
-            dl, de = eng.l1_loss_backward(c_layers, e_layers, c_emb, e_emb, grad_out)
-            dcln = eng.embed_backward_ragged((cln, ctx.lens), c_layers, saved_c, dl, de, head).reshape(ctx.shapes[1])
-        return dwav, dcln, None, None
-
-
-class _NomadLossSelectFn(torch.autograd.Function):
-    """``_NomadLossFn`` / ``_NomadLossRaggedFn`` (lens None / a list) with a weight per term, a loss per clip (reduction "none") and
-    the encoder cut behind the deepest layer with a weight.  The engine's depth is set around the engine calls of the forward and
-    again around those of the backward, and restored each time: nothing else that uses the engine ever sees a cut encoder."""
-
-    @staticmethod
-    def forward(ctx, estimate, clean, nomad, lens, weights, depth, reduction):
-        eng = nomad.engine
-        head = (nomad.lossnet_layers.embedding_weight, nomad.lossnet_layers.embedding_bias)
-        est = estimate.detach().to(eng.device, torch.float32).contiguous()
-        cln = clean.detach().to(eng.device, torch.float32).contiguous()
-        need_grad = estimate.requires_grad
-        need_clean_grad = clean.requires_grad
-        cur = torch.cuda.current_stream(eng.device)
-        frames = None if lens is None else [num_frames(n) for n in lens]
-        saved = saved_c = None
-        prev = eng.encoder_depth
-        eng.encoder_depth = depth
-        try:
-            if lens is None:
-                # a cut encoder exists on fp32 buffers only (products follow Engine.gemm_precision): no embed_bf16x3 below depth 12
-                fwd = eng.embed_bf16x3 if depth == 12 and _takes_bf16x3(nomad.precision, cln) else eng.embed
-                if need_clean_grad:
-                    c_emb, c_layers, saved_c = eng.embed_train(cln, head)
-                else:
-                    side = eng.side_stream()
-                    side.wait_stream(cur)
-                    with torch.cuda.stream(side):
-                        c_emb, c_layers = fwd(cln, head=head, want_layers=True, side=True)
-                if need_grad:
-                    e_emb, e_layers, saved = eng.embed_train(est, head)
-                else:
-                    e_emb, e_layers = fwd(est, head=head, want_layers=True)
+        with _encoder_cut(eng, selection):
+            if need_clean_grad:
+                # the uncommon case (the speech-enhancement example differentiates `estimate` only, nomad_loss_test.py:69): the clean
+                # branch keeps its activations too, on the caller's stream - the training-mode forward has one workspace per context
+                c_emb, c_layers, saved_c, cln = branch(cln, True, False)
             else:
-                if need_clean_grad:
-                    c_emb, c_layers, saved_c, c_batch = eng.embed_train_ragged(cln, lens, head)
-                else:
-                    side = eng.side_stream()
-                    side.wait_stream(cur)
-                    with torch.cuda.stream(side):
-                        c_emb, c_layers, saved_c, c_batch = eng.embed_train_ragged(cln, lens, head, save=False, side=True)
-                e_emb, e_layers, saved, e_batch = eng.embed_train_ragged(est, lens, head, save=need_grad)
-                est, cln = e_batch[0], c_batch[0]
+                # the two forwards are independent: at training batch sizes (32 x 1 s) one of them fills less than half
+                # of the chip, so the clean branch runs concurrently on a side stream with its own workspace
+                cur, side = torch.cuda.current_stream(eng.device), eng.side_stream()
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    c_emb, c_layers, saved_c, cln = branch(cln, False, True)
+            e_emb, e_layers, saved, est = branch(est, need_grad, False)
             if not need_clean_grad:
                 cur.wait_stream(side)
                 for t in (c_emb, c_layers, cln):
                     t.record_stream(cur)
-            loss, _ = eng.l1_loss_weighted(e_layers, c_layers, e_emb, c_emb, weights, reduction, frames, want_terms=False)
-        finally:
-            eng.encoder_depth = prev
+            if selection is None:
+                loss = eng.l1_loss(e_layers, c_layers, e_emb, c_emb)
+            else:
+                loss, _ = eng.l1_loss_weighted(e_layers, c_layers, e_emb, c_emb, selection[0], selection[2], frames, want_terms=False)
         if need_grad or need_clean_grad:
             ctx.nomad = nomad
-            ctx.sel = (lens, frames, weights, depth, reduction)
+            ctx.sel = (lens, frames, selection)
             ctx.shapes = (estimate.shape, clean.shape)
             ctx.save_for_backward(est, e_layers, e_emb, cln, c_layers, c_emb, saved, saved_c)
         return loss
@@ -396,19 +308,23 @@ class _NomadLossSelectFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         est, e_layers, e_emb, cln, c_layers, c_emb, saved, saved_c = ctx.saved_tensors
         eng = ctx.nomad.engine
-        lens, frames, weights, depth, reduction = ctx.sel
+        lens, frames, selection = ctx.sel
         head = (ctx.nomad.lossnet_layers.embedding_weight, ctx.nomad.lossnet_layers.embedding_bias)
 
         # Per utterance, clip b's rows are linear in upstream[b]: the chain runs with upstream 1 - every clip's own gradient, the
         # bits of its B = 1 call - and row b is scaled once at the end.  (Scaled at the start, v_b * gradient would carry the
         # rounding of the whole chain again, ~2e-6 of it for a v_b that is no power of two.)
-        per_clip = reduction == "none"
+        per_clip = selection is not None and selection[2] == "none"
         up = torch.ones(grad_out.numel(), dtype=torch.float32, device=eng.device) if per_clip else grad_out
 
         def branch(wav, layers, emb, o_layers, o_emb, sv):   # |e - c| is symmetric: the clean side is the same call, arguments swapped
-            dl, de = eng.l1_loss_weighted_backward(layers, o_layers, emb, o_emb, up, weights, reduction, frames, depth)
-            if de is None and depth == 12:   # the whole encoder, no embedding term: its head backward gets zeros
-                de = torch.zeros_like(emb)
+            if selection is None:
+                dl, de = eng.l1_loss_backward(layers, o_layers, emb, o_emb, up)
+            else:
+                weights, depth, reduction = selection
+                dl, de = eng.l1_loss_weighted_backward(layers, o_layers, emb, o_emb, up, weights, reduction, frames, depth)
+                if de is None and depth == 12:   # the whole encoder, no embedding term: its head backward gets zeros
+                    de = torch.zeros_like(emb)
             if lens is None:
                 d = eng.embed_backward(wav, layers, sv, dl, de, head)
             else:
@@ -416,16 +332,12 @@ class _NomadLossSelectFn(torch.autograd.Function):
             return d * grad_out.to(d.device, torch.float32).reshape(-1, 1) if per_clip else d
 
         dwav = dcln = None
-        prev = eng.encoder_depth
-        eng.encoder_depth = depth
-        try:
+        with _encoder_cut(eng, selection):
             if saved is not None and ctx.needs_input_grad[0]:
                 dwav = branch(est, e_layers, e_emb, c_layers, c_emb, saved).reshape(ctx.shapes[0])
             if saved_c is not None and ctx.needs_input_grad[1]:
                 dcln = branch(cln, c_layers, c_emb, e_layers, e_emb, saved_c).reshape(ctx.shapes[1])
-        finally:
-            eng.encoder_depth = prev
-        return dwav, dcln, None, None, None, None, None
+        return dwav, dcln, None, None, None
 
 
 class GraphedLoss:
@@ -880,10 +792,8 @@ class Nomad:
             lens = check_lengths(estimate, lengths)
         weights, depth = loss_selection(self.nomad_loss.L, layer_weights)
         if layer_weights is None and self.nomad_loss.L == 13 and reduction == "mean":
-            if lens is not None:
-                return _NomadLossRaggedFn.apply(estimate, clean, self, lens)
-            return _NomadLossFn.apply(estimate, clean, self)
-        return _NomadLossSelectFn.apply(estimate, clean, self, lens, weights, depth, reduction)
+            return _NomadLossFn.apply(estimate, clean, self, lens, None)
+        return _NomadLossFn.apply(estimate, clean, self, lens, (weights, depth, reduction))
 
     def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor, lengths=None) -> "GraphedLoss":
         """``forward`` + backward for inputs of this shape, captured as one HIP graph (see ``GraphedLoss``): for training loops with
