@@ -17,6 +17,7 @@
  *   nomad_cdist                    cdist + np.mean(axis=1) of src/training/train_triplet.py (:281-282, :327-328, :385-386)
  *                                  on rows of any width (768 for the baseline)
  *   nomad_paired_distance          np.diag(cdist(test, ref)) (train_triplet.py:438-439) without the matrix
+ *   nomad_cdist_backward           d / d a and d / d b of nomad_cdist's matrix and row means (the NOMAD score as a loss)
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
  *
@@ -169,6 +170,29 @@ int nomad_cdist(nomad_ctx* ctx, const float* a_dev, int Na, const float* b_dev, 
  * other N - 1 columns.  No scratch, no allocation.  NOMAD_ERR_INVALID as for nomad_cdist. */
 int nomad_paired_distance(nomad_ctx* ctx, const float* a_dev, const float* b_dev, int N, int D,
                           double* out_dev, nomad_stream_t stream);
+
+/*
+ * The backward of nomad_cdist: gradients of  sum_ij gdist_ij d_ij + sum_i gmean_i mean_i  with respect to a and b.
+ * Let d_ij be the value nomad_cdist computes (the same chain, the same bits) and c_ij = gdist_ij + gmean_i / Nb, formed in
+ * float64, a NULL upstream counting as 0.  Then
+ *   W_ij  = c_ij / d_ij, and exactly 0 where d_ij == 0 (torch.cdist's convention: a row of b equal to the row of a contributes
+ *           nothing, never NaN / Inf)
+ *   da_ik = (float) sum_j fma(W_ij, (double)a_ik - (double)b_jk, acc),  j ascending from 0, one float64 accumulator
+ *   db_jk = (float) sum_i fma(W_ij, (double)b_jk - (double)a_ik, acc),  i ascending from 0
+ * each output rounded to fp32 once, at the store; no atomics, no partial sums whose number depends on the grid.  So results are
+ * identical run to run, row i of da depends on a_i, b and row i of the upstreams only (the bits of the row's own Na = 1 call), and
+ * row j of db on b_j, a and column j of gdist (and gmean) only (the bits of its own Nb = 1 call with gmean / Nb folded into gdist).
+ *   gdist_dev [Na][Nb] float64 or NULL, gmean_dev [Na] float64 or NULL (not both NULL)
+ *   da_dev [Na][D] fp32 (out) or NULL, db_dev [Nb][D] fp32 (out) or NULL (not both NULL)
+ * Scratch is the caller's: nomad_cdist_backward_scratch_bytes(Na, Nb) bytes (the [Na][Nb] float64 W), written before it is read.
+ * Asynchronous, no allocation; argument errors return before anything is queued.
+ * NOMAD_ERR_INVALID: NULL a / b / scratch, both upstreams NULL, both outputs NULL, Na / Nb <= 0 (or above 65535 * 64), D not a
+ * multiple of 4 or outside 4 .. 4096.  NOMAD_ERR_WORKSPACE: scratch_bytes too small.
+ */
+int nomad_cdist_backward_scratch_bytes(int Na, int Nb, size_t* bytes);
+int nomad_cdist_backward(nomad_ctx* ctx, const float* a_dev, int Na, const float* b_dev, int Nb, int D,
+                         const double* gdist_dev, const double* gmean_dev, float* da_dev, float* db_dev,
+                         void* scratch_dev, size_t scratch_bytes, nomad_stream_t stream);
 
 /*
  * Pooled backbone features, Origw2v.forward (networks.py:29-34): the last encoder layer's output averaged over time - no

@@ -3532,6 +3532,35 @@ int nomad_paired_distance(nomad_ctx* c, const float* a, const float* b, int N, i
     return 0;
 }
 
+int nomad_cdist_backward_scratch_bytes(int Na, int Nb, size_t* bytes) {
+    if (!bytes || Na <= 0 || Nb <= 0) return fail(NOMAD_ERR_INVALID, "nomad_cdist_backward_scratch_bytes: bad argument (Na=%d, Nb=%d)", Na, Nb);
+    *bytes = sizeof(double) * (size_t)Na * (size_t)Nb;   // W [Na][Nb]
+    return 0;
+}
+
+// The backward of nomad_cdist (pairwise.hip.h): the weights W = c / d from the forward's chain, then one ordered reduction per output.
+int nomad_cdist_backward(nomad_ctx* c, const float* a, int Na, const float* b, int Nb, int D, const double* gdist, const double* gmean,
+                         float* da, float* db, void* scratch, size_t scratch_bytes, nomad_stream_t stream) {
+    constexpr int kMaxRows = 65535 * kPairTile;   // one grid row per 64 rows
+    if (!c || !a || !b || !scratch || (!gdist && !gmean) || (!da && !db) || Na <= 0 || Nb <= 0 || Na > kMaxRows || Nb > kMaxRows ||
+        D <= 0 || D % 4 || D > kCdistMaxD)
+        return fail(NOMAD_ERR_INVALID,
+                    "nomad_cdist_backward: bad argument (Na=%d, Nb=%d, D=%d: a positive multiple of 4, at most %d; one upstream and one "
+                    "output at least)", Na, Nb, D, kCdistMaxD);
+    if (scratch_bytes < sizeof(double) * (size_t)Na * (size_t)Nb)
+        return fail(NOMAD_ERR_WORKSPACE, "nomad_cdist_backward: scratch of %zu bytes, %zu needed", scratch_bytes,
+                    sizeof(double) * (size_t)Na * (size_t)Nb);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scope sc(c, s, NOMAD_K_PAIR, (3.0 + 3.0 * ((da != nullptr) + (db != nullptr))) * D * (double)Na * Nb);
+    double* W = static_cast<double*>(scratch);
+    const int ta = (Na + kPairTile - 1) / kPairTile, tb = (Nb + kPairTile - 1) / kPairTile, tk = (D + kPairTile - 1) / kPairTile;
+    hipLaunchKernelGGL(cdist_weights_kernel, dim3(tb, ta), dim3(256), 0, s, a, Na, b, Nb, D, gdist, gmean, W);
+    if (da) hipLaunchKernelGGL(cdist_reduce_kernel<true>, dim3(tk, ta), dim3(256), 0, s, a, Na, b, Nb, D, W, Nb, da);
+    if (db) hipLaunchKernelGGL(cdist_reduce_kernel<false>, dim3(tk, tb), dim3(256), 0, s, b, Nb, a, Na, D, W, Nb, db);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 size_t nomad_l1_scratch_bytes(void) { return sizeof(double) * (kL1Blocks + 8); }
 
 }  // extern "C"

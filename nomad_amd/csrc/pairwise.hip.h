@@ -27,15 +27,21 @@ constexpr int kPairTile = 64;
 // accumulator, e = a_k - b_k, acc = fma(e, e, acc), k ascending from 0 - so nomad_cdist at D = 256 returns the bits of
 // nomad_pairwise.  A last k-chunk shorter than 64 is staged with zeros on both sides: e = 0 and fma(0, 0, acc) = acc, they add
 // exactly nothing.  (D is a multiple of 4, so a staged float4 lies wholly inside or wholly outside the row.)
+//
+// pairwise_chain is that chain, once in the source: it leaves the thread's 4 x 4 sums of squares in acc and returns the 64 KB
+// LDS image, free to reuse behind a barrier.  What becomes of the sums is the kernel's epilogue: distances and per-tile row sums
+// in pairwise_tile_kernel (the forwards), the backward's weights in cdist_weights_kernel.
+struct PairThread {
+    int tid, tx, ty, r0, d0;
+};
 template <int kD>
-__global__ __launch_bounds__(256) void pairwise_tile_kernel(const float* __restrict__ deg, int Nd, const float* __restrict__ ref,
-                                                            int Nr, int Drt, double* __restrict__ dist, double* __restrict__ part) {
+__device__ __forceinline__ double* pairwise_chain(const float* __restrict__ deg, int Nd, const float* __restrict__ ref, int Nr, int Drt,
+                                                  double (&acc)[4][4], PairThread& t) {
     const int D = kD ? kD : Drt;
     __shared__ __attribute__((aligned(16))) double As[64][kPairTile];  // [k][deg row]
     __shared__ __attribute__((aligned(16))) double Bs[64][kPairTile];  // [k][ref]
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int r0 = blockIdx.x * kPairTile, d0 = blockIdx.y * kPairTile;
-    double acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -76,8 +82,18 @@ __global__ __launch_bounds__(256) void pairwise_tile_kernel(const float* __restr
                 }
         }
     }
+    t = PairThread{tid, tx, ty, r0, d0};
+    return &As[0][0];
+}
+
+template <int kD>
+__global__ __launch_bounds__(256) void pairwise_tile_kernel(const float* __restrict__ deg, int Nd, const float* __restrict__ ref,
+                                                            int Nr, int Drt, double* __restrict__ dist, double* __restrict__ part) {
+    double acc[4][4];
+    PairThread t;
+    double* rs = pairwise_chain<kD>(deg, Nd, ref, Nr, Drt, acc, t);  // [64 deg rows][16 tx] row sums of this tile, folded below in tx order
+    const int tid = t.tid, tx = t.tx, ty = t.ty, r0 = t.r0, d0 = t.d0;
     __syncthreads();
-    double* rs = &As[0][0];  // [64 deg rows][16 tx] row sums of this tile, folded below in tx order
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int d = d0 + 4 * ty + i;
@@ -120,6 +136,104 @@ __global__ __launch_bounds__(256) void pairwise_mean_kernel(const double* __rest
     double s = 0.0;
     for (int t = 0; t < ntiles; ++t) s += part[(long long)t * Nd + d];
     mean[d] = s / (double)Nr;
+}
+
+// ---- backward of the distance stage (nomad_cdist_backward) -----------------------------------------------------------------------
+// With c_ij = gdist_ij + gmean_i / Nb (float64, a NULL upstream counts as 0) the gradient of sum_ij c_ij d_ij is
+//   da_ik = sum_j W_ij (a_ik - b_jk),   db_jk = sum_i W_ij (b_jk - a_ik),   W_ij = c_ij / d_ij, 0 where d_ij == 0
+// (torch.cdist's convention: a reference equal to the row contributes nothing, never NaN / Inf).  Two launches: the weights - the
+// forward's chain with another epilogue, so d_ij has the forward's bits - into the caller's [Na][Nb] float64 scratch, then one
+// reduction per requested output.
+// grid (ceil(Nb / 64), ceil(Na / 64)) like pairwise_tile_kernel<0>; D: a positive multiple of 4; gdist [Na][Nb] or NULL, gmean [Na]
+// or NULL, W [Na][Nb] (out).
+__global__ __launch_bounds__(256) void cdist_weights_kernel(const float* __restrict__ a, int Na, const float* __restrict__ b, int Nb,
+                                                            int D, const double* __restrict__ gdist, const double* __restrict__ gmean,
+                                                            double* __restrict__ W) {
+    double acc[4][4];
+    PairThread t;
+    pairwise_chain<0>(a, Na, b, Nb, D, acc, t);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int d = t.d0 + 4 * t.ty + i;
+        if (d >= Na) continue;
+        const double gm = gmean ? gmean[d] / (double)Nb : 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = t.r0 + 4 * t.tx + j;
+            if (r >= Nb) continue;
+            const long long at = (long long)d * Nb + r;
+            const double c = (gdist ? gdist[at] : 0.0) + gm;
+            const double dv = sqrt(acc[i][j]);
+            W[at] = dv == 0.0 ? 0.0 : c / dv;
+        }
+    }
+}
+
+// out[r][k] = (float) sum_s fma(W(r, s), (double)x[r][k] - (double)y[s][k], acc), s ascending from 0, one float64 accumulator per
+// element, rounded to fp32 once at the store.  kRowMajorW: W(r, s) = W[r * ldw + s] (da: x = a, y = b, ldw = Nb), else
+// W(r, s) = W[s * ldw + r] (db: x = b, y = a, ldw = Nb).  grid (ceil(D / 64), ceil(R / 64)): a workgroup owns 64 rows x 64 columns
+// k, thread (ty, tx) the 4 x 4 elements rows 4ty.. x columns 4tx.. with its 16 x values in registers as doubles.  Per 64-deep
+// s-chunk W is staged as Ws[s][row] and y, converted once, as Ys[s][k]: the forward's 64 KB image and its fragment reads (two
+// ds_read_b128 per operand and s: 8 LDS doubles for 16 subtractions and 16 fused multiply-adds).  Staging: lane -> tid & 63 is
+// the LDS column (consecutive lanes write consecutive doubles of one LDS row: conflict-free), wave w takes the chunk's rows
+// 4w + 16q .. + 3.  Whatever lies outside W, y or the row width is staged as 0: fma(0, x - 0, acc) = acc, a short last chunk adds
+// exactly nothing - so an output row depends on its own x row, y and its own row of the upstreams only, whatever R is.
+template <bool kRowMajorW>
+__global__ __launch_bounds__(256) void cdist_reduce_kernel(const float* __restrict__ x, int R, const float* __restrict__ y, int S, int D,
+                                                           const double* __restrict__ W, int ldw, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double Ws[64][kPairTile];  // [s][row]
+    __shared__ __attribute__((aligned(16))) double Ys[64][kPairTile];  // [s][k]
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int k0 = blockIdx.x * kPairTile, r0 = blockIdx.y * kPairTile;
+    const int kcol = k0 + 4 * tx;  // D is a multiple of 4: the thread's four columns lie inside the row together or not at all
+    double xr[4][4], acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (kcol < D) v = *reinterpret_cast<const float4*>(x + (long long)min(r0 + 4 * ty + i, R - 1) * D + kcol);
+        xr[i][0] = (double)v.x; xr[i][1] = (double)v.y; xr[i][2] = (double)v.z; xr[i][3] = (double)v.w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+    }
+    const int scol = tid & 63, sq = (tid >> 6) * 4;
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int ss = sq + 16 * q + u, s = s0 + ss;
+                double w = 0.0, yv = 0.0;
+                if (s < S) {
+                    if (r0 + scol < R) w = kRowMajorW ? W[(long long)(r0 + scol) * ldw + s] : W[(long long)s * ldw + r0 + scol];
+                    if (k0 + scol < D) yv = (double)y[(long long)s * D + k0 + scol];
+                }
+                Ws[ss][scol] = w;
+                Ys[ss][scol] = yv;
+            }
+        __syncthreads();
+#pragma unroll 8
+        for (int s = 0; s < 64; ++s) {
+            double w[4], yv[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                w[i] = Ws[s][4 * ty + i];
+                yv[i] = Ys[s][4 * tx + i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = fma(w[i], xr[i][j] - yv[j], acc[i][j]);
+        }
+    }
+    if (kcol >= D) return;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = r0 + 4 * ty + i;
+        if (r < R)
+            *reinterpret_cast<float4*>(out + (long long)r * D + kcol) =
+                make_float4((float)acc[i][0], (float)acc[i][1], (float)acc[i][2], (float)acc[i][3]);
+    }
 }
 
 // paired_distance_kernel: out[i] = ||a_i - b_i||, the chain of pairwise_tile_kernel for the pair (i, i) - bit-identical to the

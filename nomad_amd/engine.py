@@ -95,6 +95,7 @@ class Engine:
         self._side_streams: Dict[int, "torch.cuda.Stream"] = {}
         self._l1_scratch: Optional[torch.Tensor] = None
         self._l1w_scratch: Optional[torch.Tensor] = None
+        self._cdist_scratch: Optional[torch.Tensor] = None   # cdist_backward's W, grown on demand
         # A library built WITH packed-FP32 instructions (NOMAD_PACKED_FP32=1 / the _pk A/B variants) must not run two of its
         # forwards concurrently: v_pk_fma_f32 can lose a product next to the other forward's bf16 128 x 128 GEMM (DESIGN.md
         # "The packed-FP32 hazard").  The shipped build reports 0 here; with the bit set every two-stream batch split is off.
@@ -395,6 +396,36 @@ class Engine:
                                         _ptr(dist), mean.data_ptr(), self._stream()),
                    "nomad_cdist")
         return dist, mean
+
+    def cdist_backward(self, a: torch.Tensor, b: torch.Tensor, g_dist: Optional[torch.Tensor] = None,
+                       g_mean: Optional[torch.Tensor] = None, want_a: bool = True, want_b: bool = False):
+        """The backward of ``cdist(a, b)``: g_dist (Na,Nb) and / or g_mean (Na,) float64, the upstreams of its matrix and of its row
+        means -> (da (Na,D) or None, db (Nb,D) or None), fp32.  Float64 sums in a fixed order, rounded once; a pair at distance 0
+        contributes nothing (``nomad_cdist_backward``)."""
+        self._check_dev(a, "a")
+        self._check_dev(b, "b")
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError("a and b must be matrices with rows of one width")
+        Na, Nb, D = a.shape[0], b.shape[0], a.shape[1]
+        if g_dist is None and g_mean is None:
+            raise ValueError("cdist_backward needs g_dist, g_mean or both")
+        if not (want_a or want_b):
+            raise ValueError("cdist_backward needs want_a, want_b or both")
+        for g, shape, name in ((g_dist, (Na, Nb), "g_dist"), (g_mean, (Na,), "g_mean")):
+            if g is not None and not (g.is_cuda and g.dtype == torch.float64 and g.is_contiguous() and tuple(g.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {self.device}")
+        n = C.c_size_t()
+        _lib.check(self.lib.nomad_cdist_backward_scratch_bytes(Na, Nb, C.byref(n)), "nomad_cdist_backward_scratch_bytes")
+        if self._cdist_scratch is None or self._cdist_scratch.numel() < n.value:
+            self._cdist_scratch = None
+            self._cdist_scratch = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+        self._cdist_scratch.record_stream(torch.cuda.current_stream(self.device))
+        da = torch.empty(Na, D, dtype=torch.float32, device=self.device) if want_a else None
+        db = torch.empty(Nb, D, dtype=torch.float32, device=self.device) if want_b else None
+        _lib.check(self.lib.nomad_cdist_backward(self.ctx, a.data_ptr(), Na, b.data_ptr(), Nb, D, _ptr(g_dist), _ptr(g_mean), _ptr(da),
+                                                 _ptr(db), self._cdist_scratch.data_ptr(), self._cdist_scratch.numel(),
+                                                 self._stream()), "nomad_cdist_backward")
+        return da, db
 
     def paired_distance(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         """a, b (N,D) fp32 on the GPU -> (N,) float64, out[i] = ||a_i - b_i||: the diagonal of ``cdist(a, b)`` bit for bit,

@@ -340,6 +340,95 @@ class _NomadLossFn(torch.autograd.Function):
         return dwav, dcln, None, None, None
 
 
+def check_references(references) -> None:
+    """The ``references`` argument of ``Nomad.score``: a 2-D floating-point tensor of at least one 256-dimensional embedding, as
+    ``nomad.model(wav)`` or ``get_embeddings`` make them.  Pure: looks at type, dtype and shape only."""
+    if not torch.is_tensor(references):
+        raise TypeError(f"references must be a tensor of embeddings, got {type(references).__name__}")
+    if not references.is_floating_point():
+        raise TypeError(f"references must be a floating-point tensor, got {references.dtype}")
+    if references.dim() != 2 or references.shape[1] != EMB_DIM:
+        raise ValueError(f"references must be (Nr, {EMB_DIM}) embeddings, got {tuple(references.shape)}")
+    if references.shape[0] < 1:
+        raise ValueError("references holds no embedding: the score is a mean over at least one reference")
+
+
+class _CdistFn(torch.autograd.Function):
+    """``Engine.cdist`` with a backward: (dist, mean) -> d / d a and d / d b through ``Engine.cdist_backward``."""
+
+    @staticmethod
+    def forward(ctx, a, b, engine):
+        ctx.set_materialize_grads(False)
+        a, b = a.detach(), b.detach()
+        dist, mean = engine.cdist(a, b)
+        ctx.engine = engine
+        ctx.save_for_backward(a, b)
+        return dist, mean
+
+    @staticmethod
+    def backward(ctx, g_dist, g_mean):
+        a, b = ctx.saved_tensors
+        want_a, want_b = ctx.needs_input_grad[:2]
+        if (g_dist is None and g_mean is None) or not (want_a or want_b):
+            return None, None, None
+        up = [None if g is None else g.to(a.device, torch.float64).contiguous() for g in (g_dist, g_mean)]
+        da, db = ctx.engine.cdist_backward(a, b, up[0], up[1], want_a=want_a, want_b=want_b)
+        return da, db, None
+
+
+def cdist(engine: Engine, a: torch.Tensor, b: torch.Tensor):
+    """a (Na,D), b (Nb,D) contiguous fp32 on the GPU -> (dist (Na,Nb), mean (Na,)) float64 with the values of ``Engine.cdist``,
+    differentiable in ``a`` and ``b``: float64 sums in a fixed order, rounded to fp32 once; a pair at distance 0 contributes
+    nothing to either gradient (``torch.cdist``'s convention)."""
+    return _CdistFn.apply(a, b, engine)
+
+
+class _ScoreFn(torch.autograd.Function):
+    """score[b] = mean_j ||emb(estimate_b) - references_j|| with the checkpoint's head; backward = d / d estimate through
+    ``cdist_backward`` and ``embed_backward[_ragged]`` (layer gradients NULL) and, when asked for, d / d references."""
+
+    @staticmethod
+    def forward(ctx, estimate, references, nomad, lens):
+        eng = nomad.engine
+        est = estimate.detach().to(eng.device, torch.float32).contiguous()
+        est = est.squeeze(1) if est.dim() == 3 else est
+        refs = references.detach().to(eng.device, torch.float32).contiguous()
+        ctx.nomad, ctx.lens = nomad, lens
+        ctx.meta = (estimate.shape, references.device, references.dtype)
+        if not estimate.requires_grad:   # only the references are differentiated: the scoring forward will do
+            emb, layers, saved = nomad._score_embed(est, lens), None, None
+        elif lens is None:
+            emb, layers, saved = eng.embed_train(est)
+        else:
+            emb, layers, saved, (est, _) = eng.embed_train_ragged(est, lens)
+        _, mean = eng.pairwise(emb, refs, want_matrix=False)
+        ctx.save_for_backward(est, refs, emb, layers, saved)
+        return mean
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        est, refs, emb, layers, saved = ctx.saved_tensors
+        eng = ctx.nomad.engine
+        shape, ref_device, ref_dtype = ctx.meta
+        want_a = ctx.needs_input_grad[0] and saved is not None
+        want_b = ctx.needs_input_grad[1]
+        if not (want_a or want_b):
+            return None, None, None, None
+        g = grad_out.to(eng.device, torch.float64).contiguous()
+        demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
+        dwav = None
+        if want_a:
+            Nomad._need_whole_encoder(eng)
+            if ctx.lens is None:
+                dwav = eng.embed_backward(est, layers, saved, None, demb)
+            else:
+                dwav = eng.embed_backward_ragged((est, ctx.lens), layers, saved, None, demb)
+            dwav = dwav.reshape(shape)
+        if dref is not None:
+            dref = dref.to(ref_device, ref_dtype)
+        return dwav, dref, None, None
+
+
 class GraphedLoss:
     """``nomad.forward`` + its backward to ``estimate`` for ONE input shape, captured once as a HIP graph and replayed per step.
 
@@ -760,7 +849,9 @@ class Nomad:
         return df_avg_nomad, df_dm
 
     def forward(self, estimate, clean, lengths=None, *, layer_weights=None, reduction="mean"):
-        """NOMAD loss (nomad.py:142-146), differentiable w.r.t. ``estimate``.
+        """NOMAD loss (nomad.py:142-146), differentiable w.r.t. ``estimate`` - and w.r.t. ``clean`` when it requires a gradient:
+        that branch then keeps its activations too (the fp32 ``embed_train`` on the caller's stream: no side-stream overlap, no
+        split-bf16 forward), about the cost of a second ``estimate`` branch.
 
         Which terms count: ``self.nomad_loss.L`` as in the reference (``for i in range(self.L)``, nomad.py:276) - the first L of the
         12 transformer layers + the embedding, L in 1 .. 13 - or ``layer_weights``, 13 numbers >= 0 (the layers' weights, then the
@@ -794,6 +885,55 @@ class Nomad:
         if layer_weights is None and self.nomad_loss.L == 13 and reduction == "mean":
             return _NomadLossFn.apply(estimate, clean, self, lens, None)
         return _NomadLossFn.apply(estimate, clean, self, lens, (weights, depth, reduction))
+
+    @staticmethod
+    def _need_whole_encoder(eng: Engine):
+        depth = eng.encoder_depth
+        if depth != 12:
+            raise RuntimeError(f"Nomad.score needs the whole encoder: the embedding is computed from the last layer and encoder_depth "
+                               f"is {depth} (a cut encoder is a property of forward()'s layer selections)")
+
+    def _score_embed(self, wav: torch.Tensor, lens) -> torch.Tensor:
+        """The scoring forward of ``precision`` over a (B,N) device batch -> (B,256): what ``self.model`` / ``get_embeddings*`` run."""
+        eng = self.engine
+        if lens is not None:
+            prec = self.precision
+            if prec == "bf16x3" and sum(lens) < BF16X3_MIN_SAMPLES:
+                prec = "fp32"   # as in the file pipeline: fp32 buffers, products by Engine.gemm_precision
+            return eng.embed_ragged([wav[i, :n] for i, n in enumerate(lens)], precision=prec)
+        if self.precision == "bf16":
+            return eng.embed_bf16(wav)
+        return eng.embed_bf16x3(wav) if _takes_bf16x3(self.precision, wav) else eng.embed(wav)
+
+    def score(self, estimate, references, lengths=None, reduction="none"):
+        """The NOMAD score as a differentiable quantity: ``score[b] = mean_j ||emb(estimate_b) - references_j||`` in float64, the
+        number ``predict`` reports for a file - no matching clean signal is needed, only a bank of reference embeddings.
+
+        estimate (B,1,N) or (B,N); references (Nr,256) embeddings as ``self.model(wav)`` / ``get_embeddings`` make them (the
+        checkpoint's ``embedding_layer``, not ``lossnet_layers``' head); lengths: the clips' exact lengths as in ``forward``.
+        -> (B,) float64, or with reduction="mean" their mean (plain torch on that tensor).
+
+        Under ``torch.no_grad()``, or when nothing requires a gradient, the embeddings come from the scoring forward of
+        ``precision`` and the distances from ``Engine.pairwise``: at fp32 with ``lengths`` the bits ``predict`` gives the file.  With
+        a gradient the forward is ``embed_train[_ragged]`` (fp32 buffers, products by ``Engine.gemm_precision``), and the backward
+        runs ``cdist_backward`` - float64, a reference equal to the embedding contributes nothing - then the head, the
+        normalisation and the backbone down to the waveform; the gradient carries ``feature_grad_mult`` exactly as
+        ``forward()``'s does and is zero behind every length.  ``references`` gets a gradient too when it requires one."""
+        check_reduction(reduction)
+        check_references(references)
+        if not torch.is_tensor(estimate) or estimate.dim() not in (2, 3) or (estimate.dim() == 3 and estimate.shape[1] != 1):
+            raise ValueError(f"estimate must be (B,1,N) or (B,N), got {tuple(getattr(estimate, 'shape', ()))}")
+        lens = check_lengths(estimate, lengths) if lengths is not None else None
+        self._need_whole_encoder(self.engine)
+        if torch.is_grad_enabled() and (estimate.requires_grad or references.requires_grad):
+            scores = _ScoreFn.apply(estimate, references, self, lens)
+        else:
+            eng = self.engine
+            est = estimate.detach().to(eng.device, torch.float32).contiguous()
+            est = est.squeeze(1) if est.dim() == 3 else est
+            refs = references.detach().to(eng.device, torch.float32).contiguous()
+            scores = eng.pairwise(self._score_embed(est, lens), refs, want_matrix=False)[1]
+        return scores.mean() if reduction == "mean" else scores
 
     def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor, lengths=None) -> "GraphedLoss":
         """``forward`` + backward for inputs of this shape, captured as one HIP graph (see ``GraphedLoss``): for training loops with
