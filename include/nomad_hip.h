@@ -211,6 +211,30 @@ int nomad_embed_features_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int
                                 nomad_stream_t stream);
 
 /*
+ * Embeddings over windows of frames, from ONE forward: the head (time mean, ReLU, Linear(768, 256), L2 normalisation) applied
+ * to windows of `win` encoder frames every `hop` frames instead of to the whole clip (one frame = 320 samples = 20 ms).
+ * nomad_num_windows(T, win, hop): the windows of a clip of T >= 1 frames, win >= 1, hop >= 1: 1 if T <= win (one window over the
+ * whole clip), else (T - win) / hop + 1; <= 0 for T, win or hop < 1.  Window k covers frames [k hop, k hop + min(win, T)); the
+ * frames behind the last full window belong to no window (as with torch.Tensor.unfold).  Host arithmetic, no context.
+ *   emb_dev  [sum_c W(T_c)][256] fp32 (out): clip 0's windows in order, then clip 1's, ... (B W(T) rows for equal lengths)
+ * Each window's row is computed in the arithmetic of the plain head on the window's rows as if they were a clip of their own:
+ * a window that covers a whole clip has the bits of that clip's embedding from nomad_embed* of the same precision, and a row
+ * depends on its window's frames only (batch-invariant, deterministic, no atomics).  The encoder saw the whole clip: a window
+ * is NOT the embedding of the excerpt alone.
+ * `precision`, preconditions, workspace size and statuses are those of nomad_embed_features*.  The head override (both pointers
+ * or neither) is for NOMAD_PRECISION_F32 only; with another precision, with win < 1 or hop < 1, or with a cut encoder
+ * (nomad_set_encoder_depth) the call is NOMAD_ERR_INVALID.  Asynchronous, no allocation; argument errors return before anything
+ * is queued.
+ */
+int nomad_num_windows(int T, int win, int hop);
+int nomad_embed_windows(nomad_ctx* ctx, const float* wav_dev, int B, int n_samples, int precision, int win, int hop,
+                        const float* head_w_dev, const float* head_b_dev, float* emb_dev,
+                        void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
+int nomad_embed_windows_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host,
+                               int precision, int win, int hop, const float* head_w_dev, const float* head_b_dev,
+                               float* emb_dev, void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
+
+/*
  * NomadLoss: sum_{i<12} mean|a_layers[i]-b_layers[i]| + mean|a_emb-b_emb|.
  *   a_layers_dev/b_layers_dev [12][B][T][768]; a_emb_dev/b_emb_dev [B][256]; loss_dev [1] fp32 (out)
  *   scratch_dev: >= nomad_l1_scratch_bytes() bytes of device scratch.

@@ -21,7 +21,12 @@ def main():
     ap.add_argument("--precision", type=str, default="fp32", choices=("fp32", "bf16x3", "bf16"),
                     help="bf16x3: split-operand bf16 MFMA, scores within ~1e-6 of fp32 at over twice the speed; "
                          "bf16: fastest, for long recordings (scores within ~5e-4 of fp32)")
+    ap.add_argument("--window", type=float, default=None, metavar="S",
+                    help="scores over time: one NOMAD score per window of S seconds of every test file (predict_segments)")
+    ap.add_argument("--hop", type=float, default=None, metavar="S", help="seconds between window starts (default: half the window)")
     a = ap.parse_args()
+    if a.hop is not None and a.window is None:
+        ap.error("--hop goes with --window")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = 0
     if world > 1 or "LOCAL_RANK" in os.environ:      # started by torch.distributed.run: one process per GPU
@@ -32,7 +37,14 @@ def main():
         a.device = f"cuda:{local_rank}"
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
         rank = dist.get_rank()
-    nomad_avg, _ = Nomad(device=a.device, weights=a.weights, precision=a.precision).predict(a.mode, a.nmr, a.deg, a.results_path)
+    nomad = Nomad(device=a.device, weights=a.weights, precision=a.precision)
+    if a.window is not None:
+        segments, nomad_avg = nomad.predict_segments(a.mode, a.nmr, a.deg, a.window, a.window / 2 if a.hop is None else a.hop,
+                                                     a.results_path)
+        print("Nomad scores over time, printing the first 5 windows")
+        print(segments.head())
+    else:
+        nomad_avg, _ = nomad.predict(a.mode, a.nmr, a.deg, a.results_path)
     if rank == 0:
         print("Nomad average scores, printing top 5 test files")
         print(nomad_avg.head())

@@ -53,6 +53,11 @@ SIGNATURES = {
     "nomad_embed_features": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "nomad_embed_features_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp,
                                               C.c_size_t, _fp]),
+    "nomad_num_windows": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "nomad_embed_windows": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp,
+                                      C.c_size_t, _fp]),
+    "nomad_embed_windows_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                             _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
     "nomad_wav_probe": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(WavInfo), C.POINTER(C.c_int), C.c_int]),
     "nomad_wav_frames_at": (C.c_int, [C.POINTER(WavInfo), C.c_int, C.POINTER(C.c_longlong)]),
     "nomad_wav_read_rows": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(WavInfo), C.c_int, C.POINTER(C.c_int), _fp, C.c_longlong,

@@ -760,9 +760,32 @@ int run_layernorm(nomad_ctx* c, const float* in, const float* g, const float* b,
 // mean/ReLU/Linear/normalise head in two stages (rowops.hip.h).  T: frames per clip (the longest clip's with tpref);
 // pool: scratch of at least (M / 64 + B) * 768 floats (M = total frames) - every caller passes its FFN hidden buffer.
 // features (nomad_embed_features*): `emb` is [B][768] and takes the time means themselves (head_mean_kernel) - no embedding.
+// windows (nomad_embed_windows*): `emb` is [windows of the batch][256], one row per window of mode.win frames every mode.hop
+// (head_windows_kernel, one launch, no scratch); mode.n_windows is their number.
+struct HeadMode {
+    bool features = false;
+    int win = 0, hop = 0;
+    long long n_windows = 0;
+    HeadMode() = default;
+    HeadMode(bool f) : features(f) {}
+    static HeadMode windows(int win, int hop, long long n) {
+        HeadMode m;
+        m.win = win, m.hop = hop, m.n_windows = n;
+        return m;
+    }
+};
+
 template <typename TIn>
 int run_head(nomad_ctx* c, const TIn* x, int B, int T, const float* w, const float* b, float* emb, const int* tpref,
-             float* pool, hipStream_t s, bool features = false) {
+             float* pool, hipStream_t s, HeadMode mode = {}) {
+    const bool features = mode.features;
+    if (mode.win) {
+        Scope sc(c, s, NOMAD_K_ROW, 2.0 * (double)mode.n_windows * 768 * 256);
+        hipLaunchKernelGGL(head_windows_kernel<TIn>, dim3(head_num_windows(T, mode.win, mode.hop), B), dim3(1024), 0, s, x, tpref ? 0 : T,
+                           mode.win, mode.hop, w, b, emb, tpref);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     Scope sc(c, s, NOMAD_K_ROW, features ? 0.0 : 2.0 * B * 768 * 256);
     hipLaunchKernelGGL(head_pool_kernel<TIn>, dim3((T + kHeadChunk - 1) / kHeadChunk, B), dim3(256), 0, s, x, tpref ? 0 : T, pool, tpref);
     if (features) hipLaunchKernelGGL(head_mean_kernel, dim3(B), dim3(256), 0, s, pool, tpref ? 0 : T, emb, tpref);
@@ -1093,12 +1116,12 @@ struct F32Bufs {
 // equal-length one, packed; it never splits K, so that a clip's values never depend on the batch it is in.
 static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const F32Bufs& bf, const float* head_w,
                        const float* head_b, float* emb, float* layers_out, float* splitk_block, size_t splitk_floats, hipStream_t s,
-                       const Saved* sv, bool features = false) {
+                       const Saved* sv, HeadMode mode = {}) {
     if (g.ragged() && splitk_block) return fail(NOMAD_ERR_INVALID, "fp32 forward: split-K needs an equal-length batch");
     const int B = g.B, T = g.T, M = (int)g.rows[6];
     // nomad_set_encoder_depth: layers 0 .. depth - 1, then stop - no head, rows [depth, 12) of layers_out and emb stay unwritten
     const int depth = c->encoder_depth;
-    if (depth < NOMAD_NUM_LAYERS && (!layers_out || features)) return refuse_cut(c, "fp32 forward");
+    if (depth < NOMAD_NUM_LAYERS && (!layers_out || mode.features || mode.win)) return refuse_cut(c, "fp32 forward");
     // the loss forward of Nomad.forward() (saving activations, not fine-tuning): small-M GEMMs may split K.  Round 4: so may the
     // other branch of that loss - a forward that returns the 12 layer outputs (LossNetLayers: `clean`, or `estimate` under
     // no_grad) on fewer than 4096 frames.  The split is a function of the GEMM shape only (fixed slices, ordered fold): the
@@ -1323,14 +1346,14 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
     // (a cut encoder has no embedding: every layer's LayerNorm - fused into a split-K epilogue or not - and its copy into layers_out
     // are complete when run_layer returns, so there is nothing else to flush)
     if (depth < NOMAD_NUM_LAYERS) return 0;
-    return run_head<float>(c, x, B, g.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb, g.pref[6], bf.h, s, features);
+    return run_head<float>(c, x, B, g.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb, g.pref[6], bf.h, s, mode);
 }
 
 // nomad_embed / nomad_embed_train: an equal-length batch in the Layout of make_layout.  who: the entry point the errors name;
 // features: nomad_embed_features (`emb` is [B][768], see run_head).
 static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
                         float* emb, float* layers_out, void* workspace, size_t workspace_bytes, nomad_stream_t stream,
-                        const Saved* sv, const char* who = "nomad_embed", bool features = false) {
+                        const Saved* sv, const char* who = "nomad_embed", HeadMode mode = {}) {
     Shapes sh;
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d, n_samples=%d)", who, B, n_samples);
@@ -1344,13 +1367,13 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
     if (c->tune.f32_posconv_wino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws);
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(lay.conv[i]);
     return forward_run(c, wav, geom_uniform(sh), bf, head_w, head_b, emb, layers_out, lay.splitk != 0 ? F(lay.splitk) : nullptr,
-                       layers_splitk_floats(sh), static_cast<hipStream_t>(stream), sv, features);
+                       layers_splitk_floats(sh), static_cast<hipStream_t>(stream), sv, mode);
 }
 
 // layers_out / saved (nomad_embed_train_ragged): the packed layer outputs and, with a saved block, the training-mode forward.
 static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, const float* head_w,
                           const float* head_b, float* emb, void* workspace, size_t workspace_bytes,
-                          nomad_stream_t stream, const char* who = "nomad_embed_ragged", bool features = false,
+                          nomad_stream_t stream, const char* who = "nomad_embed_ragged", HeadMode mode = {},
                           float* layers_out = nullptr, void* saved = nullptr, size_t saved_bytes = 0) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     RaggedBatch r;
@@ -1372,7 +1395,7 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
     if (c->tune.f32_posconv_wino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws), bf.pwmeta = reinterpret_cast<int*>(ws + lay.pwmeta);
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(i % 2 ? lay.convb : lay.conva);   // conv6 lands in conva, LN(512) writes to convb
-    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, layers_out, nullptr, 0, s, saved ? &sv : nullptr, features);
+    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, layers_out, nullptr, 0, s, saved ? &sv : nullptr, mode);
 }
 
 // One backward GEMM: C[M][N] = A[M][K] * Wt[N][K]^T (Wt = transposed forward weight), optional GELU' and residual.
@@ -1512,7 +1535,7 @@ static void launch_ln_bf16(const bf16_t* in, const float* g, const float* b, bf1
 // ragged batch (mixed-length long-form files, config C5 through predict: every clip sees the arithmetic of its own
 // single-clip call).  The diag library's checksum / snapshot stages are recorded on equal-length calls only.
 static int forward_bf16_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const ActLayout& lay, float* emb, char* ws,
-                            hipStream_t s, bool features = false) {
+                            hipStream_t s, HeadMode mode = {}) {
     auto H = [&](size_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
     auto asf = [](const bf16_t* p_) { return reinterpret_cast<const float*>(p_); };  // GemmParams carries typeless pointers
     auto asfm = [](bf16_t* p_) { return reinterpret_cast<float*>(p_); };
@@ -1615,13 +1638,13 @@ static int forward_bf16_run(nomad_ctx* c, const float* wav, const BatchGeom& g, 
         }
         CK(x, B, clip768);
     }
-    rc = run_head<bf16_t>(c, x, B, g.max_t, c->emb_w, c->emb_b, emb, g.pref[6], reinterpret_cast<float*>(hb), s, features);
-    CK(emb, B, sizeof(float) * (features ? 768 : 256));
+    rc = run_head<bf16_t>(c, x, B, g.max_t, c->emb_w, c->emb_b, emb, g.pref[6], reinterpret_cast<float*>(hb), s, mode);
+    CK(emb, B, sizeof(float) * (mode.features ? 768 : 256));
     return rc;
 }
 
 static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, float* emb, void* workspace,
-                        size_t workspace_bytes, nomad_stream_t stream, const char* who = "nomad_embed_bf16", bool features = false) {
+                        size_t workspace_bytes, nomad_stream_t stream, const char* who = "nomad_embed_bf16", HeadMode mode = {}) {
     Shapes sh;
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d, n_samples=%d)", who, B, n_samples);
@@ -1630,19 +1653,19 @@ static int forward_bf16(nomad_ctx* c, const float* wav, int B, int n_samples, fl
     const ActLayout lay = make_act_layout(g, sizeof(bf16_t), 0);
     if (workspace_bytes < lay.total)
         return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, lay.total);
-    return forward_bf16_run(c, wav, g, lay, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), features);
+    return forward_bf16_run(c, wav, g, lay, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), mode);
 }
 
 static int forward_ragged_bf16(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, float* emb,
                                void* workspace, size_t workspace_bytes, nomad_stream_t stream,
-                               const char* who = "nomad_embed_ragged_bf16", bool features = false) {
+                               const char* who = "nomad_embed_ragged_bf16", HeadMode mode = {}) {
     if (c && !c->bf16_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_bf16 first", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
     RaggedBatch r;
     if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, sizeof(bf16_t), 0,
                                  &r, workspace, workspace_bytes, s))
         return rc;
-    return forward_bf16_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, features);
+    return forward_bf16_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, mode);
 }
 
 
@@ -1697,7 +1720,7 @@ constexpr int kX3Split = 27, kX3F32 = 28;
 
 static int forward_x3_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const ActLayout& lay, float* emb,
                           char* ws, hipStream_t s, const float* head_w = nullptr, const float* head_b = nullptr,
-                          float* layers_out = nullptr, bool features = false) {
+                          float* layers_out = nullptr, HeadMode mode = {}) {
     auto S = [&](size_t off) { return reinterpret_cast<bf16s_t*>(ws + off); };
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const int B = g.B, M = (int)g.rows[6];
@@ -1824,12 +1847,12 @@ static int forward_x3_run(nomad_ctx* c, const float* wav, const BatchGeom& g, co
         else if ((rc = run_layernorm(c, y, d.ln2_w, d.ln2_b, reinterpret_cast<float*>(x), lo, M, 768, s))) return rc;
     }
     return run_head<float>(c, reinterpret_cast<const float*>(x), B, g.max_t, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, emb,
-                           tpref, reinterpret_cast<float*>(hb), s, features);
+                           tpref, reinterpret_cast<float*>(hb), s, mode);
 }
 
 static int forward_x3(nomad_ctx* c, const float* wav, int B, int n_samples, float* emb, void* workspace,
                       size_t workspace_bytes, nomad_stream_t stream, const float* head_w = nullptr, const float* head_b = nullptr,
-                      float* layers_out = nullptr, const char* who = "nomad_embed_bf16x3", bool features = false) {
+                      float* layers_out = nullptr, const char* who = "nomad_embed_bf16x3", HeadMode mode = {}) {
     Shapes sh;
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh) || (!head_w != !head_b))
         return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d, n_samples=%d)", who, B, n_samples);
@@ -1839,19 +1862,19 @@ static int forward_x3(nomad_ctx* c, const float* wav, int B, int n_samples, floa
     if (workspace_bytes < lay.total)
         return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, lay.total);
     return forward_x3_run(c, wav, g, lay, emb, static_cast<char*>(workspace), static_cast<hipStream_t>(stream), head_w, head_b,
-                          layers_out, features);
+                          layers_out, mode);
 }
 
 static int forward_ragged_x3(nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, float* emb,
                              void* workspace, size_t workspace_bytes, nomad_stream_t stream,
-                             const char* who = "nomad_embed_ragged_bf16x3", bool features = false) {
+                             const char* who = "nomad_embed_ragged_bf16x3", HeadMode mode = {}) {
     if (c && !c->x3_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_bf16x3 first", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
     RaggedBatch r;
     if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, 4, kXpadSlack,
                                  &r, workspace, workspace_bytes, s))
         return rc;
-    return forward_x3_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, nullptr, nullptr, nullptr, features);
+    return forward_x3_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, nullptr, nullptr, nullptr, mode);
 }
 
 extern "C" {
@@ -2330,6 +2353,54 @@ int nomad_embed_features_ragged(nomad_ctx* c, const float* wav, int B, int strid
             return forward_ragged_x3(c, wav, B, stride, lengths_host, feat, workspace, workspace_bytes, stream, who, true);
         case NOMAD_PRECISION_BF16:
             return forward_ragged_bf16(c, wav, B, stride, lengths_host, feat, workspace, workspace_bytes, stream, who, true);
+    }
+    return fail(NOMAD_ERR_INVALID, "%s: unknown precision %d", who, precision);
+}
+
+// Embeddings over windows of frames (scores over time): the forward of `precision` with head_windows_kernel as its last stage.
+// Every argument check of that forward holds; the windows add theirs ahead of it, so nothing is queued on an error.
+static int windows_args(const char* who, const nomad_ctx* c, int precision, int win, int hop, const float* head_w, const float* head_b) {
+    if (int rc = refuse_cut(c, who)) return rc;
+    if (win < 1 || hop < 1) return fail(NOMAD_ERR_INVALID, "%s: bad window (win=%d, hop=%d frames)", who, win, hop);
+    if (!head_w != !head_b) return fail(NOMAD_ERR_INVALID, "%s: head_w_dev and head_b_dev must both be set or both be NULL", who);
+    if (head_w && precision != NOMAD_PRECISION_F32)
+        return fail(NOMAD_ERR_INVALID, "%s: a head override needs NOMAD_PRECISION_F32 (precision %d)", who, precision);
+    return 0;
+}
+
+int nomad_num_windows(int T, int win, int hop) { return head_num_windows(T, win, hop); }
+
+int nomad_embed_windows(nomad_ctx* c, const float* wav, int B, int n_samples, int precision, int win, int hop, const float* head_w,
+                        const float* head_b, float* emb, void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_windows";
+    if (int rc = windows_args(who, c, precision, win, hop, head_w, head_b)) return rc;
+    const HeadMode mode = HeadMode::windows(win, hop, (long long)(B > 0 ? B : 0) * head_num_windows(nomad_num_frames(n_samples), win, hop));
+    switch (precision) {
+        case NOMAD_PRECISION_F32:
+            return forward_impl(c, wav, B, n_samples, head_w, head_b, emb, nullptr, workspace, workspace_bytes, stream, nullptr, who, mode);
+        case NOMAD_PRECISION_BF16X3:
+            return forward_x3(c, wav, B, n_samples, emb, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, who, mode);
+        case NOMAD_PRECISION_BF16:
+            return forward_bf16(c, wav, B, n_samples, emb, workspace, workspace_bytes, stream, who, mode);
+    }
+    return fail(NOMAD_ERR_INVALID, "%s: unknown precision %d", who, precision);
+}
+
+int nomad_embed_windows_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, int precision, int win,
+                               int hop, const float* head_w, const float* head_b, float* emb, void* workspace,
+                               size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_windows_ragged";
+    if (int rc = windows_args(who, c, precision, win, hop, head_w, head_b)) return rc;
+    long long n = 0;   // the kernel forms each clip's first output row from the frame prefix sums the forward uploads anyway
+    for (int i = 0; lengths_host && i < B; ++i) n += head_num_windows(nomad_num_frames(lengths_host[i]), win, hop);
+    const HeadMode mode = HeadMode::windows(win, hop, n);
+    switch (precision) {
+        case NOMAD_PRECISION_F32:
+            return forward_ragged(c, wav, B, stride, lengths_host, head_w, head_b, emb, workspace, workspace_bytes, stream, who, mode);
+        case NOMAD_PRECISION_BF16X3:
+            return forward_ragged_x3(c, wav, B, stride, lengths_host, emb, workspace, workspace_bytes, stream, who, mode);
+        case NOMAD_PRECISION_BF16:
+            return forward_ragged_bf16(c, wav, B, stride, lengths_host, emb, workspace, workspace_bytes, stream, who, mode);
     }
     return fail(NOMAD_ERR_INVALID, "%s: unknown precision %d", who, precision);
 }

@@ -256,6 +256,133 @@ __global__ __launch_bounds__(256) void head_mean_kernel(const float* __restrict_
     o[tid + 512] = s2 * inv;
 }
 
+// Windows of frames (nomad_embed_windows*): W = 1 for a clip of T <= win frames, else (T - win) / hop + 1; window k covers
+// frames [k hop, k hop + min(win, T)).  Frames behind the last full window belong to no window (torch.Tensor.unfold).
+__host__ __device__ inline int head_num_windows(int T, int win, int hop) {
+    if (T < 1 || win < 1 || hop < 1) return 0;
+    return T <= win ? 1 : (T - win) / hop + 1;
+}
+
+// The head over windows of frames, both stages in one workgroup: window k of clip b -> one row of emb, in the arithmetic
+// of head_pool_kernel + head_kernel applied to the window's rows as if they were a clip of their own, so a window that
+// covers a whole clip has the bits of that clip's embedding, and a window's 256 values are a function of its own rows only.
+// grid: (windows of the longest clip, B) blocks of 1024 threads; a block past its clip's last window returns.
+//   time sum: chunks of kHeadChunk frames counted from the WINDOW's first frame; waves 0..3 take frames w, w + 4, ... of
+//     a chunk (lane l the columns 4l + 256q), are folded in the order 0..3 by wave 0, which adds the chunk sums in chunk
+//     order to a running sum in its registers - no scratch, no atomics; overlapping windows re-read their rows from L2.
+//   then sum * (1.0f / n), ReLU, and head_kernel's Linear and norm on all 16 waves, operation for operation.
+// Output rows: clip 0's windows, then clip 1's, ...: row wbase(b) + k with wbase(b) = b W for an equal-length batch and
+// the sum of the earlier clips' window counts, formed here from the frame prefix sums, for a ragged one.
+template <typename TIn = float>
+__global__ __launch_bounds__(1024) void head_windows_kernel(const TIn* __restrict__ x, int T, int win, int hop,
+                                                            const float* __restrict__ w, const float* __restrict__ bias,
+                                                            float* __restrict__ emb, const int* __restrict__ tpref = nullptr) {
+    __shared__ float4 part[4][3][64];
+    __shared__ float pooled[768];
+    __shared__ float e[256];
+    __shared__ float wsum[4];
+    __shared__ int wcnt[16];
+    const int b = blockIdx.y, k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long row0 = (long long)b * T;
+    if (tpref) {
+        row0 = tpref[b];
+        T = tpref[b + 1] - tpref[b];
+    }
+    if (k >= head_num_windows(T, win, hop)) return;   // the same for every thread of the block
+    long long orow = (long long)b * head_num_windows(T, win, hop) + k;
+    if (tpref) {   // windows of clips 0 .. b - 1 (integers: any order gives the same sum)
+        int cnt = 0;
+        for (int c = tid; c < b; c += 1024) cnt += head_num_windows(tpref[c + 1] - tpref[c], win, hop);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+        if (lane == 0) wcnt[wave] = cnt;
+        __syncthreads();
+        int base = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) base += wcnt[i];
+        orow = (long long)base + k;
+    }
+    const int n = min(win, T);
+    const TIn* xw = x + (row0 + (long long)k * hop) * 768;   // rows [k hop, k hop + n) of the clip: k hop + n <= T
+    float4 run[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) run[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int t0 = 0; t0 < n; t0 += kHeadChunk) {   // chunks in order
+        if (wave < 4) {
+            const int t_end = min(n, t0 + kHeadChunk);
+            float4 acc[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int t = t0 + wave; t < t_end; t += 4) {
+                const TIn* r = xw + (long long)t * 768 + 4 * lane;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const float4 v = load4<TIn>(r + 256 * q);
+                    acc[q].x += v.x; acc[q].y += v.y; acc[q].z += v.z; acc[q].w += v.w;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) part[wave][q][lane] = acc[q];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                float4 a = part[0][q][lane];
+#pragma unroll
+                for (int u = 1; u < 4; ++u) {
+                    const float4 o = part[u][q][lane];
+                    a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+                }
+                run[q].x += a.x; run[q].y += a.y; run[q].z += a.z; run[q].w += a.w;
+            }
+        }
+        __syncthreads();   // part is rewritten by the next chunk
+    }
+    if (wave == 0) {
+        const float inv = 1.0f / (float)n;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            float* p = pooled + 256 * q + 4 * lane;
+            p[0] = fmaxf(run[q].x * inv, 0.f);
+            p[1] = fmaxf(run[q].y * inv, 0.f);
+            p[2] = fmaxf(run[q].z * inv, 0.f);
+            p[3] = fmaxf(run[q].w * inv, 0.f);
+        }
+    }
+    __syncthreads();
+    float p[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) p[i] = pooled[lane + 64 * i];
+#pragma unroll 1
+    for (int o0 = wave * 16; o0 < wave * 16 + 16; o0 += 4) {
+        float wv[4][12];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int i = 0; i < 12; ++i) wv[u][i] = w[(long long)(o0 + u) * 768 + lane + 64 * i];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float d = 0.f;
+#pragma unroll
+            for (int i = 0; i < 12; ++i) d = fmaf(wv[u][i], p[i], d);
+            d = wave_sum(d);
+            if (lane == 0) e[o0 + u] = d + bias[o0 + u];
+        }
+    }
+    __syncthreads();
+    if (tid < 256) {
+        const float v = e[tid];
+        const float ss = wave_sum(v * v);
+        if (lane == 0) wsum[wave] = ss;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        const float nrm = sqrtf((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
+        emb[orow * 256 + tid] = e[tid] / fmaxf(nrm, 1e-12f);  // F.normalize eps
+    }
+}
+
 // NomadLoss.  Stage 1: per-block fp64 partial sums of |a-b| over the 12 layer tensors (n_layer
 // float4s in total) and over the embeddings; stage 2: one block folds the partials in fixed order.
 constexpr int kL1Blocks = 1024;

@@ -11,7 +11,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .weights import check_state_dict, num_frames
+from .weights import check_state_dict, num_frames, num_windows
 
 P = "ssl_model."
 _SUFFIX = {"fp32": "", "bf16": "_bf16", "bf16x3": "_bf16x3"}   # of the C ABI's per-precision entry points
@@ -381,6 +381,68 @@ class Engine:
                                                             self._stream()), "nomad_embed_features_ragged")
 
         return self._forward_ragged(waves, packed, precision, 768, launch)
+
+    # ---- embeddings over windows of frames (scores over time) ------------------------------------------------------------
+    def _check_windows(self, win, hop, precision: str, head):
+        """Checked window geometry (frames), precision code and head override of ``embed_windows*`` -> (win, hop, code, hw, hb)."""
+        win, hop = int(win), int(hop)
+        if win < 1 or hop < 1:
+            raise ValueError(f"win and hop must be at least 1 frame, got win={win}, hop={hop}")
+        if precision not in _lib.PRECISION:
+            raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
+        if precision != "fp32" and head is not None:
+            raise ValueError(f"the {precision} path has no head override")
+        hw, hb = self._check_head(head)
+        return win, hop, self.enable(precision), hw, hb
+
+    def embed_windows(self, wav: torch.Tensor, win: int, hop: int, precision: str = "fp32",
+                      head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """wav (B,N) or (B,1,N) fp32 on the GPU -> (emb (W_total,256) fp32, counts): ONE forward of ``precision``, then the head
+        over windows of ``win`` encoder frames every ``hop`` frames (``weights.num_windows``; one frame = 320 samples) instead
+        of over the whole clip.  Rows: clip 0's windows in order, then clip 1's, ...; counts[c] = windows of clip c.  A window
+        that covers a whole clip has the bits of that clip's ``embed*``; the encoder saw the whole clip, so a window is not the
+        embedding of the excerpt alone.  Split over two streams by the rule of ``embed``; head: fp32 only."""
+        win, hop, prec, hw, hb = self._check_windows(win, hop, precision, head)
+        wav, B, N, T = self._check_wav(wav)
+        W = num_windows(T, win, hop)
+        emb = torch.empty(B * W, 256, dtype=torch.float32, device=self.device)
+
+        def run(lo, hi, side):
+            ws = self._workspace(self._forward_size(precision, hi - lo, N), side)
+            _lib.check(self.lib.nomad_embed_windows(self.ctx, wav[lo:hi].data_ptr(), hi - lo, N, prec, win, hop, _ptr(hw), _ptr(hb),
+                                                    emb[lo * W:hi * W].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                       "nomad_embed_windows")
+
+        self._dispatch(B, B // 2 if self._splits(precision, B, B * T) else 0, run, hint=True)
+        return emb, [W] * B
+
+    def embed_windows_ragged(self, waves=None, win: int = 0, hop: int = 0, precision: str = "fp32",
+                             packed: Optional[Tuple[torch.Tensor, list]] = None,
+                             head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """``embed_windows`` for clips of different lengths in ONE launch sequence -> (emb (W_total,256), counts); a clip's
+        windows are bit-identical to those of its own call.  waves / packed, the staging and the two-stream split: as in
+        ``embed_ragged``; a part [lo, hi) of the batch writes the rows of its own clips' windows."""
+        win, hop, prec, hw, hb = self._check_windows(win, hop, precision, head)
+        buf, lens = self._pack(waves, packed)
+        B, stride = buf.shape
+        frames = [num_frames(n) for n in lens]
+        if min(frames) < 1:
+            raise ValueError(f"a clip of {min(lens)} samples is shorter than the conv stack's receptive field")
+        counts = [num_windows(t, win, hop) for t in frames]
+        wpref = [0]
+        for w in counts:
+            wpref.append(wpref[-1] + w)
+        emb = torch.empty(wpref[-1], 256, dtype=torch.float32, device=self.device)
+
+        def run(lo, hi, side):
+            ws = self._workspace(self._forward_size_ragged(precision, lens[lo:hi]), side)
+            _lib.check(self.lib.nomad_embed_windows_ragged(self.ctx, buf[lo:hi].data_ptr(), hi - lo, stride,
+                                                           (C.c_int * (hi - lo))(*lens[lo:hi]), prec, win, hop, _ptr(hw), _ptr(hb),
+                                                           emb[wpref[lo]:wpref[hi]].data_ptr(), ws.data_ptr(), ws.numel(),
+                                                           self._stream()), "nomad_embed_windows_ragged")
+
+        self._dispatch(B, self._audio_cut(lens) if self._splits(precision, B, sum(frames)) else 0, run)
+        return emb, counts
 
     def cdist(self, a: torch.Tensor, b: torch.Tensor, want_matrix: bool = True):
         """a (Na,D), b (Nb,D) fp32 on the GPU, D a multiple of 4 up to 4096 -> (dist (Na,Nb) float64 or None, mean (Na,)

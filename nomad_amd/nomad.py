@@ -37,7 +37,7 @@ import torch
 from . import wavio
 from .dist import partition
 from .engine import Engine
-from .weights import find_checkpoint, find_feature_grad_mult, load_checkpoint, num_frames, seeded_state_dict
+from .weights import find_checkpoint, find_feature_grad_mult, load_checkpoint, num_frames, num_windows, seeded_state_dict
 
 SSL_OUT_DIM = 768
 EMB_DIM = 256
@@ -351,6 +351,80 @@ def check_references(references) -> None:
         raise ValueError(f"references must be (Nr, {EMB_DIM}) embeddings, got {tuple(references.shape)}")
     if references.shape[0] < 1:
         raise ValueError("references holds no embedding: the score is a mean over at least one reference")
+
+
+FRAMES_PER_SECOND = 50   # one encoder frame is 320 samples at 16 kHz; its receptive field is 400 samples
+
+
+def window_frames(window_s, hop_s):
+    """Window length and hop in seconds -> (win, hop) in encoder frames: ``max(1, round(s * 50))`` each.  Pure."""
+    out = []
+    for name, s in (("window_s", window_s), ("hop_s", hop_s)):
+        if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not math.isfinite(s) or s <= 0:
+            raise ValueError(f"{name} must be a positive number of seconds, got {s!r}")
+        out.append(max(1, int(round(float(s) * FRAMES_PER_SECOND))))
+    return out[0], out[1]
+
+
+def window_times(T: int, win: int, hop: int):
+    """(start_s, end_s) float64 arrays of the ``num_windows(T, win, hop)`` windows of a clip of T frames: window k of n =
+    min(win, T) frames starts at ``k * hop * 0.02`` s and ends ``(n * 320 + 80) / 16000`` s later - the samples its frames
+    see.  Both are formed as integer milliseconds / 1000, so they sit on the 3-decimal grid of the CSV writer."""
+    k = np.arange(num_windows(T, win, hop), dtype=np.int64)
+    n = min(int(win), int(T))
+    return (k * hop * 20) / 1000.0, ((k * hop + n) * 20 + 5) / 1000.0
+
+
+def segments_tables(test_files, frames, scores, win: int, hop: int):
+    """The tables of ``Nomad.predict_segments``: file labels, the files' frame counts and the window scores (files in order,
+    each file's windows in order) -> (one row per window: ``Test File``, ``start_s``, ``end_s``, ``NOMAD`` rounded to 3
+    decimals; one row per file, indexed by ``Test File``: ``NOMAD`` = the mean of the file's window scores, rounded)."""
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    counts = [num_windows(t, win, hop) for t in frames]
+    if len(test_files) != len(counts) or sum(counts) != scores.shape[0]:
+        raise ValueError(f"{scores.shape[0]} window scores for {len(test_files)} files with {sum(counts)} windows")
+    times = [window_times(t, win, hop) for t in frames]
+    df = pd.DataFrame({"Test File": np.repeat(np.asarray(test_files, dtype=object), counts),
+                       "start_s": np.concatenate([t[0] for t in times]) if times else np.zeros(0),
+                       "end_s": np.concatenate([t[1] for t in times]) if times else np.zeros(0),
+                       "NOMAD": scores}).round({"NOMAD": 3})
+    ends = np.cumsum(counts)
+    means = [scores[e - c:e].mean() for c, e in zip(counts, ends)]
+    df_mean = pd.DataFrame({"Test File": list(test_files), "NOMAD": np.asarray(means, dtype=np.float64)}).set_index("Test File").round(3)
+    return df, df_mean
+
+
+def _check_predict_paths(mode, nmr, deg) -> None:
+    """The argument checks of ``predict`` (same conditions, same messages)."""
+    if nmr is None:
+        raise Exception("nmr_path not specified, you need to pass a valid value to nmr_path")
+    if deg is None:
+        raise Exception("test_path not specified, you need to pass a valide value to test_path")
+    if mode == "dir":
+        if not os.path.isdir(nmr):
+            raise Exception(f"Path to the non-matching reference files {nmr} does not exist")
+        if not os.path.isdir(deg):
+            raise Exception(f"Path to the test files {deg} does not exist")
+    elif mode == "csv":
+        if not os.path.isfile(nmr):
+            raise Exception(f"File {nmr} does not exist")
+        if not os.path.isfile(deg):
+            raise Exception(f"File {deg} does not exist")
+    else:
+        raise Exception(f"Mode value {mode} is not valid. Valid values are dir and csv")
+
+
+def _file_table(path) -> pd.DataFrame:
+    """The file listing of ``get_embeddings``: a directory's entries, or a csv file's ``filename`` column."""
+    if os.path.isdir(path):
+        return pd.DataFrame({"filename": [os.path.join(path, x) for x in os.listdir(path)]})
+    if os.path.isfile(path):
+        data = pd.read_csv(path)
+        if "filename" not in data.columns:
+            raise Exception(f"File {path} not including a column called filename. Please pass a csv file with a "
+                            "column called filename that includes the absolute filpaths of the waveforms.")
+        return data
+    raise Exception(f"Path {path} does not exist")
 
 
 class _CdistFn(torch.autograd.Function):
@@ -934,6 +1008,102 @@ class Nomad:
             refs = references.detach().to(eng.device, torch.float32).contiguous()
             scores = eng.pairwise(self._score_embed(est, lens), refs, want_matrix=False)[1]
         return scores.mean() if reduction == "mean" else scores
+
+    def _window_precision(self, n_samples: int) -> str:
+        """The forward the windows of a batch of ``n_samples`` samples take: ``precision``, with the file pipeline's rule for bf16x3."""
+        return "fp32" if self.precision == "bf16x3" and n_samples < BF16X3_MIN_SAMPLES else self.precision
+
+    def score_over_time(self, wav, references, window_s=4.0, hop_s=2.0, lengths=None):
+        """NOMAD scores over time: -> (scores (W_total,) float64 on the GPU, counts) - for every window of ``window_s`` seconds
+        every ``hop_s`` seconds the mean distance of the window's embedding to ``references`` ((Nr,256), as ``score`` takes
+        them); clip 0's windows in order, then clip 1's, ...; counts[c] = windows of clip c.  wav (B,1,N) or (B,N) on the GPU;
+        lengths: the clips' exact lengths as in ``score``.
+
+        Seconds become encoder frames, ``max(1, round(s * 50))`` (one frame is 320 samples, its receptive field 400); the
+        windows are those of ``weights.num_windows``: a clip shorter than the window gets one window over all of it - then
+        the bits of ``score`` -, frames behind the last full window belong to no window.  All windows come from ONE forward
+        of ``precision`` (``Engine.embed_windows*``): attention and the first conv layer's GroupNorm statistics saw the whole
+        clip, so a window's score is not the score of the excerpt on its own.  No gradient is produced."""
+        win, hop = window_frames(window_s, hop_s)
+        check_references(references)
+        if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+            raise ValueError(f"wav must be (B,1,N) or (B,N), got {tuple(getattr(wav, 'shape', ()))}")
+        if wav.requires_grad or references.requires_grad:
+            raise ValueError("score_over_time produces no gradient (the windowed head has no backward): pass tensors that do not "
+                             "require one, or use score() for a differentiable whole-clip score")
+        lens = check_lengths(wav, lengths) if lengths is not None else None
+        self._need_whole_encoder(self.engine)
+        eng = self.engine
+        x = wav.detach().to(eng.device, torch.float32).contiguous()
+        x = x.squeeze(1) if x.dim() == 3 else x
+        refs = references.detach().to(eng.device, torch.float32).contiguous()
+        if lens is not None:
+            emb, counts = eng.embed_windows_ragged([x[i, :n] for i, n in enumerate(lens)], win, hop,
+                                                   precision=self._window_precision(sum(lens)))
+        else:
+            emb, counts = eng.embed_windows(x, win, hop, precision=self._window_precision(x.numel()))
+        return eng.pairwise(emb, refs, want_matrix=False)[1], counts
+
+    def _score_file_windows(self, paths, ref_t, win: int, hop: int, max_batch_samples: int):
+        """The file pipeline of ``get_embeddings_csv`` with the windowed head: -> (frames per file, window scores float64, files
+        in order).  Each staged ragged batch is embedded in windows and scored against ``ref_t`` on the GPU; only the scores
+        come back, one batch late."""
+        frames, scores = [0] * len(paths), [None] * len(paths)
+        pending = None
+
+        def collect(item):
+            idxs, counts, fetch = item
+            vals = fetch.result() if fetch is not None else np.full(sum(counts), np.nan)
+            at = 0
+            for i, c in zip(idxs, counts):
+                scores[i] = np.array(vals[at:at + c], dtype=np.float64)
+                at += c
+
+        for idxs, packed, uploaded in _staged_batches(paths, lambda p: self.load_processing(p, trim=False),
+                                                      self.engine.pack_ragged_host, max_batch_samples, self.DECODE_THREADS,
+                                                      self.PIPELINE_BATCHES, self.NATIVE_WAV_THREADS,
+                                                      device=getattr(self.engine, "device", None)):
+            for i, n in zip(idxs, packed[1]):
+                frames[i] = num_frames(n)
+            emb, counts = self.engine.embed_windows_ragged(None, win, hop, precision=self._window_precision(sum(packed[1])),
+                                                           packed=packed)
+            uploaded()
+            # (no reference to average over: NaN, what predict reports then - the distance kernels take no empty operand)
+            fetch = self.engine.fetch_async(self.engine.pairwise(emb, ref_t, want_matrix=False)[1]) if ref_t.shape[0] else None
+            if pending is not None:
+                collect(pending)
+            pending = (idxs, counts, fetch)
+        if pending is not None:
+            collect(pending)
+        return frames, (np.concatenate(scores) if scores else np.zeros(0))
+
+    def predict_segments(self, mode="dir", nmr="data/nmr-data", deg="data/test-data", window_s=4.0, hop_s=2.0, results_path=None,
+                         max_batch_samples: int = 256 * 64000):
+        """``predict`` over time: -> (df_segments, df_avg).  df_segments has one row per window of every test file, files in
+        listing order: ``Test File``, ``start_s``, ``end_s`` (``window_times``) and ``NOMAD``, the window's mean distance to the
+        reference embeddings, rounded to 3 decimals; df_avg, indexed by ``Test File``, the mean of each file's window scores.
+
+        Arguments, checks and file listing as in ``predict``.  The reference files are embedded whole; the test files go through
+        the staged ragged batches of ``get_embeddings_csv`` with the windowed head (``score_over_time`` says what a window
+        is: pooled from one forward over the whole file).  With ``results_path`` the segment table is written to
+        ``segments.csv`` there.  One process only: inside a torch.distributed job of several ranks it raises."""
+        win, hop = window_frames(window_s, hop_s)
+        _check_predict_paths(mode, nmr, deg)
+        world, _, _ = _dist_info(getattr(self, "group", None))
+        if world > 1:
+            raise RuntimeError(f"predict_segments runs in one process: this one belongs to a torch.distributed job of {world} ranks "
+                               "(sharding the windows is not implemented; predict() shards whole-file scores)")
+        print(f"Compute non-matching reference embeddings from {nmr}")
+        nmr_embeddings = self.get_embeddings(nmr).set_index("filename")
+        print(f"Compute degraded embeddings over windows of {win} frames every {hop} from {deg}")
+        paths = [str(p) for p in _file_table(deg)["filename"]]
+        ref_t = torch.from_numpy(np.ascontiguousarray(nmr_embeddings.to_numpy(dtype=np.float32))).to(self.engine.device)
+        frames, scores = self._score_file_windows(paths, ref_t, win, hop, max_batch_samples)
+        test_files = [x.split("/")[-1].split(".")[0] for x in paths]
+        df, df_mean = segments_tables(test_files, frames, scores, win, hop)
+        if results_path is not None:
+            _write_rounded_csv(df, os.path.join(results_path, "segments.csv"))
+        return df, df_mean
 
     def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor, lengths=None) -> "GraphedLoss":
         """``forward`` + backward for inputs of this shape, captured as one HIP graph (see ``GraphedLoss``): for training loops with

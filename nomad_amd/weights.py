@@ -44,6 +44,16 @@ def num_frames(n_samples: int) -> int:
     return length
 
 
+def num_windows(T: int, win: int, hop: int) -> int:
+    """Windows of ``win`` frames every ``hop`` frames over a clip of ``T`` frames (``nomad_num_windows``): 1 if T <= win - a
+    clip shorter than the window gets one window over all of it -, else (T - win) // hop + 1.  Window k covers frames
+    [k hop, k hop + min(win, T)); frames behind the last full window belong to no window, as with ``torch.Tensor.unfold``."""
+    T, win, hop = int(T), int(win), int(hop)
+    if T < 1 or win < 1 or hop < 1:
+        raise ValueError(f"num_windows needs T, win and hop >= 1, got T={T}, win={win}, hop={hop}")
+    return 1 if T <= win else (T - win) // hop + 1
+
+
 def conv_lengths(n_samples: int):
     """Output length of each of the 7 conv layers."""
     out = []
