@@ -18,6 +18,7 @@
  *                                  on rows of any width (768 for the baseline)
  *   nomad_paired_distance          np.diag(cdist(test, ref)) (train_triplet.py:438-439) without the matrix
  *   nomad_cdist_backward           d / d a and d / d b of nomad_cdist's matrix and row means (the NOMAD score as a loss)
+ *   nomad_embed_windows_backward   d / d waveform of the window embeddings (scores over time as a loss)
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
  *
@@ -359,6 +360,64 @@ int nomad_l1_loss_ragged(nomad_ctx* ctx, const float* a_layers_dev, const float*
 int nomad_l1_loss_backward_ragged(nomad_ctx* ctx, const float* a_layers_dev, const float* b_layers_dev,
                                   const float* a_emb_dev, const float* b_emb_dev, long long M, int B,
                                   const float* upstream_dev, float* dlayers_dev, float* demb_dev, nomad_stream_t stream);
+
+/* ---- the windowed head on the gradient path: differentiable scores over time ------------------------------------------------
+ * nomad_embed_windows* gives one embedding per window of a clip from one forward; these calls make the windows differentiable
+ * down to the waveform.  Window geometry (win, hop in frames), the order of the output rows and their number are those of
+ * nomad_embed_windows* (nomad_num_windows); W_total = B W(T), or sum_c W(T_c) for a ragged batch.
+ *
+ *   nomad_embed_train_windows[_ragged]     = nomad_embed_train[_ragged] (saved_dev mandatory) with the windowed head as the last
+ *                                            stage: emb_dev is [W_total][256], each row with the bits head_windows_kernel gives
+ *                                            the window's frames (a window over a whole clip: the clip's nomad_embed_train*
+ *                                            embedding).  layers_dev, saved_dev, the workspace and their sizes are those of
+ *                                            nomad_embed_train[_ragged].
+ *   nomad_windows_backward_scratch_bytes   the backward's scratch for n_windows = W_total windows: [n_windows][768] fp32, rounded
+ *                                            up to 256 bytes.  NOMAD_ERR_INVALID for n_windows <= 0 or bytes == NULL.
+ *   nomad_embed_windows_backward[_ragged]  = nomad_embed_backward[_ragged] with dlayers_dev = NULL and demb_dev [W_total][256], the
+ *                                            gradient of the window embeddings, -> dwav_dev [B][n_samples] ([B][stride], zero
+ *                                            behind every length).  The head stage is two launches without atomics: each window's
+ *                                            gradient with respect to its time mean, spread over its n = min(win, T) frames
+ *                                            (the time sum is recomputed in the forward's order, so the ReLU mask is the
+ *                                            forward's), into scratch_dev; then frame t of a clip receives the sum of the rows of
+ *                                            the windows that cover it, k ascending in one fp32 accumulator, and exact zeros when
+ *                                            none does (a gap with hop > win, the tail behind the last full window).  Every row
+ *                                            of the frame gradient and every row of scratch_dev in use is written before it is
+ *                                            read: nothing needs clearing.  feature_grad_mult and the workspace size
+ *                                            (nomad_backward_workspace_bytes[_ragged]) as in nomad_embed_backward[_ragged].
+ *   nomad_window_cover                     the windows that cover frame t of a clip of T frames: *k_lo .. *k_hi with
+ *                                            k_hi = min(W - 1, t / hop), k_lo = max(0, ceil((t - min(win, T) + 1) / hop));
+ *                                            k_lo > k_hi for a frame no window covers (the return value is still 0).  Host
+ *                                            arithmetic, no context - the helper the scatter kernel itself calls.
+ *                                            NOMAD_ERR_INVALID for T, win or hop < 1, t outside [0, T) or a NULL output.
+ *
+ * Contract: asynchronous, no allocation; deterministic, the same bits run to run.  A clip's row of dwav_dev from the ragged call
+ * does not depend on the batch it is in: it has the bits of the clip's own ragged call at B = 1 with that clip's rows of demb_dev
+ * (the ragged calls never split K; the equal-length ones may, as nomad_embed_train / nomad_embed_backward do).
+ * NOMAD_ERR_INVALID, before anything is queued: win or hop < 1; head_w_dev / head_b_dev not both set or both NULL; a NULL
+ * mandatory pointer (everything but the head override); a cut encoder (nomad_set_encoder_depth); fine-tuning mode
+ * (nomad_train_enable: its forward draws dropout and LayerDrop masks this backward does not replay); and whatever
+ * nomad_embed_train* / nomad_embed_backward* refuse.  NOMAD_ERR_WORKSPACE: scratch, workspace or saved block too small.
+ */
+int nomad_window_cover(int T, int win, int hop, int t, int* k_lo, int* k_hi);
+int nomad_windows_backward_scratch_bytes(long long n_windows, size_t* bytes);
+int nomad_embed_train_windows(nomad_ctx* ctx, const float* wav_dev, int B, int n_samples, int win, int hop,
+                              const float* head_w_dev, const float* head_b_dev, float* emb_dev, float* layers_dev,
+                              void* saved_dev, size_t saved_bytes, void* workspace_dev, size_t workspace_bytes,
+                              nomad_stream_t stream);
+int nomad_embed_train_windows_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host,
+                                     int win, int hop, const float* head_w_dev, const float* head_b_dev, float* emb_dev,
+                                     float* layers_dev, void* saved_dev, size_t saved_bytes, void* workspace_dev,
+                                     size_t workspace_bytes, nomad_stream_t stream);
+int nomad_embed_windows_backward(nomad_ctx* ctx, const float* wav_dev, int B, int n_samples, int win, int hop,
+                                 const float* head_w_dev, const float* head_b_dev, const float* layers_dev,
+                                 const void* saved_dev, size_t saved_bytes, const float* demb_dev, float* dwav_dev,
+                                 void* scratch_dev, size_t scratch_bytes, void* workspace_dev, size_t workspace_bytes,
+                                 nomad_stream_t stream);
+int nomad_embed_windows_backward_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host,
+                                        int win, int hop, const float* head_w_dev, const float* head_b_dev,
+                                        const float* layers_dev, const void* saved_dev, size_t saved_bytes,
+                                        const float* demb_dev, float* dwav_dev, void* scratch_dev, size_t scratch_bytes,
+                                        void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
 
 /* ---- NomadLoss with layer weights and per-utterance terms; the encoder cut at depth ------------------------
  * The reference's NomadLoss loops `for i in range(self.L)` (nomad.py:264, :276; L = 13): a caller who lowers L trains against the first

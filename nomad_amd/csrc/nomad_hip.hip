@@ -2616,9 +2616,15 @@ static int dw_gemm(nomad_ctx* c, const float* TA, const float* TB, int Nout, int
 // both, the way forward_run does.  Ragged: per-frame tensors are packed, the padded dU buffers of the conv stack hold clip c's
 // L_i(c) + 2 rows at row upref_i[c], the kernels that care about clip boundaries read the prefix sums; small-M GEMMs never split
 // K (a clip's gradient does not depend on its batch).  The conv feature extractor's parameter gradients need an equal-length batch.
+// wb (nomad_embed_windows_backward*): demb holds one row per WINDOW of the windowed head and the head stage is its backward - the
+// two launches of backward.hip.h through the caller's gw block - instead of head_bwd_kernel; everything below gx is unchanged.
+struct HeadWindowsBwd {
+    int win, hop;
+    float* gw;   // [windows of the batch][768]
+};
 static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const Saved& sv, const BwdLayout& lay, const float* head_w,
                         const float* head_b, const float* layers_out, const float* dlayers, const float* demb, float* dwav,
-                        char* ws, hipStream_t s, bool train) {
+                        char* ws, hipStream_t s, bool train, const HeadWindowsBwd* wb = nullptr) {
     const bool conv_pg = train && c->train_convnet;  // parameter gradients of the conv feature extractor too
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const int B = g.B, T = g.T, M = (int)g.rows[6], n_samples = g.wav_ld;
@@ -2682,7 +2688,14 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
     const int depth = train ? NOMAD_NUM_LAYERS : c->encoder_depth;
     bool first_cut = depth < NOMAD_NUM_LAYERS;
     // ---- head -> d loss / d x_12 -------------------------------------------------------------------
-    if (!first_cut) {
+    if (!first_cut && wb) {
+        Scope sc(c, s, NOMAD_K_ROW, 0.0);
+        const float* x12 = layers_out + (size_t)11 * M * 768;
+        hipLaunchKernelGGL(head_windows_bwd_kernel, dim3(head_num_windows(g.max_t, wb->win, wb->hop), B), dim3(1024), 0, s, x12, rg ? 0 : T,
+                           wb->win, wb->hop, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, demb, wb->gw, tpref);
+        hipLaunchKernelGGL(head_windows_scatter_kernel, dim3((g.max_t + 3) / 4, B), dim3(256), 0, s, wb->gw, rg ? 0 : T, wb->win, wb->hop,
+                           gx, tpref);
+    } else if (!first_cut) {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
         hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(1024), 0, s, layers_out + (size_t)11 * M * 768, T,
                            head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, demb, gx,
@@ -3046,31 +3059,31 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
 static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
                          const float* layers_out, const void* saved, size_t saved_bytes, const float* dlayers,
                          const float* demb, float* dwav, void* workspace, size_t workspace_bytes,
-                         nomad_stream_t stream, bool train) {
+                         nomad_stream_t stream, bool train, const char* who = "nomad_embed_backward", const HeadWindowsBwd* wb = nullptr) {
     Shapes sh;
     const bool cut = c && c->encoder_depth < NOMAD_NUM_LAYERS;   // a cut encoder has no embedding: demb is ignored, dlayers carries everything
     if (!c || !wav || !layers_out || !saved || (cut ? !dlayers : !demb) || (!dwav && !train) || !workspace || B <= 0 ||
         !make_shapes(B, n_samples, &sh))
-        return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: bad argument%s", cut ? " (encoder depth below 12: dlayers_dev is required)" : "");
-    if (!c->bwd_ready) return fail(NOMAD_ERR_INVALID, "nomad_embed_backward: call nomad_enable_backward first");
+        return fail(NOMAD_ERR_INVALID, "%s: bad argument%s", who, cut ? " (encoder depth below 12: dlayers_dev is required)" : "");
+    if (!c->bwd_ready) return fail(NOMAD_ERR_INVALID, "%s: call nomad_enable_backward first", who);
     if (train && !c->train_ready) return fail(NOMAD_ERR_INVALID, "nomad_train_backward: call nomad_train_enable first");
     const BatchGeom g = geom_uniform(sh);
     const Saved sv = make_saved(g, const_cast<void*>(saved));
     const BwdLayout lay = make_bwd_layout(g, train, train && c->train_convnet);
     if (saved_bytes < sv.total || workspace_bytes < lay.total)
-        return fail(NOMAD_ERR_WORKSPACE, "nomad_embed_backward: saved %zu/%zu, workspace %zu/%zu", saved_bytes, sv.total,
+        return fail(NOMAD_ERR_WORKSPACE, "%s: saved %zu/%zu, workspace %zu/%zu", who, saved_bytes, sv.total,
                     workspace_bytes, lay.total);
     if (train && c->branches > 1 && B % c->branches)
         return fail(NOMAD_ERR_INVALID, "nomad_train_backward: B=%d is not %d equal branches", B, c->branches);
     return backward_run(c, wav, g, sv, lay, head_w, head_b, layers_out, dlayers, demb, dwav, static_cast<char*>(workspace),
-                        static_cast<hipStream_t>(stream), train);
+                        static_cast<hipStream_t>(stream), train, wb);
 }
 
 // nomad_embed_backward_ragged / nomad_train_backward_ragged: the ragged prologue's steps over the BwdLayout.
 static int backward_ragged(const char* who, nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, const float* head_w,
                            const float* head_b, const float* layers_out, const void* saved, size_t saved_bytes, const float* dlayers,
                            const float* demb, float* dwav, void* workspace, size_t workspace_bytes, nomad_stream_t stream,
-                           bool train) {
+                           bool train, const HeadWindowsBwd* wb = nullptr) {
     RaggedShapes rs;
     const bool cut = c && c->encoder_depth < NOMAD_NUM_LAYERS;   // (a cut encoder: demb is ignored, dlayers is required)
     if (int rc = ragged_shapes(who, c && wav && layers_out && saved && (cut ? dlayers != nullptr : demb != nullptr) && (dwav || train) && workspace,
@@ -3089,7 +3102,7 @@ static int backward_ragged(const char* who, nomad_ctx* c, const float* wav, int 
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     if (int rc = ragged_upload(c, rs, stride, reinterpret_cast<int*>(ws + lay.meta), s, &g)) return rc;
-    return backward_run(c, wav, g, sv, lay, head_w, head_b, layers_out, dlayers, demb, dwav, ws, s, train);
+    return backward_run(c, wav, g, sv, lay, head_w, head_b, layers_out, dlayers, demb, dwav, ws, s, train, wb);
 }
 
 // ---- fine-tuning state ------------------------------------------------------------------------------------
@@ -3262,6 +3275,90 @@ int nomad_embed_backward_ragged(nomad_ctx* c, const float* wav, int B, int strid
     if (!dwav) return fail(NOMAD_ERR_INVALID, "nomad_embed_backward_ragged: bad argument");
     return backward_ragged("nomad_embed_backward_ragged", c, wav, B, stride, lengths_host, head_w, head_b, layers_out, saved, saved_bytes,
                            dlayers, demb, dwav, workspace, workspace_bytes, stream, false);
+}
+
+// ---- the windowed head on the gradient path: nomad_embed_train[_ragged] / nomad_embed_backward[_ragged] with head_windows_kernel
+// and its backward as the head stage.  Every check of those calls holds; the windows add theirs ahead, so nothing is queued on an error.
+static int windows_grad_args(const char* who, const nomad_ctx* c, int win, int hop, const float* head_w, const float* head_b) {
+    if (int rc = windows_args(who, c, NOMAD_PRECISION_F32, win, hop, head_w, head_b)) return rc;
+    // fine-tuning mode: the training-mode forward then draws dropout and LayerDrop masks that this backward (d loss / d waveform with
+    // frozen weights) does not replay, and the head's own parameter gradients have no windowed form
+    if (c && c->train_ready) return fail(NOMAD_ERR_INVALID, "%s: not in fine-tuning mode (nomad_train_enable)", who);
+    return 0;
+}
+
+int nomad_window_cover(int T, int win, int hop, int t, int* k_lo, int* k_hi) {
+    if (!k_lo || !k_hi || T < 1 || win < 1 || hop < 1 || t < 0 || t >= T)
+        return fail(NOMAD_ERR_INVALID, "nomad_window_cover: bad argument (T=%d, win=%d, hop=%d, t=%d)", T, win, hop, t);
+    head_window_cover(T, win, hop, t, k_lo, k_hi);
+    return 0;
+}
+
+int nomad_windows_backward_scratch_bytes(long long n_windows, size_t* bytes) {
+    if (!bytes || n_windows <= 0) return fail(NOMAD_ERR_INVALID, "nomad_windows_backward_scratch_bytes: bad argument (n_windows=%lld)", n_windows);
+    *bytes = align_up(sizeof(float) * 768 * (size_t)n_windows);   // gw [n_windows][768]
+    return 0;
+}
+
+int nomad_embed_train_windows(nomad_ctx* c, const float* wav, int B, int n_samples, int win, int hop, const float* head_w,
+                              const float* head_b, float* emb, float* layers_out, void* saved, size_t saved_bytes, void* workspace,
+                              size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_train_windows";
+    if (int rc = windows_grad_args(who, c, win, hop, head_w, head_b)) return rc;
+    Shapes sh;
+    if (!c || !saved || !layers_out || B <= 0 || !make_shapes(B, n_samples, &sh)) return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
+    const Saved sv = make_saved(geom_uniform(sh), saved);
+    if (saved_bytes < sv.total) return fail(NOMAD_ERR_WORKSPACE, "%s: saved block %zu < required %zu", who, saved_bytes, sv.total);
+    const HeadMode mode = HeadMode::windows(win, hop, (long long)B * head_num_windows(sh.T, win, hop));
+    return forward_impl(c, wav, B, n_samples, head_w, head_b, emb, layers_out, workspace, workspace_bytes, stream, &sv, who, mode);
+}
+
+int nomad_embed_train_windows_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, int win, int hop,
+                                     const float* head_w, const float* head_b, float* emb, float* layers_out, void* saved,
+                                     size_t saved_bytes, void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_train_windows_ragged";
+    if (int rc = windows_grad_args(who, c, win, hop, head_w, head_b)) return rc;
+    if (!c || !layers_out || !saved) return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
+    long long n = 0;
+    for (int i = 0; lengths_host && i < B; ++i) n += head_num_windows(nomad_num_frames(lengths_host[i]), win, hop);
+    return forward_ragged(c, wav, B, stride, lengths_host, head_w, head_b, emb, workspace, workspace_bytes, stream, who,
+                          HeadMode::windows(win, hop, n), layers_out, saved, saved_bytes);
+}
+
+int nomad_embed_windows_backward(nomad_ctx* c, const float* wav, int B, int n_samples, int win, int hop, const float* head_w,
+                                 const float* head_b, const float* layers_out, const void* saved, size_t saved_bytes, const float* demb,
+                                 float* dwav, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes,
+                                 nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_windows_backward";
+    if (int rc = windows_grad_args(who, c, win, hop, head_w, head_b)) return rc;
+    Shapes sh;
+    if (!c || !demb || !dwav || !scratch || B <= 0 || !make_shapes(B, n_samples, &sh)) return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
+    const size_t need = align_up(sizeof(float) * 768 * (size_t)B * head_num_windows(sh.T, win, hop));
+    if (scratch_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: scratch %zu < required %zu", who, scratch_bytes, need);
+    const HeadWindowsBwd wb{win, hop, static_cast<float*>(scratch)};
+    return backward_impl(c, wav, B, n_samples, head_w, head_b, layers_out, saved, saved_bytes, nullptr, demb, dwav, workspace,
+                         workspace_bytes, stream, false, who, &wb);
+}
+
+int nomad_embed_windows_backward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, int win, int hop,
+                                        const float* head_w, const float* head_b, const float* layers_out, const void* saved,
+                                        size_t saved_bytes, const float* demb, float* dwav, void* scratch, size_t scratch_bytes,
+                                        void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_windows_backward_ragged";
+    if (int rc = windows_grad_args(who, c, win, hop, head_w, head_b)) return rc;
+    if (!c || !demb || !dwav || !scratch || !lengths_host || B <= 0) return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
+    long long n = 0;
+    bool frames_ok = true;   // (a clip below one frame: left to the shape checks below, NOMAD_ERR_INVALID)
+    for (int i = 0; i < B; ++i) {
+        const int t = nomad_num_frames(lengths_host[i]);
+        frames_ok = frames_ok && t >= 1;
+        n += head_num_windows(t, win, hop);
+    }
+    const size_t need = align_up(sizeof(float) * 768 * (size_t)n);
+    if (frames_ok && scratch_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: scratch %zu < required %zu", who, scratch_bytes, need);
+    const HeadWindowsBwd wb{win, hop, static_cast<float*>(scratch)};
+    return backward_ragged(who, c, wav, B, stride, lengths_host, head_w, head_b, layers_out, saved, saved_bytes, nullptr, demb, dwav,
+                           workspace, workspace_bytes, stream, false, &wb);
 }
 
 int nomad_train_num_segments(void) { return (int)segments().size(); }

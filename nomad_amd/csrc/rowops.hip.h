@@ -263,6 +263,16 @@ __host__ __device__ inline int head_num_windows(int T, int win, int hop) {
     return T <= win ? 1 : (T - win) / hop + 1;
 }
 
+// The windows that cover frame t of a clip (0 <= t < T; T, win, hop >= 1): k_lo .. k_hi, consecutive.  Window k covers t when
+// k hop <= t < k hop + n with n = min(win, T), so k_hi = min(W - 1, t / hop) and k_lo = max(0, ceil((t - n + 1) / hop)).
+// k_lo > k_hi: no window covers t - a gap between windows (hop > win) or the tail behind the last full window.  The one place
+// this arithmetic lives: the backward's scatter (backward.hip.h) and nomad_window_cover.
+__host__ __device__ inline void head_window_cover(int T, int win, int hop, int t, int* k_lo, int* k_hi) {
+    const int n = win < T ? win : T, last = head_num_windows(T, win, hop) - 1, a = t - n + 1;
+    *k_hi = t / hop < last ? t / hop : last;
+    *k_lo = a <= 0 ? 0 : (a - 1) / hop + 1;
+}
+
 // The head over windows of frames, both stages in one workgroup: window k of clip b -> one row of emb, in the arithmetic
 // of head_pool_kernel + head_kernel applied to the window's rows as if they were a clip of their own, so a window that
 // covers a whole clip has the bits of that clip's embedding, and a window's 256 values are a function of its own rows only.

@@ -865,6 +865,99 @@ class Engine:
                                                         self._stream()), "nomad_embed_backward_ragged")
         return dwav
 
+    # ---- the windowed head on the gradient path (differentiable scores over time) ----------------------------------------
+    def _check_grad_windows(self, win, hop, head):
+        win, hop = int(win), int(hop)
+        if win < 1 or hop < 1:
+            raise ValueError(f"win and hop must be at least 1 frame, got win={win}, hop={hop}")
+        hw, hb = self._check_head(head)
+        return win, hop, hw, hb
+
+    def embed_train_windows(self, wav: torch.Tensor, win: int, hop: int, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """``embed_train`` with the windowed head of ``embed_windows`` as its last stage: -> (emb_w (W_total,256), counts,
+        layers (12,B,T,768), saved block for ``embed_windows_backward``).  Rows and counts as in ``embed_windows``."""
+        win, hop, hw, hb = self._check_grad_windows(win, hop, head)
+        wav, B, N, T = self._check_wav(wav)
+        self.enable_backward()
+        W = num_windows(T, win, hop)
+        emb = torch.empty(B * W, 256, dtype=torch.float32, device=self.device)
+        layers = torch.empty(12, B, T, 768, dtype=torch.float32, device=self.device)
+        saved = torch.empty(self._size(self.lib.nomad_saved_bytes, B, N, "nomad_saved_bytes"), dtype=torch.uint8,
+                            device=self.device)
+        ws = self._workspace(self.workspace_bytes(B, N))
+        _lib.check(self.lib.nomad_embed_train_windows(self.ctx, wav.data_ptr(), B, N, win, hop, _ptr(hw), _ptr(hb), emb.data_ptr(),
+                                                      layers.data_ptr(), saved.data_ptr(), saved.numel(), ws.data_ptr(), ws.numel(),
+                                                      self._stream()), "nomad_embed_train_windows")
+        return emb, [W] * B, layers, saved
+
+    def embed_train_windows_ragged(self, waves, win: int, hop: int, lengths=None,
+                                   head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """``embed_train_ragged`` with the windowed head: -> (emb_w (W_total,256), counts, packed layers (12,M,768), saved block,
+        (buffer, lengths)); the last item is the batch ``embed_windows_backward_ragged`` takes."""
+        win, hop, hw, hb = self._check_grad_windows(win, hop, head)
+        buf, lens = self.pack_ragged(waves, lengths)
+        frames = [num_frames(n) for n in lens]
+        if min(frames) < 1:
+            raise ValueError(f"a clip of {min(lens)} samples is shorter than the conv stack's receptive field")
+        self.enable_backward()
+        B, stride = buf.shape
+        counts = [num_windows(t, win, hop) for t in frames]
+        emb = torch.empty(sum(counts), 256, dtype=torch.float32, device=self.device)
+        layers = torch.empty(12, sum(frames), 768, dtype=torch.float32, device=self.device)
+        saved = torch.empty(self._size_ragged(self.lib.nomad_saved_bytes_ragged, lens, "nomad_saved_bytes_ragged"),
+                            dtype=torch.uint8, device=self.device)
+        ws = self._workspace(self._size_ragged(self.lib.nomad_workspace_bytes_ragged, lens, "nomad_workspace_bytes_ragged"))
+        _lib.check(self.lib.nomad_embed_train_windows_ragged(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), win, hop,
+                                                             _ptr(hw), _ptr(hb), emb.data_ptr(), layers.data_ptr(), saved.data_ptr(),
+                                                             saved.numel(), ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_embed_train_windows_ragged")
+        return emb, counts, layers, saved, (buf, lens)
+
+    def _windows_scratch(self, n_windows: int) -> torch.Tensor:
+        """The per-window gradient rows of the windowed head's backward: a fresh block per call, like the outputs."""
+        n = C.c_size_t()
+        _lib.check(self.lib.nomad_windows_backward_scratch_bytes(n_windows, C.byref(n)), "nomad_windows_backward_scratch_bytes")
+        return torch.empty(n.value, dtype=torch.uint8, device=self.device)
+
+    def _check_demb_w(self, demb_w: torch.Tensor, n_windows: int):
+        self._check_dev(demb_w, "demb_w")
+        if tuple(demb_w.shape) != (n_windows, 256):
+            raise ValueError(f"demb_w must be ({n_windows}, 256): one row per window, got {tuple(demb_w.shape)}")
+
+    def embed_windows_backward(self, wav, layers, saved, demb_w, win: int, hop: int, head=None) -> torch.Tensor:
+        """d loss / d wav (B,N) of an ``embed_train_windows`` call from d loss / d emb_w (W_total,256)."""
+        win, hop, hw, hb = self._check_grad_windows(win, hop, head)
+        wav, B, N, T = self._check_wav(wav)
+        self._check_demb_w(demb_w, B * num_windows(T, win, hop))
+        self.enable_backward()
+        ws = self._workspace(self._size(self.lib.nomad_backward_workspace_bytes, B, N, "nomad_backward_workspace_bytes"))
+        scratch = self._windows_scratch(demb_w.shape[0])
+        dwav = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nomad_embed_windows_backward(self.ctx, wav.data_ptr(), B, N, win, hop, _ptr(hw), _ptr(hb), layers.data_ptr(),
+                                                         saved.data_ptr(), saved.numel(), demb_w.data_ptr(), dwav.data_ptr(),
+                                                         scratch.data_ptr(), scratch.numel(), ws.data_ptr(), ws.numel(),
+                                                         self._stream()), "nomad_embed_windows_backward")
+        return dwav
+
+    def embed_windows_backward_ragged(self, batch, layers, saved, demb_w, win: int, hop: int, head=None) -> torch.Tensor:
+        """d loss / d wav (B, stride) of an ``embed_train_windows_ragged`` call (``batch``: its last result) from d loss / d emb_w
+        (W_total,256); zero behind every clip's length."""
+        win, hop, hw, hb = self._check_grad_windows(win, hop, head)
+        buf, lens = batch
+        B, stride = buf.shape
+        self._check_demb_w(demb_w, sum(num_windows(num_frames(n), win, hop) for n in lens))
+        self.enable_backward()
+        ws = self._workspace(self._size_ragged(self.lib.nomad_backward_workspace_bytes_ragged, lens,
+                                               "nomad_backward_workspace_bytes_ragged"))
+        scratch = self._windows_scratch(demb_w.shape[0])
+        dwav = torch.empty(B, stride, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nomad_embed_windows_backward_ragged(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), win, hop,
+                                                                _ptr(hw), _ptr(hb), layers.data_ptr(), saved.data_ptr(),
+                                                                saved.numel(), demb_w.data_ptr(), dwav.data_ptr(), scratch.data_ptr(),
+                                                                scratch.numel(), ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_embed_windows_backward_ragged")
+        return dwav
+
     def train_backward_ragged(self, batch, layers: torch.Tensor, saved: torch.Tensor, demb: torch.Tensor):
         """Accumulate d loss / d parameters for one ``embed_train_ragged`` call, given d loss / d emb (B,256)."""
         buf, lens = batch

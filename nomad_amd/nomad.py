@@ -503,6 +503,59 @@ class _ScoreFn(torch.autograd.Function):
         return dwav, dref, None, None
 
 
+class _WindowScoreFn(torch.autograd.Function):
+    """scores[w] = mean_j ||emb_w(window w of estimate) - references_j|| over the windows of ``Engine.embed_train_windows*``;
+    backward = ``cdist_backward`` over the window rows, then ``embed_windows_backward[_ragged]`` (the windowed head's backward
+    and the backbone down to the waveform) and, when asked for, d / d references."""
+
+    @staticmethod
+    def forward(ctx, estimate, references, nomad, lens, win, hop):
+        eng = nomad.engine
+        est = estimate.detach().to(eng.device, torch.float32).contiguous()
+        est = est.squeeze(1) if est.dim() == 3 else est
+        refs = references.detach().to(eng.device, torch.float32).contiguous()
+        ctx.nomad, ctx.lens, ctx.geom = nomad, lens, (win, hop)
+        ctx.meta = (estimate.shape, references.device, references.dtype)
+        if not estimate.requires_grad:   # only the references are differentiated: the scoring forward will do
+            if lens is not None:
+                emb, _ = eng.embed_windows_ragged([est[i, :n] for i, n in enumerate(lens)], win, hop,
+                                                  precision=nomad._window_precision(sum(lens)))
+            else:
+                emb, _ = eng.embed_windows(est, win, hop, precision=nomad._window_precision(est.numel()))
+            layers = saved = None
+        elif lens is None:
+            emb, _, layers, saved = eng.embed_train_windows(est, win, hop)
+        else:
+            emb, _, layers, saved, (est, _) = eng.embed_train_windows_ragged(est, win, hop, lens)
+        _, mean = eng.pairwise(emb, refs, want_matrix=False)
+        ctx.save_for_backward(est, refs, emb, layers, saved)
+        return mean
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        est, refs, emb, layers, saved = ctx.saved_tensors
+        eng = ctx.nomad.engine
+        shape, ref_device, ref_dtype = ctx.meta
+        win, hop = ctx.geom
+        want_a = ctx.needs_input_grad[0] and saved is not None
+        want_b = ctx.needs_input_grad[1]
+        if not (want_a or want_b):
+            return None, None, None, None, None, None
+        g = grad_out.to(eng.device, torch.float64).contiguous()
+        demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
+        dwav = None
+        if want_a:
+            Nomad._need_whole_encoder(eng)
+            if ctx.lens is None:
+                dwav = eng.embed_windows_backward(est, layers, saved, demb, win, hop)
+            else:
+                dwav = eng.embed_windows_backward_ragged((est, ctx.lens), layers, saved, demb, win, hop)
+            dwav = dwav.reshape(shape)
+        if dref is not None:
+            dref = dref.to(ref_device, ref_dtype)
+        return dwav, dref, None, None, None, None
+
+
 class GraphedLoss:
     """``nomad.forward`` + its backward to ``estimate`` for ONE input shape, captured once as a HIP graph and replayed per step.
 
@@ -1023,7 +1076,8 @@ class Nomad:
         windows are those of ``weights.num_windows``: a clip shorter than the window gets one window over all of it - then
         the bits of ``score`` -, frames behind the last full window belong to no window.  All windows come from ONE forward
         of ``precision`` (``Engine.embed_windows*``): attention and the first conv layer's GroupNorm statistics saw the whole
-        clip, so a window's score is not the score of the excerpt on its own.  No gradient is produced."""
+        clip, so a window's score is not the score of the excerpt on its own.  No gradient is produced: ``score_windows`` is the
+        differentiable form of this call."""
         win, hop = window_frames(window_s, hop_s)
         check_references(references)
         if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
@@ -1043,6 +1097,41 @@ class Nomad:
         else:
             emb, counts = eng.embed_windows(x, win, hop, precision=self._window_precision(x.numel()))
         return eng.pairwise(emb, refs, want_matrix=False)[1], counts
+
+    def score_windows(self, estimate, references, window_s=4.0, hop_s=2.0, lengths=None, reduction="none"):
+        """``score_over_time`` as a differentiable quantity: -> (scores (W_total,) float64, counts), the windows, their order and
+        ``counts`` exactly those of ``score_over_time`` (``window_frames``, ``weights.num_windows``); with reduction="mean" the
+        0-dim mean over all windows in place of ``scores``.  A loss on where a recording is bad is plain torch on that tensor -
+        the worst window of every clip::
+
+            scores, counts = nomad.score_windows(estimate, references, window_s=4.0, hop_s=2.0)
+            loss = torch.stack([s.max() for s in scores.split(counts)]).mean()
+
+        and per-window weights are ``(scores * weights).sum()``.
+
+        estimate (B,1,N) or (B,N); references (Nr,256) as ``score`` takes them; lengths: the clips' exact lengths.  Under
+        ``torch.no_grad()``, or when nothing requires a gradient, this is ``score_over_time``: the scoring forward of
+        ``precision``, then ``Engine.pairwise``, the same bits.  With a gradient the forward is ``embed_train_windows[_ragged]``
+        (fp32 buffers, products by ``Engine.gemm_precision``; a window over a whole clip then has ``score``'s value), and the
+        backward runs ``cdist_backward`` over the window rows, the windowed head's backward - a frame receives the sum of the
+        gradients of the windows that cover it, exact zeros where none does - and the backbone down to the waveform.  The
+        encoder saw the whole clip: a window's gradient reaches every sample of its clip through attention, not only the
+        window's own samples.  It carries ``feature_grad_mult`` as ``score``'s does and is zero behind every length;
+        ``references`` gets a gradient too when it requires one."""
+        win, hop = window_frames(window_s, hop_s)
+        check_reduction(reduction)
+        check_references(references)
+        if not torch.is_tensor(estimate) or estimate.dim() not in (2, 3) or (estimate.dim() == 3 and estimate.shape[1] != 1):
+            raise ValueError(f"estimate must be (B,1,N) or (B,N), got {tuple(getattr(estimate, 'shape', ()))}")
+        lens = check_lengths(estimate, lengths) if lengths is not None else None
+        if not (torch.is_grad_enabled() and (estimate.requires_grad or references.requires_grad)):
+            scores, counts = self.score_over_time(estimate.detach(), references.detach(), window_s, hop_s, lengths)
+        else:
+            self._need_whole_encoder(self.engine)
+            scores = _WindowScoreFn.apply(estimate, references, self, lens, win, hop)
+            samples = lens if lens is not None else [estimate.shape[-1]] * estimate.shape[0]
+            counts = [num_windows(num_frames(n), win, hop) for n in samples]
+        return (scores.mean() if reduction == "mean" else scores), counts
 
     def _score_file_windows(self, paths, ref_t, win: int, hop: int, max_batch_samples: int):
         """The file pipeline of ``get_embeddings_csv`` with the windowed head: -> (frames per file, window scores float64, files
