@@ -18,6 +18,8 @@
  *                                  on rows of any width (768 for the baseline)
  *   nomad_paired_distance          np.diag(cdist(test, ref)) (train_triplet.py:438-439) without the matrix
  *   nomad_cdist_backward           d / d a and d / d b of nomad_cdist's matrix and row means (the NOMAD score as a loss)
+ *   nomad_knn / nomad_knn_backward the k nearest rows of a bank and their mean distance, matrix-free, and its gradient (the
+ *                                  nearest-reference NOMAD score as a score and as a loss)
  *   nomad_embed_windows_backward   d / d waveform of the window embeddings (scores over time as a loss)
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
@@ -194,6 +196,50 @@ int nomad_cdist_backward_scratch_bytes(int Na, int Nb, size_t* bytes);
 int nomad_cdist_backward(nomad_ctx* ctx, const float* a_dev, int Na, const float* b_dev, int Nb, int D,
                          const double* gdist_dev, const double* gmean_dev, float* da_dev, float* db_dev,
                          void* scratch_dev, size_t scratch_bytes, nomad_stream_t stream);
+
+/*
+ * Nearest references: per row of a the k rows of b at the smallest distance, and their mean - the NOMAD score against the closest
+ * part of a mixed bank - without forming the [Na][Nb] matrix.  a_dev [Na][D], b_dev [Nb][D] fp32 as for nomad_cdist, 1 <= k <= 64,
+ * k <= Nb.  Contract (held bit for bit by tests/test_gpu_knn.py):
+ *   d_ij          the value nomad_cdist computes: the same chain, the same bits (at D = 256 those of nomad_pairwise).  With
+ *                 dist_dev given, that [Na][Nb] float64 matrix is nomad_cdist's; NULL: it is never formed.
+ *   neighbours    of row i: the k columns smallest under the key (d_ij, j), ascending; a NaN distance is ordered as +infinity,
+ *                 equal keys by index.  So equal distances resolve to the lower index, every output slot is always written and
+ *                 every index lies in 0 .. Nb - 1, whatever the input.  (The kernels pad a last 64-column tile with copies of the
+ *                 last row of b; those are excluded by index, not by value.)
+ *   knn_dist_dev  [Na][k] float64 (out): the r-th neighbour's d, as stored in the matrix (NaN stays NaN);
+ *   knn_idx_dev   [Na][k] int32 (out): its column.  With k = Nb the index row is the stable argsort of the matrix row.
+ *   score_dev     [Na] float64 (out): (sum_{r=0}^{k-1} knn_dist[i][r], r ascending, one float64 accumulator from 0.0) / (double)k.
+ * Row i of every output depends on a_i and b only: its bits are those of its own Na = 1 call, the same with and without dist_dev
+ * and the same run to run; no atomics.  Scratch is the caller's: nomad_knn_scratch_bytes(Na, Nb, k) bytes (the k best of every
+ * 64-column tile, 12 bytes each), written before it is read.  Asynchronous, no allocation; argument errors return before
+ * anything is queued.  Time is accounted to the distance stage's profile class.
+ * NOMAD_ERR_INVALID: a NULL operand, output (other than dist_dev) or scratch, Na / Nb <= 0 or above 65535 * 64, D not a multiple
+ * of 4 or outside 4 .. 4096, k < 1, k > 64 or k > Nb.  NOMAD_ERR_WORKSPACE: scratch_bytes too small.
+ */
+int nomad_knn_scratch_bytes(int Na, int Nb, int k, size_t* bytes);
+int nomad_knn(nomad_ctx* ctx, const float* a_dev, int Na, const float* b_dev, int Nb, int D, int k,
+              double* dist_dev, double* knn_dist_dev, int* knn_idx_dev, double* score_dev,
+              void* scratch_dev, size_t scratch_bytes, nomad_stream_t stream);
+
+/*
+ * The backward of nomad_knn: gradients of  sum_ir g_knn_ir knn_dist_ir + sum_i g_score_i score_i  with respect to a and b, the
+ * selection held fixed.  With c_ir = g_knn_ir + g_score_i / k (float64, a NULL upstream counting as 0) the outputs are BY DEFINITION
+ * the bits of nomad_cdist_backward called with gmean_dev = NULL and the dense gdist_ij = c_ir where j = knn_idx[i][r], 0 elsewhere:
+ * its order of summation, its single rounding, its rows' independence of the grid; a neighbour at distance 0 contributes nothing and
+ * is never NaN / Inf; one output alone has the bits it has next to the other.
+ *   knn_idx_dev [Na][k] int32, as nomad_knn wrote it (distinct within a row); an index outside 0 .. Nb - 1 is skipped
+ *   g_knn_dev [Na][k] float64 or NULL, g_score_dev [Na] float64 or NULL (not both NULL)
+ *   da_dev [Na][D] fp32 (out) or NULL, db_dev [Nb][D] fp32 (out) or NULL (not both NULL)
+ * Scratch is the caller's: nomad_knn_backward_scratch_bytes(Na, Nb, k) bytes (that dense upstream and nomad_cdist_backward's W, two
+ * [Na][Nb] float64 matrices), written before it is read.  Asynchronous, no allocation; argument errors return before anything is
+ * queued.  NOMAD_ERR_INVALID: as for nomad_knn, or both upstreams NULL, or both outputs NULL.  NOMAD_ERR_WORKSPACE: scratch_bytes
+ * too small.
+ */
+int nomad_knn_backward_scratch_bytes(int Na, int Nb, int k, size_t* bytes);
+int nomad_knn_backward(nomad_ctx* ctx, const float* a_dev, int Na, const float* b_dev, int Nb, int D, int k,
+                       const int* knn_idx_dev, const double* g_knn_dev, const double* g_score_dev,
+                       float* da_dev, float* db_dev, void* scratch_dev, size_t scratch_bytes, nomad_stream_t stream);
 
 /*
  * Pooled backbone features, Origw2v.forward (networks.py:29-34): the last encoder layer's output averaged over time - no

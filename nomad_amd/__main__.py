@@ -24,9 +24,14 @@ def main():
     ap.add_argument("--window", type=float, default=None, metavar="S",
                     help="scores over time: one NOMAD score per window of S seconds of every test file (predict_segments)")
     ap.add_argument("--hop", type=float, default=None, metavar="S", help="seconds between window starts (default: half the window)")
+    ap.add_argument("--knn", type=int, default=None, metavar="K",
+                    help="score every file (or window) by the mean distance to its K nearest references (1 .. 64) instead of all "
+                         "of them; without --window the neighbours go to nomad_nearest.csv")
     a = ap.parse_args()
     if a.hop is not None and a.window is None:
         ap.error("--hop goes with --window")
+    if a.knn is not None and not 1 <= a.knn <= 64:
+        ap.error(f"--knn takes a number of references from 1 to 64, got {a.knn}")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = 0
     if world > 1 or "LOCAL_RANK" in os.environ:      # started by torch.distributed.run: one process per GPU
@@ -40,11 +45,11 @@ def main():
     nomad = Nomad(device=a.device, weights=a.weights, precision=a.precision)
     if a.window is not None:
         segments, nomad_avg = nomad.predict_segments(a.mode, a.nmr, a.deg, a.window, a.window / 2 if a.hop is None else a.hop,
-                                                     a.results_path)
+                                                     a.results_path, k=a.knn)
         print("Nomad scores over time, printing the first 5 windows")
         print(segments.head())
     else:
-        nomad_avg, _ = nomad.predict(a.mode, a.nmr, a.deg, a.results_path)
+        nomad_avg = nomad.predict(a.mode, a.nmr, a.deg, a.results_path, k=a.knn)[0]
     if rank == 0:
         print("Nomad average scores, printing top 5 test files")
         print(nomad_avg.head())

@@ -3729,6 +3729,75 @@ int nomad_cdist_backward(nomad_ctx* c, const float* a, int Na, const float* b, i
     return 0;
 }
 
+// ---- nearest references (pairwise.hip.h: knn_tile_kernel, knn_merge_kernel, knn_scatter_kernel) ----
+constexpr int kKnnMaxRows = 65535 * kPairTile;   // nomad_cdist_backward's limit: one grid row per 64 rows
+
+// candidates of every (64-column tile, row): k float64 distances, then k int32 columns
+static size_t knn_candidates(int Na, int Nb, int k) { return (size_t)((Nb + kPairTile - 1) / kPairTile) * (size_t)Na * (size_t)k; }
+
+int nomad_knn_scratch_bytes(int Na, int Nb, int k, size_t* bytes) {
+    if (!bytes || Na <= 0 || Nb <= 0 || Na > kKnnMaxRows || Nb > kKnnMaxRows || k < 1 || k > kKnnMax || k > Nb)
+        return fail(NOMAD_ERR_INVALID, "nomad_knn_scratch_bytes: bad argument (Na=%d, Nb=%d, k=%d: 1 .. min(%d, Nb))", Na, Nb, k, kKnnMax);
+    *bytes = knn_candidates(Na, Nb, k) * (sizeof(double) + sizeof(int));
+    return 0;
+}
+
+int nomad_knn(nomad_ctx* c, const float* a, int Na, const float* b, int Nb, int D, int k, double* dist, double* knn_dist, int* knn_idx,
+              double* score, void* scratch, size_t scratch_bytes, nomad_stream_t stream) {
+    if (!c || !a || !b || !knn_dist || !knn_idx || !score || !scratch || Na <= 0 || Nb <= 0 || Na > kKnnMaxRows || Nb > kKnnMaxRows ||
+        D <= 0 || D % 4 || D > kCdistMaxD || k < 1 || k > kKnnMax || k > Nb)
+        return fail(NOMAD_ERR_INVALID,
+                    "nomad_knn: bad argument (Na=%d, Nb=%d, D=%d: a positive multiple of 4, at most %d; k=%d: 1 .. min(%d, Nb))", Na, Nb, D,
+                    kCdistMaxD, k, kKnnMax);
+    const size_t n = knn_candidates(Na, Nb, k);
+    if (scratch_bytes < n * (sizeof(double) + sizeof(int)))
+        return fail(NOMAD_ERR_WORKSPACE, "nomad_knn: scratch of %zu bytes, %zu needed", scratch_bytes, n * (sizeof(double) + sizeof(int)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scope sc(c, s, NOMAD_K_PAIR, 3.0 * D * (double)Na * Nb);
+    double* cand_d = static_cast<double*>(scratch);
+    int* cand_i = reinterpret_cast<int*>(cand_d + n);
+    const int ta = (Na + kPairTile - 1) / kPairTile, tb = (Nb + kPairTile - 1) / kPairTile;
+    if (D == 256)
+        hipLaunchKernelGGL(knn_tile_kernel<256>, dim3(tb, ta), dim3(256), 0, s, a, Na, b, Nb, D, k, dist, cand_d, cand_i);
+    else
+        hipLaunchKernelGGL(knn_tile_kernel<0>, dim3(tb, ta), dim3(256), 0, s, a, Na, b, Nb, D, k, dist, cand_d, cand_i);
+    hipLaunchKernelGGL(knn_merge_kernel, dim3((Na + 3) / 4), dim3(256), 0, s, cand_d, cand_i, tb, Na, k, knn_dist, knn_idx, score);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int nomad_knn_backward_scratch_bytes(int Na, int Nb, int k, size_t* bytes) {
+    if (!bytes || Na <= 0 || Nb <= 0 || Na > kKnnMaxRows || Nb > kKnnMaxRows || k < 1 || k > kKnnMax || k > Nb)
+        return fail(NOMAD_ERR_INVALID, "nomad_knn_backward_scratch_bytes: bad argument (Na=%d, Nb=%d, k=%d: 1 .. min(%d, Nb))", Na, Nb, k,
+                    kKnnMax);
+    *bytes = 2 * sizeof(double) * (size_t)Na * (size_t)Nb;   // the dense upstream G and the weights W, [Na][Nb] each
+    return 0;
+}
+
+// The backward of nomad_knn: the dense upstream of the selected pairs into the scratch, then nomad_cdist_backward's launches on it.
+int nomad_knn_backward(nomad_ctx* c, const float* a, int Na, const float* b, int Nb, int D, int k, const int* knn_idx, const double* g_knn,
+                       const double* g_score, float* da, float* db, void* scratch, size_t scratch_bytes, nomad_stream_t stream) {
+    if (!c || !a || !b || !knn_idx || !scratch || (!g_knn && !g_score) || (!da && !db) || Na <= 0 || Nb <= 0 || Na > kKnnMaxRows ||
+        Nb > kKnnMaxRows || D <= 0 || D % 4 || D > kCdistMaxD || k < 1 || k > kKnnMax || k > Nb)
+        return fail(NOMAD_ERR_INVALID,
+                    "nomad_knn_backward: bad argument (Na=%d, Nb=%d, D=%d: a positive multiple of 4, at most %d; k=%d: 1 .. min(%d, Nb); one "
+                    "upstream and one output at least)", Na, Nb, D, kCdistMaxD, k, kKnnMax);
+    const size_t matrix = sizeof(double) * (size_t)Na * (size_t)Nb;
+    if (scratch_bytes < 2 * matrix)
+        return fail(NOMAD_ERR_WORKSPACE, "nomad_knn_backward: scratch of %zu bytes, %zu needed", scratch_bytes, 2 * matrix);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scope sc(c, s, NOMAD_K_PAIR, (3.0 + 3.0 * ((da != nullptr) + (db != nullptr))) * D * (double)Na * Nb);
+    double* G = static_cast<double*>(scratch);
+    double* W = G + (size_t)Na * (size_t)Nb;   // not G itself: cdist_weights_kernel takes both as __restrict__
+    const int ta = (Na + kPairTile - 1) / kPairTile, tb = (Nb + kPairTile - 1) / kPairTile, tk = (D + kPairTile - 1) / kPairTile;
+    hipLaunchKernelGGL(knn_scatter_kernel, dim3(Na), dim3(256), 0, s, knn_idx, g_knn, g_score, Nb, k, G);
+    hipLaunchKernelGGL(cdist_weights_kernel, dim3(tb, ta), dim3(256), 0, s, a, Na, b, Nb, D, G, static_cast<const double*>(nullptr), W);
+    if (da) hipLaunchKernelGGL(cdist_reduce_kernel<true>, dim3(tk, ta), dim3(256), 0, s, a, Na, b, Nb, D, W, Nb, da);
+    if (db) hipLaunchKernelGGL(cdist_reduce_kernel<false>, dim3(tk, tb), dim3(256), 0, s, b, Nb, a, Na, D, W, Nb, db);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 size_t nomad_l1_scratch_bytes(void) { return sizeof(double) * (kL1Blocks + 8); }
 
 }  // extern "C"

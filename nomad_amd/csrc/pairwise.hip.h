@@ -236,6 +236,189 @@ __global__ __launch_bounds__(256) void cdist_reduce_kernel(const float* __restri
     }
 }
 
+// ---- nearest references (nomad_knn, nomad_knn_backward) --------------------------------------------------------------------------
+// Per row of a the k <= 64 columns smallest under the key (d_ij, j), a NaN distance ordered as +infinity: the forward's chain with a
+// selection epilogue, then a merge of the 64-column tiles in tile order.  The matrix is never formed (it is written only on request).
+//
+// Bound.  The chain is the forward's: 512 fp64 operations per pair at D = 256.  The selection is rank counting: an element's rank
+// in its row of the tile is the number of the row's 64 keys that precede it, 64 comparisons (two compares, a select and an add each:
+// ~4 lane-operations) per pair - ~256 next to the chain's 512, whatever k.  At C3 (10 000 x 1 000) that is 7.7e9 lane-operations,
+// ~0.2 ms at the fp64 vector rate, against 16 x 10 000 x k candidates of 12 bytes written and read once: 15 MB at k = 8 (0.004 ms
+// of HBM time), 123 MB at k = 64 (0.03 ms) - VALU bound like the forward, and at k <= 42 less memory traffic than the 80 MB matrix.
+//
+// knn_tile_kernel: grid and chain of pairwise_tile_kernel.  Behind the chain's last barrier the thread's 4 x 4 keys go into the LDS
+// image's first half as T[row][quad ^ ty][4] (the quads of a row swizzled by the owner's ty: the four ty of a wave read four different
+// quads of their rows - no bank conflict at a row stride of 512 bytes - and the 16 tx lanes of one ty read one address),
+// and every thread counts, for each of its 16 elements, the keys of the element's row that precede it - (key', c') < (key, c), the
+// column order decided at compile time but for the thread's own quad.  Ranks in a row are a permutation of 0 .. 63, so the elements
+// of rank < k fill the row's k candidate slots exactly once: cand_d / cand_i [tile][row][k], ascending.  Columns beyond Nb (the
+// chain's clones of the last row) take the key +infinity behind every real column of their tile - they are the tile's last columns -
+// and leave the sentinel (inf, INT_MAX) in their slot: excluded by index, whatever their value.
+constexpr int kKnnMax = 64;
+constexpr int kKnnNone = 0x7fffffff;
+
+template <int kD>
+__global__ __launch_bounds__(256) void knn_tile_kernel(const float* __restrict__ a, int Na, const float* __restrict__ b, int Nb, int Drt,
+                                                       int k, double* __restrict__ dist, double* __restrict__ cand_d,
+                                                       int* __restrict__ cand_i) {
+    double acc[4][4];
+    PairThread t;
+    double* T = pairwise_chain<kD>(a, Na, b, Nb, Drt, acc, t);
+    const int tx = t.tx, ty = t.ty, r0 = t.r0, d0 = t.d0;
+    const double inf = __builtin_inf();
+    double key[4][4];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int d = d0 + 4 * ty + i;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            acc[i][j] = sqrt(acc[i][j]);   // from here on acc is the distance, as the forwards store it
+            key[i][j] = (r0 + 4 * tx + j < Nb && acc[i][j] == acc[i][j]) ? acc[i][j] : inf;
+        }
+        if (dist && d < Na) {
+            double* dst = dist + (long long)d * Nb + r0 + 4 * tx;
+            if (r0 + 4 * tx + 3 < Nb && (Nb & 1) == 0) {  // 16-byte aligned pairs
+                *reinterpret_cast<double2*>(dst) = make_double2(acc[i][0], acc[i][1]);
+                *reinterpret_cast<double2*>(dst + 2) = make_double2(acc[i][2], acc[i][3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (r0 + 4 * tx + j < Nb) dst[j] = acc[i][j];
+            }
+        }
+        double* row = T + (4 * ty + i) * kPairTile + 4 * (tx ^ ty);
+        *reinterpret_cast<double2*>(row) = make_double2(key[i][0], key[i][1]);
+        *reinterpret_cast<double2*>(row + 2) = make_double2(key[i][2], key[i][3]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int rank[4] = {0, 0, 0, 0};
+        const double* row = T + (4 * ty + i) * kPairTile;
+#pragma unroll 4
+        for (int q = 0; q < 16; ++q) {
+            const double* quad = row + 4 * (q ^ ty);
+            const double2 lo = *reinterpret_cast<const double2*>(quad), hi = *reinterpret_cast<const double2*>(quad + 2);
+            const double kp[4] = {lo.x, lo.y, hi.x, hi.y};
+            const bool qlt = q < tx, qle = q <= tx;   // column 4q + p precedes column 4tx + j: q < tx, or q == tx and p < j
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const bool before = p < j ? qle : qlt;
+                    rank[j] += (before ? kp[p] <= key[i][j] : kp[p] < key[i][j]) ? 1 : 0;
+                }
+        }
+        const int d = d0 + 4 * ty + i;
+        if (d >= Na) continue;
+        const long long slot = ((long long)blockIdx.x * Na + d) * k;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (rank[j] < k) {
+                const bool real = r0 + 4 * tx + j < Nb;
+                cand_d[slot + rank[j]] = real ? acc[i][j] : inf;
+                cand_i[slot + rank[j]] = real ? r0 + 4 * tx + j : kKnnNone;
+            }
+    }
+}
+
+// (d1, i1) precedes (d2, i2) under the contract's key: NaN as +infinity, equal keys by index.
+__device__ __forceinline__ bool knn_before(double d1, int i1, double d2, int i2) {
+    const double k1 = d1 == d1 ? d1 : __builtin_inf(), k2 = d2 == d2 ? d2 : __builtin_inf();
+    return k1 < k2 || (k1 == k2 && i1 < i2);
+}
+// the number of the 64 ascending entries (ld, li) that precede (d, i), or - orEqual - that do not follow it
+__device__ __forceinline__ int knn_count(const double* ld, const int* li, double d, int i, bool orEqual) {
+    int n = 0;
+#pragma unroll
+    for (int step = 32; step >= 1; step >>= 1) {
+        const int at = n + step - 1;
+        if (orEqual ? !knn_before(d, i, ld[at], li[at]) : knn_before(ld[at], li[at], d, i)) n += step;
+    }
+    if (orEqual ? !knn_before(d, i, ld[n], li[n]) : knn_before(ld[n], li[n], d, i)) n += 1;
+    return n;
+}
+
+// knn_merge_kernel: one wave per row of a, four rows per workgroup (grid ceil(Na / 4)), lane r = slot r of the row's running best
+// 64 in LDS (sentinels behind the real entries).  The tiles are merged in order, a stable two-way merge per tile: lane c holds the
+// tile's candidate c (a sentinel from c = k on) and both lists are ascending, so an entry's place in the union is its own position
+// plus the number of entries of the other list in front of it - a 7-step binary search -, running entries before equal candidates.
+// The 128 places are distinct; those below 64 are the new running list, written to the other half of a double buffer.  Fixed order,
+// no atomics: a row's result depends on its own candidates only.  Then knn_dist / knn_idx [Na][k] from slots 0 .. k - 1 and
+// score_i = (sum of the k distances, r ascending, one float64 accumulator from 0.0) / (double)k by lane 0.
+__global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict__ cand_d, const int* __restrict__ cand_i, int ntiles,
+                                                        int Na, int k, double* __restrict__ knn_dist, int* __restrict__ knn_idx,
+                                                        double* __restrict__ score) {
+    __shared__ double run_d[2][4][kKnnMax];
+    __shared__ int run_i[2][4][kKnnMax];
+    __shared__ double new_d[4][kKnnMax];
+    __shared__ int new_i[4][kKnnMax];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int row = min(blockIdx.x * 4 + w, Na - 1);   // a wave behind the last row repeats it and stores nothing: barriers stay uniform
+    const bool live = blockIdx.x * 4 + w < Na;
+    run_d[0][w][lane] = __builtin_inf();
+    run_i[0][w][lane] = kKnnNone;
+    int cur = 0;
+    double next_d = __builtin_inf();
+    int next_i = kKnnNone;
+    if (lane < k) {
+        next_d = cand_d[(long long)row * k + lane];
+        next_i = cand_i[(long long)row * k + lane];
+    }
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const double cd = next_d;
+        const int ci = next_i;
+        if (tile + 1 < ntiles && lane < k) {   // the next tile's candidates are on their way while this tile is merged
+            const long long slot = ((long long)(tile + 1) * Na + row) * k;
+            next_d = cand_d[slot + lane];
+            next_i = cand_i[slot + lane];
+        }
+        new_d[w][lane] = cd;
+        new_i[w][lane] = ci;
+        __syncthreads();
+        const double rd = run_d[cur][w][lane];
+        const int ri = run_i[cur][w][lane];
+        const int rpos = lane + knn_count(new_d[w], new_i[w], rd, ri, false);
+        const int cpos = lane + knn_count(run_d[cur][w], run_i[cur][w], cd, ci, true);
+        if (rpos < kKnnMax) {
+            run_d[cur ^ 1][w][rpos] = rd;
+            run_i[cur ^ 1][w][rpos] = ri;
+        }
+        if (cpos < kKnnMax) {
+            run_d[cur ^ 1][w][cpos] = cd;
+            run_i[cur ^ 1][w][cpos] = ci;
+        }
+        cur ^= 1;
+        __syncthreads();
+    }
+    if (!live) return;
+    if (lane < k) {
+        knn_dist[(long long)row * k + lane] = run_d[cur][w][lane];
+        knn_idx[(long long)row * k + lane] = run_i[cur][w][lane];
+    }
+    if (lane == 0) {
+        double s = 0.0;
+        for (int r = 0; r < k; ++r) s += run_d[cur][w][r];
+        score[row] = s / (double)k;
+    }
+}
+
+// The dense upstream of nomad_knn_backward in the caller's scratch: row i of G [Na][Nb] is zero but for
+// G[i][knn_idx[i][r]] = g_knn[i][r] + g_score[i] / k (a NULL upstream counts as 0); an index outside 0 .. Nb - 1 is skipped.
+// grid: Na workgroups of 256 threads, one per row - zero, barrier, scatter (the indices of a row are distinct: no collisions).
+__global__ __launch_bounds__(256) void knn_scatter_kernel(const int* __restrict__ knn_idx, const double* __restrict__ g_knn,
+                                                          const double* __restrict__ g_score, int Nb, int k, double* __restrict__ G) {
+    const long long i = blockIdx.x;
+    double* g = G + i * Nb;
+    for (int j = threadIdx.x; j < Nb; j += 256) g[j] = 0.0;
+    __syncthreads();
+    if (threadIdx.x < k) {
+        const int j = knn_idx[i * k + threadIdx.x];
+        if (j >= 0 && j < Nb) g[j] = (g_knn ? g_knn[i * k + threadIdx.x] : 0.0) + (g_score ? g_score[i] / (double)k : 0.0);
+    }
+}
+
 // paired_distance_kernel: out[i] = ||a_i - b_i||, the chain of pairwise_tile_kernel for the pair (i, i) - bit-identical to the
 // diagonal of the matrix, without the other N - 1 columns (10 000 pairs: 8 x 10^4 bytes written instead of 8 x 10^8).
 // grid: ceil(N / 64) workgroups of 256 threads, one per 64 pairs.  A 64-deep k-chunk of both operands is staged through LDS as

@@ -478,15 +478,74 @@ class Engine:
                 raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {self.device}")
         n = C.c_size_t()
         _lib.check(self.lib.nomad_cdist_backward_scratch_bytes(Na, Nb, C.byref(n)), "nomad_cdist_backward_scratch_bytes")
-        if self._cdist_scratch is None or self._cdist_scratch.numel() < n.value:
-            self._cdist_scratch = None
-            self._cdist_scratch = torch.empty(n.value, dtype=torch.uint8, device=self.device)
-        self._cdist_scratch.record_stream(torch.cuda.current_stream(self.device))
+        scratch = self._distance_scratch(n.value)
         da = torch.empty(Na, D, dtype=torch.float32, device=self.device) if want_a else None
         db = torch.empty(Nb, D, dtype=torch.float32, device=self.device) if want_b else None
         _lib.check(self.lib.nomad_cdist_backward(self.ctx, a.data_ptr(), Na, b.data_ptr(), Nb, D, _ptr(g_dist), _ptr(g_mean), _ptr(da),
-                                                 _ptr(db), self._cdist_scratch.data_ptr(), self._cdist_scratch.numel(),
+                                                 _ptr(db), scratch.data_ptr(), scratch.numel(),
                                                  self._stream()), "nomad_cdist_backward")
+        return da, db
+
+    def _distance_scratch(self, nbytes: int) -> torch.Tensor:
+        """The cached scratch of ``cdist_backward`` / ``knn`` / ``knn_backward``, grown on demand (calls on one stream are ordered)."""
+        if self._cdist_scratch is None or self._cdist_scratch.numel() < nbytes:
+            self._cdist_scratch = None
+            self._cdist_scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        self._cdist_scratch.record_stream(torch.cuda.current_stream(self.device))
+        return self._cdist_scratch
+
+    def _check_knn(self, a: torch.Tensor, b: torch.Tensor, k):
+        self._check_dev(a, "a")
+        self._check_dev(b, "b")
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError("a and b must be matrices with rows of one width")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min(64, b.shape[0]):
+            raise ValueError(f"k must be an integer from 1 to min(64, rows of b = {b.shape[0]}), got {k!r}")
+        return a.shape[0], b.shape[0], a.shape[1]
+
+    def knn(self, a: torch.Tensor, b: torch.Tensor, k: int, want_matrix: bool = False):
+        """a (Na,D), b (Nb,D) fp32 on the GPU as ``cdist`` takes them, 1 <= k <= min(64, Nb) -> (knn_dist (Na,k) float64, knn_idx
+        (Na,k) int32, score (Na,) float64[, dist (Na,Nb) float64]): per row of a the k rows of b at the smallest distance, ascending
+        under (distance, index) with NaN as +infinity, and their mean.  The distances are ``cdist``'s bits; without ``want_matrix``
+        the matrix is never formed (``nomad_knn``)."""
+        Na, Nb, D = self._check_knn(a, b, k)
+        n = C.c_size_t()
+        _lib.check(self.lib.nomad_knn_scratch_bytes(Na, Nb, k, C.byref(n)), "nomad_knn_scratch_bytes")
+        scratch = self._distance_scratch(n.value)
+        dist = torch.empty(Na, Nb, dtype=torch.float64, device=self.device) if want_matrix else None
+        knn_dist = torch.empty(Na, k, dtype=torch.float64, device=self.device)
+        knn_idx = torch.empty(Na, k, dtype=torch.int32, device=self.device)
+        score = torch.empty(Na, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.nomad_knn(self.ctx, a.data_ptr(), Na, b.data_ptr(), Nb, D, k, _ptr(dist), knn_dist.data_ptr(),
+                                      knn_idx.data_ptr(), score.data_ptr(), scratch.data_ptr(), scratch.numel(), self._stream()),
+                   "nomad_knn")
+        return (knn_dist, knn_idx, score, dist) if want_matrix else (knn_dist, knn_idx, score)
+
+    def knn_backward(self, a: torch.Tensor, b: torch.Tensor, knn_idx: torch.Tensor, g_knn: Optional[torch.Tensor] = None,
+                     g_score: Optional[torch.Tensor] = None, want_a: bool = True, want_b: bool = True):
+        """The backward of ``knn(a, b, k)`` with the selection ``knn_idx`` (Na,k) int32 held fixed: g_knn (Na,k) and / or g_score
+        (Na,) float64, the upstreams of the neighbour distances and of their mean -> (da (Na,D) or None, db (Nb,D) or None), fp32:
+        the bits of ``cdist_backward`` fed the dense upstream of the selected pairs (``nomad_knn_backward``)."""
+        if not (torch.is_tensor(knn_idx) and knn_idx.is_cuda and knn_idx.dtype == torch.int32 and knn_idx.dim() == 2
+                and knn_idx.is_contiguous() and knn_idx.shape[0] == a.shape[0]):
+            raise ValueError(f"knn_idx must be a contiguous int32 tensor of shape (rows of a, k) on {self.device}")
+        k = int(knn_idx.shape[1])
+        Na, Nb, D = self._check_knn(a, b, k)
+        if g_knn is None and g_score is None:
+            raise ValueError("knn_backward needs g_knn, g_score or both")
+        if not (want_a or want_b):
+            raise ValueError("knn_backward needs want_a, want_b or both")
+        for g, shape, name in ((g_knn, (Na, k), "g_knn"), (g_score, (Na,), "g_score")):
+            if g is not None and not (g.is_cuda and g.dtype == torch.float64 and g.is_contiguous() and tuple(g.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {self.device}")
+        n = C.c_size_t()
+        _lib.check(self.lib.nomad_knn_backward_scratch_bytes(Na, Nb, k, C.byref(n)), "nomad_knn_backward_scratch_bytes")
+        scratch = self._distance_scratch(n.value)
+        da = torch.empty(Na, D, dtype=torch.float32, device=self.device) if want_a else None
+        db = torch.empty(Nb, D, dtype=torch.float32, device=self.device) if want_b else None
+        _lib.check(self.lib.nomad_knn_backward(self.ctx, a.data_ptr(), Na, b.data_ptr(), Nb, D, k, knn_idx.data_ptr(), _ptr(g_knn),
+                                               _ptr(g_score), _ptr(da), _ptr(db), scratch.data_ptr(), scratch.numel(),
+                                               self._stream()), "nomad_knn_backward")
         return da, db
 
     def paired_distance(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -353,6 +353,19 @@ def check_references(references) -> None:
         raise ValueError("references holds no embedding: the score is a mean over at least one reference")
 
 
+KNN_MAX = 64   # nomad_knn's widest neighbourhood
+
+
+def check_k(k, Nr: int) -> int:
+    """The ``k`` of the nearest-reference scores against a bank of ``Nr`` references: an integer (not a bool) from 1 to
+    ``min(64, Nr)``.  Pure; raises before any engine call."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"k must be an integer from 1 to min({KNN_MAX}, the number of references = {Nr}), got {k!r}")
+    if k < 1 or k > KNN_MAX or k > Nr:
+        raise ValueError(f"k = {int(k)} is outside 1 .. min({KNN_MAX}, the number of references = {Nr})")
+    return int(k)
+
+
 FRAMES_PER_SECOND = 50   # one encoder frame is 320 samples at 16 kHz; its receptive field is 400 samples
 
 
@@ -392,6 +405,20 @@ def segments_tables(test_files, frames, scores, win: int, hop: int):
     means = [scores[e - c:e].mean() for c, e in zip(counts, ends)]
     df_mean = pd.DataFrame({"Test File": list(test_files), "NOMAD": np.asarray(means, dtype=np.float64)}).set_index("Test File").round(3)
     return df, df_mean
+
+
+def nearest_table(test_files, ref_names, knn_dist, knn_idx) -> pd.DataFrame:
+    """The third table of ``Nomad.predict(k=...)``: one row per test file, indexed by ``Test File``, with the columns ``Ref 1``,
+    ``Dist 1``, ... ``Ref k``, ``Dist k`` - the names of the file's nearest references (as the matrix's columns are named), nearest
+    first, and the distances rounded to 3 decimals.  knn_dist (N,k) float64, knn_idx (N,k) integers into ``ref_names``."""
+    knn_dist = np.asarray(knn_dist, dtype=np.float64)
+    knn_idx = np.asarray(knn_idx, dtype=np.int64)
+    names = np.asarray(list(ref_names), dtype=object)
+    cols = {"Test File": list(test_files)}
+    for r in range(knn_idx.shape[1]):
+        cols[f"Ref {r + 1}"] = names[knn_idx[:, r]] if len(names) else np.zeros(0, dtype=object)
+        cols[f"Dist {r + 1}"] = np.round(knn_dist[:, r], 3)
+    return pd.DataFrame(cols).set_index("Test File")
 
 
 def _check_predict_paths(mode, nmr, deg) -> None:
@@ -459,10 +486,11 @@ def cdist(engine: Engine, a: torch.Tensor, b: torch.Tensor):
 
 class _ScoreFn(torch.autograd.Function):
     """score[b] = mean_j ||emb(estimate_b) - references_j|| with the checkpoint's head; backward = d / d estimate through
-    ``cdist_backward`` and ``embed_backward[_ragged]`` (layer gradients NULL) and, when asked for, d / d references."""
+    ``cdist_backward`` and ``embed_backward[_ragged]`` (layer gradients NULL) and, when asked for, d / d references.  With ``k`` the
+    mean runs over the k nearest references (``Engine.knn``; the backward is ``Engine.knn_backward`` on the saved selection)."""
 
     @staticmethod
-    def forward(ctx, estimate, references, nomad, lens):
+    def forward(ctx, estimate, references, nomad, lens, k):
         eng = nomad.engine
         est = estimate.detach().to(eng.device, torch.float32).contiguous()
         est = est.squeeze(1) if est.dim() == 3 else est
@@ -475,21 +503,28 @@ class _ScoreFn(torch.autograd.Function):
             emb, layers, saved = eng.embed_train(est)
         else:
             emb, layers, saved, (est, _) = eng.embed_train_ragged(est, lens)
-        _, mean = eng.pairwise(emb, refs, want_matrix=False)
-        ctx.save_for_backward(est, refs, emb, layers, saved)
+        idx = None
+        if k is None:
+            _, mean = eng.pairwise(emb, refs, want_matrix=False)
+        else:
+            _, idx, mean = eng.knn(emb, refs, k)
+        ctx.save_for_backward(est, refs, emb, layers, saved, idx)
         return mean
 
     @staticmethod
     def backward(ctx, grad_out):
-        est, refs, emb, layers, saved = ctx.saved_tensors
+        est, refs, emb, layers, saved, idx = ctx.saved_tensors
         eng = ctx.nomad.engine
         shape, ref_device, ref_dtype = ctx.meta
         want_a = ctx.needs_input_grad[0] and saved is not None
         want_b = ctx.needs_input_grad[1]
         if not (want_a or want_b):
-            return None, None, None, None
+            return None, None, None, None, None
         g = grad_out.to(eng.device, torch.float64).contiguous()
-        demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
+        if idx is None:
+            demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
+        else:
+            demb, dref = eng.knn_backward(emb, refs, idx, g_score=g, want_a=want_a, want_b=want_b)
         dwav = None
         if want_a:
             Nomad._need_whole_encoder(eng)
@@ -500,16 +535,16 @@ class _ScoreFn(torch.autograd.Function):
             dwav = dwav.reshape(shape)
         if dref is not None:
             dref = dref.to(ref_device, ref_dtype)
-        return dwav, dref, None, None
+        return dwav, dref, None, None, None
 
 
 class _WindowScoreFn(torch.autograd.Function):
     """scores[w] = mean_j ||emb_w(window w of estimate) - references_j|| over the windows of ``Engine.embed_train_windows*``;
     backward = ``cdist_backward`` over the window rows, then ``embed_windows_backward[_ragged]`` (the windowed head's backward
-    and the backbone down to the waveform) and, when asked for, d / d references."""
+    and the backbone down to the waveform) and, when asked for, d / d references.  ``k``: as in ``_ScoreFn``."""
 
     @staticmethod
-    def forward(ctx, estimate, references, nomad, lens, win, hop):
+    def forward(ctx, estimate, references, nomad, lens, win, hop, k):
         eng = nomad.engine
         est = estimate.detach().to(eng.device, torch.float32).contiguous()
         est = est.squeeze(1) if est.dim() == 3 else est
@@ -527,22 +562,29 @@ class _WindowScoreFn(torch.autograd.Function):
             emb, _, layers, saved = eng.embed_train_windows(est, win, hop)
         else:
             emb, _, layers, saved, (est, _) = eng.embed_train_windows_ragged(est, win, hop, lens)
-        _, mean = eng.pairwise(emb, refs, want_matrix=False)
-        ctx.save_for_backward(est, refs, emb, layers, saved)
+        idx = None
+        if k is None:
+            _, mean = eng.pairwise(emb, refs, want_matrix=False)
+        else:
+            _, idx, mean = eng.knn(emb, refs, k)
+        ctx.save_for_backward(est, refs, emb, layers, saved, idx)
         return mean
 
     @staticmethod
     def backward(ctx, grad_out):
-        est, refs, emb, layers, saved = ctx.saved_tensors
+        est, refs, emb, layers, saved, idx = ctx.saved_tensors
         eng = ctx.nomad.engine
         shape, ref_device, ref_dtype = ctx.meta
         win, hop = ctx.geom
         want_a = ctx.needs_input_grad[0] and saved is not None
         want_b = ctx.needs_input_grad[1]
         if not (want_a or want_b):
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         g = grad_out.to(eng.device, torch.float64).contiguous()
-        demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
+        if idx is None:
+            demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
+        else:
+            demb, dref = eng.knn_backward(emb, refs, idx, g_score=g, want_a=want_a, want_b=want_b)
         dwav = None
         if want_a:
             Nomad._need_whole_encoder(eng)
@@ -553,7 +595,7 @@ class _WindowScoreFn(torch.autograd.Function):
             dwav = dwav.reshape(shape)
         if dref is not None:
             dref = dref.to(ref_device, ref_dtype)
-        return dwav, dref, None, None, None, None
+        return dwav, dref, None, None, None, None, None
 
 
 class GraphedLoss:
@@ -903,7 +945,12 @@ class Nomad:
         return self
 
     # ------------------------------------------------------------------------------------------
-    def predict(self, mode="dir", nmr="data/nmr-data", deg="data/test-data", results_path=None):
+    def predict(self, mode="dir", nmr="data/nmr-data", deg="data/test-data", results_path=None, k=None):
+        """The reference's ``predict`` -> (df_avg, df_scores).  With ``k`` (1 .. min(64, references)) the ``NOMAD`` column is the mean
+        distance to the file's ``k`` NEAREST references instead of all of them, the score matrix (``nomad_scores.csv``) is unchanged,
+        and a third table comes back - ``nearest_table``, written to ``nomad_nearest.csv`` -: -> (df_avg, df_scores, df_nearest)."""
+        if k is not None:
+            check_k(k, KNN_MAX)   # the type and 1 .. 64 before any file is read; against the bank's size once it is known
         if nmr is None:
             raise Exception("nmr_path not specified, you need to pass a valid value to nmr_path")
         if deg is None:
@@ -932,6 +979,9 @@ class Nomad:
         deg_t = torch.from_numpy(np.ascontiguousarray(test_embeddings.to_numpy(dtype=np.float32))).to(self.engine.device)
         ref_t = torch.from_numpy(np.ascontiguousarray(nmr_embeddings.to_numpy(dtype=np.float32))).to(self.engine.device)
         world, rank, collective = _dist_info(getattr(self, "group", None))
+        if k is not None:
+            k = check_k(k, ref_t.shape[0])
+            knn_d, knn_i = torch.zeros(0, k, dtype=torch.float64), torch.zeros(0, k, dtype=torch.int32)
         if deg_t.shape[0] == 0 or ref_t.shape[0] == 0:
             # an empty directory: what cdist + np.mean(axis=1) give the reference - an empty matrix, and NaN means when
             # there is no reference to average over (the engine's kernels take no empty operands)
@@ -940,12 +990,20 @@ class Nomad:
             mean = torch.full((deg_t.shape[0],), float("nan"), dtype=torch.float64)
         elif collective:   # this rank's slab of the matrix (its slice of the degraded files x all references), then one gather
             lo, hi = partition(deg_t.shape[0], world, rank)
-            if hi > lo:
+            if hi > lo and k is not None:   # the neighbours of this rank's rows: gathered as the means are
+                knn_d, knn_i, mean, dist = self.engine.knn(deg_t[lo:hi].contiguous(), ref_t, k, want_matrix=True)
+            elif hi > lo:
                 dist, mean = self.engine.pairwise(deg_t[lo:hi].contiguous(), ref_t, want_matrix=True)
             else:
                 dist = torch.zeros(0, ref_t.shape[0], dtype=torch.float64, device=deg_t.device)
                 mean = torch.zeros(0, dtype=torch.float64, device=deg_t.device)
+                if k is not None:
+                    knn_d, knn_i = knn_d.to(deg_t.device), knn_i.to(deg_t.device)
             dist, mean = self._all_gather_rows(dist), self._all_gather_rows(mean)
+            if k is not None:
+                knn_d, knn_i = self._all_gather_rows(knn_d), self._all_gather_rows(knn_i)
+        elif k is not None:
+            knn_d, knn_i, mean, dist = self.engine.knn(deg_t, ref_t, k, want_matrix=True)
         else:
             dist, mean = self.engine.pairwise(deg_t, ref_t, want_matrix=True)
         distance_matrix = dist.cpu().numpy()
@@ -958,6 +1016,8 @@ class Nomad:
         df_dm["Test File"] = test_files
         df_dm.set_index("Test File", inplace=True)
         df_dm.columns = [x.split("/")[-1].split(".")[0] for x in nmr_embeddings.index]
+        if k is not None:
+            df_nearest = nearest_table(test_files, df_dm.columns, knn_d.cpu().numpy(), knn_i.cpu().numpy())
 
         if results_path is None:
             dt_string = datetime.now().strftime("%d-%m-%Y_%H-%M-%S")
@@ -966,14 +1026,18 @@ class Nomad:
                 os.makedirs(out_dir, exist_ok=True)
             results_avg_path = os.path.join(out_dir, f"{dt_string}_nomad_avg.csv")
             results_scores_path = os.path.join(out_dir, f"{dt_string}_nomad_scores.csv")
+            results_nearest_path = os.path.join(out_dir, f"{dt_string}_nomad_nearest.csv")
         else:
             results_avg_path = os.path.join(results_path, "nomad_avg.csv")
             results_scores_path = os.path.join(results_path, "nomad_scores.csv")
+            results_nearest_path = os.path.join(results_path, "nomad_nearest.csv")
 
         if rank == 0:   # every rank returns the tables, one writes the files
             df_avg_nomad.reset_index().to_csv(results_avg_path, index=False)
             _write_rounded_csv(df_dm.reset_index(), results_scores_path)
-        return df_avg_nomad, df_dm
+            if k is not None:
+                df_nearest.reset_index().to_csv(results_nearest_path, index=False)
+        return (df_avg_nomad, df_dm) if k is None else (df_avg_nomad, df_dm, df_nearest)
 
     def forward(self, estimate, clean, lengths=None, *, layer_weights=None, reduction="mean"):
         """NOMAD loss (nomad.py:142-146), differentiable w.r.t. ``estimate`` - and w.r.t. ``clean`` when it requires a gradient:
@@ -1032,7 +1096,37 @@ class Nomad:
             return eng.embed_bf16(wav)
         return eng.embed_bf16x3(wav) if _takes_bf16x3(self.precision, wav) else eng.embed(wav)
 
-    def score(self, estimate, references, lengths=None, reduction="none"):
+    def _reference_mean(self, emb: torch.Tensor, refs: torch.Tensor, k) -> torch.Tensor:
+        """(N,) float64: the mean distance of every embedding to all references (``Engine.pairwise``), or to its k nearest."""
+        if k is None:
+            return self.engine.pairwise(emb, refs, want_matrix=False)[1]
+        return self.engine.knn(emb, refs, k)[2]
+
+    def nearest_references(self, wav_or_embeddings, references, k, lengths=None):
+        """-> (knn_dist (N,k) float64, knn_idx (N,k) int32) on the GPU: for every clip the distances to and the rows of its ``k``
+        nearest ``references`` ((Nr,256), as ``score`` takes them), ascending by (distance, row).  A (N,256) tensor is taken as
+        embeddings; a (B,1,N) or (B,N) tensor as waveforms, embedded by the scoring forward of ``precision`` (``lengths`` as in
+        ``score``).  No gradient."""
+        check_references(references)
+        k = check_k(k, references.shape[0])
+        x = wav_or_embeddings
+        if not torch.is_tensor(x) or x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
+            raise ValueError(f"expected (N,{EMB_DIM}) embeddings or (B,1,N) / (B,N) waveforms, got {tuple(getattr(x, 'shape', ()))}")
+        eng = self.engine
+        refs = references.detach().to(eng.device, torch.float32).contiguous()
+        x = x.detach().to(eng.device, torch.float32).contiguous()
+        if x.dim() == 2 and x.shape[1] == EMB_DIM:
+            if lengths is not None:
+                raise ValueError("lengths go with waveforms: a (N,256) tensor is taken as embeddings")
+            emb = x
+        else:
+            lens = check_lengths(wav_or_embeddings, lengths) if lengths is not None else None
+            self._need_whole_encoder(eng)
+            emb = self._score_embed(x.squeeze(1) if x.dim() == 3 else x, lens)
+        knn_dist, knn_idx, _ = eng.knn(emb, refs, k)
+        return knn_dist, knn_idx
+
+    def score(self, estimate, references, lengths=None, reduction="none", k=None):
         """The NOMAD score as a differentiable quantity: ``score[b] = mean_j ||emb(estimate_b) - references_j||`` in float64, the
         number ``predict`` reports for a file - no matching clean signal is needed, only a bank of reference embeddings.
 
@@ -1045,28 +1139,35 @@ class Nomad:
         a gradient the forward is ``embed_train[_ragged]`` (fp32 buffers, products by ``Engine.gemm_precision``), and the backward
         runs ``cdist_backward`` - float64, a reference equal to the embedding contributes nothing - then the head, the
         normalisation and the backbone down to the waveform; the gradient carries ``feature_grad_mult`` exactly as
-        ``forward()``'s does and is zero behind every length.  ``references`` gets a gradient too when it requires one."""
+        ``forward()``'s does and is zero behind every length.  ``references`` gets a gradient too when it requires one.
+
+        k (1 .. min(64, Nr)): the mean over the ``k`` NEAREST references instead of all of them - for a bank that mixes speakers,
+        rooms and microphones the distance to the closest clean speech known, and as a loss a pull towards clean speech that is
+        like the estimate rather than towards the bank's centroid.  ``Engine.knn`` takes ``Engine.pairwise``'s place (the same
+        distances, ties to the lower row) and ``Engine.knn_backward`` ``cdist_backward``'s, with the forward's selection held fixed;
+        ``k=None`` is the mean over the whole bank, unchanged."""
         check_reduction(reduction)
         check_references(references)
+        k = check_k(k, references.shape[0]) if k is not None else None
         if not torch.is_tensor(estimate) or estimate.dim() not in (2, 3) or (estimate.dim() == 3 and estimate.shape[1] != 1):
             raise ValueError(f"estimate must be (B,1,N) or (B,N), got {tuple(getattr(estimate, 'shape', ()))}")
         lens = check_lengths(estimate, lengths) if lengths is not None else None
         self._need_whole_encoder(self.engine)
         if torch.is_grad_enabled() and (estimate.requires_grad or references.requires_grad):
-            scores = _ScoreFn.apply(estimate, references, self, lens)
+            scores = _ScoreFn.apply(estimate, references, self, lens, k)
         else:
             eng = self.engine
             est = estimate.detach().to(eng.device, torch.float32).contiguous()
             est = est.squeeze(1) if est.dim() == 3 else est
             refs = references.detach().to(eng.device, torch.float32).contiguous()
-            scores = eng.pairwise(self._score_embed(est, lens), refs, want_matrix=False)[1]
+            scores = self._reference_mean(self._score_embed(est, lens), refs, k)
         return scores.mean() if reduction == "mean" else scores
 
     def _window_precision(self, n_samples: int) -> str:
         """The forward the windows of a batch of ``n_samples`` samples take: ``precision``, with the file pipeline's rule for bf16x3."""
         return "fp32" if self.precision == "bf16x3" and n_samples < BF16X3_MIN_SAMPLES else self.precision
 
-    def score_over_time(self, wav, references, window_s=4.0, hop_s=2.0, lengths=None):
+    def score_over_time(self, wav, references, window_s=4.0, hop_s=2.0, lengths=None, k=None):
         """NOMAD scores over time: -> (scores (W_total,) float64 on the GPU, counts) - for every window of ``window_s`` seconds
         every ``hop_s`` seconds the mean distance of the window's embedding to ``references`` ((Nr,256), as ``score`` takes
         them); clip 0's windows in order, then clip 1's, ...; counts[c] = windows of clip c.  wav (B,1,N) or (B,N) on the GPU;
@@ -1077,9 +1178,10 @@ class Nomad:
         the bits of ``score`` -, frames behind the last full window belong to no window.  All windows come from ONE forward
         of ``precision`` (``Engine.embed_windows*``): attention and the first conv layer's GroupNorm statistics saw the whole
         clip, so a window's score is not the score of the excerpt on its own.  No gradient is produced: ``score_windows`` is the
-        differentiable form of this call."""
+        differentiable form of this call.  k: every window's mean over its ``k`` nearest references, as in ``score``."""
         win, hop = window_frames(window_s, hop_s)
         check_references(references)
+        k = check_k(k, references.shape[0]) if k is not None else None
         if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
             raise ValueError(f"wav must be (B,1,N) or (B,N), got {tuple(getattr(wav, 'shape', ()))}")
         if wav.requires_grad or references.requires_grad:
@@ -1096,9 +1198,9 @@ class Nomad:
                                                    precision=self._window_precision(sum(lens)))
         else:
             emb, counts = eng.embed_windows(x, win, hop, precision=self._window_precision(x.numel()))
-        return eng.pairwise(emb, refs, want_matrix=False)[1], counts
+        return self._reference_mean(emb, refs, k), counts
 
-    def score_windows(self, estimate, references, window_s=4.0, hop_s=2.0, lengths=None, reduction="none"):
+    def score_windows(self, estimate, references, window_s=4.0, hop_s=2.0, lengths=None, reduction="none", k=None):
         """``score_over_time`` as a differentiable quantity: -> (scores (W_total,) float64, counts), the windows, their order and
         ``counts`` exactly those of ``score_over_time`` (``window_frames``, ``weights.num_windows``); with reduction="mean" the
         0-dim mean over all windows in place of ``scores``.  A loss on where a recording is bad is plain torch on that tensor -
@@ -1117,23 +1219,25 @@ class Nomad:
         gradients of the windows that cover it, exact zeros where none does - and the backbone down to the waveform.  The
         encoder saw the whole clip: a window's gradient reaches every sample of its clip through attention, not only the
         window's own samples.  It carries ``feature_grad_mult`` as ``score``'s does and is zero behind every length;
-        ``references`` gets a gradient too when it requires one."""
+        ``references`` gets a gradient too when it requires one.  k: every window's mean over its ``k`` nearest references, as
+        in ``score`` (``Engine.knn`` / ``Engine.knn_backward`` over the window rows)."""
         win, hop = window_frames(window_s, hop_s)
         check_reduction(reduction)
         check_references(references)
+        k = check_k(k, references.shape[0]) if k is not None else None
         if not torch.is_tensor(estimate) or estimate.dim() not in (2, 3) or (estimate.dim() == 3 and estimate.shape[1] != 1):
             raise ValueError(f"estimate must be (B,1,N) or (B,N), got {tuple(getattr(estimate, 'shape', ()))}")
         lens = check_lengths(estimate, lengths) if lengths is not None else None
         if not (torch.is_grad_enabled() and (estimate.requires_grad or references.requires_grad)):
-            scores, counts = self.score_over_time(estimate.detach(), references.detach(), window_s, hop_s, lengths)
+            scores, counts = self.score_over_time(estimate.detach(), references.detach(), window_s, hop_s, lengths, k)
         else:
             self._need_whole_encoder(self.engine)
-            scores = _WindowScoreFn.apply(estimate, references, self, lens, win, hop)
+            scores = _WindowScoreFn.apply(estimate, references, self, lens, win, hop, k)
             samples = lens if lens is not None else [estimate.shape[-1]] * estimate.shape[0]
             counts = [num_windows(num_frames(n), win, hop) for n in samples]
         return (scores.mean() if reduction == "mean" else scores), counts
 
-    def _score_file_windows(self, paths, ref_t, win: int, hop: int, max_batch_samples: int):
+    def _score_file_windows(self, paths, ref_t, win: int, hop: int, max_batch_samples: int, k=None):
         """The file pipeline of ``get_embeddings_csv`` with the windowed head: -> (frames per file, window scores float64, files
         in order).  Each staged ragged batch is embedded in windows and scored against ``ref_t`` on the GPU; only the scores
         come back, one batch late."""
@@ -1158,7 +1262,7 @@ class Nomad:
                                                            packed=packed)
             uploaded()
             # (no reference to average over: NaN, what predict reports then - the distance kernels take no empty operand)
-            fetch = self.engine.fetch_async(self.engine.pairwise(emb, ref_t, want_matrix=False)[1]) if ref_t.shape[0] else None
+            fetch = self.engine.fetch_async(self._reference_mean(emb, ref_t, k)) if ref_t.shape[0] else None
             if pending is not None:
                 collect(pending)
             pending = (idxs, counts, fetch)
@@ -1167,7 +1271,7 @@ class Nomad:
         return frames, (np.concatenate(scores) if scores else np.zeros(0))
 
     def predict_segments(self, mode="dir", nmr="data/nmr-data", deg="data/test-data", window_s=4.0, hop_s=2.0, results_path=None,
-                         max_batch_samples: int = 256 * 64000):
+                         max_batch_samples: int = 256 * 64000, k=None):
         """``predict`` over time: -> (df_segments, df_avg).  df_segments has one row per window of every test file, files in
         listing order: ``Test File``, ``start_s``, ``end_s`` (``window_times``) and ``NOMAD``, the window's mean distance to the
         reference embeddings, rounded to 3 decimals; df_avg, indexed by ``Test File``, the mean of each file's window scores.
@@ -1175,8 +1279,11 @@ class Nomad:
         Arguments, checks and file listing as in ``predict``.  The reference files are embedded whole; the test files go through
         the staged ragged batches of ``get_embeddings_csv`` with the windowed head (``score_over_time`` says what a window
         is: pooled from one forward over the whole file).  With ``results_path`` the segment table is written to
-        ``segments.csv`` there.  One process only: inside a torch.distributed job of several ranks it raises."""
+        ``segments.csv`` there.  One process only: inside a torch.distributed job of several ranks it raises.  k: a window's
+        ``NOMAD`` is its mean distance to its ``k`` nearest references (``score_over_time(k=...)``)."""
         win, hop = window_frames(window_s, hop_s)
+        if k is not None:
+            check_k(k, KNN_MAX)
         _check_predict_paths(mode, nmr, deg)
         world, _, _ = _dist_info(getattr(self, "group", None))
         if world > 1:
@@ -1187,7 +1294,9 @@ class Nomad:
         print(f"Compute degraded embeddings over windows of {win} frames every {hop} from {deg}")
         paths = [str(p) for p in _file_table(deg)["filename"]]
         ref_t = torch.from_numpy(np.ascontiguousarray(nmr_embeddings.to_numpy(dtype=np.float32))).to(self.engine.device)
-        frames, scores = self._score_file_windows(paths, ref_t, win, hop, max_batch_samples)
+        if k is not None:
+            k = check_k(k, ref_t.shape[0])
+        frames, scores = self._score_file_windows(paths, ref_t, win, hop, max_batch_samples, k)
         test_files = [x.split("/")[-1].split(".")[0] for x in paths]
         df, df_mean = segments_tables(test_files, frames, scores, win, hop)
         if results_path is not None:
