@@ -21,6 +21,8 @@
  *   nomad_knn / nomad_knn_backward the k nearest rows of a bank and their mean distance, matrix-free, and its gradient (the
  *                                  nearest-reference NOMAD score as a score and as a loss)
  *   nomad_embed_windows_backward   d / d waveform of the window embeddings (scores over time as a loss)
+ *   nomad_degrade_noise / _clip    noise at a target SNR and percentile clipping of src/utils/degradations.py (:30-68, :70-83), G levels
+ *                                  per clip, written as the packed batch nomad_embed_ragged reads
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
  *
@@ -587,6 +589,43 @@ int nomad_train_set_stochastic(nomad_ctx* ctx, float dropout, float attention_dr
 int nomad_train_set_branches(nomad_ctx* ctx, int branches, const unsigned* layer_masks);
 int nomad_train_set_frozen(nomad_ctx* ctx, int freeze_encoder);
 int nomad_train_set_convnet(nomad_ctx* ctx, int trainable);
+
+/* ---- degradations on packed clips: noise at an SNR, percentile clipping ----------------------------------------------
+ * The two degradations of the reference's src/utils/degradations.py that are arithmetic on samples, G levels of each per clip in one
+ * call, written straight into the layout nomad_embed_ragged reads.  x_dev is [B][stride] fp32, clip b in the first lens_host[b]
+ * samples of its row (the rest of the row is never read); lens_host and the levels are HOST arrays; out_dev is [B G][stride] fp32:
+ * row b G + g is clip b at level g, with length lens_host[b]; every row is zero behind its length.
+ *
+ * nomad_degrade_noise (degradations.py:30-68), per clip of n samples, noise s of noise_len samples on the device, all in float64:
+ *   xp = sqrt(mean_i x[i]^2),  sp = sqrt(mean_i s[i mod noise_len]^2), both over i < n (the noise tiled or cut to the clip),
+ *   alpha = (xp / 10^(snr_db[g] / 10)) / sp,   out[i] = (float)((double)x[i] + alpha * (double)s[i mod noise_len])
+ * - the reference's formula as it stands: an amplitude divided by a power ratio.  10^(snr_db / 10) is formed on the host (pow).  The
+ * sums of squares are float64, one workgroup per clip: thread t of 1024 adds samples t, t + 1024, ... in order, the 1024 partial sums
+ * fold by halves; product and sum of the output are rounded separately.  No special cases: a silent clip or silent noise gives what
+ * IEEE arithmetic gives (0, inf or NaN).  alpha_out_dev: optional [B][G] float64 (out), or NULL.
+ *
+ * nomad_degrade_clip (degradations.py:70-83): per level p_lo = clip_factor[g] / 2 and p_hi = 100 - clip_factor[g] / 2, a percentile p
+ * being numpy's default linear rule on the clip's own samples, in float64:
+ *   h = (n - 1) (p / 100.0), lo = floor(h), hi = min(lo + 1, n - 1), t = h - lo, v = a + (b - a) t  (two roundings, no fused
+ *   multiply-add), a and b the lo-th and hi-th order statistics of the clip in numpy's sort order (NaN last);
+ *   out[i] = x > v_hi ? (float)v_hi : x < v_lo ? (float)v_lo : x, compared in float64 (a NaN threshold leaves the samples as they are).
+ * The order statistics are exact: each clip is radix-sorted (4 passes of 8 bits, stable) into the workspace.
+ * thresholds_out_dev: optional [B][G][2] float64 (out): (v_lo, v_hi), or NULL.
+ *
+ * Contract: asynchronous, no allocation; the levels and lengths are copied into the workspace ahead of the kernels, as the ragged
+ * entry points queue their metadata.  Deterministic, no floating-point atomics; a clip's rows, alpha and thresholds do not depend on
+ * the batch: they have the bits of the clip's own B = 1 call.  Workspace: nomad_degrade_scratch_bytes(B, stride, G) bytes (0 for
+ * arguments the calls would refuse), written before it is read.  Argument errors return before anything is queued.
+ * NOMAD_ERR_INVALID: a NULL pointer other than the optional output, G outside 1 .. 64, B < 1 (or above 65535), stride not a positive
+ * multiple of 4 or shorter than a length, a length < 1, noise_len < 1, a clip_factor outside [0, 100], a level that is not finite.
+ * NOMAD_ERR_WORKSPACE: ws_bytes too small.
+ */
+size_t nomad_degrade_scratch_bytes(int B, int stride, int G);
+int nomad_degrade_noise(nomad_ctx* ctx, const float* x_dev, int B, int stride, const int* lens_host, const float* noise_dev,
+                        int noise_len, const double* snr_db_host, int G, float* out_dev, double* alpha_out_dev,
+                        void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
+int nomad_degrade_clip(nomad_ctx* ctx, const float* x_dev, int B, int stride, const int* lens_host, const double* clip_factor_host,
+                       int G, float* out_dev, double* thresholds_out_dev, void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
 
 /* ---- bf16 path (BASELINE config C5: long-form clips) ---------------------------------------- */
 /*

@@ -3,14 +3,57 @@
 parses it and ignores it).
 
 Several GPUs: ``python -m torch.distributed.run --nproc-per-node N -m nomad_amd --mode dir ...`` - one process per GPU,
-the files shard across the ranks (RCCL all-gather of the embeddings, ``Nomad.predict``), rank 0 writes the CSV files."""
+the files shard across the ranks (RCCL all-gather of the embeddings, ``Nomad.predict``), rank 0 writes the CSV files.
+
+``--sweep`` (one process): ``--deg`` holds CLEAN files, which are degraded on the GPU at every level of ``--snr-db`` (with ``--noise
+FILE``) and / or ``--clip`` and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level."""
 import argparse
 import os
 
 from .nomad import Nomad
 
 
-def main():
+def _levels(text):
+    """'0,8,15' -> [0.0, 8.0, 15.0]."""
+    try:
+        levels = [float(v) for v in text.split(",") if v.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected numbers separated by commas, got {text!r}")
+    if not levels or not all(v == v and abs(v) != float("inf") for v in levels):
+        raise argparse.ArgumentTypeError(f"expected finite numbers separated by commas, got {text!r}")
+    return levels
+
+
+def sweep(nomad, a):
+    """--sweep: ``Nomad.intensity_sweep`` over the clean files of --deg against the references of --nmr; writes
+    ``nomad_intensity.csv`` (Degradation, Condition, NOMAD) and prints the rank correlation per degradation.  -> the table."""
+    import pandas as pd
+    import torch
+    from .nomad import _check_predict_paths
+    _check_predict_paths(a.mode, a.nmr, a.deg)
+    print(f"Compute non-matching reference embeddings from {a.nmr}")
+    refs = nomad.get_embeddings(a.nmr).set_index("filename")
+    refs = torch.from_numpy(refs.to_numpy(dtype="float32").copy())
+    noise = nomad.load_processing(a.noise).reshape(-1) if a.noise is not None else None
+    results = nomad.intensity_sweep(a.deg, refs, noise=noise, snr_db=a.snr_db, clip_factor=a.clip, k=a.knn)
+    parts = []
+    for name, res in results.items():
+        t = res["table"].sort_values(by="Condition")
+        parts.append(pd.DataFrame({"Degradation": name, "Condition": t["Condition"].to_numpy(), "NOMAD": t["Distance"].to_numpy()}))
+        print(f"{name}: SRCC of the mean NOMAD score with the level = {res['SRCC']:.3f}")
+    table = pd.concat(parts, ignore_index=True)
+    if a.results_path is None:      # as predict names its files
+        from datetime import datetime
+        stamp = datetime.now().strftime("%d-%m-%Y_%H-%M-%S")
+        path = os.path.join("results-csv", stamp, f"{stamp}_nomad_intensity.csv")
+    else:
+        path = os.path.join(a.results_path, "nomad_intensity.csv")
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    table.to_csv(path, index=False)
+    return table
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser(prog="nomad_amd")
     ap.add_argument("--mode", type=str, default="dir", help="Choose mode dir or csv")
     ap.add_argument("--nmr", "--nmr_path", dest="nmr", type=str, help="Path to non-matching reference files")
@@ -27,9 +70,29 @@ def main():
     ap.add_argument("--knn", type=int, default=None, metavar="K",
                     help="score every file (or window) by the mean distance to its K nearest references (1 .. 64) instead of all "
                          "of them; without --window the neighbours go to nomad_nearest.csv")
-    a = ap.parse_args()
+    ap.add_argument("--sweep", action="store_true",
+                    help="--deg holds CLEAN files: degrade them on the GPU at every level of --snr-db / --clip, score the result against "
+                         "--nmr and report how well the score ranks the levels (nomad_intensity.csv, Nomad.intensity_sweep)")
+    ap.add_argument("--noise", type=str, default=None, metavar="FILE", help="--sweep: the noise recording mixed in at --snr-db")
+    ap.add_argument("--snr-db", dest="snr_db", type=_levels, default=None, metavar="A,B,...", help="--sweep: target SNRs in dB")
+    ap.add_argument("--clip", type=_levels, default=None, metavar="A,B,...", help="--sweep: clip factors, percent of samples clipped")
+    a = ap.parse_args(argv)
     if a.hop is not None and a.window is None:
         ap.error("--hop goes with --window")
+    if not a.sweep and (a.noise is not None or a.snr_db is not None or a.clip is not None):
+        ap.error("--noise, --snr-db and --clip go with --sweep")
+    if a.sweep:
+        if a.window is not None:
+            ap.error("--sweep scores whole clips: it does not go with --window")
+        if a.snr_db is None and a.clip is None:
+            ap.error("--sweep needs levels: --snr-db (with --noise), --clip or both")
+        if (a.snr_db is None) != (a.noise is None):
+            ap.error("--noise and --snr-db go together")
+        for name, levels in (("--snr-db", a.snr_db), ("--clip", a.clip)):
+            if levels is not None and not 1 <= len(levels) <= 64:
+                ap.error(f"{name} takes 1 to 64 levels, got {len(levels)}")
+        if a.clip is not None and not all(0.0 <= v <= 100.0 for v in a.clip):
+            ap.error(f"--clip takes percentages from 0 to 100, got {a.clip}")
     if a.knn is not None and not 1 <= a.knn <= 64:
         ap.error(f"--knn takes a number of references from 1 to 64, got {a.knn}")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -43,6 +106,11 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
         rank = dist.get_rank()
     nomad = Nomad(device=a.device, weights=a.weights, precision=a.precision)
+    if a.sweep:
+        if world > 1:
+            raise SystemExit("--sweep runs in one process")
+        print(sweep(nomad, a))
+        return
     if a.window is not None:
         segments, nomad_avg = nomad.predict_segments(a.mode, a.nmr, a.deg, a.window, a.window / 2 if a.hop is None else a.hop,
                                                      a.results_path, k=a.knn)

@@ -25,6 +25,7 @@
 #include "attention_f32_v2.hip.h"
 #include "attention_bwd.hip.h"
 #include "backward.hip.h"
+#include "degrade.hip.h"
 #include "frontend.hip.h"
 #include "gemm_bf16.hip.h"
 #include "gemm_bf16_8phase.hip.h"
@@ -3794,6 +3795,107 @@ int nomad_knn_backward(nomad_ctx* c, const float* a, int Na, const float* b, int
     hipLaunchKernelGGL(cdist_weights_kernel, dim3(tb, ta), dim3(256), 0, s, a, Na, b, Nb, D, G, static_cast<const double*>(nullptr), W);
     if (da) hipLaunchKernelGGL(cdist_reduce_kernel<true>, dim3(tk, ta), dim3(256), 0, s, a, Na, b, Nb, D, W, Nb, da);
     if (db) hipLaunchKernelGGL(cdist_reduce_kernel<false>, dim3(tk, tb), dim3(256), 0, s, b, Nb, a, Na, D, W, Nb, db);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- degradations on packed clips (degrade.hip.h) ----
+// Scratch: [levels: 2 x 64 float64 | lengths: B int32, to 256 bytes | alpha [B][G] or thresholds [B][G][2] float64, to 256 bytes |
+// two key rows of the sort, [B][stride] uint32 each].  One size for both calls (the noise call uses the first three blocks).
+struct DegradeLayout {
+    size_t lens, stats, keys0, keys1, total;
+};
+static DegradeLayout degrade_layout(int B, int stride, int G) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    DegradeLayout l;
+    l.lens = 2 * kDegradeMaxLevels * sizeof(double);
+    l.stats = up(l.lens + sizeof(int) * (size_t)B);
+    l.keys0 = up(l.stats + 2 * sizeof(double) * (size_t)B * (size_t)G);
+    l.keys1 = l.keys0 + up(sizeof(unsigned) * (size_t)B * (size_t)stride);
+    l.total = l.keys1 + up(sizeof(unsigned) * (size_t)B * (size_t)stride);
+    return l;
+}
+
+size_t nomad_degrade_scratch_bytes(int B, int stride, int G) {
+    if (B < 1 || stride < 4 || stride % 4 || G < 1 || G > kDegradeMaxLevels) {
+        (void)fail(NOMAD_ERR_INVALID, "nomad_degrade_scratch_bytes: bad argument (B=%d, stride=%d: a positive multiple of 4, G=%d: 1 .. %d)", B,
+                   stride, G, kDegradeMaxLevels);
+        return 0;
+    }
+    return degrade_layout(B, stride, G).total;
+}
+
+// What both calls check; 0 or a status with the message set.
+static int degrade_check(const char* who, nomad_ctx* c, const float* x, int B, int stride, const int* lens, const double* levels, int G,
+                         float* out, void* ws, size_t ws_bytes) {
+    if (!c || !x || !lens || !levels || !out || !ws) return fail(NOMAD_ERR_INVALID, "%s: a NULL context, input, lengths, levels, output or workspace", who);
+    if (G < 1 || G > kDegradeMaxLevels) return fail(NOMAD_ERR_INVALID, "%s: G=%d levels, 1 .. %d are supported", who, G, kDegradeMaxLevels);
+    if (B < 1 || B > 65535) return fail(NOMAD_ERR_INVALID, "%s: B=%d clips, 1 .. 65535 are supported", who, B);
+    if (stride < 4 || stride % 4) return fail(NOMAD_ERR_INVALID, "%s: stride=%d is not a positive multiple of 4", who, stride);
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 1 || lens[b] > stride)
+            return fail(NOMAD_ERR_INVALID, "%s: clip %d has length %d, 1 .. stride=%d are supported", who, b, lens[b], stride);
+    for (int g = 0; g < G; ++g)
+        if (!std::isfinite(levels[g])) return fail(NOMAD_ERR_INVALID, "%s: level %d is not finite", who, g);
+    const size_t need = degrade_layout(B, stride, G).total;
+    if (ws_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+    return 0;
+}
+
+// The per-level factors (2 G float64 at most) and the lengths, staged in the context's ring and copied ahead of the kernels.
+static int degrade_upload(nomad_ctx* c, const double* factors, int nf, const int* lens, int B, char* ws, const DegradeLayout& l, hipStream_t s) {
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(l.lens + sizeof(int) * (size_t)B, 0);
+    memcpy(staged.data(), factors, sizeof(double) * (size_t)nf);
+    memcpy(staged.data() + l.lens, lens, sizeof(int) * (size_t)B);
+    HIP_TRY(hipMemcpyAsync(ws, staged.data(), staged.size(), hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+int nomad_degrade_noise(nomad_ctx* c, const float* x, int B, int stride, const int* lens, const float* noise, int noise_len,
+                        const double* snr_db, int G, float* out, double* alpha_out, void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    if (int rc = degrade_check("nomad_degrade_noise", c, x, B, stride, lens, snr_db, G, out, ws, ws_bytes)) return rc;
+    if (!noise || noise_len < 1) return fail(NOMAD_ERR_INVALID, "nomad_degrade_noise: a NULL noise signal or noise_len=%d < 1", noise_len);
+    double ratio[kDegradeMaxLevels];
+    for (int g = 0; g < G; ++g) ratio[g] = std::pow(10.0, snr_db[g] / 10.0);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const DegradeLayout l = degrade_layout(B, stride, G);
+    char* w = static_cast<char*>(ws);
+    if (int rc = degrade_upload(c, ratio, G, lens, B, w, l, s)) return rc;
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    const double* ratio_dev = reinterpret_cast<const double*>(w);
+    const int* lens_dev = reinterpret_cast<const int*>(w + l.lens);
+    double* alpha = reinterpret_cast<double*>(w + l.stats);
+    hipLaunchKernelGGL(degrade_noise_alpha_kernel, dim3(B), dim3(kDegradeThreads), 0, s, x, stride, lens_dev, noise, noise_len, ratio_dev, G,
+                       alpha, alpha_out);
+    hipLaunchKernelGGL(degrade_noise_write_kernel, dim3((stride + 255) / 256, B), dim3(256), 0, s, x, stride, lens_dev, noise, noise_len,
+                       static_cast<const double*>(alpha), G, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int nomad_degrade_clip(nomad_ctx* c, const float* x, int B, int stride, const int* lens, const double* clip_factor, int G, float* out,
+                       double* thresholds_out, void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    if (int rc = degrade_check("nomad_degrade_clip", c, x, B, stride, lens, clip_factor, G, out, ws, ws_bytes)) return rc;
+    double q[2 * kDegradeMaxLevels];
+    for (int g = 0; g < G; ++g) {
+        if (clip_factor[g] < 0.0 || clip_factor[g] > 100.0)
+            return fail(NOMAD_ERR_INVALID, "nomad_degrade_clip: clip factor %d is %g, outside [0, 100]", g, clip_factor[g]);
+        q[2 * g] = (clip_factor[g] / 2) / 100.0;
+        q[2 * g + 1] = (100 - clip_factor[g] / 2) / 100.0;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const DegradeLayout l = degrade_layout(B, stride, G);
+    char* w = static_cast<char*>(ws);
+    if (int rc = degrade_upload(c, q, 2 * G, lens, B, w, l, s)) return rc;
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    const double* q_dev = reinterpret_cast<const double*>(w);
+    const int* lens_dev = reinterpret_cast<const int*>(w + l.lens);
+    double* thr = reinterpret_cast<double*>(w + l.stats);
+    hipLaunchKernelGGL(degrade_sort_kernel, dim3(B), dim3(kDegradeThreads), 0, s, x, stride, lens_dev, reinterpret_cast<unsigned*>(w + l.keys0),
+                       reinterpret_cast<unsigned*>(w + l.keys1), q_dev, G, thr, thresholds_out);
+    hipLaunchKernelGGL(degrade_clip_write_kernel, dim3((stride + 255) / 256, B), dim3(256), 0, s, x, stride, lens_dev,
+                       static_cast<const double*>(thr), G, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

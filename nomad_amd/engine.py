@@ -444,6 +444,53 @@ class Engine:
         self._dispatch(B, self._audio_cut(lens) if self._splits(precision, B, sum(frames)) else 0, run)
         return emb, counts
 
+    # ---- degradations on packed clips (nomad_degrade_noise / nomad_degrade_clip) ------------------------------------------------
+    def _degrade(self, waves, lengths, levels, what: str):
+        """The shared front of the two degradations: pack, check the levels -> (buffer, lengths, level array, G, output, workspace)."""
+        if lengths is not None:
+            buf, lens = self.pack_ragged(waves, lengths)
+            if buf.shape[1] % 4:     # a padded tensor whose row stride is no multiple of 4: through the packer after all
+                buf, lens = self._pack([buf[i, :n] for i, n in enumerate(lens)])
+        else:
+            buf, lens = self._pack(waves)
+        levels = [float(v) for v in (levels.tolist() if hasattr(levels, "tolist") else levels)]
+        G = len(levels)
+        if not 1 <= G <= 64:
+            raise ValueError(f"{what} takes 1 .. 64 levels per call, got {G}")
+        B, stride = buf.shape
+        out = torch.empty(B * G, stride, dtype=torch.float32, device=self.device)
+        ws = self._workspace(int(self.lib.nomad_degrade_scratch_bytes(B, stride, G)))
+        return buf, lens, (C.c_double * G)(*levels), G, out, ws
+
+    def degrade_noise(self, waves, noise, snr_db, lengths=None):
+        """Additive noise at G target SNRs: waves as ``pack_ragged`` takes them (a list of clips, or a padded device tensor plus
+        ``lengths``), noise a 1-D signal (tiled or cut to each clip's length), snr_db G levels in dB -> (out (B G, stride) fp32 on the
+        device, lengths repeated G times, alpha (B, G) float64): row b G + g is clip b at snr_db[g], zero behind its length, and
+        ``(out, lengths)`` is what ``embed_ragged`` / ``embed_windows_ragged`` take as ``packed=`` without another copy.  The
+        formula, the reference's own, is stated in include/nomad_hip.h (``nomad_degrade_noise``)."""
+        noise = torch.as_tensor(noise, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+        if noise.numel() < 1:
+            raise ValueError("the noise signal is empty")
+        buf, lens, arr, G, out, ws = self._degrade(waves, lengths, snr_db, "degrade_noise")
+        B, stride = buf.shape
+        alpha = torch.empty(B, G, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.nomad_degrade_noise(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), noise.data_ptr(), noise.numel(),
+                                                arr, G, out.data_ptr(), alpha.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_degrade_noise")
+        return out, [n for n in lens for _ in range(G)], alpha
+
+    def degrade_clip(self, waves, clip_factor, lengths=None):
+        """Percentile clipping at G clip factors (percent of the samples clipped, 0 .. 100): -> (out (B G, stride) fp32 on the device,
+        lengths repeated G times, thresholds (B, G, 2) float64 = (v_lo, v_hi)), rows and layout as ``degrade_noise``.  The thresholds
+        are numpy's linear percentiles cf / 2 and 100 - cf / 2 of the clip's own samples, from exact order statistics
+        (``nomad_degrade_clip``)."""
+        buf, lens, arr, G, out, ws = self._degrade(waves, lengths, clip_factor, "degrade_clip")
+        B, stride = buf.shape
+        thr = torch.empty(B, G, 2, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.nomad_degrade_clip(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), arr, G, out.data_ptr(),
+                                               thr.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "nomad_degrade_clip")
+        return out, [n for n in lens for _ in range(G)], thr
+
     def cdist(self, a: torch.Tensor, b: torch.Tensor, want_matrix: bool = True):
         """a (Na,D), b (Nb,D) fp32 on the GPU, D a multiple of 4 up to 4096 -> (dist (Na,Nb) float64 or None, mean (Na,)
         float64): ``pairwise`` for rows of any width (the same bits at D = 256)."""

@@ -1303,6 +1303,137 @@ class Nomad:
             _write_rounded_csv(df, os.path.join(results_path, "segments.csv"))
         return df, df_mean
 
+    # ---- degradations on the device ----------------------------------------------------------------------------------
+    def _degrade_packed(self, buf, lens, kind: str, levels, noise):
+        """One degradation of a packed device batch -> (rows (B G, stride), lengths repeated G times, alpha or thresholds)."""
+        if kind == "noise":
+            return self.engine.degrade_noise(buf, noise, levels, lengths=lens)
+        return self.engine.degrade_clip(buf, levels, lengths=lens)
+
+    def degrade(self, wav, kind, levels, noise=None, lengths=None):
+        """Degraded copies of clean clips, made on the GPU: -> (clips (B G, stride) fp32 on the GPU, lengths): row ``b G + g`` is
+        clip ``b`` at ``levels[g]`` with length ``lengths[b]`` (``lengths`` comes back repeated G times; every row is zero behind
+        its length).  wav (B,1,N) or (B,N); lengths: the clips' exact lengths (any length from 1 sample); 1 .. 64 levels.
+
+        kind "noise": ``levels`` are target SNRs in dB and ``noise`` a 1-D signal, tiled or cut to each clip:
+        ``x + alpha s`` with ``alpha = (rms(x) / 10^(snr / 10)) / rms(s)`` - the reference's ``utils/degradations.py`` formula as it
+        stands.  kind "clip": ``levels`` are clip factors in percent (0 .. 100): samples are clamped to the clip's own percentiles
+        ``cf / 2`` and ``100 - cf / 2`` (numpy's linear rule, exact order statistics).  Neither is followed by the loudness
+        normalisation the reference's rendering scripts apply, and codecs and reverberation are not offered.  No gradient."""
+        if kind not in ("noise", "clip"):
+            raise ValueError(f"kind must be 'noise' or 'clip', got {kind!r}")
+        if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+            raise ValueError(f"wav must be (B,1,N) or (B,N), got {tuple(getattr(wav, 'shape', ()))}")
+        if wav.requires_grad or (torch.is_tensor(noise) and noise.requires_grad):
+            raise ValueError("degrade produces no gradient (the degradations have no backward): pass tensors that do not require one")
+        if kind == "noise" and noise is None:
+            raise ValueError("kind 'noise' needs a noise signal")
+        if kind == "clip" and noise is not None:
+            raise ValueError("noise goes with kind 'noise'")
+        x = wav.detach().to(self.engine.device, torch.float32)
+        x = (x.squeeze(1) if x.dim() == 3 else x).contiguous()
+        lens = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)] if lengths is not None else [x.shape[1]] * x.shape[0]
+        out, lens_rep, _ = self._degrade_packed(x, lens, kind, levels, noise)
+        return out, lens_rep
+
+    def _clean_batches(self, clean, lengths, budget: int):
+        """The clean clips of ``intensity_sweep`` as packed device batches of at most ``budget`` samples each (one clip at least):
+        yields (names, buffer, lengths)."""
+        eng = self.engine
+        if isinstance(clean, (str, os.PathLike)):
+            if lengths is not None:
+                raise ValueError("lengths go with tensors: files have their own")
+            paths = [str(p) for p in _file_table(str(clean))["filename"]]
+            for idxs, packed, uploaded in _staged_batches(paths, lambda p: self.load_processing(p, trim=False), eng.pack_ragged_host,
+                                                          budget, self.DECODE_THREADS, self.PIPELINE_BATCHES, self.NATIVE_WAV_THREADS,
+                                                          device=getattr(eng, "device", None)):
+                buf, lens = eng._pack(None, packed)
+                uploaded()
+                yield [paths[i] for i in idxs], buf, lens
+            return
+        if torch.is_tensor(clean):
+            if clean.dim() not in (2, 3) or (clean.dim() == 3 and clean.shape[1] != 1):
+                raise ValueError(f"clean must be (B,1,N) or (B,N), a list of clips, a directory or a csv file, got {tuple(clean.shape)}")
+            x = clean.squeeze(1) if clean.dim() == 3 else clean
+            lens = check_lengths(x, lengths) if lengths is not None else [x.shape[1]] * x.shape[0]
+            clips = [x[i, :n] for i, n in enumerate(lens)]
+        else:
+            if lengths is not None:
+                raise ValueError("lengths go with a padded tensor: a list of clips has its own")
+            clips = [torch.as_tensor(w).reshape(-1) for w in clean]
+        if any(torch.is_tensor(w) and w.requires_grad for w in clips):
+            raise ValueError("intensity_sweep produces no gradient (the degradations have no backward): pass tensors that do not require one")
+        lo = 0
+        while lo < len(clips):
+            hi, total = lo + 1, int(clips[lo].numel())
+            while hi < len(clips) and total + int(clips[hi].numel()) <= budget:
+                total += int(clips[hi].numel())
+                hi += 1
+            buf, lens = eng.pack_ragged([w.detach() for w in clips[lo:hi]])
+            yield [f"clip{i}" for i in range(lo, hi)], buf, lens
+            lo = hi
+
+    def intensity_sweep(self, clean, references, noise=None, snr_db=None, clip_factor=None, lengths=None, k=None,
+                        max_batch_samples: int = 256 * 64000):
+        """Does the score rank the strength of a degradation?  The reference's ``intensity`` experiment without rendered files: the
+        clean clips are degraded on the GPU (``degrade``) at every level, embedded and scored against ``references`` ((Nr,256), as
+        ``score`` takes them); -> {"NOISE": {...}, "CLIP": {...}}, a degradation whose levels are None being left out.  Each entry is
+        ``train.intensity_stats``'s result - ``table`` (``Condition`` = the level, ``Distance`` = the mean score of the clips at that
+        level, sorted by Distance), ``SRCC`` = spearmanr(Distance, Condition), ``embeddings`` - plus ``scores``, the (N G,) float64
+        scores in row order (clip b at level g in row b G + g; at fp32 the bits of ``score`` on ``degrade``'s rows).
+
+        clean: a (B,1,N) / (B,N) tensor (with ``lengths``), a list of 1-D clips, a directory of wav files or a csv file with a
+        ``filename`` column (the file pipeline of ``get_embeddings``).  snr_db needs ``noise``, a 1-D signal at 16 kHz.  k: the
+        nearest-reference score of ``score(k=...)``.  The clean audio is uploaded once per batch; batches are cut so that the
+        G-fold degraded rows stay within ``max_batch_samples`` samples."""
+        from .train import intensity_stats
+        check_references(references)
+        k = check_k(k, references.shape[0]) if k is not None else None
+        if snr_db is None and clip_factor is None:
+            raise ValueError("intensity_sweep needs snr_db, clip_factor or both")
+        if snr_db is not None and noise is None:
+            raise ValueError("snr_db needs a noise signal: pass noise=")
+        if references.requires_grad or (torch.is_tensor(noise) and noise.requires_grad):
+            raise ValueError("intensity_sweep produces no gradient (the degradations have no backward): pass tensors that do not require one")
+        sweeps = [(name, kind, [float(v) for v in np.asarray(levels, dtype=np.float64).reshape(-1)])
+                  for name, kind, levels in (("NOISE", "noise", snr_db), ("CLIP", "clip", clip_factor)) if levels is not None]
+        for name, _, levels in sweeps:
+            if not 1 <= len(levels) <= 64:
+                raise ValueError(f"{name}: 1 .. 64 levels per sweep, got {len(levels)}")
+        self._need_whole_encoder(self.engine)
+        eng = self.engine
+        refs = references.detach().to(eng.device, torch.float32).contiguous()
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).reshape(-1).to(eng.device)
+        rows = {name: ([], [], []) for name, _, _ in sweeps}      # row names, levels, embeddings in flight
+        budget = max(1, int(max_batch_samples) // max(len(levels) for _, _, levels in sweeps))
+        for names, buf, lens in self._clean_batches(clean, lengths, budget):
+            for name, kind, levels in sweeps:
+                out, lens_rep, _ = self._degrade_packed(buf, lens, kind, levels, noise)
+                emb = eng.embed_ragged(None, precision=self._window_precision(sum(lens_rep)), packed=(out, lens_rep))
+                rows[name][0].extend(f"{n}|{name}_{g}" for n in names for g in range(len(levels)))
+                rows[name][1].extend(levels * len(names))
+                rows[name][2].append(eng.fetch_async(emb))
+        ref_df = pd.DataFrame(refs.cpu().numpy())
+        results = {}
+        for name, _, _ in sweeps:
+            row_names, conds, fetches = rows[name]
+            if not row_names:
+                raise ValueError("intensity_sweep: no clean clip to degrade")
+            df_emb = pd.concat([pd.DataFrame({"filepath_deg": row_names}),
+                                pd.DataFrame(np.concatenate([f.result() for f in fetches]))], axis=1)
+            deg_data = pd.DataFrame({"filepath_deg": row_names, "Condition": conds})
+            scores = {}
+
+            def nmr_mean(test, ref):
+                dev = eng.device
+                scores["rows"] = self._reference_mean(torch.from_numpy(test).to(dev), torch.from_numpy(ref).to(dev), k).cpu().numpy()
+                return scores["rows"]
+
+            results[name] = intensity_stats(df_emb, deg_data, ref_df, nmr_mean, name)
+            results[name]["scores"] = scores["rows"]
+        return results
+
     def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor, lengths=None) -> "GraphedLoss":
         """``forward`` + backward for inputs of this shape, captured as one HIP graph (see ``GraphedLoss``): for training loops with
         a fixed batch shape - the per-step launch overhead of ~440 small kernels disappears, the bits do not change."""

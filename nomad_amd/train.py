@@ -685,11 +685,29 @@ class Training:
 
     def eval_degradation_intensity(self, model_path):
         """``intensity`` (train_triplet.py:344-401): per degradation, the rank correlation of the mean distance with the
-        degradation's level.  -> {degradation: {table, SRCC, embeddings, ref_embeddings}}."""
+        degradation's level.  -> {degradation: {table, SRCC, embeddings, ref_embeddings}}.
+
+        With the config key ``degrade_on_device: {clean: <dir|csv>, noise: <wav>, snr_db: [...], clip: [...]}`` (not a reference
+        key) no rendered files and no ``test_mono_data`` are needed: the clean files are degraded on the GPU at the listed levels
+        (``Nomad.intensity_sweep``: additive noise at an SNR and percentile clipping, without the loudness normalisation of the
+        reference's rendering scripts) and the result has the same shape, with the degradations ``NOISE`` and ``CLIP``."""
         import pandas as pd
+        on_device = self.config.get("degrade_on_device")
+        if on_device and self.config.get("eval_w2v"):
+            raise ValueError("degrade_on_device scores NOMAD embeddings (Nomad.intensity_sweep); the raw wav2vec 2.0 baseline "
+                             "(eval_w2v: True) takes rendered files (test_mono_data)")
         self._load_model(model_path, allow_w2v=True)
         ref_embeddings = self.get_nmr_embeddings()
         ref_embeddings.set_index("reference", inplace=True)
+        if on_device:
+            noise = on_device.get("noise")
+            results = self.nomad.intensity_sweep(
+                on_device["clean"], torch.from_numpy(_emb_values(ref_embeddings)),
+                noise=self.nomad.load_processing(noise).reshape(-1) if noise is not None else None,
+                snr_db=on_device.get("snr_db"), clip_factor=on_device.get("clip"))
+            for res in results.values():
+                res["ref_embeddings"] = ref_embeddings
+            return results
         test_data = pd.read_csv(self.config["test_mono_data"])
         results = {}
         for deg_name, deg_data in test_data.groupby("Degradation"):
