@@ -119,34 +119,11 @@ struct nomad_ctx {
     LayerDev layers[NOMAD_NUM_LAYERS] = {};
     float *emb_w = nullptr, *emb_b = nullptr;
     // Split-K for the small-M GEMMs of Nomad.forward()'s loss forward / backward (config C4: M = 1600 rows): partial
-    // products of up to 4 K-slices, allocated by nomad_enable_backward; splitk_ok is raised for the duration of such a
-    // call only (never for scoring forwards, whose bits must not depend on the batch; never in fine-tuning mode)
+    // products of up to 4 K-slices, kSplitKPartFloats floats allocated by nomad_enable_backward.  A resource only: whether a call
+    // may write it is that call's SplitKPlan (below), built by forward_run / backward_run.  Training-mode forwards and dX-only
+    // backwards of one context share it (the host layer keeps them on one stream); the no-gradient branches of Nomad.forward() -
+    // layer outputs wanted, nothing saved - take their block from the call's own workspace instead (Layout::splitk).
     float* splitk_part = nullptr;
-    // (the no-gradient branches of Nomad.forward() - layer outputs wanted, nothing saved - take their partial-sum block from the
-    // call's own workspace: Layout::splitk)
-    float* splitk_cur = nullptr;                            // the block of the call being enqueued
-    size_t splitk_cur_floats = 0;                           // its capacity: no split whose S x M x N partials exceed it
-    bool splitk_ok = false;
-    // A LayerNorm(768) the caller will apply to the output of the NEXT dense GEMM (run_layer: out_proj -> LN, fc2 -> LN): when that GEMM
-    // splits K, its epilogue normalises the rows itself (splitk_epilogue_ln_kernel) and sets `done`; otherwise the caller launches the
-    // stand-alone LayerNorm.  Per context, set and consumed inside one forward call.
-    struct PendingLn {
-        const float* gamma = nullptr;
-        const float* beta = nullptr;
-        float* out = nullptr;
-        float* out2 = nullptr;
-        bool armed = false, done = false;
-    } pending_ln;
-    // The backward's mirror (round 6): the LayerNorm BACKWARD the caller will apply to the output of the next dX GEMM (+ g2, the layer-output
-    // gradient).  When that GEMM splits K, the LayerNorm-backward kernel forms the GEMM's output row itself from the partial products
-    // (layernorm_bwd_kernel<3, true>) and sets `done`: no epilogue launch, the GEMM's output never goes to memory.  dX-only backward.
-    struct PendingLnBwd {
-        const float* x = nullptr;      // the LayerNorm's input (saved by the forward)
-        const float* g2 = nullptr;
-        const float* gamma = nullptr;
-        float* out = nullptr;
-        bool armed = false, done = false;
-    } pending_lnb;
     // nomad_pairwise: row sums per (64-ref tile, deg row), kPairScratchDoubles doubles PER LAUNCH STREAM - calls on
     // different streams of one context may be in flight together (Engine / ShardedScorer are driven from side streams), so
     // each stream gets its own block: the first at nomad_create, further ones on a stream's first call
@@ -306,11 +283,42 @@ GemmParams dense(const float* A, int lda, const float* W, const float* bias, con
 
 }  // namespace
 
+// What ONE forward or backward call decides about split-K, built once at its top (forward_run / backward_run) and handed to every
+// GEMM of the call that may split: where the partial products go and how many floats fit.  The empty plan: this call never splits
+// (scoring forwards, whose bits must not depend on the batch; ragged batches; fine-tuning mode).
+struct SplitKPlan {
+    float* part = nullptr;
+    size_t floats = 0;   // no split whose S x M x N partials exceed it
+};
+
+// The row operation the caller applies to a dense GEMM's output, offered to that GEMM (run_gemm): if the GEMM splits K, its epilogue
+// does the operation too and run_gemm says so; if not, the caller launches the stand-alone kernel.
+//   ln      LayerNorm(768) behind out_proj / fc2 (run_layer): the epilogue normalises its rows itself (splitk_epilogue_ln_kernel)
+//   ln_bwd  LayerNorm BACKWARD behind the dX GEMMs fc1^T / qkv^T of the dX-only backward: that kernel forms the GEMM's output row from
+//           the partial products itself (layernorm_bwd_kernel<3, true>) - no epilogue launch, the output never goes to memory
+struct SplitKFusion {
+    enum Kind { kLn, kLnBwd } kind;
+    const float* x;       // ln_bwd: the LayerNorm's input (saved by the forward)
+    const float* g2;      // ln_bwd: the layer-output gradient added to the GEMM's output, or nullptr
+    const float* gamma;
+    const float* beta;    // ln
+    float* out;
+    float* out2;          // ln: a second copy of the rows (the layer output), or nullptr
+    static SplitKFusion ln(const float* gamma, const float* beta, float* out, float* out2) {
+        return {kLn, nullptr, nullptr, gamma, beta, out, out2};
+    }
+    static SplitKFusion ln_bwd(const float* x, const float* g2, const float* gamma, float* out) {
+        return {kLnBwd, x, g2, gamma, nullptr, out, nullptr};
+    }
+};
+
 // ---- across translation units ---------------------------------------------------------------------------------------------------
-// nomad_hip.hip: split-K wrappers in front of the fp32 dispatch
-NOMAD_INTERNAL int run_gemm(nomad_ctx* c, GemmParams p, int groups, int tile, hipStream_t s, int occ = 0);
+// nomad_hip.hip: a GEMM of a call that may split K (plan), in front of the fp32 dispatch.  fuse (optional): the row operation behind
+// this GEMM; *fused says whether a split GEMM's epilogue did it.  A call site that can never split calls gemm_f32_dispatch.
+NOMAD_INTERNAL int run_gemm(nomad_ctx* c, const GemmParams& p, int groups, int tile, hipStream_t s, const SplitKPlan& plan,
+                            const SplitKFusion* fuse = nullptr, bool* fused = nullptr);
 // nomad_gemm_f32.hip
-NOMAD_INTERNAL int gemm_f32_dispatch(nomad_ctx* c, GemmParams p, int groups, int tile, hipStream_t s, int occ);
+NOMAD_INTERNAL int gemm_f32_dispatch(nomad_ctx* c, GemmParams p, int groups, int tile, hipStream_t s, int occ = 0);
 NOMAD_INTERNAL hipError_t gemm_f32_n48_split(const GemmParams& q, int groups, hipStream_t s, int S);   // the grouped pos-conv, K in S slices over blockIdx.z
 NOMAD_INTERNAL int pick_tile(const nomad_ctx* c, int M, int N, int K);
 NOMAD_INTERNAL int mixed_split_rows(const nomad_ctx* c, int M, int N);

@@ -270,7 +270,7 @@ int nomad_diag_gemm(nomad_ctx* c, const float* A, const float* W, const float* b
     if (tile == 48 || tile == 49) {
         if (N != 48 || K % 16) return fail(NOMAD_ERR_INVALID, "nomad_diag_gemm: tile 48 needs N == 48 and K %% 16 == 0");
         GemmParams p48 = dense(A, K, W, bias, R, C, M, N, K, gelu);
-        return run_gemm(c, p48, 1, tile, static_cast<hipStream_t>(stream));
+        return gemm_f32_dispatch(c, p48, 1, tile, static_cast<hipStream_t>(stream));
     }
 #ifdef NOMAD_DIAG   // probe instantiations launched directly (not through gemm_f32_dispatch)
     if (tile == 94 || tile == 95) {   // the shipped lean + skewed + direct-epilogue instantiation with timeline stamps (94) / set-up detail stamps (95)
@@ -335,7 +335,7 @@ int nomad_diag_gemm(nomad_ctx* c, const float* A, const float* W, const float* b
     if (N % bn || K % bk) return fail(NOMAD_ERR_INVALID, "nomad_diag_gemm: N %% %d or K %% %d != 0", bn, bk);
     GemmParams p = dense(A, K, W, bias, R, C, M, N, K, gelu);
     p.group_m = group_m;
-    return run_gemm(c, p, 1, tile, static_cast<hipStream_t>(stream), occ);
+    return gemm_f32_dispatch(c, p, 1, tile, static_cast<hipStream_t>(stream), occ);
 }
 
 }  // extern "C"

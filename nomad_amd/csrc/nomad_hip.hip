@@ -83,7 +83,7 @@ size_t pos_wino_s_bytes(long long q_rows) { return sizeof(float) * 16 * kPwOps *
 // floats in the split-K block of a small layer-output forward (Layout::splitk), 0 where that forward does not split: S x M x N
 // for the largest transformer problem splitk_applies / posconv_splitk_applies let through at M = s.M frames (S x N <= 6144: fc1
 // 2 x 3072, qkv 2 x 2304, fc2 / pos-conv 4 x 768), never more than the fixed cap those checks use.  The conv GEMMs of one clip
-// have M = L[i] > s.M rows: they split only where their partials fit too (nomad_ctx::splitk_cur_floats).
+// have M = L[i] > s.M rows: they split only where their partials fit too (SplitKPlan::floats).
 size_t layers_splitk_floats(const Shapes& s) {
     return s.M < kSplitKLayersMaxM ? std::min(kSplitKPartFloats, (size_t)6144 * (size_t)s.M) : 0;
 }
@@ -573,15 +573,9 @@ int upload(nomad_ctx* c, const float* host, size_t n, float** out) {
 // 44 CUs get two tiles and the launch takes two tiles' time (fc2: 82 us where a balanced split would take 48).  The
 // contraction is cut into S fixed slices - S x as many, shorter workgroups - whose partial products are added in slice
 // order by splitk_epilogue_kernel together with bias / GELU / residual: deterministic, no atomics.
-struct SplitKScope {  // raises nomad_ctx::splitk_ok for the lifetime of one forward / backward call
-    nomad_ctx* c;
-    bool prev;
-    SplitKScope(nomad_ctx* c_, bool on) : c(c_), prev(c_->splitk_ok) { c->splitk_ok = on; }
-    ~SplitKScope() { c->splitk_ok = prev; }
-};
-
-static bool splitk_applies(const nomad_ctx* c, const GemmParams& p, int groups, int tile, int* S) {
-    if (!c->splitk_ok || !c->splitk_cur || groups != 1 || tile != 37) return false;
+// Whether a GEMM splits is a function of the call's plan and the problem alone.
+static bool splitk_applies(const SplitKPlan& plan, const GemmParams& p, int groups, int tile, int* S) {
+    if (!plan.part || groups != 1 || tile != 37) return false;
     if (p.DG || p.Upre || p.c_colblk || p.kchunk != p.K || p.n_valid != p.N || p.N % 64) return false;
     const bool c_plain = p.cmap.clip_rows >= p.M && p.cmap.off == 0 && p.cmap.ld == p.N;
     const bool r_plain = !p.R || (p.rmap.clip_rows >= p.M && p.rmap.off == 0 && p.rmap.ld == p.N);
@@ -591,44 +585,43 @@ static bool splitk_applies(const nomad_ctx* c, const GemmParams& p, int groups, 
     *S = p.K >= 2304 ? 4 : 2;
     // S x M x N partials must fit the block being written: layers_splitk_floats sizes a layer-output forward's by the transformer
     // GEMMs, and a one-clip conv GEMM (M = L[i] rows, several times the frames) can exceed it
-    return p.K % (*S * 32) == 0 && (size_t)*S * p.N <= 6144 && (size_t)*S * p.M * p.N <= c->splitk_cur_floats;
+    return p.K % (*S * 32) == 0 && (size_t)*S * p.N <= 6144 && (size_t)*S * p.M * p.N <= plan.floats;
 }
 
-static int run_gemm_splitk(nomad_ctx* c, const GemmParams& p, int S, hipStream_t s) {
+// The S slices (ordinary launches: straight to the dispatch), then the epilogue - the one place that decides whether it also does the
+// row operation behind the GEMM (fuse), and the one place that reads the two Tuning switches.
+static int run_gemm_splitk(nomad_ctx* c, const SplitKPlan& plan, const GemmParams& p, int S, hipStream_t s, const SplitKFusion* fuse,
+                           bool* fused) {
     GemmParams q = p;
     q.K = p.K / S;
     q.kchunk = q.K;
     q.a_goff = q.K;
     q.w_goff = q.K;
-    q.C = c->splitk_cur;
+    q.C = plan.part;
     q.cmap = plain_map(p.M, p.N);
     q.c_goff = (long long)p.M * p.N;
     q.bias = nullptr;
     q.R = nullptr;
     q.gelu = 0;
-    const bool keep = c->splitk_ok;
-    c->splitk_ok = false;  // the slices themselves are ordinary launches
-    const int rc = run_gemm(c, q, S, 37, s);
-    c->splitk_ok = keep;
-    if (rc) return rc;
+    if (int rc = gemm_f32_dispatch(c, q, S, 37, s)) return rc;
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
-    if (c->pending_lnb.armed && !c->pending_lnb.done && p.N == 768 && !p.gelu && !p.bias && c->tune.splitk_lnb_fuse) {
-        hipLaunchKernelGGL((layernorm_bwd_kernel<3, true>), dim3((unsigned)((p.M + 3) / 4)), dim3(256), 0, s, c->pending_lnb.x, c->splitk_cur,
-                           c->pending_lnb.g2, c->pending_lnb.gamma, c->pending_lnb.out, p.M, S, p.R);
+    if (fuse && fuse->kind == SplitKFusion::kLnBwd && p.N == 768 && !p.gelu && !p.bias && c->tune.splitk_lnb_fuse) {
+        hipLaunchKernelGGL((layernorm_bwd_kernel<3, true>), dim3((unsigned)((p.M + 3) / 4)), dim3(256), 0, s, fuse->x, plan.part,
+                           fuse->g2, fuse->gamma, fuse->out, p.M, S, p.R);
         HIP_TRY(hipGetLastError());
-        c->pending_lnb.done = true;
+        *fused = true;
         return 0;
     }
-    if (c->pending_ln.armed && !c->pending_ln.done && p.N == 768 && !p.gelu) {
-        hipLaunchKernelGGL(splitk_epilogue_ln_kernel, dim3((unsigned)((p.M + 3) / 4)), dim3(256), 0, s, c->splitk_cur, S, p.M, p.bias, p.R, p.C,
-                           c->pending_ln.gamma, c->pending_ln.beta, c->pending_ln.out, c->pending_ln.out2);
+    if (fuse && fuse->kind == SplitKFusion::kLn && p.N == 768 && !p.gelu && c->tune.splitk_ln_fuse) {
+        hipLaunchKernelGGL(splitk_epilogue_ln_kernel, dim3((unsigned)((p.M + 3) / 4)), dim3(256), 0, s, plan.part, S, p.M, p.bias, p.R, p.C,
+                           fuse->gamma, fuse->beta, fuse->out, fuse->out2);
         HIP_TRY(hipGetLastError());
-        c->pending_ln.done = true;
+        *fused = true;
         return 0;
     }
     const long long count4 = (long long)p.M * p.N / 4;
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((count4 + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<const float4*>(c->splitk_cur), S, count4, p.N / 4, reinterpret_cast<const float4*>(p.bias),
+                       reinterpret_cast<const float4*>(plan.part), S, count4, p.N / 4, reinterpret_cast<const float4*>(p.bias),
                        reinterpret_cast<const float4*>(p.R), reinterpret_cast<float4*>(p.C), p.gelu);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -638,21 +631,21 @@ static int run_gemm_splitk(nomad_ctx* c, const GemmParams& p, int S, hipStream_t
 // serial K loop of 384 tiles: 331 us per launch on fewer than half of the CUs (three launches per configs[3] step).  K in 4 fixed
 // slices over blockIdx.z (448 workgroups), partial products added in slice order by posconv_splitk_epilogue_kernel.  Where the
 // dense GEMMs of the same call split (splitk_applies): never on a scoring entry point.
-static bool posconv_splitk_applies(const nomad_ctx* c, const GemmParams& p, int groups, int tile) {
-    if (!c->splitk_ok || !c->splitk_cur || groups != 16 || tile != 48) return false;
+static bool posconv_splitk_applies(const SplitKPlan& plan, const GemmParams& p, int groups, int tile) {
+    if (!plan.part || groups != 16 || tile != 48) return false;
     if (p.DG || p.K != 6144 || p.kchunk != p.K || p.n_valid != 48 || p.c_goff != 48) return false;
     const bool c_plain = p.cmap.clip_rows >= p.M && p.cmap.off == 0 && p.cmap.ld == 768;
-    return c_plain && (long long)((p.M + 255) / 256) * 16 < 256 && (size_t)4 * p.M * 768 <= c->splitk_cur_floats;
+    return c_plain && (long long)((p.M + 255) / 256) * 16 < 256 && (size_t)4 * p.M * 768 <= plan.floats;
 }
 
-static int run_posconv_splitk(nomad_ctx* c, const GemmParams& p, hipStream_t s) {
+static int run_posconv_splitk(nomad_ctx* c, const SplitKPlan& plan, const GemmParams& p, hipStream_t s) {
     constexpr int S = 4;
     GemmParams q = p;
     q.K = p.K / S;
     q.kchunk = q.K;
     q.a_soff = q.K;
     q.w_soff = q.K;
-    q.C = c->splitk_cur;
+    q.C = plan.part;
     q.cmap = plain_map(p.M, 768);
     q.c_soff = (long long)p.M * 768;
     q.bias = nullptr;
@@ -664,7 +657,7 @@ static int run_posconv_splitk(nomad_ctx* c, const GemmParams& p, hipStream_t s) 
         HIP_TRY(gemm_f32_n48_split(q, 16, s, S));
     }
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
-    hipLaunchKernelGGL(posconv_splitk_epilogue_kernel, dim3(p.M), dim3(192), 0, s, c->splitk_cur, S, p.M, p.bias, p.R, p.rmap, p.r_goff, p.Upre, p.C,
+    hipLaunchKernelGGL(posconv_splitk_epilogue_kernel, dim3(p.M), dim3(192), 0, s, plan.part, S, p.M, p.bias, p.R, p.rmap, p.r_goff, p.Upre, p.C,
                        p.gelu);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -672,14 +665,13 @@ static int run_posconv_splitk(nomad_ctx* c, const GemmParams& p, hipStream_t s) 
 
 }  // namespace
 
-// split-K wrappers in front of the fp32 GEMM dispatch (nomad_gemm_f32.hip)
-int run_gemm(nomad_ctx* c, GemmParams p, int groups, int tile, hipStream_t s, int occ) {
-    {
-        int S = 0;
-        if (splitk_applies(c, p, groups, tile, &S)) return run_gemm_splitk(c, p, S, s);
-        if (posconv_splitk_applies(c, p, groups, tile)) return run_posconv_splitk(c, p, s);
-    }
-    return gemm_f32_dispatch(c, p, groups, tile, s, occ);
+int run_gemm(nomad_ctx* c, const GemmParams& p, int groups, int tile, hipStream_t s, const SplitKPlan& plan, const SplitKFusion* fuse,
+             bool* fused) {
+    if (fused) *fused = false;
+    int S = 0;
+    if (splitk_applies(plan, p, groups, tile, &S)) return run_gemm_splitk(c, plan, p, S, s, fuse, fused);
+    if (posconv_splitk_applies(plan, p, groups, tile)) return run_posconv_splitk(c, plan, p, s);
+    return gemm_f32_dispatch(c, p, groups, tile, s);
 }
 
 namespace {
@@ -739,7 +731,7 @@ int run_posconv_wino(nomad_ctx* c, const float* xpad, const float* wt, const flo
     p.N = 64;
     p.n_valid = 48;
     int rc;
-    if ((rc = run_gemm(c, p, 16 * kPwOps, 48, s))) return rc;   // (counted with its executed FLOPs: 2 M' 48 kPwK per group)
+    if ((rc = gemm_f32_dispatch(c, p, 16 * kPwOps, 48, s))) return rc;   // never splits K (counted with its executed FLOPs: 2 M' 48 kPwK per group)
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
     hipLaunchKernelGGL(posconv_wino_output_kernel, dim3((geo.max_q + 15) / 16, 16 * geo.B), dim3(192), 0, s, ws, bias, xpad, y, upre, geo);
     HIP_TRY(hipGetLastError());
@@ -1112,13 +1104,13 @@ struct F32Bufs {
 
 // The fp32 forward, over an equal-length or a ragged batch.  sv == nullptr: scoring mode (intermediates alias inside the
 // workspace).  sv != nullptr: training mode - every tensor the backward needs is written to its slot in `sv` instead.
-// splitk_block: the workspace's split-K block of an equal-length layer-output forward (splitk_floats floats), or nullptr.
+// ws_splitk: the workspace's split-K block of an equal-length layer-output forward, or the empty plan.
 // A ragged batch takes sv, its dropout and LayerDrop (branches: equal groups of clips, of any lengths) and layers_out like an
 // equal-length one, packed; it never splits K, so that a clip's values never depend on the batch it is in.
 static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const F32Bufs& bf, const float* head_w,
-                       const float* head_b, float* emb, float* layers_out, float* splitk_block, size_t splitk_floats, hipStream_t s,
+                       const float* head_b, float* emb, float* layers_out, const SplitKPlan& ws_splitk, hipStream_t s,
                        const Saved* sv, HeadMode mode = {}) {
-    if (g.ragged() && splitk_block) return fail(NOMAD_ERR_INVALID, "fp32 forward: split-K needs an equal-length batch");
+    if (g.ragged() && ws_splitk.part) return fail(NOMAD_ERR_INVALID, "fp32 forward: split-K needs an equal-length batch");
     const int B = g.B, T = g.T, M = (int)g.rows[6];
     // nomad_set_encoder_depth: layers 0 .. depth - 1, then stop - no head, rows [depth, 12) of layers_out and emb stay unwritten
     const int depth = c->encoder_depth;
@@ -1129,19 +1121,11 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
     // results are deterministic, but they are the loss path's bits, not the scoring path's - nomad_embed WITHOUT layer outputs
     // (TripletModel / predict) never splits, whatever the batch.  The partial sums live in the call's own workspace (round 5; they
     // were two context-wide blocks handed to launch streams by hipEventQuery: whether a third stream's forward split depended on
-    // timing).
-    float* const loss_block = (sv == nullptr && layers_out != nullptr && splitk_block != nullptr) ? splitk_block : nullptr;
-    const SplitKScope splitk(c, (sv != nullptr || loss_block != nullptr) && !c->train_ready && !g.ragged());
-    float* const prev_cur = c->splitk_cur;
-    const size_t prev_cur_floats = c->splitk_cur_floats;
-    c->splitk_cur = sv != nullptr ? c->splitk_part : loss_block;
-    c->splitk_cur_floats = sv != nullptr ? kSplitKPartFloats : loss_block != nullptr ? splitk_floats : 0;
-    struct CurRestore {
-        nomad_ctx* c;
-        float* v;
-        size_t n;
-        ~CurRestore() { c->splitk_cur = v; c->splitk_cur_floats = n; }
-    } cur_restore{c, prev_cur, prev_cur_floats};
+    // timing).  Training mode: the context's block (nomad_enable_backward).
+    const SplitKPlan splitk = c->train_ready || g.ragged() ? SplitKPlan{}
+                              : sv                         ? SplitKPlan{c->splitk_part, kSplitKPartFloats}
+                              : layers_out                 ? ws_splitk
+                                                           : SplitKPlan{};
     int rc;
     // model.train() regularisation: only in the training-mode forward, only when switched on
     const bool reg = sv != nullptr;
@@ -1196,7 +1180,7 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
         p.cmap = plain_map(p.M, 512);
         p.rmap = p.cmap;
         p.gelu = 1;
-        if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, 512, p.K), s))) return rc;
+        if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, 512, p.K), s, splitk))) return rc;
     }
 
     // ---- LayerNorm(512) + post_extract_proj into the padded pos-conv buffer ------------------
@@ -1213,7 +1197,7 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
         p.cmap = g.pad_map;
         p.c_colblk = 48;
         p.c_colblk_stride = g.grp_stride;
-        if ((rc = run_gemm(c, p, 1, pick_tile(c, M, 768, 512), s))) return rc;
+        if ((rc = run_gemm(c, p, 1, pick_tile(c, M, 768, 512), s, splitk))) return rc;
     }
     if (d_in.threshold) {  // dropout_input: on the features that feed both the pos-conv and its residual
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
@@ -1247,7 +1231,7 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
         p.N = 64;
         p.n_valid = 48;
         p.gelu = 1;
-        if ((rc = run_gemm(c, p, 16, 48, s))) return rc;  // one instantiation for every batch size: same summation order
+        if ((rc = run_gemm(c, p, 16, 48, s, splitk))) return rc;  // one instantiation for every batch size: same summation order
     }
     float* x = bf.x;
     float* x2 = bf.x2;
@@ -1274,7 +1258,7 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
         float* lo = layers_out ? layers_out + (size_t)l * M * 768 + r0 * 768 : nullptr;
         const unsigned long long idx0 = (unsigned long long)r0 * 768;
         int rc;
-        if ((rc = run_gemm(c, dense(xs, 768, d.qkv_w, d.qkv_b, nullptr, qkv, Ms, 2304, 768, 0), 1, pick_tile(c, Ms, 2304, 768), s)))
+        if ((rc = run_gemm(c, dense(xs, 768, d.qkv_w, d.qkv_b, nullptr, qkv, Ms, 2304, 768, 0), 1, pick_tile(c, Ms, 2304, 768), s, splitk)))
             return rc;
         // (a ragged batch: the attention kernels address clips through the whole batch's prefix sums - whole-batch pointers)
         if (g.ragged() ? (rc = run_attention(c, g, qkv - r0 * 2304, ctxb - r0 * 768, lse ? lse - 12 * r0 : nullptr, s, &d_att, site_attn(l), c0, nc))
@@ -1282,42 +1266,25 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
             return rc;
         // residual dropout: y = x + dropout(W a + b) needs the branch on its own, so the residual add moves out
         // of the GEMM epilogue into the dropout kernel
-        // (the LayerNorm behind a residual GEMM: inside the GEMM's split-K epilogue where it has one - configs[3] - else on its own)
-        auto arm_ln = [&](const float* g_, const float* b_, float* out_, float* out2_) {
-            c->pending_ln = {};
-            if (!c->tune.splitk_ln_fuse || d_res.threshold) return;   // (residual dropout moves the residual add out of the GEMM)
-            c->pending_ln.gamma = g_;
-            c->pending_ln.beta = b_;
-            c->pending_ln.out = out_;
-            c->pending_ln.out2 = out2_;
-            c->pending_ln.armed = true;
-        };
-        auto ln_after = [&](const float* in_, const float* g_, const float* b_, float* out_, float* out2_) -> int {
-            const bool done = c->pending_ln.armed && c->pending_ln.done;
-            c->pending_ln = {};
-            return done ? 0 : run_layernorm(c, in_, g_, b_, out_, out2_, Ms, 768, s);
-        };
-        arm_ln(d.ln1_w, d.ln1_b, x2s, nullptr);
+        // (the LayerNorm behind a residual GEMM: inside the GEMM's split-K epilogue where it has one - configs[3] - else on its own;
+        // not offered under residual dropout, where the residual is no longer the GEMM's)
+        const SplitKFusion ln1 = SplitKFusion::ln(d.ln1_w, d.ln1_b, x2s, nullptr), ln2 = SplitKFusion::ln(d.ln2_w, d.ln2_b, xs, lo);
+        bool ln_done = false;
         if ((rc = run_gemm(c, dense(ctxb, 768, d.o_w, d.o_b, d_res.threshold ? nullptr : xs, y1, Ms, 768, 768, 0), 1,
-                           pick_tile(c, Ms, 768, 768), s))) {
-            c->pending_ln = {};
+                           pick_tile(c, Ms, 768, 768), s, splitk, d_res.threshold ? nullptr : &ln1, &ln_done)))
             return rc;
-        }
         if (d_res.threshold && (rc = run_dropout(c, y1, xs, y1, acts, d_res, site_proj(l), s, idx0))) return rc;
-        if ((rc = ln_after(y1, d.ln1_w, d.ln1_b, x2s, nullptr))) return rc;
+        if (!ln_done && (rc = run_layernorm(c, y1, d.ln1_w, d.ln1_b, x2s, nullptr, Ms, 768, s))) return rc;
         {
             GemmParams p = dense(x2s, 768, d.fc1_w, d.fc1_b, nullptr, hs, Ms, 3072, 768, 1);
             p.Upre = sv ? sv->L[l].u + r0 * 3072 : nullptr;
-            if ((rc = run_gemm(c, p, 1, pick_tile(c, Ms, 3072, 768), s))) return rc;
+            if ((rc = run_gemm(c, p, 1, pick_tile(c, Ms, 3072, 768), s, splitk))) return rc;
         }
-        arm_ln(d.ln2_w, d.ln2_b, xs, lo);
         if ((rc = run_gemm(c, dense(hs, 3072, d.fc2_w, d.fc2_b, d_res.threshold ? nullptr : x2s, y2, Ms, 768, 3072, 0), 1,
-                           pick_tile(c, Ms, 768, 3072), s))) {
-            c->pending_ln = {};
+                           pick_tile(c, Ms, 768, 3072), s, splitk, d_res.threshold ? nullptr : &ln2, &ln_done)))
             return rc;
-        }
         if (d_res.threshold && (rc = run_dropout(c, y2, x2s, y2, acts, d_res, site_ffn(l), s, idx0))) return rc;
-        return ln_after(y2, d.ln2_w, d.ln2_b, xs, lo);
+        return ln_done ? 0 : run_layernorm(c, y2, d.ln2_w, d.ln2_b, xs, lo, Ms, 768, s);
     };
     for (int l = 0; l < depth; ++l) {
         unsigned all = 1u, any = 0u;
@@ -1367,8 +1334,8 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
     if (c->tune.f32_posconv_wino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws);
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(lay.conv[i]);
-    return forward_run(c, wav, geom_uniform(sh), bf, head_w, head_b, emb, layers_out, lay.splitk != 0 ? F(lay.splitk) : nullptr,
-                       layers_splitk_floats(sh), static_cast<hipStream_t>(stream), sv, mode);
+    const SplitKPlan ws_splitk = lay.splitk != 0 ? SplitKPlan{F(lay.splitk), layers_splitk_floats(sh)} : SplitKPlan{};
+    return forward_run(c, wav, geom_uniform(sh), bf, head_w, head_b, emb, layers_out, ws_splitk, static_cast<hipStream_t>(stream), sv, mode);
 }
 
 // layers_out / saved (nomad_embed_train_ragged): the packed layer outputs and, with a saved block, the training-mode forward.
@@ -1396,16 +1363,17 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
     if (c->tune.f32_posconv_wino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws), bf.pwmeta = reinterpret_cast<int*>(ws + lay.pwmeta);
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(i % 2 ? lay.convb : lay.conva);   // conv6 lands in conva, LN(512) writes to convb
-    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, layers_out, nullptr, 0, s, saved ? &sv : nullptr, mode);
+    return forward_run(c, wav, r.g, bf, head_w, head_b, emb, layers_out, SplitKPlan{}, s, saved ? &sv : nullptr, mode);
 }
 
 // One backward GEMM: C[M][N] = A[M][K] * Wt[N][K]^T (Wt = transposed forward weight), optional GELU' and residual.
+// plan / fuse / fused: run_gemm's.
 static int bwd_gemm(nomad_ctx* c, const float* A, const float* Wt, float* C, int M, int N, int K, const float* DG,
-                    const float* R, hipStream_t s) {
+                    const float* R, hipStream_t s, const SplitKPlan& plan, const SplitKFusion* fuse = nullptr, bool* fused = nullptr) {
     GemmParams p = dense(A, K, Wt, nullptr, R, C, M, N, K, 0);
     p.DG = DG;
     p.dgmap = plain_map(M, N);
-    return run_gemm(c, p, 1, pick_tile(c, M, N, K), s);
+    return run_gemm(c, p, 1, pick_tile(c, M, N, K), s, plan, fuse, fused);
 }
 
 static int run_ln_bwd(nomad_ctx* c, const float* x, const float* g, const float* g2, const float* gamma, float* dx, int M,
@@ -2279,7 +2247,7 @@ int nomad_diag_posconv(nomad_ctx* c, const float* x, const float* v, const float
         p.N = 64;
         p.n_valid = 48;
         p.gelu = 1;
-        rc = run_gemm(c, p, 16, 48, s);
+        rc = gemm_f32_dispatch(c, p, 16, 48, s);
     }
     if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_diag_posconv: kernel");
     (void)hipFree(d);
@@ -2597,7 +2565,7 @@ static int dw_gemm(nomad_ctx* c, const float* TA, const float* TB, int Nout, int
     p.w_goff = Kc;
     p.c_goff = (long long)Nout * Kin;
     int rc;
-    if ((rc = run_gemm(c, p, S, tile, s))) return rc;
+    if ((rc = gemm_f32_dispatch(c, p, S, tile, s))) return rc;   // (its own split over the groups: never run_gemm's)
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
     const long long n4 = (long long)Nout * Kin / 4, n4s = (long long)rows_scaled * Kin / 4;
     const float4* p4 = reinterpret_cast<const float4*>(part);
@@ -2631,17 +2599,8 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
     const int B = g.B, T = g.T, M = (int)g.rows[6], n_samples = g.wav_ld;
     const bool rg = g.ragged();
     const int* const tpref = g.pref[6];   // kNoInts for an equal-length batch
-    const SplitKScope splitk(c, !train && !c->train_ready && !rg);  // d loss / d waveform of Nomad.forward(): small-M GEMMs may split K
-    float* const prev_cur_b = c->splitk_cur;
-    const size_t prev_cur_floats_b = c->splitk_cur_floats;
-    c->splitk_cur = c->splitk_part;
-    c->splitk_cur_floats = kSplitKPartFloats;
-    struct CurRestoreB {
-        nomad_ctx* c;
-        float* v;
-        size_t n;
-        ~CurRestoreB() { c->splitk_cur = v; c->splitk_cur_floats = n; }
-    } cur_restore_b{c, prev_cur_b, prev_cur_floats_b};
+    // d loss / d waveform of Nomad.forward(): small-M GEMMs may split K, into the context's block
+    const SplitKPlan splitk = train || c->train_ready || rg ? SplitKPlan{} : SplitKPlan{c->splitk_part, kSplitKPartFloats};
     float *gx = F(lay.gx), *dya = F(lay.dya), *dyb = F(lay.dyb), *dh = F(lay.dh), *dqkv = F(lay.dqkv);
     int rc;
     // the regularisation of the forward this backward belongs to (the caller re-sets it: nomad_train_set_stochastic)
@@ -2743,7 +2702,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
             tpose(u, 3072, TB, true, Ms, Mps);  // h = gelu(u), recomputed
             if ((rc = dw_gemm(c, TA, TB, 768, 3072, Mps, part, G(lo.fc2_w), 0, 1.0f, s))) return rc;
         }
-        if ((rc = bwd_gemm(c, dy2b, c->fc2_wT[l], dhs, Ms, 3072, 768, u, nullptr, s))) return rc;      // du = (dy2 W2) * gelu'(u)
+        if ((rc = bwd_gemm(c, dy2b, c->fc2_wT[l], dhs, Ms, 3072, 768, u, nullptr, s, splitk))) return rc;      // du = (dy2 W2) * gelu'(u)
         if (pg) {
             tpose(dhs, 3072, TA, false, Ms, Mps);
             rowsum(TA, 3072, G(lo.fc1_b), 1.0f, Mps);
@@ -2752,15 +2711,11 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
             tpose(gxs, 768, TB, false, Ms, Mps);
             if ((rc = dw_gemm(c, TA, TB, 3072, 768, Mps, part, G(lo.fc1_w), 0, 1.0f, s))) return rc;
         }
-        // (dX-only backward: when the GEMM splits K, the LayerNorm backward forms dx1 from the partial products itself - pending_lnb)
-        c->pending_lnb = {};
-        if (!train) {
-            c->pending_lnb.x = y1; c->pending_lnb.gamma = d.ln1_w; c->pending_lnb.out = dyas; c->pending_lnb.armed = true;
-        }
-        rc = bwd_gemm(c, dhs, c->fc1_wT[l], dybs, Ms, 768, 3072, nullptr, dyas, s);                    // dx1 = du W1 + dy2
-        const bool ln1_done = c->pending_lnb.armed && c->pending_lnb.done;
-        c->pending_lnb = {};
-        if (rc) return rc;
+        // (dX-only backward: when the GEMM splits K, the LayerNorm backward forms dx1 from the partial products itself)
+        const SplitKFusion ln1_bwd = SplitKFusion::ln_bwd(y1, nullptr, d.ln1_w, dyas);
+        bool ln1_done = false;
+        if ((rc = bwd_gemm(c, dhs, c->fc1_wT[l], dybs, Ms, 768, 3072, nullptr, dyas, s, splitk, train ? nullptr : &ln1_bwd, &ln1_done)))
+            return rc;                                                                                 // dx1 = du W1 + dy2
         if (!ln1_done && (rc = run_ln_bwd(c, y1, dybs, nullptr, d.ln1_w, dyas, Ms, 768, s))) return rc;   // dy1
         if (pg) ln_params(y1, dybs, nullptr, 768, G(lo.ln1_w), G(lo.ln1_b), Ms);
         const float* dy1b = dyas;  // dy1 through out_proj's dropout mask
@@ -2774,7 +2729,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
             tpose(ctx, 768, TB, false, Ms, Mps);
             if ((rc = dw_gemm(c, TA, TB, 768, 768, Mps, part, G(lo.o_w), 0, 1.0f, s))) return rc;
         }
-        if ((rc = bwd_gemm(c, dy1b, c->o_wT[l], dybs, Ms, 768, 768, nullptr, nullptr, s))) return rc;  // dctx
+        if ((rc = bwd_gemm(c, dy1b, c->o_wT[l], dybs, Ms, 768, 768, nullptr, nullptr, s, splitk))) return rc;  // dctx
         if (rg) {   // the whole batch's pointers and prefix sums, clips [c0, c0 + nc); fused or three kernels by each CLIP's length
             Scope sc(c, s, NOMAD_K_ATTN, 3.5 * g.attn_flops * nc / B);
             HIP_TRY(launch_attention_bwd_ragged(sl0.qkv, sl0.ctx, dyb, sl0.lse, F(lay.attnd), dqkv, tpref, B, c0, nc, (int)r0, (int)r0 + Ms,
@@ -2799,20 +2754,11 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
         }
         // dx_in = dqkv Wqkv + dy1; what follows it is the LayerNorm backward of the layer below (its LN2, with that layer's output gradient) or
         // of the encoder's LayerNorm: fused into the split-K epilogue where the whole batch walks the layers together (no LayerDrop)
-        c->pending_lnb = {};
-        if (!train && whole_batch && !d_res.threshold) {
-            if (l > 0) {
-                c->pending_lnb.x = sv.L[l - 1].y2; c->pending_lnb.gamma = c->layers[l - 1].ln2_w;
-                c->pending_lnb.g2 = dlayers ? dlayers + (size_t)(l - 1) * M * 768 : nullptr;
-            } else {
-                c->pending_lnb.x = sv.y0; c->pending_lnb.gamma = c->eln_w;
-            }
-            c->pending_lnb.out = dya; c->pending_lnb.armed = true;
-        }
-        rc = bwd_gemm(c, dqkvs, c->qkv_wT[l], gxs, Ms, 768, 2304, nullptr, dyas, s);
-        lnb_prefused = c->pending_lnb.armed && c->pending_lnb.done;
-        c->pending_lnb = {};
-        return rc;
+        const SplitKFusion below = l > 0 ? SplitKFusion::ln_bwd(sv.L[l - 1].y2, dlayers ? dlayers + (size_t)(l - 1) * M * 768 : nullptr,
+                                                                c->layers[l - 1].ln2_w, dya)
+                                         : SplitKFusion::ln_bwd(sv.y0, nullptr, c->eln_w, dya);
+        const bool offer = !train && whole_batch && !d_res.threshold;
+        return bwd_gemm(c, dqkvs, c->qkv_wT[l], gxs, Ms, 768, 2304, nullptr, dyas, s, splitk, offer ? &below : nullptr, &lnb_prefused);
     };
     for (int l = depth - 1; l >= 0; --l) {
         unsigned all = 1u;
@@ -2857,7 +2803,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
         p.M = M;
         p.N = 64;
         p.n_valid = 48;
-        if ((rc = run_gemm(c, p, 16, 48, s))) return rc;  // one instantiation for every batch size: same summation order
+        if ((rc = run_gemm(c, p, 16, 48, s, splitk))) return rc;  // one instantiation for every batch size: same summation order
     }
     if (train) {
         float *dug = F(lay.dug), *xg = F(lay.xg), *dwe = F(lay.dwe), *featln = F(lay.f2);
@@ -2880,7 +2826,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
             p.cmap = g.pad_map;
             p.c_colblk = 48;
             p.c_colblk_stride = grp_stride;
-            if ((rc = run_gemm(c, p, 1, pick_tile(c, M, 768, 512), s))) return rc;
+            if ((rc = gemm_f32_dispatch(c, p, 1, pick_tile(c, M, 768, 512), s))) return rc;   // (fine-tuning only)
         }
         if (d_in.threshold) {
             Scope sc(c, s, NOMAD_K_ROW, 0.0);
@@ -2905,7 +2851,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
         if ((rc = dw_gemm(c, TA, TB, 768, 512, Mp, part, G(po.proj_w), 0, 1.0f, s))) return rc;
     }
     // ---- post_extract_proj, LayerNorm(512), GELU of conv6 ----------------------------------------------
-    if ((rc = bwd_gemm(c, dyb, c->proj_wT, F(lay.f1), M, 512, 768, nullptr, nullptr, s))) return rc;
+    if ((rc = bwd_gemm(c, dyb, c->proj_wT, F(lay.f1), M, 512, 768, nullptr, nullptr, s, splitk))) return rc;
     if (train) ln_params(sv.c6, F(lay.f1), nullptr, 512, G(po.fln_w), G(po.fln_b), M);
     HIP_TRY(hipGetLastError());
     if (!dwav && !conv_pg) return 0;  // frozen conv feature extractor (freeze_convnet: True): nothing upstream needs a gradient
@@ -3005,7 +2951,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
             p.cmap = cmap_of(out_off, Lout, g.pref[i]);
             p.dgmap = dgmap_of(0, Lout, g.pref[i]);
             p.kchunk = p.K; p.ldw = p.K; p.n_valid = p.N;
-            if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s))) return rc;
+            if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s, splitk))) return rc;
         } else {
             const int E = (Lin + 1) / 2, O = Lin / 2;
             // even input frames 2t': dU[t'-1] W_tap2 + dU[t'] W_tap0
@@ -3017,7 +2963,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
             p.cmap = cmap_of(out_off, E, g.epref[i - 1]);
             p.dgmap = dgmap_of(0, E, g.epref[i - 1]);
             p.kchunk = p.K; p.ldw = p.K; p.n_valid = p.N;
-            if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s))) return rc;
+            if ((rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s, splitk))) return rc;
             // odd input frames 2t'+1: dU[t'] W_tap1
             p.amap = amap_of(512, O, g.opref[i - 1]);
             p.K = 512;
@@ -3026,7 +2972,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
             p.cmap = cmap_of(out_off + 512, O, g.opref[i - 1]);
             p.dgmap = dgmap_of(512, O, g.opref[i - 1]);
             p.kchunk = p.K; p.ldw = p.K;
-            if (p.M > 0 && (rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s))) return rc;
+            if (p.M > 0 && (rc = run_gemm(c, p, 1, pick_tile(c, p.M, p.N, p.K), s, splitk))) return rc;
         }
     }
     // ---- conv0 + GroupNorm -> d loss / d waveform -------------------------------------------------------

@@ -307,7 +307,8 @@ def test_splitk_epilogue_with_its_layernorm_is_bit_identical(built_lib, sd0, mon
 def test_layernorm_backward_inside_the_split_k_epilogue_is_bit_identical(built_lib, sd0, monkeypatch):
     """Round 6: in the dX-only backward of a small batch the GEMMs in front of a LayerNorm backward (fc1^T, and qkv^T in front of the layer
     below's LN2 / the encoder LN) split K; the LayerNorm-backward kernel then forms their output row from the partial products itself
-    (layernorm_bwd_kernel<3, true>) - 25 epilogue launches fewer per configs[3] step.  Against NOMAD_SPLITK_LNB=0 (epilogue + stand-alone
+    (layernorm_bwd_kernel<3, true>) - 24 epilogue launches fewer per configs[3] step (12 fc1^T, 11 qkv^T in front of an LN2, 1 in front
+    of the encoder LayerNorm: counted by test_gpu_splitk_plan.py).  Against NOMAD_SPLITK_LNB=0 (epilogue + stand-alone
     kernel): d loss / d waveform bit for bit, with and without layer-output gradients, and for a batch too large to split (unchanged path)."""
     from nomad_amd.engine import Engine
     gen = torch.Generator().manual_seed(6)
