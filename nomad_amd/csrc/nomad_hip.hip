@@ -514,58 +514,179 @@ BwdLayout make_bwd_layout(const BatchGeom& s, bool train = false, bool train_con
     return l;
 }
 
-// Trainable parameters (everything after the frozen conv feature extractor) as ONE flat fp32 vector; gradients and
-// the Adam moments use the same offsets.  q/k/v of a layer are stored fused [q | k | v] in checkpoint scale.
+// The master parameters as ONE flat fp32 vector: every parameter of nomad_best_model.pt that train_triplet.py can train
+// (mask_emb gets no gradient with mask=False) - encoder front, the 12 layers, the conv feature extractor, the head last, so that
+// `emb_w` splits body from head.  Gradients and the Adam moments use the same offsets.  q/k/v of a layer are stored fused
+// [q | k | v] in checkpoint scale.
 struct LayerOffsets {
     size_t qkv_w, qkv_b, o_w, o_b, ln1_w, ln1_b, fc1_w, fc1_b, fc2_w, fc2_b, ln2_w, ln2_b;
 };
 struct ParamOffsets {
     size_t fln_w, fln_b, proj_w, proj_b, pos_g, pos_v, pos_b, eln_w, eln_b;
     LayerOffsets L[NOMAD_NUM_LAYERS];
-    size_t conv0_w, gn_w, gn_b, conv_w[7];  // the conv feature extractor (checkpoint layout [co][ci][tap]); frozen unless
-                                            // nomad_train_set_convnet says otherwise
+    size_t conv0_w, gn_w, gn_b, conv_w[7];  // the conv feature extractor (checkpoint layout [co][ci][tap]): its slices keep a zero
+                                            // gradient unless nomad_train_set_convnet(ctx, 1) (config freeze_convnet: False)
     size_t emb_w, emb_b, total;
 };
 
-ParamOffsets make_param_offsets() {
-    ParamOffsets o{};
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        size_t r = off;
-        off += n;  // every segment is a multiple of 4 floats: 16-byte alignment is preserved
-        return r;
+// One tensor of the checkpoint, as for_each_param visits it.
+struct Param {
+    std::string key;    // checkpoint key (nomad_train_segment)
+    size_t count;       // floats
+    const float* host;  // where it sits in nomad_weights
+    size_t* slot;       // its offset in the master vector is *slot + sub (sub != 0: k and v inside the fused [q | k | v])
+    size_t sub;
+    float** alias;      // the context pointer the engine reads it through when that is the tensor as it stands (uploaded as it
+                        // is by nomad_create, pointed at the master vector by nomad_train_enable); nullptr where the engine reads
+                        // a derived copy: q/k/v (fused, q scaled), pos_g / pos_v (weight norm folded), conv1..6 (repacked)
+};
+
+// THE parameter inventory, in the master vector's order: everything that uploads, lays out, names or aliases the checkpoint's
+// parameters walks it.  w, po, c: the structures the visits point into (a walk that needs only names and sizes passes blanks).
+template <class F>
+void for_each_param(const nomad_weights& w, ParamOffsets& po, nomad_ctx& c, F&& f) {
+    auto v = [&](const std::string& key, size_t n, const float* host, size_t& slot, float** alias, size_t sub = 0) {
+        f(Param{key, n, host, &slot, sub, alias});
     };
-    o.fln_w = take(512); o.fln_b = take(512);
-    o.proj_w = take(768 * 512); o.proj_b = take(768);
-    o.pos_g = take(128); o.pos_v = take((size_t)768 * 48 * 128); o.pos_b = take(768);
-    o.eln_w = take(768); o.eln_b = take(768);
+    const std::string p = "ssl_model.";
+    v(p + "layer_norm.weight", 512, w.feat_ln_w, po.fln_w, &c.fln_w);
+    v(p + "layer_norm.bias", 512, w.feat_ln_b, po.fln_b, &c.fln_b);
+    v(p + "post_extract_proj.weight", 768 * 512, w.proj_w, po.proj_w, &c.proj_w);
+    v(p + "post_extract_proj.bias", 768, w.proj_b, po.proj_b, &c.proj_b);
+    v(p + "encoder.pos_conv.0.weight_g", 128, w.pos_g, po.pos_g, nullptr);
+    v(p + "encoder.pos_conv.0.weight_v", (size_t)768 * 48 * 128, w.pos_v, po.pos_v, nullptr);
+    v(p + "encoder.pos_conv.0.bias", 768, w.pos_b, po.pos_b, &c.pos_b);
+    v(p + "encoder.layer_norm.weight", 768, w.enc_ln_w, po.eln_w, &c.eln_w);
+    v(p + "encoder.layer_norm.bias", 768, w.enc_ln_b, po.eln_b, &c.eln_b);
     for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
-        LayerOffsets& q = o.L[l];
-        q.qkv_w = take((size_t)2304 * 768); q.qkv_b = take(2304);
-        q.o_w = take(768 * 768); q.o_b = take(768);
-        q.ln1_w = take(768); q.ln1_b = take(768);
-        q.fc1_w = take((size_t)3072 * 768); q.fc1_b = take(3072);
-        q.fc2_w = take((size_t)768 * 3072); q.fc2_b = take(768);
-        q.ln2_w = take(768); q.ln2_b = take(768);
+        const nomad_layer_weights& lw = w.layers[l];
+        LayerOffsets& lo = po.L[l];
+        LayerDev& d = c.layers[l];
+        const std::string b = p + "encoder.layers." + std::to_string(l) + ".";
+        const size_t ww = 768 * 768;
+        v(b + "self_attn.q_proj.weight", ww, lw.q_w, lo.qkv_w, nullptr);
+        v(b + "self_attn.k_proj.weight", ww, lw.k_w, lo.qkv_w, nullptr, ww);
+        v(b + "self_attn.v_proj.weight", ww, lw.v_w, lo.qkv_w, nullptr, 2 * ww);
+        v(b + "self_attn.q_proj.bias", 768, lw.q_b, lo.qkv_b, nullptr);
+        v(b + "self_attn.k_proj.bias", 768, lw.k_b, lo.qkv_b, nullptr, 768);
+        v(b + "self_attn.v_proj.bias", 768, lw.v_b, lo.qkv_b, nullptr, 1536);
+        v(b + "self_attn.out_proj.weight", ww, lw.o_w, lo.o_w, &d.o_w);
+        v(b + "self_attn.out_proj.bias", 768, lw.o_b, lo.o_b, &d.o_b);
+        v(b + "self_attn_layer_norm.weight", 768, lw.ln1_w, lo.ln1_w, &d.ln1_w);
+        v(b + "self_attn_layer_norm.bias", 768, lw.ln1_b, lo.ln1_b, &d.ln1_b);
+        v(b + "fc1.weight", (size_t)3072 * 768, lw.fc1_w, lo.fc1_w, &d.fc1_w);
+        v(b + "fc1.bias", 3072, lw.fc1_b, lo.fc1_b, &d.fc1_b);
+        v(b + "fc2.weight", (size_t)768 * 3072, lw.fc2_w, lo.fc2_w, &d.fc2_w);
+        v(b + "fc2.bias", 768, lw.fc2_b, lo.fc2_b, &d.fc2_b);
+        v(b + "final_layer_norm.weight", 768, lw.ln2_w, lo.ln2_w, &d.ln2_w);
+        v(b + "final_layer_norm.bias", 768, lw.ln2_b, lo.ln2_b, &d.ln2_b);
     }
-    o.conv0_w = take(512 * 10); o.gn_w = take(512); o.gn_b = take(512);
-    for (int i = 1; i < 7; ++i) o.conv_w[i] = take((size_t)512 * 512 * kConvK[i]);
-    o.emb_w = take(256 * 768); o.emb_b = take(256);
-    o.total = off;
-    return o;
+    const std::string fe = p + "feature_extractor.conv_layers.";
+    v(fe + "0.0.weight", 512 * 10, w.conv_w[0], po.conv0_w, &c.conv0_w);
+    v(fe + "0.2.weight", 512, w.gn_w, po.gn_w, &c.gn_w);
+    v(fe + "0.2.bias", 512, w.gn_b, po.gn_b, &c.gn_b);
+    for (int i = 1; i < 7; ++i) v(fe + std::to_string(i) + ".0.weight", (size_t)512 * 512 * kConvK[i], w.conv_w[i], po.conv_w[i], nullptr);
+    v("embedding_layer.1.weight", 256 * 768, w.emb_w, po.emb_w, &c.emb_w);
+    v("embedding_layer.1.bias", 256, w.emb_b, po.emb_b, &c.emb_b);
 }
 
-}  // namespace
+// Checkpoint key -> slice of the master vector (nomad_train_segment), and the offsets the kernels' call sites use: one walk, once.
+struct Segment {
+    std::string name;
+    size_t offset, count;
+};
+struct ParamTable {
+    ParamOffsets off;
+    std::vector<Segment> segs;
+};
+const ParamTable& param_table() {
+    static const ParamTable table = [] {
+        ParamTable t{};
+        const nomad_weights no_weights{};
+        nomad_ctx no_ctx;   // only addresses are formed
+        size_t off = 0;
+        for_each_param(no_weights, t.off, no_ctx, [&](const Param& p) {
+            if (p.sub == 0) *p.slot = off;
+            t.segs.push_back({p.key, off, p.count});
+            off += p.count;  // every segment is a multiple of 4 floats: 16-byte alignment is preserved
+        });
+        t.off.total = off;
+        return t;
+    }();
+    return table;
+}
+const ParamOffsets& param_offsets() { return param_table().off; }
+const std::vector<Segment>& segments() { return param_table().segs; }
 
-namespace {
-
-int upload(nomad_ctx* c, const float* host, size_t n, float** out) {
+// Every device buffer a context owns comes from here: allocated once - a pointer that is already set is kept, so an enable call
+// that is repeated after a weight update, or retried after a failure, allocates nothing twice - optionally cleared, and recorded
+// for nomad_destroy.
+template <class T>
+int dev_alloc(nomad_ctx* c, const char* who, size_t n, T** out, bool zero = false) {
+    if (*out) return 0;
     void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, n * sizeof(float)));
+    hipError_t e = hipMalloc(&d, n * sizeof(T));
+    if (e == hipSuccess && zero && (e = hipMemset(d, 0, n * sizeof(T))) != hipSuccess) (void)hipFree(d);
+    if (e != hipSuccess) return fail(NOMAD_ERR_HIP, "%s: %zu bytes of device memory: %s", who, n * sizeof(T), hipGetErrorString(e));
     c->allocs.push_back(d);
-    HIP_TRY(hipMemcpy(d, host, n * sizeof(float), hipMemcpyHostToDevice));
-    *out = static_cast<float*>(d);
+    *out = static_cast<T*>(d);
     return 0;
+}
+
+int upload(nomad_ctx* c, const char* who, const float* host, size_t n, float** out) {
+    if (int rc = dev_alloc(c, who, n, out)) return rc;
+    HIP_TRY(hipMemcpy(*out, host, n * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// One GEMM weight of the model and the copies the other paths keep of it; a copy that a weight does not have is a null slot.
+struct GemmWeight {
+    const float* w;  // fp32 in kernel layout [N][K]: what the fp32 forward contracts with
+    int N, K;
+    bf16_t** w16;    // nomad_enable_bf16
+    bf16s_t** wx;    // nomad_enable_bf16x3: hi | lo bf16 planes
+    float** wT;      // build_backward_weights: [K][N]
+};
+
+// THE list of GEMM weights: f(GemmWeight) -> error code; the walk ends at the first failure.
+template <class F>
+int for_each_gemm_weight(nomad_ctx* c, F&& f) {
+    int rc = 0;
+    auto v = [&](const float* w, int N, int K, bf16_t** w16, bf16s_t** wx, float** wT) {
+        if (rc == 0) rc = f(GemmWeight{w, N, K, w16, wx, wT});
+    };
+    for (int i = 1; i < 7; ++i)  // (their dX copies are cut by tap, not one transpose: build_backward_weights)
+        v(c->conv_w[i], 512, kConvK[i] * 512, &c->conv_w16[i], &c->conv_wx[i], nullptr);
+    v(c->proj_w, 768, 512, &c->proj_w16, &c->proj_wx, &c->proj_wT);
+    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
+        const LayerDev& d = c->layers[l];
+        v(d.qkv_w, 2304, 768, &c->qkv_w16[l], &c->qkv_wx[l], &c->qkv_wT[l]);
+        v(d.o_w, 768, 768, &c->o_w16[l], &c->o_wx[l], &c->o_wT[l]);
+        v(d.fc1_w, 3072, 768, &c->fc1_w16[l], &c->fc1_wx[l], &c->fc1_wT[l]);
+        v(d.fc2_w, 768, 3072, &c->fc2_w16[l], &c->fc2_wx[l], &c->fc2_wT[l]);
+    }
+    return rc;
+}
+
+void transpose(const float* in, int ld_in, float* out, int ld_out, int R, int C, hipStream_t s) {  // out[C][R] = in[R][C]^T
+    hipLaunchKernelGGL(transpose_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(32, 8), 0, s, in, ld_in, out, ld_out, R, C);
+}
+
+// Every weight copy the dX chain of the backward contracts with, from the kernel-layout forward weights, queued on s
+// (nomad_enable_backward: the null stream; refresh_weights: the caller's).  The buffers are nomad_enable_backward's.
+void build_backward_weights(nomad_ctx* c, hipStream_t s) {
+    for (int i = 1; i <= 4; ++i) {  // k = 3: forward repack is [n][tap*512 + c]
+        transpose(c->conv_w[i] + 2 * 512, 1536, c->conv_bw_even[i], 1024, 512, 512, s);        // tap 2 pairs with dU[t'-1]
+        transpose(c->conv_w[i], 1536, c->conv_bw_even[i] + 512, 1024, 512, 512, s);            // tap 0 pairs with dU[t']
+        transpose(c->conv_w[i] + 512, 1536, c->conv_bw_odd[i], 512, 512, 512, s);              // tap 1
+    }
+    for (int i = 5; i <= 6; ++i)  // k = 2: [n][tap*512 + c] -> [(tap*512 + c)][n]
+        transpose(c->conv_w[i], 1024, c->conv_bw2[i], 512, 512, 1024, s);
+    hipLaunchKernelGGL(posconv_bwd_weight_kernel, dim3(16 * 64), dim3(256), 0, s, c->pos_w, c->pos_wb);
+    (void)for_each_gemm_weight(c, [&](const GemmWeight& g) {
+        if (g.wT) transpose(g.w, g.K, *g.wT, g.N, g.N, g.K, s);
+        return 0;
+    });
 }
 
 
@@ -949,9 +1070,17 @@ int nomad_create(nomad_ctx** out, int device, const nomad_weights* w) {
 #endif
     int rc = 0;
     auto up = [&](const float* h, size_t n, float** d) {
-        if (rc == 0) rc = upload(c, h, n, d);
+        if (rc == 0) rc = upload(c, "nomad_create", h, n, d);
     };
-    up(w->conv_w[0], 512 * 10, &c->conv0_w);
+    // every tensor the engine reads as it stands ...
+    ParamOffsets po = param_offsets();
+    for_each_param(*w, po, *c, [&](const Param& p) {
+        if (p.alias) up(p.host, p.count, p.alias);
+    });
+    // ... and the derived copies, formed on the HOST here: conv1..6 repacked, weight norm folded, q/k/v fused with q scaled.
+    // refresh_weights forms the same three from the master vector on the DEVICE after a weight update (conv_repack_kernel,
+    // posconv_fold_kernel, scale_rows_kernel).  The repack and the scale are exact either way; the two weight-norm folds add
+    // their 36 864 squares per tap in different orders, so a scale can differ in its last bit - two routes on purpose.
     for (int i = 1; i < 7 && rc == 0; ++i) {
         const int k = kConvK[i];
         std::vector<float> r((size_t)512 * k * 512);
@@ -960,12 +1089,6 @@ int nomad_create(nomad_ctx** out, int device, const nomad_weights* w) {
                 for (int t = 0; t < k; ++t) r[(size_t)n * k * 512 + t * 512 + ci] = w->conv_w[i][((size_t)n * 512 + ci) * k + t];
         up(r.data(), r.size(), &c->conv_w[i]);
     }
-    up(w->gn_w, 512, &c->gn_w);
-    up(w->gn_b, 512, &c->gn_b);
-    up(w->feat_ln_w, 512, &c->fln_w);
-    up(w->feat_ln_b, 512, &c->fln_b);
-    up(w->proj_w, 768 * 512, &c->proj_w);
-    up(w->proj_b, 768, &c->proj_b);
     if (rc == 0) {  // fold weight_norm(dim=2): w = v * g[k] / ||v[:, :, k]||, then [group][64][tap*48 + cin]
         std::vector<double> nrm(128, 0.0);
         for (size_t o = 0; o < 768; ++o)
@@ -984,23 +1107,13 @@ int nomad_create(nomad_ctx** out, int device, const nomad_weights* w) {
                         r[(g * 64 + n) * 6144 + t * 48 + ci] = w->pos_v[((g * 48 + n) * 48 + ci) * 128 + t] * sc[t];
         up(r.data(), r.size(), &c->pos_w);
         if (rc == 0 && c->tune.f32_posconv_wino) {
-            void* d = nullptr;
-            const hipError_t e = hipMalloc(&d, sizeof(float) * 16 * kPwOps * 64 * kPwK);
-            if (e != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_create: pos-conv weights: %s", hipGetErrorString(e));
-            else {
-                c->allocs.push_back(d);
-                c->pos_wt = static_cast<float*>(d);
-                rc = rebuild_posconv_wino_weights(c, nullptr);
-                if (rc == 0 && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_create: pos-conv weights: kernel");
-            }
+            rc = dev_alloc(c, "nomad_create: pos-conv weights", (size_t)16 * kPwOps * 64 * kPwK, &c->pos_wt);
+            if (rc == 0) rc = rebuild_posconv_wino_weights(c, nullptr);
+            if (rc == 0 && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_create: pos-conv weights: kernel");
         }
     }
-    up(w->pos_b, 768, &c->pos_b);
-    up(w->enc_ln_w, 768, &c->eln_w);
-    up(w->enc_ln_b, 768, &c->eln_b);
     for (int l = 0; l < NOMAD_NUM_LAYERS && rc == 0; ++l) {
         const nomad_layer_weights& lw = w->layers[l];
-        LayerDev& d = c->layers[l];
         std::vector<float> qkv((size_t)2304 * 768), qb(2304);
         for (size_t i = 0; i < (size_t)768 * 768; ++i) {
             qkv[i] = lw.q_w[i] * 0.125f;  // fairseq MultiheadAttention: q *= head_dim^-0.5 (exact in fp32)
@@ -1012,29 +1125,13 @@ int nomad_create(nomad_ctx** out, int device, const nomad_weights* w) {
             qb[768 + i] = lw.k_b[i];
             qb[1536 + i] = lw.v_b[i];
         }
-        up(qkv.data(), qkv.size(), &d.qkv_w);
-        up(qb.data(), qb.size(), &d.qkv_b);
-        up(lw.o_w, 768 * 768, &d.o_w);
-        up(lw.o_b, 768, &d.o_b);
-        up(lw.ln1_w, 768, &d.ln1_w);
-        up(lw.ln1_b, 768, &d.ln1_b);
-        up(lw.fc1_w, (size_t)3072 * 768, &d.fc1_w);
-        up(lw.fc1_b, 3072, &d.fc1_b);
-        up(lw.fc2_w, (size_t)768 * 3072, &d.fc2_w);
-        up(lw.fc2_b, 768, &d.fc2_b);
-        up(lw.ln2_w, 768, &d.ln2_w);
-        up(lw.ln2_b, 768, &d.ln2_b);
+        up(qkv.data(), qkv.size(), &c->layers[l].qkv_w);
+        up(qb.data(), qb.size(), &c->layers[l].qkv_b);
     }
-    up(w->emb_w, 256 * 768, &c->emb_w);
-    up(w->emb_b, 256, &c->emb_b);
     if (rc == 0) {
-        void* d = nullptr;
-        const hipError_t e = hipMalloc(&d, sizeof(double) * kPairScratchDoubles);
-        if (e != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_create: pairwise scratch: %s", hipGetErrorString(e));
-        else {
-            c->allocs.push_back(d);
-            c->pair_scratch.emplace_back(kNoStream, static_cast<double*>(d));
-        }
+        double* d = nullptr;
+        rc = dev_alloc(c, "nomad_create: pairwise scratch", (size_t)kPairScratchDoubles, &d);
+        if (rc == 0) c->pair_scratch.emplace_back(kNoStream, d);
     }
     if (rc != 0) {
         nomad_destroy(c);
@@ -1855,50 +1952,26 @@ int nomad_enable_bf16(nomad_ctx* c) {
     // A weight update (nomad_train_adam_step / nomad_train_write) rebuilt the fp32 kernel-layout weights on the CALLER's
     // stream, which may be a non-blocking stream the null stream does not wait for: drain the device before converting.
     HIP_TRY(hipDeviceSynchronize());
-    auto conv = [&](const float* src, size_t n, bf16_t** out) -> int {
-        if (!*out) {  // re-enabling after a weight update reuses the buffers
-            void* d = nullptr;
-            HIP_TRY(hipMalloc(&d, n * sizeof(bf16_t)));
-            c->allocs.push_back(d);
-            *out = static_cast<bf16_t*>(d);
-        }
+    static const char who[] = "nomad_enable_bf16";   // (a buffer that exists is reused: re-enabling after a weight update)
+    auto to_bf16 = [&](const float* src, size_t n, bf16_t** out) -> int {
+        if (int rc = dev_alloc(c, who, n, out)) return rc;
         hipLaunchKernelGGL(to_bf16_kernel, dim3(1024), dim3(256), 0, 0, src, *out, (long long)(n / 4));
         return 0;
     };
     int rc;
-    if (!c->conv0_wfrag) {
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, (size_t)8 * 4 * 64 * 8 * sizeof(bf16_t)));
-        c->allocs.push_back(d);
-        c->conv0_wfrag = static_cast<bf16_t*>(d);
-    }
+    if ((rc = for_each_gemm_weight(c, [&](const GemmWeight& g) { return to_bf16(g.w, (size_t)g.N * g.K, g.w16); }))) return rc;
+    // what is not a plain conversion of one GEMM weight: conv0's and the pos-conv's operands in MFMA fragment order ...
+    if ((rc = dev_alloc(c, who, (size_t)8 * 4 * 64 * 8, &c->conv0_wfrag))) return rc;
     hipLaunchKernelGGL(conv0_wfrag_kernel, dim3(32), dim3(64), 0, 0, c->conv0_w, c->conv0_wfrag);
-    for (int i = 1; i < 7; ++i)
-        if ((rc = conv(c->conv_w[i], (size_t)512 * kConvK[i] * 512, &c->conv_w16[i]))) return rc;
-    if ((rc = conv(c->proj_w, (size_t)768 * 512, &c->proj_w16))) return rc;
-    if ((rc = conv(c->pos_w, (size_t)16 * 64 * 6144, &c->pos_w16))) return rc;
-    if (!c->pos_wfrag16) {
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, posconv_wfrag_elems() * sizeof(bf16_t)));
-        c->allocs.push_back(d);
-        c->pos_wfrag16 = static_cast<bf16_t*>(d);
-    }
+    if ((rc = to_bf16(c->pos_w, (size_t)16 * 64 * 6144, &c->pos_w16))) return rc;
+    if ((rc = dev_alloc(c, who, posconv_wfrag_elems(), &c->pos_wfrag16))) return rc;
     hipLaunchKernelGGL(posconv_wfrag_kernel, dim3(16 * 192), dim3(192), 0, 0, c->pos_w, c->pos_wfrag16);
-    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
+    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {  // ... and the q rows of the fused QKV weight and bias, which also carry log2(e)
         const LayerDev& d = c->layers[l];
-        if ((rc = conv(d.qkv_w, (size_t)2304 * 768, &c->qkv_w16[l]))) return rc;
         hipLaunchKernelGGL(to_bf16_scaled_kernel, dim3(1024), dim3(256), 0, 0, d.qkv_w, c->qkv_w16[l], (long long)2304 * 768 / 4,
                            (long long)768 * 768 / 4, kLog2e);  // q rows: q * 64^-0.5 * log2(e), rounded to bf16 once
-        if (!c->qkv_b16[l]) {
-            void* p = nullptr;
-            HIP_TRY(hipMalloc(&p, 2304 * sizeof(float)));
-            c->allocs.push_back(p);
-            c->qkv_b16[l] = static_cast<float*>(p);
-        }
+        if ((rc = dev_alloc(c, who, 2304, &c->qkv_b16[l]))) return rc;
         hipLaunchKernelGGL(scale_head_kernel, dim3(9), dim3(256), 0, 0, d.qkv_b, c->qkv_b16[l], 2304, 768, kLog2e);
-        if ((rc = conv(d.o_w, (size_t)768 * 768, &c->o_w16[l]))) return rc;
-        if ((rc = conv(d.fc1_w, (size_t)3072 * 768, &c->fc1_w16[l]))) return rc;
-        if ((rc = conv(d.fc2_w, (size_t)768 * 3072, &c->fc2_w16[l]))) return rc;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -1926,40 +1999,20 @@ int nomad_enable_bf16x3(nomad_ctx* c) {
     if (c->x3_ready) return 0;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());  // see nomad_enable_bf16: the fp32 weights may have been rebuilt on another stream
-    auto conv = [&](const float* src, size_t n, bf16s_t** out) -> int {
-        if (!*out) {  // re-enabling after a weight update reuses the buffers
-            void* d = nullptr;
-            HIP_TRY(hipMalloc(&d, 2 * n * sizeof(bf16_t)));
-            c->allocs.push_back(d);
-            *out = static_cast<bf16s_t*>(d);
-        }
-        hipLaunchKernelGGL(split_bf16_kernel, dim3(1024), dim3(256), 0, 0, src, *out, (long long)n, (long long)(n / 4));
+    static const char who[] = "nomad_enable_bf16x3";   // (a buffer that exists is reused: re-enabling after a weight update)
+    int rc = for_each_gemm_weight(c, [&](const GemmWeight& g) -> int {
+        const size_t n = (size_t)g.N * g.K;
+        if (int rc = dev_alloc(c, who, 2 * n, g.wx)) return rc;
+        hipLaunchKernelGGL(split_bf16_kernel, dim3(1024), dim3(256), 0, 0, g.w, *g.wx, (long long)n, (long long)(n / 4));
         return 0;
-    };
-    int rc;
-    for (int i = 1; i < 7; ++i)
-        if ((rc = conv(c->conv_w[i], (size_t)512 * kConvK[i] * 512, &c->conv_wx[i]))) return rc;
-    if ((rc = conv(c->proj_w, (size_t)768 * 512, &c->proj_wx))) return rc;
-    {
+    });
+    if (rc) return rc;
+    {  // what is not a split copy of one GEMM weight: the pos-conv in Toeplitz form and its bias
         const size_t n = (size_t)16 * 256 * kPosKt;
-        if (!c->pos_wx) {
-            void* d = nullptr;
-            HIP_TRY(hipMalloc(&d, 2 * n * sizeof(bf16_t)));
-            c->allocs.push_back(d);
-            c->pos_wx = static_cast<bf16s_t*>(d);
-            HIP_TRY(hipMalloc(&d, 16 * 256 * sizeof(float)));
-            c->allocs.push_back(d);
-            c->pos_bx = static_cast<float*>(d);
-        }
+        if ((rc = dev_alloc(c, who, 2 * n, &c->pos_wx))) return rc;
+        if ((rc = dev_alloc(c, who, (size_t)16 * 256, &c->pos_bx))) return rc;
         hipLaunchKernelGGL(posconv_toeplitz_kernel, dim3(16 * 256), dim3(256), 0, 0, c->pos_w, c->pos_wx, (long long)n);
         hipLaunchKernelGGL(posconv_toeplitz_bias_kernel, dim3(16), dim3(256), 0, 0, c->pos_b, c->pos_bx);
-    }
-    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
-        const LayerDev& d = c->layers[l];
-        if ((rc = conv(d.qkv_w, (size_t)2304 * 768, &c->qkv_wx[l]))) return rc;
-        if ((rc = conv(d.o_w, (size_t)768 * 768, &c->o_wx[l]))) return rc;
-        if ((rc = conv(d.fc1_w, (size_t)3072 * 768, &c->fc1_wx[l]))) return rc;
-        if ((rc = conv(d.fc2_w, (size_t)768 * 3072, &c->fc2_wx[l]))) return rc;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -2452,58 +2505,24 @@ int nomad_embed_train_ragged(nomad_ctx* c, const float* wav, int B, int stride, 
                           "nomad_embed_train_ragged", false, layers_out, saved, saved_bytes);
 }
 
-}  // extern "C"
-namespace {
-void rebuild_conv_bwd_weights(nomad_ctx* c, hipStream_t s);
-}
-extern "C" {
-
 int nomad_enable_backward(nomad_ctx* c) {
     if (!c) return fail(NOMAD_ERR_INVALID, "null ctx");
     if (c->bwd_ready) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    auto alloc = [&](size_t floats, float** out) -> int {
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, floats * sizeof(float)));
-        c->allocs.push_back(d);
-        *out = static_cast<float*>(d);
-        return 0;
-    };
-    auto transpose = [&](const float* in, int ld_in, float* out, int ld_out, int R, int C) {
-        hipLaunchKernelGGL(transpose_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(32, 8), 0, 0, in, ld_in, out, ld_out, R, C);
-    };
+    static const char who[] = "nomad_enable_backward";
     int rc;
     for (int i = 1; i <= 4; ++i) {
-        if ((rc = alloc(512 * 1024, &c->conv_bw_even[i]))) return rc;
-        if ((rc = alloc(512 * 512, &c->conv_bw_odd[i]))) return rc;
+        if ((rc = dev_alloc(c, who, (size_t)512 * 1024, &c->conv_bw_even[i]))) return rc;
+        if ((rc = dev_alloc(c, who, (size_t)512 * 512, &c->conv_bw_odd[i]))) return rc;
     }
     for (int i = 5; i <= 6; ++i)
-        if ((rc = alloc(1024 * 512, &c->conv_bw2[i]))) return rc;
-    rebuild_conv_bwd_weights(c, 0);
-    if ((rc = alloc(512 * 768, &c->proj_wT))) return rc;
-    transpose(c->proj_w, 512, c->proj_wT, 768, 768, 512);
-    if ((rc = alloc((size_t)16 * 64 * 6144, &c->pos_wb))) return rc;
-    hipLaunchKernelGGL(posconv_bwd_weight_kernel, dim3(16 * 64), dim3(256), 0, 0, c->pos_w, c->pos_wb);
-    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
-        const LayerDev& d = c->layers[l];
-        if ((rc = alloc((size_t)768 * 2304, &c->qkv_wT[l]))) return rc;
-        if ((rc = alloc((size_t)768 * 768, &c->o_wT[l]))) return rc;
-        if ((rc = alloc((size_t)768 * 3072, &c->fc1_wT[l]))) return rc;
-        if ((rc = alloc((size_t)3072 * 768, &c->fc2_wT[l]))) return rc;
-        transpose(d.qkv_w, 768, c->qkv_wT[l], 2304, 2304, 768);
-        transpose(d.o_w, 768, c->o_wT[l], 768, 768, 768);
-        transpose(d.fc1_w, 768, c->fc1_wT[l], 3072, 3072, 768);
-        transpose(d.fc2_w, 3072, c->fc2_wT[l], 768, 768, 3072);
-    }
+        if ((rc = dev_alloc(c, who, (size_t)1024 * 512, &c->conv_bw2[i]))) return rc;
+    if ((rc = dev_alloc(c, who, (size_t)16 * 64 * 6144, &c->pos_wb))) return rc;
+    if ((rc = for_each_gemm_weight(c, [&](const GemmWeight& g) { return g.wT ? dev_alloc(c, who, (size_t)g.N * g.K, g.wT) : 0; }))) return rc;
+    build_backward_weights(c, 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    if (!c->splitk_part) {
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, kSplitKPartFloats * sizeof(float)));
-        c->allocs.push_back(d);
-        c->splitk_part = static_cast<float*>(d);
-    }
-
+    if ((rc = dev_alloc(c, who, kSplitKPartFloats, &c->splitk_part))) return rc;
     c->bwd_ready = true;
     return 0;
 }
@@ -2617,7 +2636,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
     float* dmask = train ? F(lay.dmask) : nullptr;
 
     // ---- parameter-gradient helpers (train only); Ms rows of the (sub-)batch, Mps = Ms rounded up to 512 ------
-    const ParamOffsets po = make_param_offsets();
+    const ParamOffsets& po = param_offsets();
     auto G = [&](size_t off) { return c->grad + off; };
     float *TA = train ? F(lay.ta) : nullptr, *TB = train ? F(lay.tb) : nullptr, *part = train ? F(lay.kpart) : nullptr;
     auto tpose = [&](const float* in, int C, float* out, bool gelu, int Ms, int Mps) {  // out[C][Mps] = f(in[Ms][C])^T, zero padded
@@ -3055,97 +3074,25 @@ static int backward_ragged(const char* who, nomad_ctx* c, const float* wav, int 
 // ---- fine-tuning state ------------------------------------------------------------------------------------
 namespace {
 
-struct Segment {
-    std::string name;
-    size_t offset, count;
-};
-
-// Checkpoint key -> slice of the flat parameter vector: every parameter of nomad_best_model.pt that train_triplet.py can
-// train (mask_emb gets no gradient with mask=False).  The conv feature extractor's slices keep a zero gradient unless
-// nomad_train_set_convnet(ctx, 1) (config freeze_convnet: False).
-const std::vector<Segment>& segments() {
-    static const std::vector<Segment> segs = [] {
-        std::vector<Segment> v;
-        const ParamOffsets o = make_param_offsets();
-        const std::string p = "ssl_model.";
-        v.push_back({p + "layer_norm.weight", o.fln_w, 512});
-        v.push_back({p + "layer_norm.bias", o.fln_b, 512});
-        v.push_back({p + "post_extract_proj.weight", o.proj_w, 768 * 512});
-        v.push_back({p + "post_extract_proj.bias", o.proj_b, 768});
-        v.push_back({p + "encoder.pos_conv.0.weight_g", o.pos_g, 128});
-        v.push_back({p + "encoder.pos_conv.0.weight_v", o.pos_v, (size_t)768 * 48 * 128});
-        v.push_back({p + "encoder.pos_conv.0.bias", o.pos_b, 768});
-        v.push_back({p + "encoder.layer_norm.weight", o.eln_w, 768});
-        v.push_back({p + "encoder.layer_norm.bias", o.eln_b, 768});
-        for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
-            const LayerOffsets& q = o.L[l];
-            const std::string b = p + "encoder.layers." + std::to_string(l) + ".";
-            const size_t ww = 768 * 768;
-            v.push_back({b + "self_attn.q_proj.weight", q.qkv_w, ww});
-            v.push_back({b + "self_attn.k_proj.weight", q.qkv_w + ww, ww});
-            v.push_back({b + "self_attn.v_proj.weight", q.qkv_w + 2 * ww, ww});
-            v.push_back({b + "self_attn.q_proj.bias", q.qkv_b, 768});
-            v.push_back({b + "self_attn.k_proj.bias", q.qkv_b + 768, 768});
-            v.push_back({b + "self_attn.v_proj.bias", q.qkv_b + 1536, 768});
-            v.push_back({b + "self_attn.out_proj.weight", q.o_w, ww});
-            v.push_back({b + "self_attn.out_proj.bias", q.o_b, 768});
-            v.push_back({b + "self_attn_layer_norm.weight", q.ln1_w, 768});
-            v.push_back({b + "self_attn_layer_norm.bias", q.ln1_b, 768});
-            v.push_back({b + "fc1.weight", q.fc1_w, (size_t)3072 * 768});
-            v.push_back({b + "fc1.bias", q.fc1_b, 3072});
-            v.push_back({b + "fc2.weight", q.fc2_w, (size_t)768 * 3072});
-            v.push_back({b + "fc2.bias", q.fc2_b, 768});
-            v.push_back({b + "final_layer_norm.weight", q.ln2_w, 768});
-            v.push_back({b + "final_layer_norm.bias", q.ln2_b, 768});
-        }
-        const std::string fe = p + "feature_extractor.conv_layers.";
-        v.push_back({fe + "0.0.weight", o.conv0_w, 512 * 10});
-        v.push_back({fe + "0.2.weight", o.gn_w, 512});
-        v.push_back({fe + "0.2.bias", o.gn_b, 512});
-        for (int i = 1; i < 7; ++i) v.push_back({fe + std::to_string(i) + ".0.weight", o.conv_w[i], (size_t)512 * 512 * kConvK[i]});
-        v.push_back({"embedding_layer.1.weight", o.emb_w, 256 * 768});
-        v.push_back({"embedding_layer.1.bias", o.emb_b, 256});
-        return v;
-    }();
-    return segs;
-}
-
-// The transposed conv weights the dX chain of the backward contracts with (from the kernel-layout forward weights).
-void rebuild_conv_bwd_weights(nomad_ctx* c, hipStream_t s) {
-    auto transpose = [&](const float* in, int ld_in, float* out, int ld_out, int R, int C) {
-        hipLaunchKernelGGL(transpose_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(32, 8), 0, s, in, ld_in, out, ld_out, R, C);
-    };
-    for (int i = 1; i <= 4; ++i) {  // k = 3: forward repack is [n][tap*512 + c]
-        transpose(c->conv_w[i] + 2 * 512, 1536, c->conv_bw_even[i], 1024, 512, 512);        // tap 2 pairs with dU[t'-1]
-        transpose(c->conv_w[i], 1536, c->conv_bw_even[i] + 512, 1024, 512, 512);            // tap 0 pairs with dU[t']
-        transpose(c->conv_w[i] + 512, 1536, c->conv_bw_odd[i], 512, 512, 512);              // tap 1
-    }
-    for (int i = 5; i <= 6; ++i)  // k = 2: [n][tap*512 + c] -> [(tap*512 + c)][n]
-        transpose(c->conv_w[i], 1024, c->conv_bw2[i], 512, 512, 1024);
-}
-
 // Rebuild every kernel-layout weight that is not a plain alias of the master vector: the fused, q-scaled q/k/v
-// weights, the weight-normed pos-conv kernel, and the transposed copies the backward contracts with.
+// weights, the weight-normed pos-conv kernel, the repacked convs, and the copies the backward contracts with.
 int refresh_weights(nomad_ctx* c, hipStream_t s) {
-    const ParamOffsets po = make_param_offsets();
-    auto transpose = [&](const float* in, int ld_in, float* out, int ld_out, int R, int C) {
-        hipLaunchKernelGGL(transpose_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(32, 8), 0, s, in, ld_in, out, ld_out, R, C);
-    };
+    const ParamOffsets& po = param_offsets();
+    // The derived fp32 weights, formed on the DEVICE from the master vector: weight norm folded, conv1..6 repacked, q/k/v scaled.
+    // nomad_create forms the same three on the HOST from the checkpoint; the repack and the scale are exact either way, the two
+    // weight-norm folds add their squares in different orders (a scale can differ in its last bit) - two routes on purpose.
     hipLaunchKernelGGL(tap_dot_partial_kernel, dim3(576), dim3(256), 0, s, c->theta + po.pos_v, (const float*)nullptr,
                        c->tap_partial);
     hipLaunchKernelGGL(tap_sum_final_kernel, dim3(1), dim3(1024), 0, s, c->tap_partial, 576, c->pos_nrm2);
     hipLaunchKernelGGL(posconv_fold_kernel, dim3(768), dim3(256), 0, s, c->theta + po.pos_v, c->theta + po.pos_g,
                        c->pos_nrm2, c->pos_w);
-    hipLaunchKernelGGL(posconv_bwd_weight_kernel, dim3(16 * 64), dim3(256), 0, s, c->pos_w, c->pos_wb);
     if (c->pos_wt)
         if (int rc = rebuild_posconv_wino_weights(c, s)) return rc;
-    transpose(c->proj_w, 512, c->proj_wT, 768, 768, 512);
-    for (int i = 1; i < 7; ++i) {  // conv feature extractor: kernel layout [co][tap * 512 + ci] and the dX GEMMs' copies
+    for (int i = 1; i < 7; ++i) {  // conv feature extractor: kernel layout [co][tap * 512 + ci]
         const long long n = 512LL * 512 * kConvK[i];
         hipLaunchKernelGGL(conv_repack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->theta + po.conv_w[i], c->conv_w[i],
                            kConvK[i]);
     }
-    rebuild_conv_bwd_weights(c, s);
     for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
         const LayerDev& d = c->layers[l];
         const LayerOffsets& lo = po.L[l];
@@ -3154,11 +3101,8 @@ int refresh_weights(nomad_ctx* c, hipStream_t s) {
                            reinterpret_cast<const float4*>(c->theta + lo.qkv_w), reinterpret_cast<float4*>(d.qkv_w), w4, q4, 0.125f);
         hipLaunchKernelGGL(scale_rows_kernel, dim3(3), dim3(256), 0, s, reinterpret_cast<const float4*>(c->theta + lo.qkv_b),
                            reinterpret_cast<float4*>(d.qkv_b), 576LL, 192LL, 0.125f);
-        transpose(d.qkv_w, 768, c->qkv_wT[l], 2304, 2304, 768);
-        transpose(d.o_w, 768, c->o_wT[l], 768, 768, 768);
-        transpose(d.fc1_w, 768, c->fc1_wT[l], 3072, 3072, 768);
-        transpose(d.fc2_w, 3072, c->fc2_wT[l], 768, 768, 3072);
     }
+    build_backward_weights(c, s);
     HIP_TRY(hipGetLastError());
     c->bf16_ready = false;  // the bf16 copies (if any) are stale now; nomad_enable_bf16 rebuilds them
     c->x3_ready = false;    // likewise the split copies (nomad_enable_bf16x3)
@@ -3322,7 +3266,7 @@ int nomad_train_segment(int i, char* name, size_t name_cap, size_t* offset, size
 
 int nomad_train_param_count(size_t* total, size_t* head_begin) {
     if (!total) return fail(NOMAD_ERR_INVALID, "nomad_train_param_count: null argument");
-    const ParamOffsets po = make_param_offsets();
+    const ParamOffsets& po = param_offsets();
     *total = po.total;
     if (head_begin) *head_begin = po.emb_w;
     return 0;
@@ -3334,64 +3278,25 @@ int nomad_train_enable(nomad_ctx* c, const nomad_weights* w) {
     int rc;
     if ((rc = nomad_enable_backward(c))) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const ParamOffsets po = make_param_offsets();
-    auto alloc = [&](size_t bytes, void** out) -> int {
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, bytes));
-        c->allocs.push_back(d);
-        HIP_TRY(hipMemset(d, 0, bytes));
-        *out = d;
-        return 0;
-    };
-    if ((rc = alloc(po.total * sizeof(float), (void**)&c->theta))) return rc;
-    if ((rc = alloc(po.total * sizeof(float), (void**)&c->grad))) return rc;
-    if ((rc = alloc(po.total * sizeof(float), (void**)&c->adam_m))) return rc;
-    if ((rc = alloc(po.total * sizeof(float), (void**)&c->adam_v))) return rc;
-    if ((rc = alloc(128 * sizeof(double), (void**)&c->pos_nrm2))) return rc;
-    if ((rc = alloc(128 * sizeof(double), (void**)&c->tap_dot))) return rc;
-    if ((rc = alloc((size_t)576 * 128 * sizeof(double), (void**)&c->tap_partial))) return rc;
-    auto put = [&](size_t off, const float* host, size_t n) {
-        if (rc == 0 && hipMemcpy(c->theta + off, host, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    static const char who[] = "nomad_train_enable";
+    ParamOffsets po = param_offsets();
+    if ((rc = dev_alloc(c, who, po.total, &c->theta, true))) return rc;
+    if ((rc = dev_alloc(c, who, po.total, &c->grad, true))) return rc;
+    if ((rc = dev_alloc(c, who, po.total, &c->adam_m, true))) return rc;
+    if ((rc = dev_alloc(c, who, po.total, &c->adam_v, true))) return rc;
+    if ((rc = dev_alloc(c, who, 128, &c->pos_nrm2, true))) return rc;
+    if ((rc = dev_alloc(c, who, 128, &c->tap_dot, true))) return rc;
+    if ((rc = dev_alloc(c, who, (size_t)576 * 128, &c->tap_partial, true))) return rc;
+    for_each_param(*w, po, *c, [&](const Param& p) {
+        if (rc == 0 && hipMemcpy(c->theta + *p.slot + p.sub, p.host, p.count * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             rc = fail(NOMAD_ERR_HIP, "nomad_train_enable: upload failed");
-    };
-    put(po.fln_w, w->feat_ln_w, 512); put(po.fln_b, w->feat_ln_b, 512);
-    put(po.proj_w, w->proj_w, 768 * 512); put(po.proj_b, w->proj_b, 768);
-    put(po.pos_g, w->pos_g, 128); put(po.pos_v, w->pos_v, (size_t)768 * 48 * 128); put(po.pos_b, w->pos_b, 768);
-    put(po.eln_w, w->enc_ln_w, 768); put(po.eln_b, w->enc_ln_b, 768);
-    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
-        const nomad_layer_weights& lw = w->layers[l];
-        const LayerOffsets& lo = po.L[l];
-        const size_t ww = 768 * 768;
-        put(lo.qkv_w, lw.q_w, ww); put(lo.qkv_w + ww, lw.k_w, ww); put(lo.qkv_w + 2 * ww, lw.v_w, ww);
-        put(lo.qkv_b, lw.q_b, 768); put(lo.qkv_b + 768, lw.k_b, 768); put(lo.qkv_b + 1536, lw.v_b, 768);
-        put(lo.o_w, lw.o_w, ww); put(lo.o_b, lw.o_b, 768);
-        put(lo.ln1_w, lw.ln1_w, 768); put(lo.ln1_b, lw.ln1_b, 768);
-        put(lo.fc1_w, lw.fc1_w, (size_t)3072 * 768); put(lo.fc1_b, lw.fc1_b, 3072);
-        put(lo.fc2_w, lw.fc2_w, (size_t)768 * 3072); put(lo.fc2_b, lw.fc2_b, 768);
-        put(lo.ln2_w, lw.ln2_w, 768); put(lo.ln2_b, lw.ln2_b, 768);
-    }
-    put(po.conv0_w, w->conv_w[0], 512 * 10); put(po.gn_w, w->gn_w, 512); put(po.gn_b, w->gn_b, 512);
-    for (int i = 1; i < 7; ++i) put(po.conv_w[i], w->conv_w[i], (size_t)512 * 512 * kConvK[i]);
-    put(po.emb_w, w->emb_w, 256 * 768); put(po.emb_b, w->emb_b, 256);
+    });
     if (rc) return rc;
-    // From here on the engine reads these parameters straight from the master vector (same layout as the
-    // checkpoint); only q/k/v (fused, q scaled), the pos-conv kernel and the transposes are derived copies.
-    float* th = c->theta;
-    c->fln_w = th + po.fln_w; c->fln_b = th + po.fln_b;
-    c->proj_w = th + po.proj_w; c->proj_b = th + po.proj_b;
-    c->pos_b = th + po.pos_b;
-    c->eln_w = th + po.eln_w; c->eln_b = th + po.eln_b;
-    for (int l = 0; l < NOMAD_NUM_LAYERS; ++l) {
-        LayerDev& d = c->layers[l];
-        const LayerOffsets& lo = po.L[l];
-        d.o_w = th + lo.o_w; d.o_b = th + lo.o_b;
-        d.ln1_w = th + lo.ln1_w; d.ln1_b = th + lo.ln1_b;
-        d.fc1_w = th + lo.fc1_w; d.fc1_b = th + lo.fc1_b;
-        d.fc2_w = th + lo.fc2_w; d.fc2_b = th + lo.fc2_b;
-        d.ln2_w = th + lo.ln2_w; d.ln2_b = th + lo.ln2_b;
-    }
-    c->emb_w = th + po.emb_w; c->emb_b = th + po.emb_b;
-    c->conv0_w = th + po.conv0_w; c->gn_w = th + po.gn_w; c->gn_b = th + po.gn_b;  // conv1..6: derived copies (refresh_weights)
+    // From here on the engine reads these parameters straight from the master vector (same layout as the checkpoint); only
+    // q/k/v (fused, q scaled), the pos-conv kernel, conv1..6 and the backward's copies are derived (refresh_weights).
+    for_each_param(*w, po, *c, [&](const Param& p) {
+        if (p.alias) *p.alias = c->theta + *p.slot + p.sub;
+    });
     if ((rc = refresh_weights(c, 0))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     c->adam_t = 0;
@@ -3409,7 +3314,7 @@ int nomad_train_workspace_bytes(const nomad_ctx* c, int B, int n_samples, size_t
 
 int nomad_train_zero_grad(nomad_ctx* c, nomad_stream_t stream) {
     if (!c || !c->train_ready) return fail(NOMAD_ERR_INVALID, "nomad_train_zero_grad: call nomad_train_enable first");
-    HIP_TRY(hipMemsetAsync(c->grad, 0, make_param_offsets().total * sizeof(float), static_cast<hipStream_t>(stream)));
+    HIP_TRY(hipMemsetAsync(c->grad, 0, param_offsets().total * sizeof(float), static_cast<hipStream_t>(stream)));
     return 0;
 }
 
@@ -3444,7 +3349,7 @@ int nomad_train_adam_step(nomad_ctx* c, float lr_body, float lr_head, double bet
                           nomad_stream_t stream) {
     if (!c || !c->train_ready) return fail(NOMAD_ERR_INVALID, "nomad_train_adam_step: call nomad_train_enable first");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const ParamOffsets po = make_param_offsets();
+    const ParamOffsets& po = param_offsets();
     c->adam_t += 1;
     const double bc1 = 1.0 - std::pow(beta1, (double)c->adam_t);
     const double bc2 = 1.0 - std::pow(beta2, (double)c->adam_t);
@@ -3474,7 +3379,7 @@ static float* train_buffer(nomad_ctx* c, int what) {
 int nomad_train_read(nomad_ctx* c, int what, float* dst_dev, nomad_stream_t stream) {
     if (!c || !c->train_ready || !dst_dev || !train_buffer(c, what))
         return fail(NOMAD_ERR_INVALID, "nomad_train_read: bad argument");
-    HIP_TRY(hipMemcpyAsync(dst_dev, train_buffer(c, what), make_param_offsets().total * sizeof(float),
+    HIP_TRY(hipMemcpyAsync(dst_dev, train_buffer(c, what), param_offsets().total * sizeof(float),
                            hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -3483,7 +3388,7 @@ int nomad_train_write(nomad_ctx* c, int what, const float* src_dev, nomad_stream
     if (!c || !c->train_ready || !src_dev || !train_buffer(c, what))
         return fail(NOMAD_ERR_INVALID, "nomad_train_write: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(train_buffer(c, what), src_dev, make_param_offsets().total * sizeof(float),
+    HIP_TRY(hipMemcpyAsync(train_buffer(c, what), src_dev, param_offsets().total * sizeof(float),
                            hipMemcpyDeviceToDevice, s));
     return what == 0 ? refresh_weights(c, s) : 0;
 }
@@ -3576,12 +3481,9 @@ static int pair_scratch_for(nomad_ctx* c, hipStream_t s, double** out) {
             c->pair_scratch[0].first = s;
             scratch = c->pair_scratch[0].second;
         } else {
-            void* d = nullptr;
             HIP_TRY(hipSetDevice(c->device));
-            HIP_TRY(hipMalloc(&d, sizeof(double) * kPairScratchDoubles));
-            c->allocs.push_back(d);
-            c->pair_scratch.emplace_back(s, static_cast<double*>(d));
-            scratch = static_cast<double*>(d);
+            if (int rc = dev_alloc(c, "pairwise scratch", (size_t)kPairScratchDoubles, &scratch)) return rc;
+            c->pair_scratch.emplace_back(s, scratch);
         }
     }
     pair_lock.unlock();

@@ -243,6 +243,29 @@ def test_embed_bf16_vs_fp32_path(engine):
     assert err < 3e-3 and cos > 0.99997 and serr < 1.2e-3      # measured 9.5e-4 / 0.99999 / 3.6e-4
 
 
+def test_bf16_follows_weight_updates(built_lib, sd0):
+    """The bf16 weight copies are rebuilt after the master weights change (fine-tuning, nomad_train_write): the twin of
+    test_gpu_bf16x3.py::test_bf16x3_follows_weight_updates, held to the bf16-against-fp32 bound of test_embed_bf16_vs_fp32_path."""
+    from nomad_amd.engine import Engine
+    eng = Engine(sd0, 0)
+    try:
+        gen = torch.Generator().manual_seed(8)
+        wav = (0.1 * torch.randn(2, 20000, generator=gen)).cuda()
+        before = eng.embed_bf16(wav).clone()
+        eng.train_enable()
+        theta = eng.train_read()
+        eng.train_write(0, theta * 1.01)
+        after = eng.embed_bf16(wav)
+        ref = eng.embed(wav)
+        err = (after - ref).abs().max().item()
+        cos = F.cosine_similarity(after, ref, dim=1).min().item()
+        print(f"bf16 after a weight update vs fp32: embedding max|err| {err:.3e}, min cosine {cos:.6f}")
+        assert not torch.equal(before, after)
+        assert err < 3e-3 and cos > 0.99997
+    finally:
+        eng.close()
+
+
 def test_embed_bf16_peaky_weights(engine_peaky):
     """The same against the conftest 'peaky' model (q / k gain 6: attention logits with sigma ~ 6, a few dominant keys per row, activation
     outliers - what trained weights look like and the seeded ones do not): the bf16 attention's late rescales, the bf16-output GELU's tails
