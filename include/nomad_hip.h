@@ -467,6 +467,70 @@ int nomad_embed_windows_backward_ragged(nomad_ctx* ctx, const float* wav_dev, in
                                         const float* demb_dev, float* dwav_dev, void* scratch_dev, size_t scratch_bytes,
                                         void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
 
+/* ---- the head over caller-given spans of frames: speech-only and per-turn embeddings, differentiable --------------------------
+ * The windows calls pool the head over frames the library chooses (win frames every hop).  These pool it over frames the CALLER
+ * names.  A span is frames [t0, t1) of one clip, 0 <= t0 < t1 <= T_c (one frame = 320 samples and sees 400).  A row is an ordered
+ * list of one or more spans of the same clip, ascending and not overlapping (t1_i <= t0_{i+1}; touching is allowed); there is one
+ * output embedding per row.  Different rows may overlap freely and a clip may have no row.  A row's embedding is the plain head
+ * applied to the concatenation of its spans' frames as if they were a clip of their own: time mean over n = sum (t1 - t0) frames,
+ * ReLU, Linear(768, 256), L2 normalisation.  The encoder saw the WHOLE clip, exactly as with windows: a row is not the embedding
+ * of the excerpt alone.
+ *
+ * The table, all host memory that may be freed on return (its copy is staged like the ragged metadata):
+ *   R                 rows, >= 1
+ *   row_clip[R]       the clip of each row, in [0, B), not decreasing: the rows of a clip are contiguous
+ *   row_ptr[R + 1]    row r pools spans row_ptr[r] .. row_ptr[r + 1] - 1; row_ptr[0] = 0, strictly increasing; S = row_ptr[R]
+ *   spans[S][2]       (t0, t1) in frames of the row's clip
+ *
+ *   nomad_spans_scratch_bytes            the scratch of the three calls below for B clips, R rows and S spans: the table's device
+ *                                        copy (with the per-clip row ranges), plus [R][768] fp32 when backward != 0.
+ *                                        NOMAD_ERR_INVALID for B or R < 1, S < R or bytes == NULL.
+ *   nomad_embed_spans_ragged             = nomad_embed_windows_ragged with the table in place of (win, hop): ONE forward of
+ *                                        `precision`, emb_dev is [R][256] in table order.  Bit contracts: a row of one span
+ *                                        [a, a + n) has the bits nomad_embed_windows* gives a window over those frames; a row
+ *                                        whose spans concatenate to the whole clip ([0, T), or [0, 64), [64, T)) has the bits of
+ *                                        the clip's plain embedding of that precision (chunks of 64 frames are counted from the
+ *                                        row's first frame and run across span boundaries).
+ *   nomad_embed_train_spans_ragged       = nomad_embed_train_windows_ragged with the table, plus the scratch (sized with
+ *                                        backward = 0) for the table's device copy.
+ *   nomad_embed_spans_backward_ragged    = nomad_embed_windows_backward_ragged with the table; demb_dev is [R][256]; scratch sized
+ *                                        with backward = 1.  Two launches without atomics: each row's gradient with respect to
+ *                                        its time mean, already divided by n (the time sum is recomputed in the forward's order,
+ *                                        so the ReLU mask is the forward's), into the scratch; then frame t of clip b receives
+ *                                        the sum of those of the rows of clip b that contain t, in ascending row order in one
+ *                                        fp32 accumulator; a frame no row contains, and a clip without a row, gets exact zeros.
+ *                                        Everything is written before it is read: nothing needs clearing.
+ *   nomad_frame_energy                   energy_dev[frame t of clip c] = (sum_{i < 400} (double)x_c[320 t + i]^2) / 400, clips
+ *                                        packed in order ([sum_c T_c] doubles): every product and sum in float64 in a fixed order,
+ *                                        no atomics, a frame a function of its own 400 samples only.  No scratch.
+ *                                        NOMAD_ERR_INVALID: a NULL pointer, B < 1, a clip longer than stride or shorter than a frame.
+ *
+ * Contract of the three nomad_embed_*spans* calls: as for the windows calls - precision preconditions (nomad_enable_bf16*,
+ * nomad_enable_backward), workspace and saved sizes, statuses; the head override is fp32 only; asynchronous, no allocation (the
+ * table's device copy lives in the caller's scratch); deterministic.  The ragged calls never split K, so a clip's rows and its
+ * row of dwav_dev have the bits of its own B = 1 call.  NOMAD_ERR_INVALID before anything is queued, nomad_last_error naming the
+ * entry point, the row and the span: R < 1; a NULL table pointer; row_clip decreasing or out of range; a row without a span;
+ * t0 < 0, t1 > T_c or t0 >= t1; spans of a row overlapping or out of order; a cut encoder; fine-tuning mode (the two gradient
+ * calls); and whatever the windows calls refuse.  NOMAD_ERR_WORKSPACE: scratch, workspace or saved block too small.
+ */
+int nomad_spans_scratch_bytes(int B, int R, int S, int backward, size_t* bytes);
+int nomad_embed_spans_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host, int precision,
+                             int R, const int* row_clip, const int* row_ptr, const int* spans, const float* head_w_dev,
+                             const float* head_b_dev, float* emb_dev, void* scratch_dev, size_t scratch_bytes,
+                             void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
+int nomad_embed_train_spans_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host, int R,
+                                   const int* row_clip, const int* row_ptr, const int* spans, const float* head_w_dev,
+                                   const float* head_b_dev, float* emb_dev, float* layers_dev, void* saved_dev,
+                                   size_t saved_bytes, void* scratch_dev, size_t scratch_bytes, void* workspace_dev,
+                                   size_t workspace_bytes, nomad_stream_t stream);
+int nomad_embed_spans_backward_ragged(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host, int R,
+                                      const int* row_clip, const int* row_ptr, const int* spans, const float* head_w_dev,
+                                      const float* head_b_dev, const float* layers_dev, const void* saved_dev,
+                                      size_t saved_bytes, const float* demb_dev, float* dwav_dev, void* scratch_dev,
+                                      size_t scratch_bytes, void* workspace_dev, size_t workspace_bytes, nomad_stream_t stream);
+int nomad_frame_energy(nomad_ctx* ctx, const float* wav_dev, int B, int stride, const int* lengths_host, double* energy_dev,
+                       nomad_stream_t stream);
+
 /* ---- NomadLoss with layer weights and per-utterance terms; the encoder cut at depth ------------------------
  * The reference's NomadLoss loops `for i in range(self.L)` (nomad.py:264, :276; L = 13): a caller who lowers L trains against the first
  * L terms only.  These entry points give that, a weight per term, and one loss per utterance - and let the encoder stop behind the

@@ -5,6 +5,9 @@ parses it and ignores it).
 Several GPUs: ``python -m torch.distributed.run --nproc-per-node N -m nomad_amd --mode dir ...`` - one process per GPU,
 the files shard across the ranks (RCCL all-gather of the embeddings, ``Nomad.predict``), rank 0 writes the CSV files.
 
+``--spans CSV`` / ``--active-db DB`` (one process): one score per caller-given row of spans, or per file over its non-silent frames
+(``Nomad.predict_spans``, ``spans.csv``).
+
 ``--sweep`` (one process): ``--deg`` holds CLEAN files, which are degraded on the GPU at every level of ``--snr-db`` (with ``--noise
 FILE``) and / or ``--clip`` and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level."""
 import argparse
@@ -70,6 +73,12 @@ def main(argv=None):
     ap.add_argument("--knn", type=int, default=None, metavar="K",
                     help="score every file (or window) by the mean distance to its K nearest references (1 .. 64) instead of all "
                          "of them; without --window the neighbours go to nomad_nearest.csv")
+    ap.add_argument("--spans", type=str, default=None, metavar="CSV",
+                    help="scores over spans: one NOMAD score per row of CSV (columns Test File, start_s, end_s and optionally Row; lines "
+                         "that share a Row label pool into one score), each pooled from one forward over the whole file (predict_spans)")
+    ap.add_argument("--active-db", dest="active_db", type=float, default=None, metavar="DB",
+                    help="score what is not silent: one score per test file over the frames within DB dB of its loudest frame (an "
+                         "energy gate, not a speech detector; predict_spans)")
     ap.add_argument("--sweep", action="store_true",
                     help="--deg holds CLEAN files: degrade them on the GPU at every level of --snr-db / --clip, score the result against "
                          "--nmr and report how well the score ranks the levels (nomad_intensity.csv, Nomad.intensity_sweep)")
@@ -81,6 +90,16 @@ def main(argv=None):
         ap.error("--hop goes with --window")
     if not a.sweep and (a.noise is not None or a.snr_db is not None or a.clip is not None):
         ap.error("--noise, --snr-db and --clip go with --sweep")
+    if a.spans is not None and a.active_db is not None:
+        ap.error("--spans and --active-db exclude each other: the rows come from the csv or from the energy gate")
+    if a.spans is not None or a.active_db is not None:
+        which = "--spans" if a.spans is not None else "--active-db"
+        if a.window is not None:
+            ap.error(f"{which} names its own frames: it does not go with --window")
+        if a.sweep:
+            ap.error(f"{which} does not go with --sweep")
+        if a.active_db is not None and not (a.active_db == a.active_db and abs(a.active_db) != float("inf")):
+            ap.error(f"--active-db takes a finite number of dB, got {a.active_db}")
     if a.sweep:
         if a.window is not None:
             ap.error("--sweep scores whole clips: it does not go with --window")
@@ -111,7 +130,14 @@ def main(argv=None):
             raise SystemExit("--sweep runs in one process")
         print(sweep(nomad, a))
         return
-    if a.window is not None:
+    if a.spans is not None or a.active_db is not None:
+        if world > 1:
+            raise SystemExit("--spans and --active-db run in one process")
+        rows, nomad_avg = nomad.predict_spans(a.mode, a.nmr, a.deg, spans=a.spans, active_db=a.active_db, results_path=a.results_path,
+                                              k=a.knn)
+        print("Nomad scores over spans, printing the first 5 rows")
+        print(rows.head())
+    elif a.window is not None:
         segments, nomad_avg = nomad.predict_segments(a.mode, a.nmr, a.deg, a.window, a.window / 2 if a.hop is None else a.hop,
                                                      a.results_path, k=a.knn)
         print("Nomad scores over time, printing the first 5 windows")

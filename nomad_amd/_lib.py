@@ -78,6 +78,16 @@ SIGNATURES = {
                                                _fp, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
     "nomad_embed_windows_backward_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _fp,
                                                       _fp, _fp, _fp, C.c_size_t, _fp, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
+    "nomad_spans_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "nomad_embed_spans_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _fp, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
+    "nomad_embed_train_spans_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp,
+                                                 C.c_size_t, _fp, C.c_size_t, _fp]),
+    "nomad_embed_spans_backward_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                                    C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp,
+                                                    _fp, C.c_size_t, _fp, C.c_size_t, _fp]),
+    "nomad_frame_energy": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp]),
     "nomad_wav_probe": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(WavInfo), C.POINTER(C.c_int), C.c_int]),
     "nomad_wav_frames_at": (C.c_int, [C.POINTER(WavInfo), C.c_int, C.POINTER(C.c_longlong)]),
     "nomad_wav_read_rows": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(WavInfo), C.c_int, C.POINTER(C.c_int), _fp, C.c_longlong,

@@ -391,6 +391,22 @@ int ragged_upload(nomad_ctx* c, const RaggedShapes& rs, int stride, int* meta, h
     return 0;
 }
 
+// The span table of nomad_embed_spans* travels the same way: checked and laid out on the host (spans_stage), its device copy queued
+// by span_upload right behind the ragged metadata's - after every check of the call, ahead of its kernels - from a ring slot of its
+// own: a span call takes two slots, so a score_spans step with a gradient (one forward, one backward) takes the four of ragged_upload.
+struct SpanStage {
+    std::vector<int> host;  // laid out as the device block: rowops.hip.h, span_table
+    int* dev = nullptr;     // the head of the caller's scratch
+    int R = 0, S = 0;
+    float* gw = nullptr;    // [R][768] behind the table: the backward's per-row gradients
+};
+int span_upload(nomad_ctx* c, const SpanStage& st, hipStream_t s) {
+    std::vector<int>& staged = c->ragged_meta_ring[c->ragged_seq++ % kMetaRing];
+    staged = st.host;
+    HIP_TRY(hipMemcpyAsync(st.dev, staged.data(), sizeof(int) * staged.size(), hipMemcpyHostToDevice, s));
+    return 0;
+}
+
 // The scoring forwards' prologue: the three steps over the ActLayout.  c == nullptr: nomad_workspace_bytes_ragged*, sizing only.
 int ragged_prologue(const char* who, nomad_ctx* c, bool ok, int B, int stride, const int* lens_host, size_t elem_bytes,
                     size_t xpad_slack, RaggedBatch* r, void* workspace = nullptr, size_t workspace_bytes = 0, hipStream_t s = nullptr,
@@ -876,15 +892,22 @@ int run_layernorm(nomad_ctx* c, const float* in, const float* g, const float* b,
 // features (nomad_embed_features*): `emb` is [B][768] and takes the time means themselves (head_mean_kernel) - no embedding.
 // windows (nomad_embed_windows*): `emb` is [windows of the batch][256], one row per window of mode.win frames every mode.hop
 // (head_windows_kernel, one launch, no scratch); mode.n_windows is their number.
+// spans (nomad_embed_spans*): `emb` is [R][256], one row per row of the caller's span table (head_spans_kernel, one launch; SpanStage).
 struct HeadMode {
     bool features = false;
     int win = 0, hop = 0;
     long long n_windows = 0;
+    const SpanStage* spans = nullptr;
     HeadMode() = default;
     HeadMode(bool f) : features(f) {}
     static HeadMode windows(int win, int hop, long long n) {
         HeadMode m;
         m.win = win, m.hop = hop, m.n_windows = n;
+        return m;
+    }
+    static HeadMode over_spans(const SpanStage* st) {
+        HeadMode m;
+        m.spans = st;
         return m;
     }
 };
@@ -893,6 +916,14 @@ template <typename TIn>
 int run_head(nomad_ctx* c, const TIn* x, int B, int T, const float* w, const float* b, float* emb, const int* tpref,
              float* pool, hipStream_t s, HeadMode mode = {}) {
     const bool features = mode.features;
+    if (mode.spans) {
+        const SpanStage& st = *mode.spans;
+        if (!tpref) return fail(NOMAD_ERR_INVALID, "run_head: the span head needs a ragged batch");
+        Scope sc(c, s, NOMAD_K_ROW, 2.0 * (double)st.R * 768 * 256);
+        hipLaunchKernelGGL(head_spans_kernel<TIn>, dim3(st.R), dim3(1024), 0, s, x, st.dev, st.R, st.S, w, b, emb, tpref);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (mode.win) {
         Scope sc(c, s, NOMAD_K_ROW, 2.0 * (double)mode.n_windows * 768 * 256);
         hipLaunchKernelGGL(head_windows_kernel<TIn>, dim3(head_num_windows(T, mode.win, mode.hop), B), dim3(1024), 0, s, x, tpref ? 0 : T,
@@ -1453,6 +1484,8 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
         if (c->branches > 1 && B % c->branches) return fail(NOMAD_ERR_INVALID, "%s: B=%d is not %d equal branches", who, B, c->branches);
     }
     if (int rc = ragged_upload(c, r.rs, stride, reinterpret_cast<int*>(static_cast<char*>(workspace) + r.lay.meta), s, &r.g)) return rc;
+    if (mode.spans)
+        if (int rc = span_upload(c, *mode.spans, s)) return rc;
     char* ws = static_cast<char*>(workspace);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const ActLayout& lay = r.lay;
@@ -1731,6 +1764,8 @@ static int forward_ragged_bf16(nomad_ctx* c, const float* wav, int B, int stride
     if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, sizeof(bf16_t), 0,
                                  &r, workspace, workspace_bytes, s))
         return rc;
+    if (mode.spans)
+        if (int rc = span_upload(c, *mode.spans, s)) return rc;
     return forward_bf16_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, mode);
 }
 
@@ -1940,6 +1975,8 @@ static int forward_ragged_x3(nomad_ctx* c, const float* wav, int B, int stride, 
     if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, 4, kXpadSlack,
                                  &r, workspace, workspace_bytes, s))
         return rc;
+    if (mode.spans)
+        if (int rc = span_upload(c, *mode.spans, s)) return rc;
     return forward_x3_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, nullptr, nullptr, nullptr, mode);
 }
 
@@ -2606,9 +2643,12 @@ static int dw_gemm(nomad_ctx* c, const float* TA, const float* TB, int Nout, int
 // K (a clip's gradient does not depend on its batch).  The conv feature extractor's parameter gradients need an equal-length batch.
 // wb (nomad_embed_windows_backward*): demb holds one row per WINDOW of the windowed head and the head stage is its backward - the
 // two launches of backward.hip.h through the caller's gw block - instead of head_bwd_kernel; everything below gx is unchanged.
+// wb->spans (nomad_embed_spans_backward_ragged): demb holds one row per ROW of the span table and the two launches are the span
+// head's (head_spans_bwd_kernel, head_spans_scatter_kernel) through the table and the gw block in the caller's scratch.
 struct HeadWindowsBwd {
     int win, hop;
     float* gw;   // [windows of the batch][768]
+    const SpanStage* spans = nullptr;
 };
 static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const Saved& sv, const BwdLayout& lay, const float* head_w,
                         const float* head_b, const float* layers_out, const float* dlayers, const float* demb, float* dwav,
@@ -2667,7 +2707,14 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
     const int depth = train ? NOMAD_NUM_LAYERS : c->encoder_depth;
     bool first_cut = depth < NOMAD_NUM_LAYERS;
     // ---- head -> d loss / d x_12 -------------------------------------------------------------------
-    if (!first_cut && wb) {
+    if (!first_cut && wb && wb->spans) {
+        const SpanStage& st = *wb->spans;
+        if (!rg) return fail(NOMAD_ERR_INVALID, "backward_run: the span head needs a ragged batch");
+        Scope sc(c, s, NOMAD_K_ROW, 0.0);
+        hipLaunchKernelGGL(head_spans_bwd_kernel, dim3(st.R), dim3(1024), 0, s, layers_out + (size_t)11 * M * 768, st.dev, st.R, st.S,
+                           head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, demb, st.gw, tpref);
+        hipLaunchKernelGGL(head_spans_scatter_kernel, dim3((g.max_t + 3) / 4, B), dim3(256), 0, s, st.gw, st.dev, st.R, st.S, gx, tpref);
+    } else if (!first_cut && wb) {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
         const float* x12 = layers_out + (size_t)11 * M * 768;
         hipLaunchKernelGGL(head_windows_bwd_kernel, dim3(head_num_windows(g.max_t, wb->win, wb->hop), B), dim3(1024), 0, s, x12, rg ? 0 : T,
@@ -3068,6 +3115,8 @@ static int backward_ragged(const char* who, nomad_ctx* c, const float* wav, int 
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     if (int rc = ragged_upload(c, rs, stride, reinterpret_cast<int*>(ws + lay.meta), s, &g)) return rc;
+    if (wb && wb->spans)
+        if (int rc = span_upload(c, *wb->spans, s)) return rc;
     return backward_run(c, wav, g, sv, lay, head_w, head_b, layers_out, dlayers, demb, dwav, ws, s, train, wb);
 }
 
@@ -3250,6 +3299,135 @@ int nomad_embed_windows_backward_ragged(nomad_ctx* c, const float* wav, int B, i
     const HeadWindowsBwd wb{win, hop, static_cast<float*>(scratch)};
     return backward_ragged(who, c, wav, B, stride, lengths_host, head_w, head_b, layers_out, saved, saved_bytes, nullptr, demb, dwav,
                            workspace, workspace_bytes, stream, false, &wb);
+}
+
+// ---- the head over caller-given spans of frames: nomad_embed_spans_ragged and its gradient path.  The windows calls with a table of
+// rows of spans in place of (win, hop): every check of those calls holds, the table's come ahead, nothing is queued on an error.
+static size_t span_table_bytes(int B, int R, int S) { return align_up(sizeof(int) * span_table_ints(B, R, S)); }
+
+// The table's checks, then its host copy in the device block's layout and its place (and gw's) in the caller's scratch.
+static int spans_stage(const char* who, int B, const int* lens_host, int R, const int* row_clip, const int* row_ptr, const int* spans,
+                       void* scratch, size_t scratch_bytes, bool backward, SpanStage* st) {
+    if (R < 1) return fail(NOMAD_ERR_INVALID, "%s: a span table needs at least one row (R=%d)", who, R);
+    if (!row_clip || !row_ptr || !spans) return fail(NOMAD_ERR_INVALID, "%s: a NULL span table pointer (row_clip, row_ptr or spans)", who);
+    if (!lens_host || B <= 0 || !scratch) return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d)", who, B);
+    if (row_ptr[0] != 0) return fail(NOMAD_ERR_INVALID, "%s: row_ptr[0] is %d, not 0", who, row_ptr[0]);
+    for (int r = 0; r < R; ++r) {
+        const int cl = row_clip[r];
+        if (cl < 0 || cl >= B) return fail(NOMAD_ERR_INVALID, "%s: row %d names clip %d, outside [0, %d)", who, r, cl, B);
+        if (r && cl < row_clip[r - 1]) return fail(NOMAD_ERR_INVALID, "%s: row %d names clip %d behind row %d's clip %d (row_clip must not decrease)", who, r, cl, r - 1, row_clip[r - 1]);
+        if (row_ptr[r + 1] <= row_ptr[r]) return fail(NOMAD_ERR_INVALID, "%s: row %d has no span (row_ptr %d .. %d)", who, r, row_ptr[r], row_ptr[r + 1]);
+        const int T = nomad_num_frames(lens_host[cl]);
+        for (int i = row_ptr[r]; i < row_ptr[r + 1]; ++i) {
+            const int t0 = spans[2 * i], t1 = spans[2 * i + 1], k = i - row_ptr[r];
+            if (t0 < 0 || t1 > T || t0 >= t1)
+                return fail(NOMAD_ERR_INVALID, "%s: row %d, span %d is [%d, %d): not inside clip %d's %d frames", who, r, k, t0, t1, cl, T);
+            if (k && t0 < spans[2 * i - 1])
+                return fail(NOMAD_ERR_INVALID, "%s: row %d, span %d [%d, %d) overlaps or precedes span %d, which ends at %d", who, r, k, t0, t1, k - 1, spans[2 * i - 1]);
+        }
+    }
+    const int S = row_ptr[R];
+    const size_t need = span_table_bytes(B, R, S) + (backward ? align_up(sizeof(float) * 768 * (size_t)R) : 0);
+    if (scratch_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: scratch %zu < required %zu", who, scratch_bytes, need);
+    st->R = R, st->S = S;
+    st->dev = static_cast<int*>(scratch);
+    st->gw = backward ? reinterpret_cast<float*>(static_cast<char*>(scratch) + span_table_bytes(B, R, S)) : nullptr;
+    st->host.reserve(span_table_ints(B, R, S));
+    st->host.assign(row_clip, row_clip + R);
+    st->host.insert(st->host.end(), row_ptr, row_ptr + R + 1);
+    st->host.insert(st->host.end(), spans, spans + 2 * (size_t)S);
+    for (int b = 0, r = 0; b <= B; ++b) {   // clip_row[b]: the first row of a clip >= b
+        while (r < R && row_clip[r] < b) ++r;
+        st->host.push_back(r);
+    }
+    return 0;
+}
+
+int nomad_spans_scratch_bytes(int B, int R, int S, int backward, size_t* bytes) {
+    if (!bytes || B < 1 || R < 1 || S < R)
+        return fail(NOMAD_ERR_INVALID, "nomad_spans_scratch_bytes: bad argument (B=%d, R=%d, S=%d)", B, R, S);
+    *bytes = span_table_bytes(B, R, S) + (backward ? align_up(sizeof(float) * 768 * (size_t)R) : 0);
+    return 0;
+}
+
+int nomad_embed_spans_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, int precision, int R,
+                             const int* row_clip, const int* row_ptr, const int* spans, const float* head_w, const float* head_b,
+                             float* emb, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes,
+                             nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_spans_ragged";
+    if (int rc = windows_args(who, c, precision, 1, 1, head_w, head_b)) return rc;
+    if (precision != NOMAD_PRECISION_F32 && precision != NOMAD_PRECISION_BF16X3 && precision != NOMAD_PRECISION_BF16)
+        return fail(NOMAD_ERR_INVALID, "%s: unknown precision %d", who, precision);
+    SpanStage st;
+    if (int rc = spans_stage(who, B, lengths_host, R, row_clip, row_ptr, spans, scratch, scratch_bytes, false, &st)) return rc;
+    const HeadMode mode = HeadMode::over_spans(&st);
+    switch (precision) {
+        case NOMAD_PRECISION_F32:
+            return forward_ragged(c, wav, B, stride, lengths_host, head_w, head_b, emb, workspace, workspace_bytes, stream, who, mode);
+        case NOMAD_PRECISION_BF16X3:
+            return forward_ragged_x3(c, wav, B, stride, lengths_host, emb, workspace, workspace_bytes, stream, who, mode);
+        default:
+            return forward_ragged_bf16(c, wav, B, stride, lengths_host, emb, workspace, workspace_bytes, stream, who, mode);
+    }
+}
+
+int nomad_embed_train_spans_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, int R,
+                                   const int* row_clip, const int* row_ptr, const int* spans, const float* head_w, const float* head_b,
+                                   float* emb, float* layers_out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                   void* workspace, size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_train_spans_ragged";
+    if (int rc = windows_grad_args(who, c, 1, 1, head_w, head_b)) return rc;
+    if (!c || !layers_out || !saved) return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
+    SpanStage st;
+    if (int rc = spans_stage(who, B, lengths_host, R, row_clip, row_ptr, spans, scratch, scratch_bytes, false, &st)) return rc;
+    return forward_ragged(c, wav, B, stride, lengths_host, head_w, head_b, emb, workspace, workspace_bytes, stream, who,
+                          HeadMode::over_spans(&st), layers_out, saved, saved_bytes);
+}
+
+int nomad_embed_spans_backward_ragged(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, int R,
+                                      const int* row_clip, const int* row_ptr, const int* spans, const float* head_w,
+                                      const float* head_b, const float* layers_out, const void* saved, size_t saved_bytes,
+                                      const float* demb, float* dwav, void* scratch, size_t scratch_bytes, void* workspace,
+                                      size_t workspace_bytes, nomad_stream_t stream) {
+    static const char who[] = "nomad_embed_spans_backward_ragged";
+    if (int rc = windows_grad_args(who, c, 1, 1, head_w, head_b)) return rc;
+    if (!c || !demb || !dwav) return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
+    SpanStage st;
+    if (int rc = spans_stage(who, B, lengths_host, R, row_clip, row_ptr, spans, scratch, scratch_bytes, true, &st)) return rc;
+    const HeadWindowsBwd wb{0, 0, st.gw, &st};
+    return backward_ragged(who, c, wav, B, stride, lengths_host, head_w, head_b, layers_out, saved, saved_bytes, nullptr, demb, dwav,
+                           workspace, workspace_bytes, stream, false, &wb);
+}
+
+// Frame energies (rowops.hip.h, frame_energy_kernel): the clips go to the kernel kEnergyClips at a time, their metadata by value,
+// so the call needs neither scratch nor a staged copy.
+int nomad_frame_energy(nomad_ctx* c, const float* wav, int B, int stride, const int* lengths_host, double* energy, nomad_stream_t stream) {
+    static const char who[] = "nomad_frame_energy";
+    if (!c || !wav || !lengths_host || !energy || B <= 0 || stride <= 0) return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d)", who, B);
+    for (int i = 0; i < B; ++i) {
+        if (lengths_host[i] > stride) return fail(NOMAD_ERR_INVALID, "%s: clip %d longer than the row stride", who, i);
+        if (nomad_num_frames(lengths_host[i]) < 1)
+            return fail(NOMAD_ERR_INVALID, "%s: clip %d of %d samples is shorter than one frame", who, i, lengths_host[i]);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    long long done = 0;
+    for (int c0 = 0; c0 < B; c0 += kEnergyClips) {
+        const int nc = B - c0 < kEnergyClips ? B - c0 : kEnergyClips;
+        EnergyClips cl{};
+        int max_t = 0;
+        for (int i = 0; i < nc; ++i) {
+            const int t = nomad_num_frames(lengths_host[c0 + i]);
+            cl.len[i] = lengths_host[c0 + i];
+            cl.fpref[i + 1] = cl.fpref[i] + t;
+            max_t = t > max_t ? t : max_t;
+        }
+        Scope sc(c, s, NOMAD_K_ROW, 0.0);
+        hipLaunchKernelGGL(frame_energy_kernel, dim3((max_t + 3) / 4, nc), dim3(256), 0, s, wav + (size_t)c0 * stride, (long long)stride, cl,
+                           energy + done);
+        done += cl.fpref[nc];
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int nomad_train_num_segments(void) { return (int)segments().size(); }

@@ -393,6 +393,166 @@ __global__ __launch_bounds__(1024) void head_windows_kernel(const TIn* __restric
     }
 }
 
+// ---- spans of frames (nomad_embed_spans*) -----------------------------------------------------------------------------------
+// The span table on the device, one block of ints: row_clip[R], row_ptr[R + 1], spans[S][2] = (t0, t1), clip_row[B + 1].
+// Row r belongs to clip row_clip[r] and pools spans row_ptr[r] .. row_ptr[r + 1] - 1 (ascending, not overlapping, inside the clip:
+// the host checks all of it before the table is queued); the rows of clip b are clip_row[b] .. clip_row[b + 1] - 1.
+struct SpanTable {
+    const int *row_clip, *row_ptr, *spans, *clip_row;
+};
+__host__ __device__ inline size_t span_table_ints(int B, int R, int S) { return (size_t)2 * R + 1 + (size_t)2 * S + B + 1; }
+__host__ __device__ inline SpanTable span_table(const int* tab, int R, int S) {
+    return SpanTable{tab, tab + R, tab + 2 * R + 1, tab + 2 * R + 1 + 2 * S};
+}
+
+// The row's virtual frame index (0 .. n - 1 over the concatenation of its spans) -> the frame of the clip.  Virtual indices are
+// asked for in ascending order, so the cursor only moves forward; v < n keeps it inside the row's spans.
+struct SpanCursor {
+    const int* sp;   // the row's first span
+    int vbase, t0, len;
+    __device__ explicit SpanCursor(const int* first) : sp(first), vbase(0), t0(first[0]), len(first[1] - first[0]) {}
+    __device__ int frame(int v) {
+        while (v >= vbase + len) {
+            vbase += len;
+            sp += 2;
+            t0 = sp[0];
+            len = sp[1] - t0;
+        }
+        return t0 + (v - vbase);
+    }
+};
+
+__device__ inline int span_row_frames(const SpanTable& tb, int r) {
+    int n = 0;
+    for (int i = tb.row_ptr[r]; i < tb.row_ptr[r + 1]; ++i) n += tb.spans[2 * i + 1] - tb.spans[2 * i];
+    return n;
+}
+
+// The head over rows of spans: row r -> emb[r][256].  head_windows_kernel, operation for operation, on the row's virtual frames
+// 0 .. n - 1 (n = the sum of its spans' lengths): chunks of kHeadChunk virtual frames counted from the row's first frame run
+// across span boundaries, waves 0..3 take virtual frames w, w + 4, ... of a chunk and are folded 0..3 into the running sum in
+// chunk order; then sum * (1.0f / n), ReLU, head_kernel's Linear and norm on 16 waves.  Only the virtual -> actual mapping (a
+// SpanCursor per wave) is new, so a row of one span [a, a + n) has the bits of a window over those frames and a row whose spans
+// concatenate to the whole clip has the bits of the clip's embedding.  grid: R blocks of 1024 threads; ragged batches only
+// (tpref: the frame prefix sums).  No scratch, no atomics.
+template <typename TIn = float>
+__global__ __launch_bounds__(1024) void head_spans_kernel(const TIn* __restrict__ x, const int* __restrict__ tab, int R, int S,
+                                                          const float* __restrict__ w, const float* __restrict__ bias,
+                                                          float* __restrict__ emb, const int* __restrict__ tpref) {
+    __shared__ float4 part[4][3][64];
+    __shared__ float pooled[768];
+    __shared__ float e[256];
+    __shared__ float wsum[4];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SpanTable tb = span_table(tab, R, S);
+    const long long row0 = tpref[tb.row_clip[r]];
+    const int n = span_row_frames(tb, r);   // the same for every thread of the block
+    const TIn* xc = x + row0 * 768;
+    SpanCursor cur(tb.spans + 2 * tb.row_ptr[r]);
+    float4 run[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) run[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int v0 = 0; v0 < n; v0 += kHeadChunk) {   // chunks in order
+        if (wave < 4) {
+            const int v_end = min(n, v0 + kHeadChunk);
+            float4 acc[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int v = v0 + wave; v < v_end; v += 4) {
+                const TIn* rp = xc + (long long)cur.frame(v) * 768 + 4 * lane;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const float4 val = load4<TIn>(rp + 256 * q);
+                    acc[q].x += val.x; acc[q].y += val.y; acc[q].z += val.z; acc[q].w += val.w;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) part[wave][q][lane] = acc[q];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                float4 a = part[0][q][lane];
+#pragma unroll
+                for (int u = 1; u < 4; ++u) {
+                    const float4 o = part[u][q][lane];
+                    a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+                }
+                run[q].x += a.x; run[q].y += a.y; run[q].z += a.z; run[q].w += a.w;
+            }
+        }
+        __syncthreads();   // part is rewritten by the next chunk
+    }
+    if (wave == 0) {
+        const float inv = 1.0f / (float)n;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            float* p = pooled + 256 * q + 4 * lane;
+            p[0] = fmaxf(run[q].x * inv, 0.f);
+            p[1] = fmaxf(run[q].y * inv, 0.f);
+            p[2] = fmaxf(run[q].z * inv, 0.f);
+            p[3] = fmaxf(run[q].w * inv, 0.f);
+        }
+    }
+    __syncthreads();
+    float p[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) p[i] = pooled[lane + 64 * i];
+#pragma unroll 1
+    for (int o0 = wave * 16; o0 < wave * 16 + 16; o0 += 4) {
+        float wv[4][12];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int i = 0; i < 12; ++i) wv[u][i] = w[(long long)(o0 + u) * 768 + lane + 64 * i];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float d = 0.f;
+#pragma unroll
+            for (int i = 0; i < 12; ++i) d = fmaf(wv[u][i], p[i], d);
+            d = wave_sum(d);
+            if (lane == 0) e[o0 + u] = d + bias[o0 + u];
+        }
+    }
+    __syncthreads();
+    if (tid < 256) {
+        const float v = e[tid];
+        const float ss = wave_sum(v * v);
+        if (lane == 0) wsum[wave] = ss;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        const float nrm = sqrtf((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
+        emb[(long long)r * 256 + tid] = e[tid] / fmaxf(nrm, 1e-12f);  // F.normalize eps
+    }
+}
+
+// Mean square of every encoder frame's 400 samples (nomad_frame_energy): e[fpref[c] + t] = (sum_{i < 400} x_c[320 t + i]^2) / 400
+// in float64 - a float's square is exact in double.  One wave per frame: lane l adds samples l, l + 64, ... in order, then the
+// wave's xor butterfly; a frame is a function of its own samples only, in a fixed order.  Up to kEnergyClips clips per launch,
+// their frame prefix sums and lengths by value.  grid: (ceil(frames of the longest clip / 4), clips) blocks of 256 threads.
+constexpr int kEnergyClips = 64;
+struct EnergyClips {
+    int fpref[kEnergyClips + 1];   // frames ahead of clip c inside this launch's part of e
+    int len[kEnergyClips];         // samples of clip c
+};
+__global__ __launch_bounds__(256) void frame_energy_kernel(const float* __restrict__ x, long long stride, EnergyClips cl,
+                                                           double* __restrict__ e) {
+    const int c = blockIdx.y, lane = threadIdx.x & 63, t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= cl.fpref[c + 1] - cl.fpref[c]) return;
+    const float* xf = x + (long long)c * stride + 320LL * t;
+    const int avail = min(400, cl.len[c] - 320 * t);   // 400 for every frame the conv stack counts
+    double acc = 0.0;
+    for (int i = lane; i < avail; i += 64) {
+        const double v = (double)xf[i];
+        acc += v * v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) e[cl.fpref[c] + t] = acc / 400.0;
+}
+
 // NomadLoss.  Stage 1: per-block fp64 partial sums of |a-b| over the 12 layer tensors (n_layer
 // float4s in total) and over the embeddings; stage 2: one block folds the partials in fixed order.
 constexpr int kL1Blocks = 1024;

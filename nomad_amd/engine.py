@@ -444,6 +444,114 @@ class Engine:
         self._dispatch(B, self._audio_cut(lens) if self._splits(precision, B, sum(frames)) else 0, run)
         return emb, counts
 
+    # ---- embeddings over caller-given spans of frames (speech-only and per-turn scores) ------------------------------------------
+    @staticmethod
+    def _check_table(table, frames):
+        """A span table ``(row_clip, row_ptr, spans)`` - the clip of each row (not decreasing), row r's span range
+        ``row_ptr[r]:row_ptr[r + 1]`` and the ``(t0, t1)`` frame pairs - checked against the clips' frame counts -> the three as
+        lists of ints.  The library checks the same again: these messages come before anything is packed or enabled."""
+        row_clip, row_ptr, spans = table
+        row_clip, row_ptr = [int(c) for c in row_clip], [int(p) for p in row_ptr]
+        spans = [(int(a), int(b)) for a, b in spans]
+        R = len(row_clip)
+        if R < 1:
+            raise ValueError("a span table needs at least one row")
+        if len(row_ptr) != R + 1 or row_ptr[0] != 0 or row_ptr[-1] != len(spans):
+            raise ValueError(f"row_ptr must hold {R + 1} entries from 0 to the number of spans ({len(spans)})")
+        for r, c in enumerate(row_clip):
+            if not 0 <= c < len(frames):
+                raise ValueError(f"row {r} names clip {c}, outside [0, {len(frames)})")
+            if r and c < row_clip[r - 1]:
+                raise ValueError(f"row {r} names clip {c} behind row {r - 1}'s clip {row_clip[r - 1]}: the rows of a clip are contiguous")
+            if row_ptr[r + 1] <= row_ptr[r]:
+                raise ValueError(f"row {r} has no span")
+            for k, (t0, t1) in enumerate(spans[row_ptr[r]:row_ptr[r + 1]]):
+                if t0 < 0 or t1 > frames[c] or t0 >= t1:
+                    raise ValueError(f"row {r}, span {k} is [{t0}, {t1}): not inside clip {c}'s {frames[c]} frames")
+                if k and t0 < spans[row_ptr[r] + k - 1][1]:
+                    raise ValueError(f"row {r}, span {k} [{t0}, {t1}) overlaps or precedes span {k - 1}")
+        return row_clip, row_ptr, spans
+
+    @staticmethod
+    def _table_part(table, lo: int, hi: int):
+        """The rows of clips lo .. hi - 1 as a table of their own (clips renumbered from 0) -> (first row, table or None)."""
+        row_clip, row_ptr, spans = table
+        rows = [r for r, c in enumerate(row_clip) if lo <= c < hi]
+        if not rows:
+            return 0, None
+        r0, r1 = rows[0], rows[-1] + 1
+        s0 = row_ptr[r0]
+        return r0, ([c - lo for c in row_clip[r0:r1]], [p - s0 for p in row_ptr[r0:r1 + 1]], spans[s0:row_ptr[r1]])
+
+    @staticmethod
+    def _table_args(table):
+        """The table as the C ABI takes it: R, row_clip, row_ptr, spans (host arrays that may die on return)."""
+        row_clip, row_ptr, spans = table
+        flat = [t for s in spans for t in s]
+        return len(row_clip), (C.c_int * len(row_clip))(*row_clip), (C.c_int * len(row_ptr))(*row_ptr), (C.c_int * len(flat))(*flat)
+
+    def _spans_scratch(self, B: int, table, backward: bool) -> torch.Tensor:
+        """The span calls' scratch - the table's device copy, plus the per-row gradient rows of the backward: a fresh block per
+        call, like the outputs."""
+        n = C.c_size_t()
+        _lib.check(self.lib.nomad_spans_scratch_bytes(B, len(table[0]), len(table[2]), int(backward), C.byref(n)), "nomad_spans_scratch_bytes")
+        return torch.empty(n.value, dtype=torch.uint8, device=self.device)
+
+    def embed_spans_ragged(self, waves=None, table=None, precision: str = "fp32",
+                           head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                           packed: Optional[Tuple[torch.Tensor, list]] = None) -> torch.Tensor:
+        """Clips of different lengths in ONE launch sequence -> emb (R,256) fp32: ONE forward of ``precision``, then the head over
+        the R rows of ``table = (row_clip, row_ptr, spans)`` (``_check_table``) instead of over whole clips.  A row is an ordered
+        list of spans ``[t0, t1)`` of encoder frames of one clip (one frame = 320 samples), ascending and not overlapping; its
+        embedding is the plain head applied to the concatenation of its spans' frames as if they were a clip of their own (time
+        mean over all of them, ReLU, Linear, L2 norm).  The encoder saw the whole clip, so a row is not the embedding of the
+        excerpt alone.  A row of one span has the bits of ``embed_windows*``' window over those frames, a row that covers the
+        whole clip the bits of ``embed_ragged``, and a clip's rows do not depend on the batch.  waves / packed, the staging and
+        the two-stream split: as in ``embed_ragged`` (a part without a row is not run); head: fp32 only."""
+        if precision not in _lib.PRECISION:
+            raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
+        if precision != "fp32" and head is not None:
+            raise ValueError(f"the {precision} path has no head override")
+        hw, hb = self._check_head(head)
+        buf, lens = self._pack(waves, packed)
+        B, stride = buf.shape
+        frames = [num_frames(n) for n in lens]
+        if min(frames) < 1:
+            raise ValueError(f"a clip of {min(lens)} samples is shorter than the conv stack's receptive field")
+        table = self._check_table(table, frames)
+        prec = self.enable(precision)
+        emb = torch.empty(len(table[0]), 256, dtype=torch.float32, device=self.device)
+
+        def run(lo, hi, side):
+            r0, part = self._table_part(table, lo, hi)
+            if part is None:
+                return
+            R, row_clip, row_ptr, spans = self._table_args(part)
+            ws = self._workspace(self._forward_size_ragged(precision, lens[lo:hi]), side)
+            scratch = self._spans_scratch(hi - lo, part, False)
+            _lib.check(self.lib.nomad_embed_spans_ragged(self.ctx, buf[lo:hi].data_ptr(), hi - lo, stride,
+                                                         (C.c_int * (hi - lo))(*lens[lo:hi]), prec, R, row_clip, row_ptr, spans,
+                                                         _ptr(hw), _ptr(hb), emb[r0:r0 + R].data_ptr(), scratch.data_ptr(),
+                                                         scratch.numel(), ws.data_ptr(), ws.numel(), self._stream()),
+                       "nomad_embed_spans_ragged")
+
+        self._dispatch(B, self._audio_cut(lens) if self._splits(precision, B, sum(frames)) else 0, run)
+        return emb
+
+    def frame_energy(self, waves=None, packed: Optional[Tuple[torch.Tensor, list]] = None):
+        """Mean square of the 400 samples every encoder frame sees -> float64 (sum of the clips' frames,) on the GPU: clip 0's
+        ``num_frames`` values, then clip 1's, ...  Every product and sum is in float64 in a fixed order; a frame's value depends on its own
+        samples only.  waves / packed: as in ``embed_ragged``."""
+        buf, lens = self._pack(waves, packed)
+        B, stride = buf.shape
+        frames = [num_frames(n) for n in lens]
+        if min(frames) < 1:
+            raise ValueError(f"a clip of {min(lens)} samples is shorter than the conv stack's receptive field")
+        e = torch.empty(sum(frames), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.nomad_frame_energy(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), e.data_ptr(), self._stream()),
+                   "nomad_frame_energy")
+        return e
+
     # ---- degradations on packed clips (nomad_degrade_noise / nomad_degrade_clip) ------------------------------------------------
     def _degrade(self, waves, lengths, levels, what: str):
         """The shared front of the two degradations: pack, check the levels -> (buffer, lengths, level array, G, output, workspace)."""
@@ -1062,6 +1170,57 @@ class Engine:
                                                                 saved.numel(), demb_w.data_ptr(), dwav.data_ptr(), scratch.data_ptr(),
                                                                 scratch.numel(), ws.data_ptr(), ws.numel(), self._stream()),
                    "nomad_embed_windows_backward_ragged")
+        return dwav
+
+    # ---- the span head on the gradient path ------------------------------------------------------------------------------------
+    def embed_train_spans_ragged(self, waves, table, lengths=None, head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """``embed_train_ragged`` with the span head of ``embed_spans_ragged`` as its last stage: -> (emb (R,256), packed layers
+        (12,M,768), saved block, (buffer, lengths)); the last item is the batch ``embed_spans_backward_ragged`` takes.  Rows, spans
+        and the table as in ``embed_spans_ragged``: a row pools the concatenation of its spans' frames as if they were a clip of
+        their own, and the encoder saw the whole clip."""
+        hw, hb = self._check_head(head)
+        buf, lens = self.pack_ragged(waves, lengths)
+        frames = [num_frames(n) for n in lens]
+        if min(frames) < 1:
+            raise ValueError(f"a clip of {min(lens)} samples is shorter than the conv stack's receptive field")
+        table = self._check_table(table, frames)
+        self.enable_backward()
+        B, stride = buf.shape
+        R, row_clip, row_ptr, spans = self._table_args(table)
+        emb = torch.empty(R, 256, dtype=torch.float32, device=self.device)
+        layers = torch.empty(12, sum(frames), 768, dtype=torch.float32, device=self.device)
+        saved = torch.empty(self._size_ragged(self.lib.nomad_saved_bytes_ragged, lens, "nomad_saved_bytes_ragged"),
+                            dtype=torch.uint8, device=self.device)
+        ws = self._workspace(self._size_ragged(self.lib.nomad_workspace_bytes_ragged, lens, "nomad_workspace_bytes_ragged"))
+        scratch = self._spans_scratch(B, table, False)
+        _lib.check(self.lib.nomad_embed_train_spans_ragged(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), R, row_clip,
+                                                           row_ptr, spans, _ptr(hw), _ptr(hb), emb.data_ptr(), layers.data_ptr(),
+                                                           saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(),
+                                                           ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_embed_train_spans_ragged")
+        return emb, layers, saved, (buf, lens)
+
+    def embed_spans_backward_ragged(self, batch, layers, saved, demb_r, table, head=None) -> torch.Tensor:
+        """d loss / d wav (B, stride) of an ``embed_train_spans_ragged`` call (``batch``: its last result, ``table``: its table) from
+        d loss / d emb (R,256); zero behind every clip's length, and all zero for a clip without a row."""
+        hw, hb = self._check_head(head)
+        buf, lens = batch
+        B, stride = buf.shape
+        table = self._check_table(table, [num_frames(n) for n in lens])
+        R, row_clip, row_ptr, spans = self._table_args(table)
+        self._check_dev(demb_r, "demb_r")
+        if tuple(demb_r.shape) != (R, 256):
+            raise ValueError(f"demb_r must be ({R}, 256): one row per row of the table, got {tuple(demb_r.shape)}")
+        self.enable_backward()
+        ws = self._workspace(self._size_ragged(self.lib.nomad_backward_workspace_bytes_ragged, lens,
+                                               "nomad_backward_workspace_bytes_ragged"))
+        scratch = self._spans_scratch(B, table, True)
+        dwav = torch.empty(B, stride, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nomad_embed_spans_backward_ragged(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), R, row_clip,
+                                                              row_ptr, spans, _ptr(hw), _ptr(hb), layers.data_ptr(), saved.data_ptr(),
+                                                              saved.numel(), demb_r.data_ptr(), dwav.data_ptr(), scratch.data_ptr(),
+                                                              scratch.numel(), ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_embed_spans_backward_ragged")
         return dwav
 
     def train_backward_ragged(self, batch, layers: torch.Tensor, saved: torch.Tensor, demb: torch.Tensor):

@@ -407,6 +407,127 @@ def segments_tables(test_files, frames, scores, win: int, hop: int):
     return df, df_mean
 
 
+def span_frames(start_s, end_s, T: int):
+    """A span in seconds -> (t0, t1), encoder frames [t0, t1) of a clip of T frames: ``t0 = round(start_s * 50)``, ``t1 =
+    round((end_s - 0.005) * 50)``, both clamped to [0, T].  The inverse of ``window_times``: a window's (start_s, end_s) gives that
+    window's frames back (its end is the last sample its frames SEE, 80 samples = 5 ms past their 20 ms grid).  Pure; a span that
+    is empty after clamping raises a ValueError that names it."""
+    for name, s in (("start_s", start_s), ("end_s", end_s)):
+        if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not math.isfinite(s):
+            raise ValueError(f"{name} must be a finite number of seconds, got {s!r}")
+    T = int(T)
+    t0 = min(max(int(round(float(start_s) * FRAMES_PER_SECOND)), 0), T)
+    t1 = min(max(int(round((float(end_s) - 0.005) * FRAMES_PER_SECOND)), 0), T)
+    if t1 <= t0:
+        raise ValueError(f"the span ({start_s!r} s, {end_s!r} s) holds no frame of a clip of {T} frames (frames [{t0}, {t1}))")
+    return t0, t1
+
+
+def span_times(t0: int, t1: int):
+    """Frames [t0, t1) -> (start_s, end_s) on ``window_times``' 3-decimal grid: ``span_frames`` gives (t0, t1) back."""
+    return (int(t0) * 20) / 1000.0, (int(t1) * 20 + 5) / 1000.0
+
+
+def active_frames(energy, floor_db: float = 40.0, min_speech_frames: int = 5, min_gap_frames: int = 15):
+    """The rule of ``Nomad.active_spans`` on one clip's frame energies (a 1-D array) -> a list of (t0, t1) in frames.  Pure.
+    1. a frame is active when ``e[t] >= max(e) * 10 ** (-floor_db / 10)``; 2. inactive runs of at most ``min_gap_frames`` frames
+    between two active frames become active; 3. active runs shorter than ``min_speech_frames`` frames are dropped; 4. if nothing is
+    left, or ``max(e)`` is 0 or not finite, the whole clip [0, T) is returned.  An energy gate, not a speech detector."""
+    e = np.asarray(energy, dtype=np.float64).reshape(-1)
+    T = int(e.shape[0])
+    if T < 1:
+        raise ValueError("a clip has at least one frame")
+    top = float(np.max(e))
+    if not math.isfinite(top) or top <= 0.0:
+        return [(0, T)]
+    active = e >= top * 10.0 ** (-float(floor_db) / 10.0)
+
+    def runs(mask):
+        edge = np.flatnonzero(np.diff(np.concatenate(([False], mask, [False])).astype(np.int8)))
+        return list(zip(edge[0::2].tolist(), edge[1::2].tolist()))
+
+    on = runs(active)
+    for (_, a), (b, _) in zip(on[:-1], on[1:]):      # the gap [a, b) lies between two active frames
+        if b - a <= int(min_gap_frames):
+            active[a:b] = True
+    kept = [(a, b) for a, b in runs(active) if b - a >= int(min_speech_frames)]
+    return kept if kept else [(0, T)]
+
+
+def span_table(rows, frames, unit: str = "s"):
+    """The Python form of the spans -> the table ``Engine.embed_spans_ragged`` takes, ``(row_clip, row_ptr, spans)``, and the rows
+    per clip.  ``rows[c]`` is the list of rows of clip c (empty: the clip has none); a row is one ``(start, end)`` pair or a list
+    of them, in seconds (``span_frames``) or, with unit="frames", frames [t0, t1) as they are.  frames[c]: the clip's frame count.
+    Spans inside a row must be ascending and must not overlap; the error names clip, row and span.  Pure."""
+    if unit not in ("s", "frames"):
+        raise ValueError(f"unit must be 's' or 'frames', got {unit!r}")
+    if len(rows) != len(frames):
+        raise ValueError(f"spans holds the rows of {len(rows)} clips for a batch of {len(frames)}")
+    row_clip, row_ptr, spans, counts = [], [0], [], []
+    for c, clip_rows in enumerate(rows):
+        counts.append(len(clip_rows))
+        for r, row in enumerate(clip_rows):
+            row = list(row)
+            if len(row) == 2 and not isinstance(row[0], (list, tuple, np.ndarray)):
+                row = [tuple(row)]
+            if not row:
+                raise ValueError(f"clip {c}, row {r} has no span")
+            for s, pair in enumerate(row):
+                if len(pair) != 2:
+                    raise ValueError(f"clip {c}, row {r}, span {s}: expected a (start, end) pair, got {pair!r}")
+                if unit == "s":
+                    try:
+                        t0, t1 = span_frames(pair[0], pair[1], frames[c])
+                    except ValueError as err:
+                        raise ValueError(f"clip {c}, row {r}, span {s}: {err}") from None
+                else:
+                    t0, t1 = int(pair[0]), int(pair[1])
+                    if t0 < 0 or t1 > frames[c] or t0 >= t1:
+                        raise ValueError(f"clip {c}, row {r}, span {s} is [{t0}, {t1}): not inside the clip's {frames[c]} frames")
+                if s and t0 < spans[-1][1]:
+                    raise ValueError(f"clip {c}, row {r}, span {s} [{t0}, {t1}) overlaps or precedes the span before it")
+                spans.append((t0, t1))
+            row_clip.append(c)
+            row_ptr.append(len(spans))
+    if not row_clip:
+        raise ValueError("spans holds no row")
+    return (row_clip, row_ptr, spans), counts
+
+
+def spans_from_csv(spans, test_files):
+    """The csv form of ``Nomad.predict_spans``: a DataFrame or a csv path with the columns ``Test File``, ``start_s``, ``end_s`` and
+    optionally ``Row`` -> {test file: [(row label, [(start_s, end_s), ...]), ...]}, rows in the order their first line appears,
+    a row's spans ascending by start.  Lines that share a ``Row`` label (of the same file) pool into one row; without the column
+    every line is a row of its own, labelled by its position among the file's lines.  A file that ``test_files`` does not list is
+    an error; a listed file without a line gets no row."""
+    df = pd.read_csv(spans) if isinstance(spans, (str, os.PathLike)) else spans
+    if not isinstance(df, pd.DataFrame):
+        raise TypeError(f"spans must be a DataFrame or the path of a csv file, got {type(spans).__name__}")
+    missing = [c for c in ("Test File", "start_s", "end_s") if c not in df.columns]
+    if missing:
+        raise ValueError(f"the span table lacks the column(s) {missing}: it needs Test File, start_s, end_s (and optionally Row)")
+    known = set(test_files)
+    out = {}
+    for i, (f, a, b) in enumerate(zip(df["Test File"], df["start_s"], df["end_s"])):
+        f = str(f)
+        if f not in known:
+            raise ValueError(f"the span table names the test file {f!r} (line {i}), which is not among the test files")
+        rows = out.setdefault(f, [])
+        if "Row" in df.columns:
+            label = df["Row"].iloc[i]
+            row = next((r for r in rows if r[0] == label), None)
+            if row is None:
+                rows.append((label, [(float(a), float(b))]))
+            else:
+                row[1].append((float(a), float(b)))
+        else:
+            rows.append((len(rows), [(float(a), float(b))]))
+    for rows in out.values():
+        for _, pairs in rows:
+            pairs.sort()
+    return out
+
+
 def nearest_table(test_files, ref_names, knn_dist, knn_idx) -> pd.DataFrame:
     """The third table of ``Nomad.predict(k=...)``: one row per test file, indexed by ``Test File``, with the columns ``Ref 1``,
     ``Dist 1``, ... ``Ref k``, ``Dist k`` - the names of the file's nearest references (as the matrix's columns are named), nearest
@@ -596,6 +717,55 @@ class _WindowScoreFn(torch.autograd.Function):
         if dref is not None:
             dref = dref.to(ref_device, ref_dtype)
         return dwav, dref, None, None, None, None, None
+
+
+class _SpanScoreFn(torch.autograd.Function):
+    """scores[r] = mean_j ||emb_r(row r of the span table) - references_j|| over the rows of ``Engine.embed_train_spans_ragged``;
+    backward = ``cdist_backward`` over the rows, then ``embed_spans_backward_ragged`` (the span head's backward and the backbone
+    down to the waveform) and, when asked for, d / d references.  ``k``: as in ``_ScoreFn``."""
+
+    @staticmethod
+    def forward(ctx, estimate, references, nomad, lens, table, k):
+        eng = nomad.engine
+        est = estimate.detach().to(eng.device, torch.float32).contiguous()
+        est = est.squeeze(1) if est.dim() == 3 else est
+        refs = references.detach().to(eng.device, torch.float32).contiguous()
+        ctx.nomad, ctx.lens, ctx.table = nomad, lens, table
+        ctx.meta = (estimate.shape, references.device, references.dtype)
+        if not estimate.requires_grad:   # only the references are differentiated: the scoring forward will do
+            emb = eng.embed_spans_ragged([est[i, :n] for i, n in enumerate(lens)], table, precision=nomad._window_precision(sum(lens)))
+            layers = saved = None
+        else:
+            emb, layers, saved, (est, _) = eng.embed_train_spans_ragged(est, table, lens)
+        idx = None
+        if k is None:
+            _, mean = eng.pairwise(emb, refs, want_matrix=False)
+        else:
+            _, idx, mean = eng.knn(emb, refs, k)
+        ctx.save_for_backward(est, refs, emb, layers, saved, idx)
+        return mean
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        est, refs, emb, layers, saved, idx = ctx.saved_tensors
+        eng = ctx.nomad.engine
+        shape, ref_device, ref_dtype = ctx.meta
+        want_a = ctx.needs_input_grad[0] and saved is not None
+        want_b = ctx.needs_input_grad[1]
+        if not (want_a or want_b):
+            return None, None, None, None, None, None
+        g = grad_out.to(eng.device, torch.float64).contiguous()
+        if idx is None:
+            demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
+        else:
+            demb, dref = eng.knn_backward(emb, refs, idx, g_score=g, want_a=want_a, want_b=want_b)
+        dwav = None
+        if want_a:
+            Nomad._need_whole_encoder(eng)
+            dwav = eng.embed_spans_backward_ragged((est, ctx.lens), layers, saved, demb, ctx.table).reshape(shape)
+        if dref is not None:
+            dref = dref.to(ref_device, ref_dtype)
+        return dwav, dref, None, None, None, None
 
 
 class GraphedLoss:
@@ -1301,6 +1471,190 @@ class Nomad:
         df, df_mean = segments_tables(test_files, frames, scores, win, hop)
         if results_path is not None:
             _write_rounded_csv(df, os.path.join(results_path, "segments.csv"))
+        return df, df_mean
+
+    # ---- scores over caller-given spans: speech only, per utterance, per speaker turn ------------------------------------
+    span_frames = staticmethod(span_frames)
+
+    def score_spans(self, wav, references, spans, lengths=None, reduction="none", k=None, unit="s"):
+        """NOMAD scores over spans the CALLER names: -> (scores (R,) float64 on the GPU, counts) - for every row the mean distance
+        of the row's embedding to ``references`` ((Nr,256), as ``score`` takes them); clip 0's rows in order, then clip 1's, ...;
+        counts[c] = rows of clip c.  wav (B,1,N) or (B,N); lengths: the clips' exact lengths as in ``score``.
+
+        ``spans[c]`` is the list of rows of clip c (an empty list: no row).  A row is one ``(start, end)`` pair or a list of
+        them - ascending, not overlapping - in seconds (``span_frames``: ``t0 = round(start * 50)``, ``t1 = round((end - 0.005)
+        * 50)``, the inverse of ``window_times``) or, with unit="frames", encoder frames [t0, t1) as they are.  A row's embedding
+        is the plain head applied to the concatenation of its spans' frames as if they were a clip of their own: one time mean
+        over all of them, ReLU, Linear, L2 norm - "the score of what is speech" is ONE row over the union of the speech spans,
+        which per-window scores cannot give.  All rows come from ONE forward (``Engine.embed_spans_ragged``): the encoder saw
+        the whole clip, so a row's score is not the score of the excerpt on its own.  A row ``[(0, T)]`` has the bits of
+        ``score``, a row of one span the bits of ``score_over_time``'s window over those frames.
+
+        Under ``torch.no_grad()``, or when nothing requires a gradient, the embeddings come from the scoring forward of
+        ``precision``, then ``Engine.pairwise`` (k: ``Engine.knn``).  With a gradient the forward is
+        ``embed_train_spans_ragged`` (fp32 buffers, products by ``Engine.gemm_precision``) and the backward runs
+        ``cdist_backward`` / ``knn_backward`` over the rows, the span head's backward - a frame receives the sum of the gradients
+        of the rows that contain it, exact zeros where none does - and the backbone down to the waveform; it carries
+        ``feature_grad_mult`` as ``score``'s does and is zero behind every length.  ``references`` gets a gradient too when it
+        requires one.  With reduction="mean" the 0-dim mean over all rows takes the place of ``scores``; weights per turn are
+        plain torch, ``(scores * weights).sum()``."""
+        check_reduction(reduction)
+        check_references(references)
+        k = check_k(k, references.shape[0]) if k is not None else None
+        if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+            raise ValueError(f"wav must be (B,1,N) or (B,N), got {tuple(getattr(wav, 'shape', ()))}")
+        lens = check_lengths(wav, lengths) if lengths is not None else [int(wav.shape[-1])] * int(wav.shape[0])
+        if min(lens) < MIN_SAMPLES:
+            raise ValueError(f"a clip of {min(lens)} samples is shorter than one encoder frame ({MIN_SAMPLES} samples)")
+        table, counts = span_table(spans, [num_frames(n) for n in lens], unit)
+        self._need_whole_encoder(self.engine)
+        if torch.is_grad_enabled() and (wav.requires_grad or references.requires_grad):
+            scores = _SpanScoreFn.apply(wav, references, self, lens, table, k)
+        else:
+            eng = self.engine
+            x = wav.detach().to(eng.device, torch.float32).contiguous()
+            x = x.squeeze(1) if x.dim() == 3 else x
+            refs = references.detach().to(eng.device, torch.float32).contiguous()
+            emb = eng.embed_spans_ragged([x[i, :n] for i, n in enumerate(lens)], table, precision=self._window_precision(sum(lens)))
+            scores = self._reference_mean(emb, refs, k)
+        return (scores.mean() if reduction == "mean" else scores), counts
+
+    @staticmethod
+    def _active_frame_counts(min_speech_s, min_gap_s):
+        for name, s in (("min_speech_s", min_speech_s), ("min_gap_s", min_gap_s)):
+            if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not math.isfinite(s) or s < 0:
+                raise ValueError(f"{name} must be a non-negative number of seconds, got {s!r}")
+        return int(round(float(min_speech_s) * FRAMES_PER_SECOND)), int(round(float(min_gap_s) * FRAMES_PER_SECOND))
+
+    def _active_from_packed(self, packed, floor_db, min_speech, min_gap):
+        """Frame energies of a packed batch (``Engine.frame_energy``), down to the host, through ``active_frames`` per clip."""
+        frames = [num_frames(n) for n in packed[1]]
+        e = self.engine.frame_energy(None, packed=packed)
+        e = e.cpu().numpy() if torch.is_tensor(e) else np.asarray(e)
+        out, at = [], 0
+        for t in frames:
+            out.append(active_frames(e[at:at + t], floor_db, min_speech, min_gap))
+            at += t
+        return out
+
+    def active_spans(self, wav, lengths=None, floor_db=40.0, min_speech_s=0.1, min_gap_s=0.3):
+        """Where a recording is not silent: -> per clip a list of ``(t0, t1)`` in encoder frames, ascending and not overlapping -
+        what ``score_spans(..., spans=[[s] for s in active], unit="frames")`` takes as one row per clip.  wav (B,1,N) or (B,N);
+        lengths as in ``score``.  The energy of a frame is the mean square of the 400 samples it sees (``Engine.frame_energy``,
+        float64 on the GPU); the rule on them runs on the host (``active_frames``): a frame is active within ``floor_db`` dB of
+        the clip's loudest frame, gaps of at most ``min_gap_s`` between active frames are closed, runs shorter than
+        ``min_speech_s`` dropped; a clip where nothing is left (or that is all zeros, or not finite) gets its whole length.
+        Deliberately simple: an energy gate, not a speech detector - music, noise and a slammed door are "active" too."""
+        if not isinstance(floor_db, (int, float, np.integer, np.floating)) or isinstance(floor_db, bool) or not math.isfinite(floor_db):
+            raise ValueError(f"floor_db must be a finite number of dB, got {floor_db!r}")
+        min_speech, min_gap = self._active_frame_counts(min_speech_s, min_gap_s)
+        if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+            raise ValueError(f"wav must be (B,1,N) or (B,N), got {tuple(getattr(wav, 'shape', ()))}")
+        lens = check_lengths(wav, lengths) if lengths is not None else [int(wav.shape[-1])] * int(wav.shape[0])
+        if min(lens) < MIN_SAMPLES:
+            raise ValueError(f"a clip of {min(lens)} samples is shorter than one encoder frame ({MIN_SAMPLES} samples)")
+        x = wav.detach().to(self.engine.device, torch.float32).contiguous()
+        x = x.squeeze(1) if x.dim() == 3 else x
+        return self._active_from_packed((x, lens), floor_db, min_speech, min_gap)
+
+    def _score_file_spans(self, paths, test_files, ref_t, rows_of, active, max_batch_samples: int, k=None):
+        """The file pipeline of ``_score_file_windows`` with the span head: -> one record per row, files in order: (file index,
+        row label, spans in frames, score).  rows_of: ``spans_from_csv``'s result, or None with ``active`` = (floor_db, min speech
+        frames, min gap frames): one row per file over its active spans, which costs a host round trip per staged batch (the
+        energies come down, the table goes up)."""
+        records = [[] for _ in paths]
+        pending = None
+
+        def collect(item):
+            meta, fetch = item
+            vals = fetch.result() if fetch is not None else np.full(len(meta), np.nan)
+            for (i, label, spans), v in zip(meta, vals):
+                records[i].append((i, label, spans, float(v)))
+
+        for idxs, packed, uploaded in _staged_batches(paths, lambda p: self.load_processing(p, trim=False),
+                                                      self.engine.pack_ragged_host, max_batch_samples, self.DECODE_THREADS,
+                                                      self.PIPELINE_BATCHES, self.NATIVE_WAV_THREADS,
+                                                      device=getattr(self.engine, "device", None)):
+            frames = [num_frames(n) for n in packed[1]]
+            if torch.is_tensor(packed[0]):   # one upload serves the energies and the forward
+                packed = (packed[0].to(self.engine.device, non_blocking=True), packed[1])
+            if rows_of is None:
+                act = self._active_from_packed(packed, *active)
+                rows, labels = [[a] for a in act], [["active"] for _ in act]
+                unit = "frames"
+            else:
+                per_file = [rows_of.get(test_files[i], []) for i in idxs]
+                rows, labels = [[p for _, p in r] for r in per_file], [[lab for lab, _ in r] for r in per_file]
+                unit = "s"
+            if not any(rows):
+                uploaded()
+                continue
+            try:
+                table, _ = span_table(rows, frames, unit)
+            except ValueError as err:
+                raise ValueError(f"{err} (clips of this batch: {[test_files[i] for i in idxs]})") from None
+            emb = self.engine.embed_spans_ragged(None, table, precision=self._window_precision(sum(packed[1])), packed=packed)
+            uploaded()
+            meta = [(idxs[c], labels[c][r - table[0].index(c)], table[2][table[1][r]:table[1][r + 1]]) for r, c in enumerate(table[0])]
+            fetch = self.engine.fetch_async(self._reference_mean(emb, ref_t, k)) if ref_t.shape[0] else None
+            if pending is not None:
+                collect(pending)
+            pending = (meta, fetch)
+        if pending is not None:
+            collect(pending)
+        return [r for rec in records for r in rec]
+
+    def predict_spans(self, mode="dir", nmr="data/nmr-data", deg="data/test-data", spans=None, active_db=None, results_path=None,
+                      max_batch_samples: int = 256 * 64000, k=None):
+        """``predict`` over spans the caller names: -> (df_spans, df_avg).  Exactly one of:
+
+        spans      a DataFrame or a csv path with the columns ``Test File`` (the label ``predict`` prints: the file's name without
+                   directory and extension), ``start_s``, ``end_s`` and optionally ``Row``.  Lines of a file that share a ``Row``
+                   label pool into ONE row (a speaker's turns, the speech of a call); without the column every line is its own row.
+                   A file the csv names but ``deg`` does not list is an error; a test file without a line produces no row.
+        active_db  one row per file over its active spans: ``active_spans(floor_db=active_db)`` with its default times.
+
+        df_spans has one row per row, files in listing order: ``Test File``, ``Row``, ``start_s`` / ``end_s`` (the first span's
+        start and the last span's end, ``span_times``), ``active_s`` (the seconds the row's frames cover, 0.02 s each) and
+        ``NOMAD``, the row's mean distance to the reference embeddings rounded to 3 decimals; df_avg, indexed by ``Test File``,
+        the mean of each file's rows.  Seconds become frames by ``span_frames``.  The test files go through the staged ragged
+        batches of ``predict_segments`` with the span head (``score_spans`` says what a row is: pooled from one forward over the
+        whole file, as if its spans' frames were a clip of their own).  With ``results_path`` the table is written to
+        ``spans.csv`` there.  One process only, like ``predict_segments``.  k: as in ``predict_segments``."""
+        if (spans is None) == (active_db is None):
+            raise ValueError("predict_spans takes exactly one of spans= (a DataFrame or csv path) and active_db= (a floor in dB)")
+        if active_db is not None and (isinstance(active_db, bool) or not isinstance(active_db, (int, float, np.integer, np.floating))
+                                      or not math.isfinite(active_db)):
+            raise ValueError(f"active_db must be a finite number of dB, got {active_db!r}")
+        if k is not None:
+            check_k(k, KNN_MAX)
+        _check_predict_paths(mode, nmr, deg)
+        world, _, _ = _dist_info(getattr(self, "group", None))
+        if world > 1:
+            raise RuntimeError(f"predict_spans runs in one process: this one belongs to a torch.distributed job of {world} ranks "
+                               "(sharding the rows is not implemented; predict() shards whole-file scores)")
+        paths = [str(p) for p in _file_table(deg)["filename"]]
+        test_files = [x.split("/")[-1].split(".")[0] for x in paths]
+        rows_of = spans_from_csv(spans, test_files) if spans is not None else None
+        active = (float(active_db),) + self._active_frame_counts(0.1, 0.3) if active_db is not None else None
+        print(f"Compute non-matching reference embeddings from {nmr}")
+        nmr_embeddings = self.get_embeddings(nmr).set_index("filename")
+        print(f"Compute degraded embeddings over spans from {deg}")
+        ref_t = torch.from_numpy(np.ascontiguousarray(nmr_embeddings.to_numpy(dtype=np.float32))).to(self.engine.device)
+        if k is not None:
+            k = check_k(k, ref_t.shape[0])
+        recs = self._score_file_spans(paths, test_files, ref_t, rows_of, active, max_batch_samples, k)
+        times = [(span_times(s[0][0], s[-1][1]), sum(b - a for a, b in s) * 20 / 1000.0) for _, _, s, _ in recs]
+        df = pd.DataFrame({"Test File": np.asarray([test_files[i] for i, _, _, _ in recs], dtype=object),
+                           "Row": np.asarray([lab for _, lab, _, _ in recs], dtype=object),
+                           "start_s": np.asarray([t[0][0] for t in times], dtype=np.float64),
+                           "end_s": np.asarray([t[0][1] for t in times], dtype=np.float64),
+                           "active_s": np.asarray([t[1] for t in times], dtype=np.float64),
+                           "NOMAD": np.asarray([v for _, _, _, v in recs], dtype=np.float64)}).round({"NOMAD": 3})
+        raw = pd.DataFrame({"Test File": [test_files[i] for i, _, _, _ in recs], "NOMAD": [v for _, _, _, v in recs]})
+        df_mean = raw.groupby("Test File", sort=False)["NOMAD"].mean().to_frame().round(3)
+        if results_path is not None:
+            df.to_csv(os.path.join(results_path, "spans.csv"), index=False)   # (two label columns: not _write_rounded_csv's table)
         return df, df_mean
 
     # ---- degradations on the device ----------------------------------------------------------------------------------
