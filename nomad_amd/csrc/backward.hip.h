@@ -243,7 +243,7 @@ __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict_
         const float s2 = (psum[0][tid + 512] + psum[1][tid + 512]) + (psum[2][tid + 512] + psum[3][tid + 512]);
         const float inv = 1.0f / (float)T;
         const float m0 = s0 * inv, m1 = s1 * inv, m2 = s2 * inv;
-        pooled[tid] = fmaxf(m0, 0.f); pooled[tid + 256] = fmaxf(m1, 0.f); pooled[tid + 512] = fmaxf(m2, 0.f);
+        pooled[tid] = relu_keep_nan(m0); pooled[tid + 256] = relu_keep_nan(m1); pooled[tid + 512] = relu_keep_nan(m2);
         mask[tid] = m0 > 0.f ? inv : 0.f; mask[tid + 256] = m1 > 0.f ? inv : 0.f; mask[tid + 512] = m2 > 0.f ? inv : 0.f;
     }
     __syncthreads();
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(1024) void head_windows_bwd_kernel(const float* __r
             const float m[4] = {run[q].x * inv, run[q].y * inv, run[q].z * inv, run[q].w * inv};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                pooled[256 * q + 4 * lane + j] = fmaxf(m[j], 0.f);
+                pooled[256 * q + 4 * lane + j] = relu_keep_nan(m[j]);
                 mask[256 * q + 4 * lane + j] = m[j] > 0.f ? inv : 0.f;
             }
         }
@@ -574,7 +574,7 @@ __global__ __launch_bounds__(1024) void head_spans_bwd_kernel(const float* __res
             const float m[4] = {run[q].x * inv, run[q].y * inv, run[q].z * inv, run[q].w * inv};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                pooled[256 * q + 4 * lane + j] = fmaxf(m[j], 0.f);
+                pooled[256 * q + 4 * lane + j] = relu_keep_nan(m[j]);
                 mask[256 * q + 4 * lane + j] = m[j] > 0.f ? inv : 0.f;
             }
         }

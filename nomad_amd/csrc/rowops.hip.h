@@ -20,6 +20,11 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// torch.relu / clamp_min(0): max(x, 0) that keeps a NaN.  `fmaxf(x, 0.f)` returns 0 for a NaN (IEEE maxNum), which turned a clip whose
+// encoder output is NaN into the finite embedding normalize(bias).  Both selects are true selects, so every other x gives the bits
+// v_max_f32(x, 0) gave: x for x > 0 (+Inf included), +0 for x < 0, -Inf, -0 and +0.
+__device__ __forceinline__ float relu_keep_nan(float x) { return x > 0.f ? x : (x != x ? x : 0.f); }
+
 // Sum over the S slices of a split-K GEMM's partial products for one float4: ((p[0] + p[stride4]) + p[2 stride4]) + ... in slice order,
 // with the loads of the first kSliceBurst slices issued BEFORE the first add.  Round 6: written as `for (s = 1; s < S; ++s) a += p[s * stride4]`
 // with a run-time S hipcc emits load - s_waitcnt vmcnt(0) - add per slice, and the epilogue kernels of configs[3] (1632 rows: one wave of
@@ -191,9 +196,9 @@ __global__ __launch_bounds__(1024) void head_kernel(const float* __restrict__ po
             s2 += r[tid + 512];
         }
         const float inv = 1.0f / (float)T;
-        pooled[tid] = fmaxf(s0 * inv, 0.f);
-        pooled[tid + 256] = fmaxf(s1 * inv, 0.f);
-        pooled[tid + 512] = fmaxf(s2 * inv, 0.f);
+        pooled[tid] = relu_keep_nan(s0 * inv);
+        pooled[tid + 256] = relu_keep_nan(s1 * inv);
+        pooled[tid + 512] = relu_keep_nan(s2 * inv);
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;
@@ -354,10 +359,10 @@ __global__ __launch_bounds__(1024) void head_windows_kernel(const TIn* __restric
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             float* p = pooled + 256 * q + 4 * lane;
-            p[0] = fmaxf(run[q].x * inv, 0.f);
-            p[1] = fmaxf(run[q].y * inv, 0.f);
-            p[2] = fmaxf(run[q].z * inv, 0.f);
-            p[3] = fmaxf(run[q].w * inv, 0.f);
+            p[0] = relu_keep_nan(run[q].x * inv);
+            p[1] = relu_keep_nan(run[q].y * inv);
+            p[2] = relu_keep_nan(run[q].z * inv);
+            p[3] = relu_keep_nan(run[q].w * inv);
         }
     }
     __syncthreads();
@@ -489,10 +494,10 @@ __global__ __launch_bounds__(1024) void head_spans_kernel(const TIn* __restrict_
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             float* p = pooled + 256 * q + 4 * lane;
-            p[0] = fmaxf(run[q].x * inv, 0.f);
-            p[1] = fmaxf(run[q].y * inv, 0.f);
-            p[2] = fmaxf(run[q].z * inv, 0.f);
-            p[3] = fmaxf(run[q].w * inv, 0.f);
+            p[0] = relu_keep_nan(run[q].x * inv);
+            p[1] = relu_keep_nan(run[q].y * inv);
+            p[2] = relu_keep_nan(run[q].z * inv);
+            p[3] = relu_keep_nan(run[q].w * inv);
         }
     }
     __syncthreads();

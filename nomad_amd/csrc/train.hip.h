@@ -486,7 +486,7 @@ __global__ __launch_bounds__(256) void triplet_loss_kernel(const float* __restri
         const float dap = sqrtf(wave_sum((ap[0] * ap[0] + ap[1] * ap[1]) + (ap[2] * ap[2] + ap[3] * ap[3])));
         const float dan = sqrtf(wave_sum((an[0] * an[0] + an[1] * an[1]) + (an[2] * an[2] + an[3] * an[3])));
         const float l = dap - dan + margin;
-        total += fmaxf(l, 0.f);
+        total += relu_keep_nan(l);
         if (da) {
             const float on = l > 0.f ? invB : 0.f;
             const float ip = dap > 0.f ? on / dap : 0.f, in_ = dan > 0.f ? on / dan : 0.f;
