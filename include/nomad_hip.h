@@ -23,6 +23,7 @@
  *   nomad_embed_windows_backward   d / d waveform of the window embeddings (scores over time as a loss)
  *   nomad_degrade_noise / _clip    noise at a target SNR and percentile clipping of src/utils/degradations.py (:30-68, :70-83), G levels
  *                                  per clip, written as the packed batch nomad_embed_ragged reads
+ *   nomad_degrade_convolve         every clip convolved with G impulse responses (reverberation as a causal FIR filter), same layout
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
  *
@@ -690,6 +691,33 @@ int nomad_degrade_noise(nomad_ctx* ctx, const float* x_dev, int B, int stride, c
                         void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
 int nomad_degrade_clip(nomad_ctx* ctx, const float* x_dev, int B, int stride, const int* lens_host, const double* clip_factor_host,
                        int G, float* out_dev, double* thresholds_out_dev, void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
+
+/* ---- reverberation on packed clips: every clip convolved with G impulse responses --------------------------------------
+ * For any fixed setting a reverberator is a linear, time-invariant filter.  x_dev is [B][stride] fp32 with lens_host as above; ir_dev
+ * is [G][ir_stride] fp32, response g in the first ir_lens_host[g] taps of its row (the rest of either row is never read: anything,
+ * NaN included, may stand there); the G responses are applied to EVERY clip.  out_dev is [B G][stride] fp32, row b G + g being clip b
+ * through response g, causal and cut to the clip's length n_b (sox's effect chain leaves the same):
+ *   out[b G + g][i] = sum_{k = 0}^{min(L_g - 1, i)} h_g[k] x_b[i - k]   for i < n_b,      0 for n_b <= i < stride.
+ * Arithmetic: fp32 products, fp32 accumulation, no fp32 rounding skipped or added (v_mfma_f32_16x16x4_f32, an fmaf chain).  Order as
+ * built: the taps in chunks of 241 (k = 0 .. 240, 241 .. 481, ...) in ascending order, inside a chunk from its LAST tap down to its
+ * first, one chain per output; samples before the clip's start and the taps a chunk lacks enter as zeros (products with them are
+ * formed and add +-0).  The order depends on (n_b, L_g) and the output's index only: row b G + g of any batch has the bits of the
+ * clip's own B = 1, G = 1 call.  Integer-valued inputs whose partial sums stay below 2^24 give the exact sums.
+ * Non-finite values: a non-finite sample at position p of clip b makes out[b G + g][p .. min(p + L_g, n_b) - 1] non-finite for every
+ * g, a non-finite tap k makes out[b G + g][k .. n_b - 1] non-finite for every b; no row of another clip and, for a tap, no row of
+ * another response changes.  Within the affected row FURTHER samples may turn non-finite (0 x NaN against a padding zero of a
+ * 16 x 256 Toeplitz tile: up to 255 outputs around the formula's range, and outputs ahead of a bad tap).
+ * Contract as the degradations above: asynchronous, no allocation, deterministic; the two length tables are copied into the
+ * workspace ahead of the kernel; workspace nomad_degrade_convolve_scratch_bytes(B, G) bytes (0 for arguments the call would refuse),
+ * written before it is read.  Argument errors return before anything is queued.
+ * NOMAD_ERR_INVALID: a NULL pointer, G outside 1 .. 64, B < 1 (or above 65535), stride or ir_stride not a positive multiple of 4 or
+ * shorter than a length, a clip length < 1, a response length outside 1 .. 65536 (4.096 s at 16 kHz).
+ * NOMAD_ERR_WORKSPACE: ws_bytes too small.
+ */
+size_t nomad_degrade_convolve_scratch_bytes(int B, int G);
+int nomad_degrade_convolve(nomad_ctx* ctx, const float* x_dev, int B, int stride, const int* lens_host, const float* ir_dev, int G,
+                           int ir_stride, const int* ir_lens_host, float* out_dev, void* ws_dev, size_t ws_bytes,
+                           nomad_stream_t stream);
 
 /* ---- bf16 path (BASELINE config C5: long-form clips) ---------------------------------------- */
 /*

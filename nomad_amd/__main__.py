@@ -9,7 +9,7 @@ the files shard across the ranks (RCCL all-gather of the embeddings, ``Nomad.pre
 (``Nomad.predict_spans``, ``spans.csv``).
 
 ``--sweep`` (one process): ``--deg`` holds CLEAN files, which are degraded on the GPU at every level of ``--snr-db`` (with ``--noise
-FILE``) and / or ``--clip`` and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level."""
+FILE``), ``--clip`` and / or ``--rt60`` (synthetic rooms, ``nomad_amd.nomad.synthetic_rir``) and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level."""
 import argparse
 import os
 
@@ -38,7 +38,8 @@ def sweep(nomad, a):
     refs = nomad.get_embeddings(a.nmr).set_index("filename")
     refs = torch.from_numpy(refs.to_numpy(dtype="float32").copy())
     noise = nomad.load_processing(a.noise).reshape(-1) if a.noise is not None else None
-    results = nomad.intensity_sweep(a.deg, refs, noise=noise, snr_db=a.snr_db, clip_factor=a.clip, k=a.knn)
+    reverb = {"rt60_s": a.rt60} if a.rt60 is not None else {}
+    results = nomad.intensity_sweep(a.deg, refs, noise=noise, snr_db=a.snr_db, clip_factor=a.clip, k=a.knn, **reverb)
     parts = []
     for name, res in results.items():
         t = res["table"].sort_values(by="Condition")
@@ -80,16 +81,20 @@ def main(argv=None):
                     help="score what is not silent: one score per test file over the frames within DB dB of its loudest frame (an "
                          "energy gate, not a speech detector; predict_spans)")
     ap.add_argument("--sweep", action="store_true",
-                    help="--deg holds CLEAN files: degrade them on the GPU at every level of --snr-db / --clip, score the result against "
+                    help="--deg holds CLEAN files: degrade them on the GPU at every level of --snr-db / --clip / --rt60, score the result against "
                          "--nmr and report how well the score ranks the levels (nomad_intensity.csv, Nomad.intensity_sweep)")
     ap.add_argument("--noise", type=str, default=None, metavar="FILE", help="--sweep: the noise recording mixed in at --snr-db")
     ap.add_argument("--snr-db", dest="snr_db", type=_levels, default=None, metavar="A,B,...", help="--sweep: target SNRs in dB")
     ap.add_argument("--clip", type=_levels, default=None, metavar="A,B,...", help="--sweep: clip factors, percent of samples clipped")
+    ap.add_argument("--rt60", type=_levels, default=None, metavar="A,B,...",
+                    help="--sweep: reverberation times in seconds (synthetic diffuse rooms, not sox's reverb), each in (0, 4.096]")
     a = ap.parse_args(argv)
     if a.hop is not None and a.window is None:
         ap.error("--hop goes with --window")
     if not a.sweep and (a.noise is not None or a.snr_db is not None or a.clip is not None):
         ap.error("--noise, --snr-db and --clip go with --sweep")
+    if not a.sweep and a.rt60 is not None:
+        ap.error("--rt60 goes with --sweep")
     if a.spans is not None and a.active_db is not None:
         ap.error("--spans and --active-db exclude each other: the rows come from the csv or from the energy gate")
     if a.spans is not None or a.active_db is not None:
@@ -103,15 +108,17 @@ def main(argv=None):
     if a.sweep:
         if a.window is not None:
             ap.error("--sweep scores whole clips: it does not go with --window")
-        if a.snr_db is None and a.clip is None:
-            ap.error("--sweep needs levels: --snr-db (with --noise), --clip or both")
+        if a.snr_db is None and a.clip is None and a.rt60 is None:
+            ap.error("--sweep needs levels: --snr-db (with --noise), --clip or both, or --rt60")
         if (a.snr_db is None) != (a.noise is None):
             ap.error("--noise and --snr-db go together")
-        for name, levels in (("--snr-db", a.snr_db), ("--clip", a.clip)):
+        for name, levels in (("--snr-db", a.snr_db), ("--clip", a.clip), ("--rt60", a.rt60)):
             if levels is not None and not 1 <= len(levels) <= 64:
                 ap.error(f"{name} takes 1 to 64 levels, got {len(levels)}")
         if a.clip is not None and not all(0.0 <= v <= 100.0 for v in a.clip):
             ap.error(f"--clip takes percentages from 0 to 100, got {a.clip}")
+        if a.rt60 is not None and not all(0.0 < v <= 4.096 for v in a.rt60):
+            ap.error(f"--rt60 takes seconds above 0 up to 4.096, got {a.rt60}")
     if a.knn is not None and not 1 <= a.knn <= 64:
         ap.error(f"--knn takes a number of references from 1 to 64, got {a.knn}")
     world = int(os.environ.get("WORLD_SIZE", "1"))

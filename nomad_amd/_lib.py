@@ -60,6 +60,9 @@ SIGNATURES = {
                                       _fp, _fp, _fp, C.c_size_t, _fp]),
     "nomad_degrade_clip": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, _fp, _fp, _fp,
                                      C.c_size_t, _fp]),
+    "nomad_degrade_convolve_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "nomad_degrade_convolve": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                         _fp, _fp, C.c_size_t, _fp]),
     "nomad_embed_features": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "nomad_embed_features_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp,
                                               C.c_size_t, _fp]),

@@ -189,7 +189,7 @@ struct nomad_ctx {
     // the same for the frame / chunk prefix sums of nomad_l1_loss_weighted[_backward] (a ring of its own: a loss step queues up to three)
     std::vector<int> l1w_meta_ring[16];
     unsigned l1w_seq = 0;
-    // the same for the levels and lengths of nomad_degrade_noise / nomad_degrade_clip (a sweep queues one of each per batch)
+    // the same for the levels and lengths of nomad_degrade_noise / _clip / _convolve (a sweep queues one of each per batch)
     std::vector<char> degrade_meta_ring[16];
     unsigned degrade_seq = 0;
     // profiling

@@ -26,6 +26,7 @@
 #include "attention_bwd.hip.h"
 #include "backward.hip.h"
 #include "degrade.hip.h"
+#include "degrade_convolve.hip.h"
 #include "frontend.hip.h"
 #include "gemm_bf16.hip.h"
 #include "gemm_bf16_8phase.hip.h"
@@ -3922,6 +3923,60 @@ int nomad_degrade_clip(nomad_ctx* c, const float* x, int B, int stride, const in
                        reinterpret_cast<unsigned*>(w + l.keys1), q_dev, G, thr, thresholds_out);
     hipLaunchKernelGGL(degrade_clip_write_kernel, dim3((stride + 255) / 256, B), dim3(256), 0, s, x, stride, lens_dev,
                        static_cast<const double*>(thr), G, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- convolution with impulse responses (degrade_convolve.hip.h) ----
+// Scratch: [clip lengths: B int32, to 256 bytes | response lengths: G int32, to 256 bytes].
+static size_t convolve_lens_bytes(int B) { return (sizeof(int) * (size_t)B + 255) / 256 * 256; }
+
+size_t nomad_degrade_convolve_scratch_bytes(int B, int G) {
+    if (B < 1 || B > 65535 || G < 1 || G > kRirMaxResponses) {
+        (void)fail(NOMAD_ERR_INVALID, "nomad_degrade_convolve_scratch_bytes: bad argument (B=%d: 1 .. 65535, G=%d: 1 .. %d)", B, G, kRirMaxResponses);
+        return 0;
+    }
+    return convolve_lens_bytes(B) + convolve_lens_bytes(G);
+}
+
+int nomad_degrade_convolve(nomad_ctx* c, const float* x, int B, int stride, const int* lens, const float* ir, int G, int ir_stride,
+                           const int* ir_lens, float* out, void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_degrade_convolve";
+    if (!c || !x || !lens || !ir || !ir_lens || !out || !ws)
+        return fail(NOMAD_ERR_INVALID, "%s: a NULL context, input, lengths, responses, response lengths, output or workspace", who);
+    if (G < 1 || G > kRirMaxResponses) return fail(NOMAD_ERR_INVALID, "%s: G=%d responses, 1 .. %d are supported", who, G, kRirMaxResponses);
+    if (B < 1 || B > 65535) return fail(NOMAD_ERR_INVALID, "%s: B=%d clips, 1 .. 65535 are supported", who, B);
+    if (stride < 4 || stride % 4) return fail(NOMAD_ERR_INVALID, "%s: stride=%d is not a positive multiple of 4", who, stride);
+    if (ir_stride < 4 || ir_stride % 4) return fail(NOMAD_ERR_INVALID, "%s: ir_stride=%d is not a positive multiple of 4", who, ir_stride);
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 1 || lens[b] > stride)
+            return fail(NOMAD_ERR_INVALID, "%s: clip %d has length %d, 1 .. stride=%d are supported", who, b, lens[b], stride);
+    for (int g = 0; g < G; ++g)
+        if (ir_lens[g] < 1 || ir_lens[g] > kRirMaxTaps || ir_lens[g] > ir_stride)
+            return fail(NOMAD_ERR_INVALID, "%s: response %d has %d taps, 1 .. min(%d, ir_stride=%d) are supported", who, g, ir_lens[g],
+                        kRirMaxTaps, ir_stride);
+    const long long tiles = ((long long)stride + kRirTile - 1) / kRirTile;
+    if (tiles * B * G > 0x7fffffffLL)
+        return fail(NOMAD_ERR_INVALID, "%s: B G ceil(stride / %d) = %lld workgroups, more than one launch holds", who, kRirTile, tiles * B * G);
+    const size_t need = convolve_lens_bytes(B) + convolve_lens_bytes(G);
+    if (ws_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    // the two length tables, staged in the context's ring and copied ahead of the kernel (as degrade_upload does)
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(need, 0);
+    memcpy(staged.data(), lens, sizeof(int) * (size_t)B);
+    memcpy(staged.data() + convolve_lens_bytes(B), ir_lens, sizeof(int) * (size_t)G);
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), need, hipMemcpyHostToDevice, s));
+    double flops = 0.0;   // 2 sum_i min(L, i + 1) per row
+    for (int b = 0; b < B; ++b)
+        for (int g = 0; g < G; ++g) {
+            const double m = ir_lens[g] < lens[b] ? ir_lens[g] : lens[b];
+            flops += 2.0 * (m * (m + 1) / 2 + ((double)lens[b] - m) * ir_lens[g]);
+        }
+    Scope sc(c, s, NOMAD_K_ROW, flops);
+    hipLaunchKernelGGL(degrade_convolve_kernel, dim3((unsigned)(tiles * B * G)), dim3(kRirThreads), 0, s, x, stride,
+                       reinterpret_cast<const int*>(w), ir, ir_stride, reinterpret_cast<const int*>(w + convolve_lens_bytes(B)), G, (int)tiles, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -599,6 +599,54 @@ class Engine:
                                                thr.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "nomad_degrade_clip")
         return out, [n for n in lens for _ in range(G)], thr
 
+    def pack_responses(self, irs, ir_lengths=None):
+        """Impulse responses -> (device (G, ir_stride) fp32 buffer, tap counts): a list of 1-D responses (tensors or arrays), or a
+        (G, L) tensor with optional ``ir_lengths``; packed on the host and uploaded once (taps behind a length are never read)."""
+        if torch.is_tensor(irs) and irs.dim() == 2:
+            lens = [int(n) for n in (ir_lengths.tolist() if torch.is_tensor(ir_lengths) else ir_lengths)] if ir_lengths is not None \
+                else [int(irs.shape[1])] * int(irs.shape[0])
+            if len(lens) != irs.shape[0] or any(n > irs.shape[1] for n in lens):
+                raise ValueError("ir_lengths must hold one entry per row of the (G,L) responses, none above L")
+            rows = [irs[g, :n] for g, n in enumerate(lens)]
+        else:
+            if ir_lengths is not None:
+                raise ValueError("ir_lengths go with a (G,L) tensor: a list of responses has its own")
+            rows = list(irs)
+        flat = [torch.as_tensor(h, dtype=torch.float32).reshape(-1).detach().cpu() for h in rows]
+        G = len(flat)
+        if not 1 <= G <= 64:
+            raise ValueError(f"degrade_convolve takes 1 .. 64 responses per call, got {G}")
+        lens = [int(h.numel()) for h in flat]
+        if min(lens) < 1 or max(lens) > 65536:
+            raise ValueError(f"a response has {min(lens) if min(lens) < 1 else max(lens)} taps, 1 .. 65536 are supported")
+        host = torch.zeros(G, (max(lens) + 3) // 4 * 4, dtype=torch.float32)
+        for g, h in enumerate(flat):
+            host[g, :lens[g]] = h
+        return host.to(self.device), lens
+
+    def degrade_convolve(self, waves, irs, lengths=None, ir_lengths=None):
+        """Every clip convolved with each of G impulse responses (reverberation as a causal FIR filter, cut to the clip's length):
+        waves as ``degrade_noise`` takes them, irs as ``pack_responses`` takes them (or its result, to reuse one upload) -> (out
+        (B G, stride) fp32 on the device, lengths repeated G times): row b G + g is clip b through response g, zero behind its
+        length, and ``(out, lengths)`` goes into ``embed_ragged(packed=...)`` without another copy.  fp32 products and sums on the
+        matrix cores in an order that depends on the clip's and the response's length only (``nomad_degrade_convolve``)."""
+        if lengths is not None:
+            buf, lens = self.pack_ragged(waves, lengths)
+            if buf.shape[1] % 4:     # a padded tensor whose row stride is no multiple of 4: through the packer after all
+                buf, lens = self._pack([buf[i, :n] for i, n in enumerate(lens)])
+        else:
+            buf, lens = self._pack(waves)
+        packed_ir = isinstance(irs, tuple) and len(irs) == 2 and torch.is_tensor(irs[0]) and irs[0].dim() == 2 and isinstance(irs[1], list)
+        ir, ir_lens = irs if packed_ir else self.pack_responses(irs, ir_lengths)
+        B, stride = buf.shape
+        G = len(ir_lens)
+        out = torch.empty(B * G, stride, dtype=torch.float32, device=self.device)
+        ws = self._workspace(int(self.lib.nomad_degrade_convolve_scratch_bytes(B, G)))
+        _lib.check(self.lib.nomad_degrade_convolve(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), ir.data_ptr(), G,
+                                                   ir.shape[1], (C.c_int * G)(*ir_lens), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   self._stream()), "nomad_degrade_convolve")
+        return out, [n for n in lens for _ in range(G)]
+
     def cdist(self, a: torch.Tensor, b: torch.Tensor, want_matrix: bool = True):
         """a (Na,D), b (Nb,D) fp32 on the GPU, D a multiple of 4 up to 4096 -> (dist (Na,Nb) float64 or None, mean (Na,)
         float64): ``pairwise`` for rows of any width (the same bits at D = 256)."""

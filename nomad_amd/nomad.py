@@ -1051,6 +1051,30 @@ def _staged_batches(paths, load, pack, max_batch_samples: int, decode_threads: i
         th.join(timeout=30)
 
 
+def synthetic_rir(rt60_s, seed: int = 0, drr_db: float = 0.0) -> np.ndarray:
+    """A synthetic diffuse room at 16 kHz for ``Nomad.convolve`` -> float32 (L,), L = min(ceil(rt60_s 16000), 65536): a direct path
+    ``h[0] = 1`` and, from tap 1 on, Gaussian noise (``np.random.RandomState(seed).standard_normal(L)``; its first value is not used)
+    under an envelope that has fallen by 60 dB at ``rt60_s``, ``10^(-3 k / (rt60_s 16000))``, scaled so that the tail's energy is
+    ``10^(-drr_db / 10)`` - ``drr_db`` is the direct-to-reverberant ratio.  rt60_s: finite, in (0, 4.096] seconds.  This is NOT
+    sox's reverb (Freeverb: comb and all-pass filters with its own parameters), which the reference's renderings use: it is a
+    stand-in with a stated RT60 for sweeps and augmentation; measured responses go into ``convolve`` as they are."""
+    rt60_s, drr_db = float(rt60_s), float(drr_db)
+    if not (math.isfinite(rt60_s) and 0.0 < rt60_s <= 4.096):
+        raise ValueError(f"rt60_s must be finite and in (0, 4.096] seconds, got {rt60_s}")
+    if not math.isfinite(drr_db):
+        raise ValueError(f"drr_db must be finite, got {drr_db}")
+    L = min(int(math.ceil(rt60_s * 16000)), 65536)
+    r = np.random.RandomState(seed).standard_normal(L)
+    tail = r * 10.0 ** (-3.0 * np.arange(L, dtype=np.float64) / (rt60_s * 16000))
+    tail[0] = 0.0
+    energy = float(np.sum(tail ** 2))
+    if energy > 0.0:          # a room of one tap (or a tail of zeros) has no tail to scale
+        tail *= math.sqrt(10.0 ** (-drr_db / 10.0) / energy)
+    h = tail
+    h[0] = 1.0
+    return h.astype(np.float32)
+
+
 class Nomad:
     def __init__(self, device=None, weights: Union[None, str, Dict[str, torch.Tensor]] = None, precision: str = "fp32",
                  feature_grad_mult: Union[None, float] = None, group=None):
@@ -1659,7 +1683,10 @@ class Nomad:
 
     # ---- degradations on the device ----------------------------------------------------------------------------------
     def _degrade_packed(self, buf, lens, kind: str, levels, noise):
-        """One degradation of a packed device batch -> (rows (B G, stride), lengths repeated G times, alpha or thresholds)."""
+        """One degradation of a packed device batch -> (rows (B G, stride), lengths repeated G times, alpha or thresholds or None);
+        kind "reverb": ``noise`` holds the responses."""
+        if kind == "reverb":
+            return self.engine.degrade_convolve(buf, noise, lengths=lens) + (None,)
         if kind == "noise":
             return self.engine.degrade_noise(buf, noise, levels, lengths=lens)
         return self.engine.degrade_clip(buf, levels, lengths=lens)
@@ -1673,7 +1700,8 @@ class Nomad:
         ``x + alpha s`` with ``alpha = (rms(x) / 10^(snr / 10)) / rms(s)`` - the reference's ``utils/degradations.py`` formula as it
         stands.  kind "clip": ``levels`` are clip factors in percent (0 .. 100): samples are clamped to the clip's own percentiles
         ``cf / 2`` and ``100 - cf / 2`` (numpy's linear rule, exact order statistics).  Neither is followed by the loudness
-        normalisation the reference's rendering scripts apply, and codecs and reverberation are not offered.  No gradient."""
+        normalisation the reference's rendering scripts apply, and codecs are not offered; reverberation is ``convolve``.  No
+        gradient."""
         if kind not in ("noise", "clip"):
             raise ValueError(f"kind must be 'noise' or 'clip', got {kind!r}")
         if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
@@ -1689,6 +1717,27 @@ class Nomad:
         lens = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)] if lengths is not None else [x.shape[1]] * x.shape[0]
         out, lens_rep, _ = self._degrade_packed(x, lens, kind, levels, noise)
         return out, lens_rep
+
+    def convolve(self, wav, irs, lengths=None, ir_lengths=None):
+        """Reverberant copies of clean clips, made on the GPU: every clip convolved with each of G impulse responses -> (clips
+        (B G, stride) fp32 on the GPU, lengths): row ``b G + g`` is clip ``b`` through response ``g``, causal and cut to the clip's
+        length (``lengths`` comes back repeated G times; every row is zero behind its length).  wav (B,1,N) or (B,N); lengths: the
+        clips' exact lengths (any length from 1 sample); irs: a list of 1 .. 64 1-D responses of 1 .. 65536 taps each, or a (G,L)
+        tensor with optional ``ir_lengths`` - measured rooms, or ``synthetic_rir``.  For a fixed setting a reverberator is this
+        filter; sox's parameters, the loudness normalisation of the reference's rendering scripts and codecs are not offered.  fp32
+        products and sums (``nomad_degrade_convolve``); a row does not depend on the batch it is made in.  No gradient."""
+        if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+            raise ValueError(f"wav must be (B,1,N) or (B,N), got {tuple(getattr(wav, 'shape', ()))}")
+        rows = [irs] if torch.is_tensor(irs) else list(irs)
+        if wav.requires_grad or any(torch.is_tensor(h) and h.requires_grad for h in rows):
+            raise ValueError("convolve produces no gradient (the degradations have no backward): pass tensors that do not require one")
+        G = int(irs.shape[0]) if torch.is_tensor(irs) and irs.dim() == 2 else len(rows)
+        if (torch.is_tensor(irs) and irs.dim() != 2) or not 1 <= G <= 64:
+            raise ValueError(f"irs must be a list of 1 .. 64 1-D responses or a (G,L) tensor, got {tuple(irs.shape) if torch.is_tensor(irs) else G}")
+        x = wav.detach().to(self.engine.device, torch.float32)
+        x = (x.squeeze(1) if x.dim() == 3 else x).contiguous()
+        lens = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)] if lengths is not None else [x.shape[1]] * x.shape[0]
+        return self.engine.degrade_convolve(x, irs, lengths=lens, ir_lengths=ir_lengths)
 
     def _clean_batches(self, clean, lengths, budget: int):
         """The clean clips of ``intensity_sweep`` as packed device batches of at most ``budget`` samples each (one clip at least):
@@ -1728,32 +1777,36 @@ class Nomad:
             lo = hi
 
     def intensity_sweep(self, clean, references, noise=None, snr_db=None, clip_factor=None, lengths=None, k=None,
-                        max_batch_samples: int = 256 * 64000):
+                        max_batch_samples: int = 256 * 64000, rt60_s=None, rir_seed: int = 0, drr_db: float = 0.0):
         """Does the score rank the strength of a degradation?  The reference's ``intensity`` experiment without rendered files: the
         clean clips are degraded on the GPU (``degrade``) at every level, embedded and scored against ``references`` ((Nr,256), as
-        ``score`` takes them); -> {"NOISE": {...}, "CLIP": {...}}, a degradation whose levels are None being left out.  Each entry is
+        ``score`` takes them); -> {"NOISE": {...}, "CLIP": {...}, "REVERB": {...}}, a degradation whose levels are None being left out.  Each entry is
         ``train.intensity_stats``'s result - ``table`` (``Condition`` = the level, ``Distance`` = the mean score of the clips at that
         level, sorted by Distance), ``SRCC`` = spearmanr(Distance, Condition), ``embeddings`` - plus ``scores``, the (N G,) float64
         scores in row order (clip b at level g in row b G + g; at fp32 the bits of ``score`` on ``degrade``'s rows).
 
         clean: a (B,1,N) / (B,N) tensor (with ``lengths``), a list of 1-D clips, a directory of wav files or a csv file with a
         ``filename`` column (the file pipeline of ``get_embeddings``).  snr_db needs ``noise``, a 1-D signal at 16 kHz.  k: the
-        nearest-reference score of ``score(k=...)``.  The clean audio is uploaded once per batch; batches are cut so that the
+        nearest-reference score of ``score(k=...)``.  rt60_s: reverberation times in seconds, each in (0, 4.096]: the clips are
+        convolved (``convolve``) with ``synthetic_rir(rt60, rir_seed, drr_db)`` - a synthetic diffuse room, NOT sox's reverb -
+        and ``Condition`` is the RT60; whether the score ranks it is not claimed.  The clean audio is uploaded once per batch; batches are cut so that the
         G-fold degraded rows stay within ``max_batch_samples`` samples."""
         from .train import intensity_stats
         check_references(references)
         k = check_k(k, references.shape[0]) if k is not None else None
-        if snr_db is None and clip_factor is None:
-            raise ValueError("intensity_sweep needs snr_db, clip_factor or both")
+        if snr_db is None and clip_factor is None and rt60_s is None:
+            raise ValueError("intensity_sweep needs snr_db, clip_factor or both, or rt60_s")
         if snr_db is not None and noise is None:
             raise ValueError("snr_db needs a noise signal: pass noise=")
         if references.requires_grad or (torch.is_tensor(noise) and noise.requires_grad):
             raise ValueError("intensity_sweep produces no gradient (the degradations have no backward): pass tensors that do not require one")
         sweeps = [(name, kind, [float(v) for v in np.asarray(levels, dtype=np.float64).reshape(-1)])
-                  for name, kind, levels in (("NOISE", "noise", snr_db), ("CLIP", "clip", clip_factor)) if levels is not None]
+                  for name, kind, levels in (("NOISE", "noise", snr_db), ("CLIP", "clip", clip_factor), ("REVERB", "reverb", rt60_s))
+                  if levels is not None]
         for name, _, levels in sweeps:
             if not 1 <= len(levels) <= 64:
                 raise ValueError(f"{name}: 1 .. 64 levels per sweep, got {len(levels)}")
+        rirs = [torch.from_numpy(synthetic_rir(v, rir_seed, drr_db)) for v in sweeps[-1][2]] if rt60_s is not None else None
         self._need_whole_encoder(self.engine)
         eng = self.engine
         refs = references.detach().to(eng.device, torch.float32).contiguous()
@@ -1763,7 +1816,9 @@ class Nomad:
         budget = max(1, int(max_batch_samples) // max(len(levels) for _, _, levels in sweeps))
         for names, buf, lens in self._clean_batches(clean, lengths, budget):
             for name, kind, levels in sweeps:
-                out, lens_rep, _ = self._degrade_packed(buf, lens, kind, levels, noise)
+                if kind == "reverb" and isinstance(rirs, list):
+                    rirs = eng.pack_responses(rirs)      # packed and uploaded once, with the first batch
+                out, lens_rep, _ = self._degrade_packed(buf, lens, kind, levels, rirs if kind == "reverb" else noise)
                 emb = eng.embed_ragged(None, precision=self._window_precision(sum(lens_rep)), packed=(out, lens_rep))
                 rows[name][0].extend(f"{n}|{name}_{g}" for n in names for g in range(len(levels)))
                 rows[name][1].extend(levels * len(names))
