@@ -3,9 +3,9 @@
 // Weights are frozen (the user's purpose is the gradient w.r.t. `estimate`), so only dX is propagated:
 // every dense contraction of the backward is the SAME fp32 MFMA GEMM kernel as the forward, fed with
 // transposed weight copies; this file holds what is not a GEMM:
-//   LayerNorm backward, GELU' multiplies (fused into GEMM epilogues or as row kernels), head / L1-loss
+//   LayerNorm backward, GELU' multiplies (fused into GEMM epilogues or as row kernels), L1-loss
 //   backward, GroupNorm + conv0 backward, and the one-time weight transposes.  The attention backward
-//   (MFMA, flash style, no atomics) is in attention_bwd.hip.h.
+//   (MFMA, flash style, no atomics) is in attention_bwd.hip.h, the head's in head.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -199,477 +199,6 @@ __global__ __launch_bounds__(192) void dgelu_to_groups_kernel(const float* __res
     const int col = threadIdx.x * 4, grp = col / 48, cc = col - grp * 48;
     float* dst = dug + grp * grp_stride + (frame0 + 64 + t) * 48 + cc;
     *reinterpret_cast<float4*>(dst) = r;
-}
-
-// ---- head backward ----------------------------------------------------------------------------------
-// e = normalize(W relu(mean_t x) + b).  Given de -> gx[b][t][:] = relu'(mean) * (W^T dz) / T for every t.
-// grid: B blocks of 1024 threads (round 6: 16 waves - with 4 the kernel took 55 us for the 32 clips of configs[3], all of it the latency
-// of streaming W twice through 128 waves).  The time sum keeps the forward's order (waves 0 .. 3 take frames w, w + 4, ..: for T <= 64 the
-// same bits as head_pool_kernel, so the ReLU mask is the forward's); z = W pooled + b as in head_kernel (a row's dot product is one
-// wave's, same order); W^T dz in four fixed slices of 64 rows, folded in slice order.
-__global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict__ x, int T, const float* __restrict__ w,
-                                                        const float* __restrict__ bias, const float* __restrict__ de,
-                                                        float* __restrict__ gx, float* __restrict__ pooled_out = nullptr,
-                                                        float* __restrict__ dz_out = nullptr,
-                                                        const int* __restrict__ tpref = nullptr) {
-    __shared__ float mask[768], z[256], dz[256], red[4], red2[4];
-    __shared__ __attribute__((aligned(16))) float pooled[768], psum[4][768];   // (both are read as float4)
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long row0 = (long long)b * T;
-    if (tpref) {      // ragged batch: this clip's own frame range
-        row0 = tpref[b];
-        T = tpref[b + 1] - tpref[b];
-    }
-    const float* xb = x + row0 * 768;
-    if (wave < 4) {   // time sum: wave w takes frames w, w+4, ... (16-byte loads), the four partial sums are combined in fixed order
-        float4 acc[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int t = wave; t < T; t += 4) {
-            const float4* r = reinterpret_cast<const float4*>(xb + (long long)t * 768);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const float4 v = r[lane + 64 * i];
-                acc[i].x += v.x; acc[i].y += v.y; acc[i].z += v.z; acc[i].w += v.w;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) reinterpret_cast<float4*>(psum[wave])[lane + 64 * i] = acc[i];
-    }
-    __syncthreads();
-    if (tid < 256) {
-        const float s0 = (psum[0][tid] + psum[1][tid]) + (psum[2][tid] + psum[3][tid]);
-        const float s1 = (psum[0][tid + 256] + psum[1][tid + 256]) + (psum[2][tid + 256] + psum[3][tid + 256]);
-        const float s2 = (psum[0][tid + 512] + psum[1][tid + 512]) + (psum[2][tid + 512] + psum[3][tid + 512]);
-        const float inv = 1.0f / (float)T;
-        const float m0 = s0 * inv, m1 = s1 * inv, m2 = s2 * inv;
-        pooled[tid] = relu_keep_nan(m0); pooled[tid + 256] = relu_keep_nan(m1); pooled[tid + 512] = relu_keep_nan(m2);
-        mask[tid] = m0 > 0.f ? inv : 0.f; mask[tid + 256] = m1 > 0.f ? inv : 0.f; mask[tid + 512] = m2 > 0.f ? inv : 0.f;
-    }
-    __syncthreads();
-    float p[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) p[i] = pooled[lane + 64 * i];
-#pragma unroll 1
-    for (int o0 = wave * 16; o0 < wave * 16 + 16; o0 += 4) {
-        float wv[4][12];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int i = 0; i < 12; ++i) wv[u][i] = w[(long long)(o0 + u) * 768 + lane + 64 * i];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float d = 0.f;
-#pragma unroll
-            for (int i = 0; i < 12; ++i) d = fmaf(wv[u][i], p[i], d);
-            d = wave_sum(d);
-            if (lane == 0) z[o0 + u] = d + bias[o0 + u];
-        }
-    }
-    __syncthreads();
-    float zv = 0.f, dev = 0.f;
-    if (tid < 256) {
-        zv = z[tid];
-        dev = de[(long long)b * 256 + tid];
-        const float ss = wave_sum(zv * zv);
-        if (lane == 0) red[wave] = ss;
-    }
-    __syncthreads();
-    const float nrm = fmaxf(sqrtf((red[0] + red[1]) + (red[2] + red[3])), 1e-12f);
-    const float ev = zv / nrm;
-    if (tid < 256) {
-        const float dot = wave_sum(ev * dev);
-        if (lane == 0) red2[wave] = dot;
-    }
-    __syncthreads();
-    if (tid < 256) {
-        const float edot = (red2[0] + red2[1]) + (red2[2] + red2[3]);
-        dz[tid] = (dev - ev * edot) / nrm;
-        if (dz_out) {  // what the head's own parameter gradients need (train.hip.h: head_param_grad_kernel)
-            dz_out[(long long)b * 256 + tid] = dz[tid];
-            pooled_out[(long long)b * 768 + tid] = pooled[tid];
-            pooled_out[(long long)b * 768 + tid + 256] = pooled[tid + 256];
-            pooled_out[(long long)b * 768 + tid + 512] = pooled[tid + 512];
-        }
-    }
-    __syncthreads();
-    // dp[c] = sum_o W[o][c] dz[o]: slice q = tid / 256 takes o = 64 q .. 64 q + 63 for the columns c = tid % 256 + 256 j (coalesced over c);
-    // psum is free again and carries the four slices' sums
-    {
-        const int q = tid >> 8, c0 = tid & 255;
-        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-#pragma unroll 8
-        for (int o = 64 * q; o < 64 * q + 64; ++o) {
-            const float* wr = w + (long long)o * 768;
-            const float dzo = dz[o];
-            d0 = fmaf(wr[c0], dzo, d0); d1 = fmaf(wr[c0 + 256], dzo, d1); d2 = fmaf(wr[c0 + 512], dzo, d2);
-        }
-        psum[q][c0] = d0; psum[q][c0 + 256] = d1; psum[q][c0 + 512] = d2;
-    }
-    __syncthreads();
-    if (tid < 768) {
-        const float d = (psum[0][tid] + psum[1][tid]) + (psum[2][tid] + psum[3][tid]);
-        pooled[tid] = d * mask[tid];     // (pooled is dead: it carries the per-column gradient to the broadcast below)
-    }
-    __syncthreads();
-    float4 gv[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gv[i] = reinterpret_cast<const float4*>(pooled)[lane + 64 * i];
-    float* gb = gx + row0 * 768;
-    for (int t = wave; t < T; t += 16) {
-        float4* r = reinterpret_cast<float4*>(gb + (long long)t * 768);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) r[lane + 64 * i] = gv[i];
-    }
-}
-
-// ---- windowed head backward (nomad_embed_windows_backward*) ------------------------------------------------------------
-// The backward of head_windows_kernel in two launches, no atomics.  Stage 1, head_windows_bwd_kernel: window k of clip b, row
-// wbase(b) + k of de [windows][256] -> the gradient of the window's time MEAN's columns spread over its n = min(win, T) frames,
-// gw[wbase(b) + k][c] = (mean_c > 0 ? 1 / n : 0) (W^T dz)[c]: what every frame of the window receives from it.
-// grid: (windows of the longest clip, B) blocks of 1024 threads, rows ordered as the forward orders them (its wbase included); a
-// block past its clip's last window returns.  The time sum is head_windows_kernel's own - chunks of kHeadChunk frames from the
-// window's first frame, waves 0..3 on frames w, w + 4, .., folded 0..3, then chunk order - so pooled and the ReLU mask have
-// the forward's bits; from there head_bwd_kernel, operation for operation.  Every row of gw is written whole.
-__global__ __launch_bounds__(1024) void head_windows_bwd_kernel(const float* __restrict__ x, int T, int win, int hop,
-                                                                const float* __restrict__ w, const float* __restrict__ bias,
-                                                                const float* __restrict__ de, float* __restrict__ gw,
-                                                                const int* __restrict__ tpref = nullptr) {
-    __shared__ float mask[768], z[256], dz[256], red[4], red2[4];
-    __shared__ int wcnt[16];
-    __shared__ __attribute__((aligned(16))) float pooled[768], psum[4][768];   // (both are read as float4)
-    const int b = blockIdx.y, k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long row0 = (long long)b * T;
-    if (tpref) {      // ragged batch: this clip's own frame range
-        row0 = tpref[b];
-        T = tpref[b + 1] - tpref[b];
-    }
-    if (k >= head_num_windows(T, win, hop)) return;   // the same for every thread of the block
-    long long orow = (long long)b * head_num_windows(T, win, hop) + k;
-    if (tpref) {   // windows of clips 0 .. b - 1, as head_windows_kernel counts them
-        int cnt = 0;
-        for (int c = tid; c < b; c += 1024) cnt += head_num_windows(tpref[c + 1] - tpref[c], win, hop);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-        if (lane == 0) wcnt[wave] = cnt;
-        __syncthreads();
-        int base = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) base += wcnt[i];
-        orow = (long long)base + k;
-    }
-    const int n = min(win, T);
-    const float* xw = x + (row0 + (long long)k * hop) * 768;   // rows [k hop, k hop + n) of the clip: k hop + n <= T
-    float4 run[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) run[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t0 = 0; t0 < n; t0 += kHeadChunk) {   // chunks in order; psum[wave] carries lane l's columns 4l + 256q at float4 l + 64q
-        if (wave < 4) {
-            const int t_end = min(n, t0 + kHeadChunk);
-            float4 acc[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int t = t0 + wave; t < t_end; t += 4) {
-                const float4* r = reinterpret_cast<const float4*>(xw + (long long)t * 768);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float4 v = r[lane + 64 * q];
-                    acc[q].x += v.x; acc[q].y += v.y; acc[q].z += v.z; acc[q].w += v.w;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(psum[wave])[lane + 64 * q] = acc[q];
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                float4 a = reinterpret_cast<const float4*>(psum[0])[lane + 64 * q];
-#pragma unroll
-                for (int u = 1; u < 4; ++u) {
-                    const float4 o = reinterpret_cast<const float4*>(psum[u])[lane + 64 * q];
-                    a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
-                }
-                run[q].x += a.x; run[q].y += a.y; run[q].z += a.z; run[q].w += a.w;
-            }
-        }
-        __syncthreads();   // psum is rewritten by the next chunk
-    }
-    if (wave == 0) {
-        const float inv = 1.0f / (float)n;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const float m[4] = {run[q].x * inv, run[q].y * inv, run[q].z * inv, run[q].w * inv};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                pooled[256 * q + 4 * lane + j] = relu_keep_nan(m[j]);
-                mask[256 * q + 4 * lane + j] = m[j] > 0.f ? inv : 0.f;
-            }
-        }
-    }
-    __syncthreads();
-    float p[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) p[i] = pooled[lane + 64 * i];
-#pragma unroll 1
-    for (int o0 = wave * 16; o0 < wave * 16 + 16; o0 += 4) {
-        float wv[4][12];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int i = 0; i < 12; ++i) wv[u][i] = w[(long long)(o0 + u) * 768 + lane + 64 * i];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float d = 0.f;
-#pragma unroll
-            for (int i = 0; i < 12; ++i) d = fmaf(wv[u][i], p[i], d);
-            d = wave_sum(d);
-            if (lane == 0) z[o0 + u] = d + bias[o0 + u];
-        }
-    }
-    __syncthreads();
-    float zv = 0.f, dev = 0.f;
-    if (tid < 256) {
-        zv = z[tid];
-        dev = de[orow * 256 + tid];
-        const float ss = wave_sum(zv * zv);
-        if (lane == 0) red[wave] = ss;
-    }
-    __syncthreads();
-    const float nrm = fmaxf(sqrtf((red[0] + red[1]) + (red[2] + red[3])), 1e-12f);
-    const float ev = zv / nrm;
-    if (tid < 256) {
-        const float dot = wave_sum(ev * dev);
-        if (lane == 0) red2[wave] = dot;
-    }
-    __syncthreads();
-    if (tid < 256) {
-        const float edot = (red2[0] + red2[1]) + (red2[2] + red2[3]);
-        dz[tid] = (dev - ev * edot) / nrm;
-    }
-    __syncthreads();
-    // dp[c] = sum_o W[o][c] dz[o] in four slices of 64 rows (slice q = tid / 256, columns tid % 256 + 256 j), as in head_bwd_kernel
-    {
-        const int q = tid >> 8, c0 = tid & 255;
-        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-#pragma unroll 8
-        for (int o = 64 * q; o < 64 * q + 64; ++o) {
-            const float* wr = w + (long long)o * 768;
-            const float dzo = dz[o];
-            d0 = fmaf(wr[c0], dzo, d0); d1 = fmaf(wr[c0 + 256], dzo, d1); d2 = fmaf(wr[c0 + 512], dzo, d2);
-        }
-        psum[q][c0] = d0; psum[q][c0 + 256] = d1; psum[q][c0 + 512] = d2;
-    }
-    __syncthreads();
-    if (tid < 768) {
-        const float d = (psum[0][tid] + psum[1][tid]) + (psum[2][tid] + psum[3][tid]);
-        pooled[tid] = d * mask[tid];     // (pooled is dead: it carries the row to the 16-byte store below)
-    }
-    __syncthreads();
-    if (tid < 192) reinterpret_cast<float4*>(gw + orow * 768)[tid] = reinterpret_cast<const float4*>(pooled)[tid];
-}
-
-// Stage 2, head_windows_scatter_kernel: gx[frame t of clip b][:] = sum of gw[wbase(b) + k][:] over the windows k_lo .. k_hi
-// that cover t (head_window_cover), k ascending into one fp32 accumulator - the order depends on (T, win, hop, t) only.  A frame
-// no window covers (a gap with hop > win, the tail behind the last full window) gets exact zeros: EVERY row of gx is written,
-// nothing is assumed cleared.  grid: (ceil(frames of the longest clip / 4), B) blocks of 256 threads, one wave per frame,
-// lane l the float4s l, l + 64, l + 128 of the row.
-__global__ __launch_bounds__(256) void head_windows_scatter_kernel(const float* __restrict__ gw, int T, int win, int hop,
-                                                                   float* __restrict__ gx, const int* __restrict__ tpref = nullptr) {
-    __shared__ int wcnt[4];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long row0 = (long long)b * T;
-    if (tpref) {
-        row0 = tpref[b];
-        T = tpref[b + 1] - tpref[b];
-    }
-    if ((int)blockIdx.x * 4 >= T) return;   // the same for every thread of the block
-    long long wbase = (long long)b * head_num_windows(T, win, hop);
-    if (tpref) {   // windows of clips 0 .. b - 1
-        int cnt = 0;
-        for (int c = tid; c < b; c += 256) cnt += head_num_windows(tpref[c + 1] - tpref[c], win, hop);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-        if (lane == 0) wcnt[wave] = cnt;
-        __syncthreads();
-        wbase = (long long)wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-    }
-    const int t = blockIdx.x * 4 + wave;
-    if (t >= T) return;
-    int k_lo, k_hi;
-    head_window_cover(T, win, hop, t, &k_lo, &k_hi);
-    float4 acc[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = k_lo; k <= k_hi; ++k) {
-        const float4* r = reinterpret_cast<const float4*>(gw + (wbase + k) * 768);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float4 v = r[lane + 64 * i];
-            acc[i].x += v.x; acc[i].y += v.y; acc[i].z += v.z; acc[i].w += v.w;
-        }
-    }
-    float4* o = reinterpret_cast<float4*>(gx + (row0 + t) * 768);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[lane + 64 * i] = acc[i];
-}
-
-// ---- span head backward (nomad_embed_spans_backward_ragged) -----------------------------------------------------------------------
-// The backward of head_spans_kernel, the two launches of the windowed one with the span table (rowops.hip.h) in place of (win, hop).
-// Stage 1, head_spans_bwd_kernel: row r of de [R][256] -> gw[r][c] = (mean_c > 0 ? 1 / n : 0) (W^T dz)[c], what every one of the
-// row's n frames receives from it.  The time sum is head_spans_kernel's own (virtual frames in chunks of kHeadChunk, waves 0..3,
-// folded 0..3, chunk order), so pooled and the ReLU mask have the forward's bits; from there head_windows_bwd_kernel, operation
-// for operation.  grid: R blocks of 1024 threads.  Every row of gw is written whole.
-__global__ __launch_bounds__(1024) void head_spans_bwd_kernel(const float* __restrict__ x, const int* __restrict__ tab, int R, int S,
-                                                              const float* __restrict__ w, const float* __restrict__ bias,
-                                                              const float* __restrict__ de, float* __restrict__ gw,
-                                                              const int* __restrict__ tpref) {
-    __shared__ float mask[768], z[256], dz[256], red[4], red2[4];
-    __shared__ __attribute__((aligned(16))) float pooled[768], psum[4][768];   // (both are read as float4)
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const SpanTable tb = span_table(tab, R, S);
-    const long long row0 = tpref[tb.row_clip[r]];
-    const int n = span_row_frames(tb, r);   // the same for every thread of the block
-    const float* xc = x + row0 * 768;
-    SpanCursor cur(tb.spans + 2 * tb.row_ptr[r]);
-    float4 run[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) run[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int v0 = 0; v0 < n; v0 += kHeadChunk) {   // chunks in order; psum[wave] carries lane l's columns 4l + 256q at float4 l + 64q
-        if (wave < 4) {
-            const int v_end = min(n, v0 + kHeadChunk);
-            float4 acc[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int v = v0 + wave; v < v_end; v += 4) {
-                const float4* rp = reinterpret_cast<const float4*>(xc + (long long)cur.frame(v) * 768);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float4 val = rp[lane + 64 * q];
-                    acc[q].x += val.x; acc[q].y += val.y; acc[q].z += val.z; acc[q].w += val.w;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(psum[wave])[lane + 64 * q] = acc[q];
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                float4 a = reinterpret_cast<const float4*>(psum[0])[lane + 64 * q];
-#pragma unroll
-                for (int u = 1; u < 4; ++u) {
-                    const float4 o = reinterpret_cast<const float4*>(psum[u])[lane + 64 * q];
-                    a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
-                }
-                run[q].x += a.x; run[q].y += a.y; run[q].z += a.z; run[q].w += a.w;
-            }
-        }
-        __syncthreads();   // psum is rewritten by the next chunk
-    }
-    if (wave == 0) {
-        const float inv = 1.0f / (float)n;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const float m[4] = {run[q].x * inv, run[q].y * inv, run[q].z * inv, run[q].w * inv};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                pooled[256 * q + 4 * lane + j] = relu_keep_nan(m[j]);
-                mask[256 * q + 4 * lane + j] = m[j] > 0.f ? inv : 0.f;
-            }
-        }
-    }
-    __syncthreads();
-    float p[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) p[i] = pooled[lane + 64 * i];
-#pragma unroll 1
-    for (int o0 = wave * 16; o0 < wave * 16 + 16; o0 += 4) {
-        float wv[4][12];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int i = 0; i < 12; ++i) wv[u][i] = w[(long long)(o0 + u) * 768 + lane + 64 * i];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float d = 0.f;
-#pragma unroll
-            for (int i = 0; i < 12; ++i) d = fmaf(wv[u][i], p[i], d);
-            d = wave_sum(d);
-            if (lane == 0) z[o0 + u] = d + bias[o0 + u];
-        }
-    }
-    __syncthreads();
-    float zv = 0.f, dev = 0.f;
-    if (tid < 256) {
-        zv = z[tid];
-        dev = de[(long long)r * 256 + tid];
-        const float ss = wave_sum(zv * zv);
-        if (lane == 0) red[wave] = ss;
-    }
-    __syncthreads();
-    const float nrm = fmaxf(sqrtf((red[0] + red[1]) + (red[2] + red[3])), 1e-12f);
-    const float ev = zv / nrm;
-    if (tid < 256) {
-        const float dot = wave_sum(ev * dev);
-        if (lane == 0) red2[wave] = dot;
-    }
-    __syncthreads();
-    if (tid < 256) {
-        const float edot = (red2[0] + red2[1]) + (red2[2] + red2[3]);
-        dz[tid] = (dev - ev * edot) / nrm;
-    }
-    __syncthreads();
-    // dp[c] = sum_o W[o][c] dz[o] in four slices of 64 rows (slice q = tid / 256, columns tid % 256 + 256 j), as in head_bwd_kernel
-    {
-        const int q = tid >> 8, c0 = tid & 255;
-        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-#pragma unroll 8
-        for (int o = 64 * q; o < 64 * q + 64; ++o) {
-            const float* wr = w + (long long)o * 768;
-            const float dzo = dz[o];
-            d0 = fmaf(wr[c0], dzo, d0); d1 = fmaf(wr[c0 + 256], dzo, d1); d2 = fmaf(wr[c0 + 512], dzo, d2);
-        }
-        psum[q][c0] = d0; psum[q][c0 + 256] = d1; psum[q][c0 + 512] = d2;
-    }
-    __syncthreads();
-    if (tid < 768) {
-        const float d = (psum[0][tid] + psum[1][tid]) + (psum[2][tid] + psum[3][tid]);
-        pooled[tid] = d * mask[tid];     // (pooled is dead: it carries the row to the 16-byte store below)
-    }
-    __syncthreads();
-    if (tid < 192) reinterpret_cast<float4*>(gw + (long long)r * 768)[tid] = reinterpret_cast<const float4*>(pooled)[tid];
-}
-
-// Stage 2, head_spans_scatter_kernel: gx[frame t of clip b][:] = sum of gw[r][:] over the rows r of clip b that contain t, r
-// ascending (clip_row[b] .. clip_row[b + 1] - 1) into one fp32 accumulator.  A row contains t when one of its spans does: the
-// row's spans are scanned per frame, every lane of a wave on the same frame.  A frame no row contains, and every frame of a clip
-// without a row, gets exact zeros: EVERY row of gx is written, nothing is assumed cleared.
-// grid: (ceil(frames of the longest clip / 4), B) blocks of 256 threads, one wave per frame, lane l the float4s l, l + 64, l + 128.
-__global__ __launch_bounds__(256) void head_spans_scatter_kernel(const float* __restrict__ gw, const int* __restrict__ tab, int R, int S,
-                                                                 float* __restrict__ gx, const int* __restrict__ tpref) {
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long row0 = tpref[b];
-    const int T = tpref[b + 1] - tpref[b], t = blockIdx.x * 4 + wave;
-    if (t >= T) return;
-    const SpanTable tb = span_table(tab, R, S);
-    float4 acc[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = tb.clip_row[b]; r < tb.clip_row[b + 1]; ++r) {
-        bool in = false;
-        for (int i = tb.row_ptr[r]; i < tb.row_ptr[r + 1] && tb.spans[2 * i] <= t; ++i) in = in || t < tb.spans[2 * i + 1];
-        if (!in) continue;
-        const float4* rp = reinterpret_cast<const float4*>(gw + (long long)r * 768);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float4 v = rp[lane + 64 * i];
-            acc[i].x += v.x; acc[i].y += v.y; acc[i].z += v.z; acc[i].w += v.w;
-        }
-    }
-    float4* o = reinterpret_cast<float4*>(gx + (row0 + t) * 768);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[lane + 64 * i] = acc[i];
 }
 
 // ---- L1 loss backward: d/da sum_i mean|a_i - b_i| = sign(a - b) / numel_i, times the upstream scalar ------

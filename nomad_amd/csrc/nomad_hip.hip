@@ -33,6 +33,7 @@
 #include "gemm_bf16_p9.hip.h"
 #include "gemm_bf16x3.hip.h"
 #include "gemm_f32.hip.h"
+#include "head.hip.h"
 #ifdef NOMAD_DIAG  // libnomad_diag.so only: experiments kept for A/B measurements (tools/, tests of the experimental tiles)
 #endif
 #include "pairwise.hip.h"
@@ -396,7 +397,7 @@ int ragged_upload(nomad_ctx* c, const RaggedShapes& rs, int stride, int* meta, h
 // by span_upload right behind the ragged metadata's - after every check of the call, ahead of its kernels - from a ring slot of its
 // own: a span call takes two slots, so a score_spans step with a gradient (one forward, one backward) takes the four of ragged_upload.
 struct SpanStage {
-    std::vector<int> host;  // laid out as the device block: rowops.hip.h, span_table
+    std::vector<int> host;  // laid out as the device block: head.hip.h, span_table
     int* dev = nullptr;     // the head of the caller's scratch
     int R = 0, S = 0;
     float* gw = nullptr;    // [R][768] behind the table: the backward's per-row gradients
@@ -888,27 +889,51 @@ int run_layernorm(nomad_ctx* c, const float* in, const float* g, const float* b,
     return 0;
 }
 
-// mean/ReLU/Linear/normalise head in two stages (rowops.hip.h).  T: frames per clip (the longest clip's with tpref);
-// pool: scratch of at least (M / 64 + B) * 768 floats (M = total frames) - every caller passes its FFN hidden buffer.
-// features (nomad_embed_features*): `emb` is [B][768] and takes the time means themselves (head_mean_kernel) - no embedding.
-// windows (nomad_embed_windows*): `emb` is [windows of the batch][256], one row per window of mode.win frames every mode.hop
-// (head_windows_kernel, one launch, no scratch); mode.n_windows is their number.
-// spans (nomad_embed_spans*): `emb` is [R][256], one row per row of the caller's span table (head_spans_kernel, one launch; SpanStage).
+// Which rows of frames the head pools, forward and backward: whole clips (the default), windows of `win` frames every `hop`
+// (nomad_embed_windows*), or the rows of the caller's span table (nomad_embed_spans*, SpanStage; ragged batches only).
+// gw (backward only): [rows][768], the per-row gradients between the backward's two launches, in the caller's scratch.
+struct HeadRows {
+    int win = 0, hop = 0;
+    const SpanStage* spans = nullptr;
+    float* gw = nullptr;
+    bool whole_clips() const { return !win && !spans; }
+    static HeadRows over_spans(const SpanStage* st) { return {0, 0, st, st->gw}; }
+};
+
+// One launch over the rows, for run_head and backward_run: launch(rows, grid) with the device's WindowRows or SpanRows (head.hip.h).
+// T: frames per clip of an equal-length batch; max_t: frames of the longest clip.
+template <class Launch>
+int head_rows_launch(const char* who, const HeadRows& h, int B, int T, int max_t, const int* tpref, Launch&& launch) {
+    if (h.spans) {
+        if (!tpref) return fail(NOMAD_ERR_INVALID, "%s: the span head needs a ragged batch", who);
+        launch(SpanRows{h.spans->dev, h.spans->R, h.spans->S, tpref}, dim3(h.spans->R));
+    } else {
+        launch(WindowRows{tpref ? 0 : T, h.win, h.hop, tpref}, dim3(head_num_windows(max_t, h.win, h.hop), B));
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// mean/ReLU/Linear/normalise head (head.hip.h).  T: frames per clip (the longest clip's with tpref).
+// Whole clips, two stages; pool: scratch of at least (M / 64 + B) * 768 floats (M = total frames) - every caller passes its FFN
+// hidden buffer.  features (nomad_embed_features*): `emb` is [B][768] and takes the time means themselves (head_mean_kernel) - no
+// embedding.
+// rows (windows or spans): `emb` is [n_rows][256], one row per window / per row of the span table (head_rows_kernel, one launch, no
+// scratch).
 struct HeadMode {
     bool features = false;
-    int win = 0, hop = 0;
-    long long n_windows = 0;
-    const SpanStage* spans = nullptr;
+    HeadRows rows;
+    long long n_rows = 0;
     HeadMode() = default;
     HeadMode(bool f) : features(f) {}
     static HeadMode windows(int win, int hop, long long n) {
         HeadMode m;
-        m.win = win, m.hop = hop, m.n_windows = n;
+        m.rows.win = win, m.rows.hop = hop, m.n_rows = n;
         return m;
     }
     static HeadMode over_spans(const SpanStage* st) {
         HeadMode m;
-        m.spans = st;
+        m.rows = HeadRows::over_spans(st), m.n_rows = st->R;
         return m;
     }
 };
@@ -917,20 +942,11 @@ template <typename TIn>
 int run_head(nomad_ctx* c, const TIn* x, int B, int T, const float* w, const float* b, float* emb, const int* tpref,
              float* pool, hipStream_t s, HeadMode mode = {}) {
     const bool features = mode.features;
-    if (mode.spans) {
-        const SpanStage& st = *mode.spans;
-        if (!tpref) return fail(NOMAD_ERR_INVALID, "run_head: the span head needs a ragged batch");
-        Scope sc(c, s, NOMAD_K_ROW, 2.0 * (double)st.R * 768 * 256);
-        hipLaunchKernelGGL(head_spans_kernel<TIn>, dim3(st.R), dim3(1024), 0, s, x, st.dev, st.R, st.S, w, b, emb, tpref);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    if (mode.win) {
-        Scope sc(c, s, NOMAD_K_ROW, 2.0 * (double)mode.n_windows * 768 * 256);
-        hipLaunchKernelGGL(head_windows_kernel<TIn>, dim3(head_num_windows(T, mode.win, mode.hop), B), dim3(1024), 0, s, x, tpref ? 0 : T,
-                           mode.win, mode.hop, w, b, emb, tpref);
-        HIP_TRY(hipGetLastError());
-        return 0;
+    if (!mode.rows.whole_clips()) {
+        Scope sc(c, s, NOMAD_K_ROW, 2.0 * (double)mode.n_rows * 768 * 256);
+        return head_rows_launch("run_head", mode.rows, B, T, T, tpref, [&](auto rows, dim3 grid) {
+            hipLaunchKernelGGL((head_rows_kernel<TIn, decltype(rows)>), grid, dim3(1024), 0, s, x, rows, w, b, emb);
+        });
     }
     Scope sc(c, s, NOMAD_K_ROW, features ? 0.0 : 2.0 * B * 768 * 256);
     hipLaunchKernelGGL(head_pool_kernel<TIn>, dim3((T + kHeadChunk - 1) / kHeadChunk, B), dim3(256), 0, s, x, tpref ? 0 : T, pool, tpref);
@@ -1243,7 +1259,7 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
     const int B = g.B, T = g.T, M = (int)g.rows[6];
     // nomad_set_encoder_depth: layers 0 .. depth - 1, then stop - no head, rows [depth, 12) of layers_out and emb stay unwritten
     const int depth = c->encoder_depth;
-    if (depth < NOMAD_NUM_LAYERS && (!layers_out || mode.features || mode.win)) return refuse_cut(c, "fp32 forward");
+    if (depth < NOMAD_NUM_LAYERS && (!layers_out || mode.features || mode.rows.win)) return refuse_cut(c, "fp32 forward");
     // the loss forward of Nomad.forward() (saving activations, not fine-tuning): small-M GEMMs may split K.  Round 4: so may the
     // other branch of that loss - a forward that returns the 12 layer outputs (LossNetLayers: `clean`, or `estimate` under
     // no_grad) on fewer than 4096 frames.  The split is a function of the GEMM shape only (fixed slices, ordered fold): the
@@ -1485,8 +1501,8 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
         if (c->branches > 1 && B % c->branches) return fail(NOMAD_ERR_INVALID, "%s: B=%d is not %d equal branches", who, B, c->branches);
     }
     if (int rc = ragged_upload(c, r.rs, stride, reinterpret_cast<int*>(static_cast<char*>(workspace) + r.lay.meta), s, &r.g)) return rc;
-    if (mode.spans)
-        if (int rc = span_upload(c, *mode.spans, s)) return rc;
+    if (mode.rows.spans)
+        if (int rc = span_upload(c, *mode.rows.spans, s)) return rc;
     char* ws = static_cast<char*>(workspace);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const ActLayout& lay = r.lay;
@@ -1765,8 +1781,8 @@ static int forward_ragged_bf16(nomad_ctx* c, const float* wav, int B, int stride
     if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, sizeof(bf16_t), 0,
                                  &r, workspace, workspace_bytes, s))
         return rc;
-    if (mode.spans)
-        if (int rc = span_upload(c, *mode.spans, s)) return rc;
+    if (mode.rows.spans)
+        if (int rc = span_upload(c, *mode.rows.spans, s)) return rc;
     return forward_bf16_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, mode);
 }
 
@@ -1976,8 +1992,8 @@ static int forward_ragged_x3(nomad_ctx* c, const float* wav, int B, int stride, 
     if (int rc = ragged_prologue(who, c, c && wav && emb && workspace, B, stride, lens_host, 4, kXpadSlack,
                                  &r, workspace, workspace_bytes, s))
         return rc;
-    if (mode.spans)
-        if (int rc = span_upload(c, *mode.spans, s)) return rc;
+    if (mode.rows.spans)
+        if (int rc = span_upload(c, *mode.rows.spans, s)) return rc;
     return forward_x3_run(c, wav, r.g, r.lay, emb, static_cast<char*>(workspace), s, nullptr, nullptr, nullptr, mode);
 }
 
@@ -2642,18 +2658,12 @@ static int dw_gemm(nomad_ctx* c, const float* TA, const float* TB, int Nout, int
 // both, the way forward_run does.  Ragged: per-frame tensors are packed, the padded dU buffers of the conv stack hold clip c's
 // L_i(c) + 2 rows at row upref_i[c], the kernels that care about clip boundaries read the prefix sums; small-M GEMMs never split
 // K (a clip's gradient does not depend on its batch).  The conv feature extractor's parameter gradients need an equal-length batch.
-// wb (nomad_embed_windows_backward*): demb holds one row per WINDOW of the windowed head and the head stage is its backward - the
-// two launches of backward.hip.h through the caller's gw block - instead of head_bwd_kernel; everything below gx is unchanged.
-// wb->spans (nomad_embed_spans_backward_ragged): demb holds one row per ROW of the span table and the two launches are the span
-// head's (head_spans_bwd_kernel, head_spans_scatter_kernel) through the table and the gw block in the caller's scratch.
-struct HeadWindowsBwd {
-    int win, hop;
-    float* gw;   // [windows of the batch][768]
-    const SpanStage* spans = nullptr;
-};
+// wb (nomad_embed_windows_backward*, nomad_embed_spans_backward_ragged): demb holds one row per WINDOW, or per ROW of the span
+// table, and the head stage is the rows head's backward - head_rows_bwd_kernel and the windows' or the spans' scatter (head.hip.h)
+// through the gw block in the caller's scratch - instead of head_bwd_kernel; everything below gx is unchanged.
 static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const Saved& sv, const BwdLayout& lay, const float* head_w,
                         const float* head_b, const float* layers_out, const float* dlayers, const float* demb, float* dwav,
-                        char* ws, hipStream_t s, bool train, const HeadWindowsBwd* wb = nullptr) {
+                        char* ws, hipStream_t s, bool train, const HeadRows* wb = nullptr) {
     const bool conv_pg = train && c->train_convnet;  // parameter gradients of the conv feature extractor too
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const int B = g.B, T = g.T, M = (int)g.rows[6], n_samples = g.wav_ld;
@@ -2708,20 +2718,18 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
     const int depth = train ? NOMAD_NUM_LAYERS : c->encoder_depth;
     bool first_cut = depth < NOMAD_NUM_LAYERS;
     // ---- head -> d loss / d x_12 -------------------------------------------------------------------
-    if (!first_cut && wb && wb->spans) {
-        const SpanStage& st = *wb->spans;
-        if (!rg) return fail(NOMAD_ERR_INVALID, "backward_run: the span head needs a ragged batch");
-        Scope sc(c, s, NOMAD_K_ROW, 0.0);
-        hipLaunchKernelGGL(head_spans_bwd_kernel, dim3(st.R), dim3(1024), 0, s, layers_out + (size_t)11 * M * 768, st.dev, st.R, st.S,
-                           head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, demb, st.gw, tpref);
-        hipLaunchKernelGGL(head_spans_scatter_kernel, dim3((g.max_t + 3) / 4, B), dim3(256), 0, s, st.gw, st.dev, st.R, st.S, gx, tpref);
-    } else if (!first_cut && wb) {
+    if (!first_cut && wb) {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
         const float* x12 = layers_out + (size_t)11 * M * 768;
-        hipLaunchKernelGGL(head_windows_bwd_kernel, dim3(head_num_windows(g.max_t, wb->win, wb->hop), B), dim3(1024), 0, s, x12, rg ? 0 : T,
-                           wb->win, wb->hop, head_w ? head_w : c->emb_w, head_b ? head_b : c->emb_b, demb, wb->gw, tpref);
-        hipLaunchKernelGGL(head_windows_scatter_kernel, dim3((g.max_t + 3) / 4, B), dim3(256), 0, s, wb->gw, rg ? 0 : T, wb->win, wb->hop,
-                           gx, tpref);
+        const dim3 per_frame((g.max_t + 3) / 4, B);
+        auto stage1 = [&](auto rows, dim3 grid) {
+            hipLaunchKernelGGL(head_rows_bwd_kernel<decltype(rows)>, grid, dim3(1024), 0, s, x12, rows, head_w ? head_w : c->emb_w,
+                               head_b ? head_b : c->emb_b, demb, wb->gw);
+            if constexpr (std::is_same_v<decltype(rows), SpanRows>)
+                hipLaunchKernelGGL(head_spans_scatter_kernel, per_frame, dim3(256), 0, s, wb->gw, rows, gx);
+            else hipLaunchKernelGGL(head_windows_scatter_kernel, per_frame, dim3(256), 0, s, wb->gw, rows, gx);
+        };
+        if ((rc = head_rows_launch("backward_run", *wb, B, T, g.max_t, tpref, stage1))) return rc;
     } else if (!first_cut) {
         Scope sc(c, s, NOMAD_K_ROW, 0.0);
         hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(1024), 0, s, layers_out + (size_t)11 * M * 768, T,
@@ -3073,7 +3081,7 @@ static int backward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, cons
 static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, const float* head_w, const float* head_b,
                          const float* layers_out, const void* saved, size_t saved_bytes, const float* dlayers,
                          const float* demb, float* dwav, void* workspace, size_t workspace_bytes,
-                         nomad_stream_t stream, bool train, const char* who = "nomad_embed_backward", const HeadWindowsBwd* wb = nullptr) {
+                         nomad_stream_t stream, bool train, const char* who = "nomad_embed_backward", const HeadRows* wb = nullptr) {
     Shapes sh;
     const bool cut = c && c->encoder_depth < NOMAD_NUM_LAYERS;   // a cut encoder has no embedding: demb is ignored, dlayers carries everything
     if (!c || !wav || !layers_out || !saved || (cut ? !dlayers : !demb) || (!dwav && !train) || !workspace || B <= 0 ||
@@ -3097,7 +3105,7 @@ static int backward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, c
 static int backward_ragged(const char* who, nomad_ctx* c, const float* wav, int B, int stride, const int* lens_host, const float* head_w,
                            const float* head_b, const float* layers_out, const void* saved, size_t saved_bytes, const float* dlayers,
                            const float* demb, float* dwav, void* workspace, size_t workspace_bytes, nomad_stream_t stream,
-                           bool train, const HeadWindowsBwd* wb = nullptr) {
+                           bool train, const HeadRows* wb = nullptr) {
     RaggedShapes rs;
     const bool cut = c && c->encoder_depth < NOMAD_NUM_LAYERS;   // (a cut encoder: demb is ignored, dlayers is required)
     if (int rc = ragged_shapes(who, c && wav && layers_out && saved && (cut ? dlayers != nullptr : demb != nullptr) && (dwav || train) && workspace,
@@ -3276,7 +3284,7 @@ int nomad_embed_windows_backward(nomad_ctx* c, const float* wav, int B, int n_sa
     if (!c || !demb || !dwav || !scratch || B <= 0 || !make_shapes(B, n_samples, &sh)) return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
     const size_t need = align_up(sizeof(float) * 768 * (size_t)B * head_num_windows(sh.T, win, hop));
     if (scratch_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: scratch %zu < required %zu", who, scratch_bytes, need);
-    const HeadWindowsBwd wb{win, hop, static_cast<float*>(scratch)};
+    const HeadRows wb{win, hop, nullptr, static_cast<float*>(scratch)};
     return backward_impl(c, wav, B, n_samples, head_w, head_b, layers_out, saved, saved_bytes, nullptr, demb, dwav, workspace,
                          workspace_bytes, stream, false, who, &wb);
 }
@@ -3297,7 +3305,7 @@ int nomad_embed_windows_backward_ragged(nomad_ctx* c, const float* wav, int B, i
     }
     const size_t need = align_up(sizeof(float) * 768 * (size_t)n);
     if (frames_ok && scratch_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: scratch %zu < required %zu", who, scratch_bytes, need);
-    const HeadWindowsBwd wb{win, hop, static_cast<float*>(scratch)};
+    const HeadRows wb{win, hop, nullptr, static_cast<float*>(scratch)};
     return backward_ragged(who, c, wav, B, stride, lengths_host, head_w, head_b, layers_out, saved, saved_bytes, nullptr, demb, dwav,
                            workspace, workspace_bytes, stream, false, &wb);
 }
@@ -3395,7 +3403,7 @@ int nomad_embed_spans_backward_ragged(nomad_ctx* c, const float* wav, int B, int
     if (!c || !demb || !dwav) return fail(NOMAD_ERR_INVALID, "%s: bad argument", who);
     SpanStage st;
     if (int rc = spans_stage(who, B, lengths_host, R, row_clip, row_ptr, spans, scratch, scratch_bytes, true, &st)) return rc;
-    const HeadWindowsBwd wb{0, 0, st.gw, &st};
+    const HeadRows wb = HeadRows::over_spans(&st);
     return backward_ragged(who, c, wav, B, stride, lengths_host, head_w, head_b, layers_out, saved, saved_bytes, nullptr, demb, dwav,
                            workspace, workspace_bytes, stream, false, &wb);
 }

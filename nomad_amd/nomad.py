@@ -605,138 +605,86 @@ def cdist(engine: Engine, a: torch.Tensor, b: torch.Tensor):
     return _CdistFn.apply(a, b, engine)
 
 
+class _ClipRows:
+    """What ``_ScoreFn`` scores: one row per clip (``Nomad.score``)."""
+
+    def embed(self, nomad, est, lens):
+        return nomad._score_embed(est, lens)
+
+    def embed_train(self, eng, est, lens):
+        if lens is None:
+            return (*eng.embed_train(est), est)
+        emb, layers, saved, (est, _) = eng.embed_train_ragged(est, lens)
+        return emb, layers, saved, est
+
+    def backward(self, eng, est, lens, layers, saved, demb):
+        if lens is None:
+            return eng.embed_backward(est, layers, saved, None, demb)
+        return eng.embed_backward_ragged((est, lens), layers, saved, None, demb)
+
+
+class _WindowRows:
+    """... one row per window of ``win`` frames every ``hop`` (``Nomad.score_windows``)."""
+
+    def __init__(self, win, hop):
+        self.win, self.hop = win, hop
+
+    def embed(self, nomad, est, lens):
+        if lens is None:
+            return nomad.engine.embed_windows(est, self.win, self.hop, precision=nomad._window_precision(est.numel()))[0]
+        return nomad.engine.embed_windows_ragged([est[i, :n] for i, n in enumerate(lens)], self.win, self.hop,
+                                                 precision=nomad._window_precision(sum(lens)))[0]
+
+    def embed_train(self, eng, est, lens):
+        if lens is None:
+            emb, _, layers, saved = eng.embed_train_windows(est, self.win, self.hop)
+        else:
+            emb, _, layers, saved, (est, _) = eng.embed_train_windows_ragged(est, self.win, self.hop, lens)
+        return emb, layers, saved, est
+
+    def backward(self, eng, est, lens, layers, saved, demb):
+        if lens is None:
+            return eng.embed_windows_backward(est, layers, saved, demb, self.win, self.hop)
+        return eng.embed_windows_backward_ragged((est, lens), layers, saved, demb, self.win, self.hop)
+
+
+class _TableRows:
+    """... one row per row of a span table (``Nomad.score_spans``: always with ``lens``)."""
+
+    def __init__(self, table):
+        self.table = table
+
+    def embed(self, nomad, est, lens):
+        return nomad.engine.embed_spans_ragged([est[i, :n] for i, n in enumerate(lens)], self.table,
+                                               precision=nomad._window_precision(sum(lens)))
+
+    def embed_train(self, eng, est, lens):
+        emb, layers, saved, (est, _) = eng.embed_train_spans_ragged(est, self.table, lens)
+        return emb, layers, saved, est
+
+    def backward(self, eng, est, lens, layers, saved, demb):
+        return eng.embed_spans_backward_ragged((est, lens), layers, saved, demb, self.table)
+
+
 class _ScoreFn(torch.autograd.Function):
-    """score[b] = mean_j ||emb(estimate_b) - references_j|| with the checkpoint's head; backward = d / d estimate through
-    ``cdist_backward`` and ``embed_backward[_ragged]`` (layer gradients NULL) and, when asked for, d / d references.  With ``k`` the
-    mean runs over the k nearest references (``Engine.knn``; the backward is ``Engine.knn_backward`` on the saved selection)."""
+    """score[r] = mean_j ||emb_r - references_j|| with the checkpoint's head, over the rows ``rows`` names: clips, windows or the rows
+    of a span table (above).  backward = d / d estimate through ``cdist_backward`` over the rows and the rows' own ``backward`` -
+    ``embed_backward[_ragged]`` with layer gradients NULL, ``embed_windows_backward[_ragged]`` or ``embed_spans_backward_ragged``: the
+    head's backward and the backbone down to the waveform - and, when asked for, d / d references.  With ``k`` the mean runs over the
+    k nearest references (``Engine.knn``; the backward is ``Engine.knn_backward`` on the saved selection)."""
 
     @staticmethod
-    def forward(ctx, estimate, references, nomad, lens, k):
+    def forward(ctx, estimate, references, nomad, lens, rows, k):
         eng = nomad.engine
         est = estimate.detach().to(eng.device, torch.float32).contiguous()
         est = est.squeeze(1) if est.dim() == 3 else est
         refs = references.detach().to(eng.device, torch.float32).contiguous()
-        ctx.nomad, ctx.lens = nomad, lens
+        ctx.nomad, ctx.lens, ctx.rows = nomad, lens, rows
         ctx.meta = (estimate.shape, references.device, references.dtype)
         if not estimate.requires_grad:   # only the references are differentiated: the scoring forward will do
-            emb, layers, saved = nomad._score_embed(est, lens), None, None
-        elif lens is None:
-            emb, layers, saved = eng.embed_train(est)
+            emb, layers, saved = rows.embed(nomad, est, lens), None, None
         else:
-            emb, layers, saved, (est, _) = eng.embed_train_ragged(est, lens)
-        idx = None
-        if k is None:
-            _, mean = eng.pairwise(emb, refs, want_matrix=False)
-        else:
-            _, idx, mean = eng.knn(emb, refs, k)
-        ctx.save_for_backward(est, refs, emb, layers, saved, idx)
-        return mean
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        est, refs, emb, layers, saved, idx = ctx.saved_tensors
-        eng = ctx.nomad.engine
-        shape, ref_device, ref_dtype = ctx.meta
-        want_a = ctx.needs_input_grad[0] and saved is not None
-        want_b = ctx.needs_input_grad[1]
-        if not (want_a or want_b):
-            return None, None, None, None, None
-        g = grad_out.to(eng.device, torch.float64).contiguous()
-        if idx is None:
-            demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
-        else:
-            demb, dref = eng.knn_backward(emb, refs, idx, g_score=g, want_a=want_a, want_b=want_b)
-        dwav = None
-        if want_a:
-            Nomad._need_whole_encoder(eng)
-            if ctx.lens is None:
-                dwav = eng.embed_backward(est, layers, saved, None, demb)
-            else:
-                dwav = eng.embed_backward_ragged((est, ctx.lens), layers, saved, None, demb)
-            dwav = dwav.reshape(shape)
-        if dref is not None:
-            dref = dref.to(ref_device, ref_dtype)
-        return dwav, dref, None, None, None
-
-
-class _WindowScoreFn(torch.autograd.Function):
-    """scores[w] = mean_j ||emb_w(window w of estimate) - references_j|| over the windows of ``Engine.embed_train_windows*``;
-    backward = ``cdist_backward`` over the window rows, then ``embed_windows_backward[_ragged]`` (the windowed head's backward
-    and the backbone down to the waveform) and, when asked for, d / d references.  ``k``: as in ``_ScoreFn``."""
-
-    @staticmethod
-    def forward(ctx, estimate, references, nomad, lens, win, hop, k):
-        eng = nomad.engine
-        est = estimate.detach().to(eng.device, torch.float32).contiguous()
-        est = est.squeeze(1) if est.dim() == 3 else est
-        refs = references.detach().to(eng.device, torch.float32).contiguous()
-        ctx.nomad, ctx.lens, ctx.geom = nomad, lens, (win, hop)
-        ctx.meta = (estimate.shape, references.device, references.dtype)
-        if not estimate.requires_grad:   # only the references are differentiated: the scoring forward will do
-            if lens is not None:
-                emb, _ = eng.embed_windows_ragged([est[i, :n] for i, n in enumerate(lens)], win, hop,
-                                                  precision=nomad._window_precision(sum(lens)))
-            else:
-                emb, _ = eng.embed_windows(est, win, hop, precision=nomad._window_precision(est.numel()))
-            layers = saved = None
-        elif lens is None:
-            emb, _, layers, saved = eng.embed_train_windows(est, win, hop)
-        else:
-            emb, _, layers, saved, (est, _) = eng.embed_train_windows_ragged(est, win, hop, lens)
-        idx = None
-        if k is None:
-            _, mean = eng.pairwise(emb, refs, want_matrix=False)
-        else:
-            _, idx, mean = eng.knn(emb, refs, k)
-        ctx.save_for_backward(est, refs, emb, layers, saved, idx)
-        return mean
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        est, refs, emb, layers, saved, idx = ctx.saved_tensors
-        eng = ctx.nomad.engine
-        shape, ref_device, ref_dtype = ctx.meta
-        win, hop = ctx.geom
-        want_a = ctx.needs_input_grad[0] and saved is not None
-        want_b = ctx.needs_input_grad[1]
-        if not (want_a or want_b):
-            return None, None, None, None, None, None, None
-        g = grad_out.to(eng.device, torch.float64).contiguous()
-        if idx is None:
-            demb, dref = eng.cdist_backward(emb, refs, g_mean=g, want_a=want_a, want_b=want_b)
-        else:
-            demb, dref = eng.knn_backward(emb, refs, idx, g_score=g, want_a=want_a, want_b=want_b)
-        dwav = None
-        if want_a:
-            Nomad._need_whole_encoder(eng)
-            if ctx.lens is None:
-                dwav = eng.embed_windows_backward(est, layers, saved, demb, win, hop)
-            else:
-                dwav = eng.embed_windows_backward_ragged((est, ctx.lens), layers, saved, demb, win, hop)
-            dwav = dwav.reshape(shape)
-        if dref is not None:
-            dref = dref.to(ref_device, ref_dtype)
-        return dwav, dref, None, None, None, None, None
-
-
-class _SpanScoreFn(torch.autograd.Function):
-    """scores[r] = mean_j ||emb_r(row r of the span table) - references_j|| over the rows of ``Engine.embed_train_spans_ragged``;
-    backward = ``cdist_backward`` over the rows, then ``embed_spans_backward_ragged`` (the span head's backward and the backbone
-    down to the waveform) and, when asked for, d / d references.  ``k``: as in ``_ScoreFn``."""
-
-    @staticmethod
-    def forward(ctx, estimate, references, nomad, lens, table, k):
-        eng = nomad.engine
-        est = estimate.detach().to(eng.device, torch.float32).contiguous()
-        est = est.squeeze(1) if est.dim() == 3 else est
-        refs = references.detach().to(eng.device, torch.float32).contiguous()
-        ctx.nomad, ctx.lens, ctx.table = nomad, lens, table
-        ctx.meta = (estimate.shape, references.device, references.dtype)
-        if not estimate.requires_grad:   # only the references are differentiated: the scoring forward will do
-            emb = eng.embed_spans_ragged([est[i, :n] for i, n in enumerate(lens)], table, precision=nomad._window_precision(sum(lens)))
-            layers = saved = None
-        else:
-            emb, layers, saved, (est, _) = eng.embed_train_spans_ragged(est, table, lens)
+            emb, layers, saved, est = rows.embed_train(eng, est, lens)
         idx = None
         if k is None:
             _, mean = eng.pairwise(emb, refs, want_matrix=False)
@@ -762,7 +710,7 @@ class _SpanScoreFn(torch.autograd.Function):
         dwav = None
         if want_a:
             Nomad._need_whole_encoder(eng)
-            dwav = eng.embed_spans_backward_ragged((est, ctx.lens), layers, saved, demb, ctx.table).reshape(shape)
+            dwav = ctx.rows.backward(eng, est, ctx.lens, layers, saved, demb).reshape(shape)
         if dref is not None:
             dref = dref.to(ref_device, ref_dtype)
         return dwav, dref, None, None, None, None
@@ -1348,7 +1296,7 @@ class Nomad:
         lens = check_lengths(estimate, lengths) if lengths is not None else None
         self._need_whole_encoder(self.engine)
         if torch.is_grad_enabled() and (estimate.requires_grad or references.requires_grad):
-            scores = _ScoreFn.apply(estimate, references, self, lens, k)
+            scores = _ScoreFn.apply(estimate, references, self, lens, _ClipRows(), k)
         else:
             eng = self.engine
             est = estimate.detach().to(eng.device, torch.float32).contiguous()
@@ -1426,7 +1374,7 @@ class Nomad:
             scores, counts = self.score_over_time(estimate.detach(), references.detach(), window_s, hop_s, lengths, k)
         else:
             self._need_whole_encoder(self.engine)
-            scores = _WindowScoreFn.apply(estimate, references, self, lens, win, hop, k)
+            scores = _ScoreFn.apply(estimate, references, self, lens, _WindowRows(win, hop), k)
             samples = lens if lens is not None else [estimate.shape[-1]] * estimate.shape[0]
             counts = [num_windows(num_frames(n), win, hop) for n in samples]
         return (scores.mean() if reduction == "mean" else scores), counts
@@ -1533,7 +1481,7 @@ class Nomad:
         table, counts = span_table(spans, [num_frames(n) for n in lens], unit)
         self._need_whole_encoder(self.engine)
         if torch.is_grad_enabled() and (wav.requires_grad or references.requires_grad):
-            scores = _SpanScoreFn.apply(wav, references, self, lens, table, k)
+            scores = _ScoreFn.apply(wav, references, self, lens, _TableRows(table), k)
         else:
             eng = self.engine
             x = wav.detach().to(eng.device, torch.float32).contiguous()

@@ -19,8 +19,8 @@ again - and asserts
        cdist_backward: da and db elementwise against float64 autograd;
        train_backward: every parameter segment elementwise (the oracle makes every element of every trainable tensor NaN).
 
-The kernels that had to change: the ReLU of the seven head sites (head_kernel, head_windows_kernel, head_spans_kernel and the pooled
-recomputation of head_bwd_kernel, head_windows_bwd_kernel, head_spans_bwd_kernel) and the hinge of triplet_loss_kernel computed
+The kernels that had to change: the ReLU of the head - then seven copies, now three sites in head.hip.h: head_kernel,
+head_pooled_from_sum (head_rows_kernel, head_rows_bwd_kernel) and head_pooled_one_pass (head_bwd_kernel) - and the hinge of triplet_loss_kernel computed
 ``fmaxf(x, 0.f)``, which is 0 for a NaN: an all-NaN clip got the finite embedding normalize(bias) and a finite score, a NaN triplet
 added 0 to the loss.  They now run ``relu_keep_nan`` (rowops.hip.h), two true selects.  No GEMM, conv, attention, pos-conv,
 LayerNorm or split-K kernel failed containment or visibility in any case below: none was changed.

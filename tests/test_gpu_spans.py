@@ -1,4 +1,4 @@
-"""GPU: embeddings over caller-given spans of frames (``nomad_embed_spans_ragged``, ``head_spans_kernel``;
+"""GPU: embeddings over caller-given spans of frames (``nomad_embed_spans_ragged``, ``head_rows_kernel<TIn, SpanRows>``;
 ``Engine.embed_spans_ragged``, ``Nomad.score_spans`` / ``active_spans`` / ``predict_spans``) and ``nomad_frame_energy``.
 
 Every engine call runs inside ``guard.guarded()``: outputs and the span scratch between guards, the workspace at exactly the size

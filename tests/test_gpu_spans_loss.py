@@ -1,4 +1,4 @@
-"""GPU: ``Nomad.score_spans`` as a differentiable quantity and what carries it: ``head_spans_bwd_kernel`` +
+"""GPU: ``Nomad.score_spans`` as a differentiable quantity and what carries it: ``head_rows_bwd_kernel<SpanRows>`` +
 ``head_spans_scatter_kernel`` (the span head's backward), ``nomad_embed_train_spans_ragged`` / ``nomad_embed_spans_backward_ragged``,
 ``Engine.embed_train_spans_ragged`` / ``embed_spans_backward_ragged``.  Every engine call runs inside ``guard.guarded()``: outputs,
 the span scratch and the workspaces at exactly the size asked for, between guards.

@@ -1,4 +1,4 @@
-"""GPU: embeddings and scores over windows of frames (``nomad_embed_windows*``, ``head_windows_kernel``; ``Engine.embed_windows*``,
+"""GPU: embeddings and scores over windows of frames (``nomad_embed_windows*``, ``head_rows_kernel<TIn, WindowRows>``; ``Engine.embed_windows*``,
 ``Nomad.score_over_time`` / ``predict_segments``).
 
 Every engine call runs inside ``guard.guarded()``: the output between guards, the workspace at exactly the size of the plain

@@ -1,4 +1,4 @@
-"""GPU: ``Nomad.score_windows`` - scores over time as a differentiable quantity - and what carries it: ``head_windows_bwd_kernel`` +
+"""GPU: ``Nomad.score_windows`` - scores over time as a differentiable quantity - and what carries it: ``head_rows_bwd_kernel<WindowRows>`` +
 ``head_windows_scatter_kernel`` (the windowed head's backward), ``nomad_embed_train_windows*`` / ``nomad_embed_windows_backward*``,
 ``Engine.embed_train_windows*`` / ``embed_windows_backward*``.  Every engine call runs inside ``guard.guarded()``: outputs, the
 per-window scratch and the workspaces at exactly the size asked for, between guards.
@@ -22,7 +22,8 @@ at least half an fp32 ulp of the largest score.
 
 Bits: without a gradient ``score_windows`` is ``score_over_time``; with every clip inside one window and a gradient required its
 values are ``score``'s; two identical calls give the same gradient; a clip's row of the ragged call's gradient is that of its own
-B = 1 call; ``references.grad`` is ``cdist_backward``'s.  Buffers: ``nomad_embed_windows_backward`` through ctypes with scratch,
+B = 1 call; 260 clips in one batch - more than the scatter has threads to count the earlier clips' windows with - give the rows and
+the gradient of the same clips as two batches of 130; ``references.grad`` is ``cdist_backward``'s.  Buffers: ``nomad_embed_windows_backward`` through ctypes with scratch,
 workspace and output filled with NaN, then with 0 - finite and identical.  Refusals: status, ``nomad_last_error`` naming the
 entry point, a poisoned output left untouched.
 
@@ -314,6 +315,33 @@ def test_references_get_the_gradient_of_cdist_backward(nmd_f32, data):
     assert counts == [7] and r.grad.dtype == torch.float32 and torch.equal(r.grad, want)
     assert torch.equal(r2.grad, want_t) and xg.grad is not None and xg.grad.abs().max() > 0
     assert r3.grad.dtype == torch.float64 and r3.grad.device.type == "cpu" and torch.equal(r3.grad, want.cpu().double())
+
+
+def test_more_clips_than_the_scatter_has_threads(nmd_f32):
+    """B = 260 clips of 1, 2, 3 frames (cycled), win 2 hop 1 - 1, 1, 2 windows: a clip's first output row is the sum of the earlier
+    clips' window counts, which every workgroup forms for itself with a stride of its own size (1024 threads in the two head
+    kernels, 256 in the scatter).  260 clips make the scatter's count loop take a second trip.  Rows and gradient of the one batch
+    against clips 0..129 and 130..259 run as two batches, bit for bit: the batch-invariance contract."""
+    eng = nmd_f32.engine
+    lens = [(400, 720, 1040)[i % 3] for i in range(260)]
+    assert [num_frames(n) for n in lens[:3]] == [1, 2, 3]
+    clips = [_wav(n, 300 + i).cuda() for i, n in enumerate(lens)]
+    counts = [num_windows(num_frames(n), 2, 1) for n in lens]
+    demb_w = torch.randn(sum(counts), 256, generator=torch.Generator().manual_seed(260)).cuda()
+
+    def run(lo, hi):
+        emb, cnt, layers, saved, batch = eng.embed_train_windows_ragged(clips[lo:hi], 2, 1)
+        assert cnt == counts[lo:hi]
+        at = sum(counts[:lo])
+        return emb, eng.embed_windows_backward_ragged(batch, layers, saved, demb_w[at:at + sum(cnt)], 2, 1)
+
+    with guard.guarded(case="windows of 260 clips"):
+        emb, dwav = run(0, 260)
+        (emb_a, dwav_a), (emb_b, dwav_b) = run(0, 130), run(130, 260)
+        torch.cuda.synchronize()
+    assert emb.shape == (sum(counts), 256) and bool(torch.isfinite(emb).all()) and dwav.abs().max() > 0
+    assert torch.equal(emb, torch.cat([emb_a, emb_b])), "a window's row depends on the clips ahead of it"
+    assert torch.equal(dwav, torch.cat([dwav_a, dwav_b])), "a clip's gradient depends on the clips ahead of it"
 
 
 # ---- buffers and refusals at the C ABI ------------------------------------------------------------------------------------------
