@@ -24,6 +24,8 @@
  *   nomad_degrade_noise / _clip    noise at a target SNR and percentile clipping of src/utils/degradations.py (:30-68, :70-83), G levels
  *                                  per clip, written as the packed batch nomad_embed_ragged reads
  *   nomad_degrade_convolve         every clip convolved with G impulse responses (reverberation as a causal FIR filter), same layout
+ *   nomad_degrade_normalize        BS.1770-4 loudness (or rms / peak level) of packed rows and the linear gain to a target, in place:
+ *                                  the ffmpeg-normalize step of audio_degrader_training.py / audio_degrader_test.py
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
  *
@@ -718,6 +720,49 @@ size_t nomad_degrade_convolve_scratch_bytes(int B, int G);
 int nomad_degrade_convolve(nomad_ctx* ctx, const float* x_dev, int B, int stride, const int* lens_host, const float* ir_dev, int G,
                            int ir_stride, const int* ir_lens_host, float* out_dev, void* ws_dev, size_t ws_bytes,
                            nomad_stream_t stream);
+
+/* ---- loudness normalisation of packed rows: ITU-R BS.1770-4 (mono), linear gain to a target ------------------------------
+ * The reference's rendering scripts follow every degraded file with `ffmpeg-normalize FILE -o FILE -f -ar 16000`: EBU R128, integrated
+ * loudness brought to -23 LUFS, so that its intensity experiment ranks degradations at equal loudness.  This call measures R packed
+ * rows and scales each by ONE gain, in place if wanted.  x_dev is [R][stride] fp32, row r in its first lens_host[r] samples (the rest
+ * is never read); lens_host is a HOST array.
+ *
+ * K-weighting: two cascaded biquads in transposed direct form II, state and output float64, coefficients formed on the host in
+ * float64 from sample_rate = fs:
+ *   shelf:     f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196, K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *              Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *              b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0], a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *   high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, same K and a0 forms, b = [1, -2, 1], a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ * (at 48 kHz the standard's table).  Blocks: hop = fs / 10 samples, block j covers filtered samples [j hop, j hop + 4 hop) (400 ms,
+ * 75 % overlap); only whole blocks count: nb = (n - 4 hop) / hop + 1 for n >= 4 hop, else 0; z_j = mean square of block j,
+ * l_j = -0.691 + 10 log10 z_j.  Gating: absolute l_j > -70; relative Gamma = -0.691 + 10 log10(mean z_j over the absolute-gated
+ * blocks) - 10; L = -0.691 + 10 log10(mean z_j over the blocks with l_j > -70 and l_j > Gamma); L = -inf if no block passes the
+ * absolute gate (digital silence, any row shorter than 400 ms).
+ * mode 0 (ebu): the level is L, in LUFS; 1 (rms): 20 log10 sqrt(mean x^2) over the row, dBFS; 2 (peak): 20 log10 max|x|, dBFS -
+ * ffmpeg-normalize -nt's three.  The peak, measured in every mode, is the SAMPLE peak max|x|, not the 4x oversampled true peak.
+ * Gain: g = 10^((target - level) / 20) in float64; with a ceiling peak_db (NaN: none) g = min(g, 10^(peak_db / 20) / peak);
+ * out[i] = (float)((double)x[i] g) for i < n, zero behind the length.  A row whose level is -inf is copied unchanged (g = 1, no
+ * ceiling).  This is the LINEAR gain of ffmpeg's loudnorm; its dynamic mode, loudness-range target and true-peak limiter are not offered.
+ *
+ * How the recurrence runs in parallel (csrc/loudness.hip.h): the row is cut into chunks of hop samples, each walked from a zero
+ * state, the true entry states follow from s_{j+1} = M s_j + e_j (M: the cascade's 4 x 4 transition over hop samples, from the host),
+ * each whole chunk is walked again from its true state for its sum of y^2, and block j is chunks j .. j + 3 added in that order.
+ * Every sum is float64 in an order fixed by (n, fs): a row's statistics and output have the bits of its own R = 1 call.
+ * out_dev: [R][stride] fp32; may be x_dev exactly (in place), or NULL (measure only).  stats_out_dev: optional [R][4] float64 =
+ * (level, sample peak, applied gain, blocks that passed both gates - 0 in the rms and peak modes), or NULL.
+ * Non-finite input: a NaN or infinite sample makes its row's level, gain and block count NaN, its peak NaN or inf and its output
+ * samples [0, n) NaN; no other row changes, and zeros stay behind the length.
+ * Contract as the degradations above: asynchronous, no allocation, deterministic, no floating-point atomics; the lengths are copied
+ * into the workspace ahead of the kernels; workspace nomad_degrade_normalize_scratch_bytes(R, stride, sample_rate) bytes (0 for
+ * arguments the call would refuse), written before it is read.  Argument errors return before anything is queued.
+ * NOMAD_ERR_INVALID: a NULL x_dev (context, lengths, workspace), both outputs NULL, R outside 1 .. 65535, stride not a positive
+ * multiple of 4 or shorter than a length, a length < 1, sample_rate outside 8000 .. 192000 or no multiple of 10, mode outside 0 .. 2,
+ * a target that is not finite, out_dev overlapping x_dev other than exactly.  NOMAD_ERR_WORKSPACE: ws_bytes too small.
+ */
+size_t nomad_degrade_normalize_scratch_bytes(int R, int stride, int sample_rate);
+int nomad_degrade_normalize(nomad_ctx* ctx, const float* x_dev, int R, int stride, const int* lens_host, int sample_rate, int mode,
+                            double target, double peak_db, float* out_dev, double* stats_out_dev, void* ws_dev, size_t ws_bytes,
+                            nomad_stream_t stream);
 
 /* ---- bf16 path (BASELINE config C5: long-form clips) ---------------------------------------- */
 /*

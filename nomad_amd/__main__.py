@@ -9,7 +9,8 @@ the files shard across the ranks (RCCL all-gather of the embeddings, ``Nomad.pre
 (``Nomad.predict_spans``, ``spans.csv``).
 
 ``--sweep`` (one process): ``--deg`` holds CLEAN files, which are degraded on the GPU at every level of ``--snr-db`` (with ``--noise
-FILE``), ``--clip`` and / or ``--rt60`` (synthetic rooms, ``nomad_amd.nomad.synthetic_rir``) and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level."""
+FILE``), ``--clip`` and / or ``--rt60`` (synthetic rooms, ``nomad_amd.nomad.synthetic_rir``) and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level.  ``--normalize [LUFS]`` brings every
+degraded clip to one BS.1770 loudness first (bare: -23), as the reference's ``ffmpeg-normalize`` step does."""
 import argparse
 import os
 
@@ -39,6 +40,8 @@ def sweep(nomad, a):
     refs = torch.from_numpy(refs.to_numpy(dtype="float32").copy())
     noise = nomad.load_processing(a.noise).reshape(-1) if a.noise is not None else None
     reverb = {"rt60_s": a.rt60} if a.rt60 is not None else {}
+    if a.normalize is not None:
+        reverb["normalize"] = a.normalize
     results = nomad.intensity_sweep(a.deg, refs, noise=noise, snr_db=a.snr_db, clip_factor=a.clip, k=a.knn, **reverb)
     parts = []
     for name, res in results.items():
@@ -88,6 +91,9 @@ def main(argv=None):
     ap.add_argument("--clip", type=_levels, default=None, metavar="A,B,...", help="--sweep: clip factors, percent of samples clipped")
     ap.add_argument("--rt60", type=_levels, default=None, metavar="A,B,...",
                     help="--sweep: reverberation times in seconds (synthetic diffuse rooms, not sox's reverb), each in (0, 4.096]")
+    ap.add_argument("--normalize", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS",
+                    help="--sweep: bring every degraded clip to this BS.1770 integrated loudness before it is scored (bare: -23, EBU R128, "
+                         "what the reference's ffmpeg-normalize step does), so that the score ranks the degradation at equal loudness")
     a = ap.parse_args(argv)
     if a.hop is not None and a.window is None:
         ap.error("--hop goes with --window")
@@ -95,6 +101,11 @@ def main(argv=None):
         ap.error("--noise, --snr-db and --clip go with --sweep")
     if not a.sweep and a.rt60 is not None:
         ap.error("--rt60 goes with --sweep")
+    if a.normalize is not None:
+        if not a.sweep:
+            ap.error("--normalize goes with --sweep")
+        if not (a.normalize == a.normalize and abs(a.normalize) != float("inf")):
+            ap.error(f"--normalize takes a finite level in LUFS, got {a.normalize}")
     if a.spans is not None and a.active_db is not None:
         ap.error("--spans and --active-db exclude each other: the rows come from the csv or from the energy gate")
     if a.spans is not None or a.active_db is not None:

@@ -63,6 +63,9 @@ SIGNATURES = {
     "nomad_degrade_convolve_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "nomad_degrade_convolve": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, C.c_int, C.c_int, C.POINTER(C.c_int),
                                          _fp, _fp, C.c_size_t, _fp]),
+    "nomad_degrade_normalize_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nomad_degrade_normalize": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_double, C.c_double,
+                                          _fp, _fp, _fp, C.c_size_t, _fp]),
     "nomad_embed_features": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "nomad_embed_features_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp,
                                               C.c_size_t, _fp]),
@@ -219,6 +222,9 @@ L1_REDUCTION = {"mean": 0, "none": 1}
 
 # precision argument of nomad_embed_features* (include/nomad_hip.h)
 PRECISION = {"fp32": 0, "bf16x3": 1, "bf16": 2}
+
+# mode argument of nomad_degrade_normalize (include/nomad_hip.h): ffmpeg-normalize -nt's three
+LOUDNESS_MODE = {"ebu": 0, "rms": 1, "peak": 2}
 
 # nomad_status (include/nomad_hip.h)
 NOMAD_OK, NOMAD_ERR_INVALID, NOMAD_ERR_NO_DEVICE, NOMAD_ERR_HIP, NOMAD_ERR_WORKSPACE, NOMAD_ERR_IO, NOMAD_ERR_FORMAT = 0, -1, -2, -3, -4, -5, -6

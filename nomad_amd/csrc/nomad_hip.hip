@@ -27,6 +27,7 @@
 #include "backward.hip.h"
 #include "degrade.hip.h"
 #include "degrade_convolve.hip.h"
+#include "loudness.hip.h"
 #include "frontend.hip.h"
 #include "gemm_bf16.hip.h"
 #include "gemm_bf16_8phase.hip.h"
@@ -3985,6 +3986,97 @@ int nomad_degrade_convolve(nomad_ctx* c, const float* x, int B, int stride, cons
     Scope sc(c, s, NOMAD_K_ROW, flops);
     hipLaunchKernelGGL(degrade_convolve_kernel, dim3((unsigned)(tiles * B * G)), dim3(kRirThreads), 0, s, x, stride,
                        reinterpret_cast<const int*>(w), ir, ir_stride, reinterpret_cast<const int*>(w + convolve_lens_bytes(B)), G, (int)tiles, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- loudness normalisation of packed rows (loudness.hip.h) ----
+// Scratch: [lengths: R int32, to 256 bytes | per chunk (end state, max|x|, sum x^2): [R][C][6] float64 | entry states [R][C][4] |
+// sums of y^2 [R][C] | statistics [R][4]], C = ceil(stride / hop) chunks of hop = sample_rate / 10 samples per row.
+struct LoudnessLayout {
+    int hop, C;
+    size_t cs, entry, ysum, stats, total;
+};
+static LoudnessLayout loudness_layout(int R, int stride, int sample_rate) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    LoudnessLayout l;
+    l.hop = sample_rate / 10;
+    l.C = (int)(((long long)stride + l.hop - 1) / l.hop);
+    const size_t slots = (size_t)R * (size_t)l.C;
+    l.cs = up(sizeof(int) * (size_t)R);
+    l.entry = l.cs + up(sizeof(double) * kLoudnessChunkStats * slots);
+    l.ysum = l.entry + up(sizeof(double) * 4 * slots);
+    l.stats = l.ysum + up(sizeof(double) * slots);
+    l.total = l.stats + up(sizeof(double) * 4 * (size_t)R);
+    return l;
+}
+static bool loudness_shape_ok(int R, int stride, int sample_rate) {
+    return R >= 1 && R <= 65535 && stride >= 4 && stride % 4 == 0 && sample_rate >= 8000 && sample_rate <= 192000 && sample_rate % 10 == 0;
+}
+
+size_t nomad_degrade_normalize_scratch_bytes(int R, int stride, int sample_rate) {
+    if (!loudness_shape_ok(R, stride, sample_rate)) {
+        (void)fail(NOMAD_ERR_INVALID,
+                   "nomad_degrade_normalize_scratch_bytes: bad argument (R=%d: 1 .. 65535, stride=%d: a positive multiple of 4, sample_rate=%d: "
+                   "a multiple of 10 in 8000 .. 192000)", R, stride, sample_rate);
+        return 0;
+    }
+    return loudness_layout(R, stride, sample_rate).total;
+}
+
+int nomad_degrade_normalize(nomad_ctx* c, const float* x, int R, int stride, const int* lens, int sample_rate, int mode, double target,
+                            double peak_db, float* out, double* stats_out, void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_degrade_normalize";
+    if (!c || !x || !lens || !ws) return fail(NOMAD_ERR_INVALID, "%s: a NULL context, input, lengths or workspace", who);
+    if (!out && !stats_out) return fail(NOMAD_ERR_INVALID, "%s: both outputs are NULL: nothing to do", who);
+    if (R < 1 || R > 65535) return fail(NOMAD_ERR_INVALID, "%s: R=%d rows, 1 .. 65535 are supported", who, R);
+    if (stride < 4 || stride % 4) return fail(NOMAD_ERR_INVALID, "%s: stride=%d is not a positive multiple of 4", who, stride);
+    if (sample_rate < 8000 || sample_rate > 192000 || sample_rate % 10)
+        return fail(NOMAD_ERR_INVALID, "%s: sample_rate=%d, a multiple of 10 in 8000 .. 192000 is supported", who, sample_rate);
+    if (mode < kLoudnessEbu || mode > kLoudnessPeak) return fail(NOMAD_ERR_INVALID, "%s: mode=%d, 0 (ebu), 1 (rms) or 2 (peak)", who, mode);
+    if (!std::isfinite(target)) return fail(NOMAD_ERR_INVALID, "%s: the target level is not finite", who);
+    for (int r = 0; r < R; ++r)
+        if (lens[r] < 1 || lens[r] > stride)
+            return fail(NOMAD_ERR_INVALID, "%s: row %d has length %d, 1 .. stride=%d are supported", who, r, lens[r], stride);
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(x), oa = reinterpret_cast<uintptr_t>(out), bytes = sizeof(float) * (size_t)R * (size_t)stride;
+    if (out && oa != xa && oa < xa + bytes && xa < oa + bytes)
+        return fail(NOMAD_ERR_INVALID, "%s: the output overlaps the input without being the input (in place: out_dev = x_dev)", who);
+    const LoudnessLayout l = loudness_layout(R, stride, sample_rate);
+    if (ws_bytes < l.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(sizeof(int) * (size_t)R, 0);
+    memcpy(staged.data(), lens, staged.size());
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), staged.size(), hipMemcpyHostToDevice, s));
+    const LoudnessFilter f = loudness_filter(sample_rate, l.hop);
+    const bool ebu = mode == kLoudnessEbu;
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    const int* lens_dev = reinterpret_cast<const int*>(w);
+    double* cs = reinterpret_cast<double*>(w + l.cs);
+    double* entry = reinterpret_cast<double*>(w + l.entry);
+    double* ysum = reinterpret_cast<double*>(w + l.ysum);
+    double* stats = reinterpret_cast<double*>(w + l.stats);
+    const dim3 chunk_grid((unsigned)((l.C + 63) / 64), (unsigned)R), row_grid((unsigned)((R + 63) / 64));
+    hipLaunchKernelGGL(loudness_chunk_kernel<false>, chunk_grid, dim3(64), 0, s, x, stride, lens_dev, l.hop, l.C, f, ebu, cs,
+                       static_cast<const double*>(nullptr), static_cast<double*>(nullptr));
+    if (ebu) {
+        hipLaunchKernelGGL(loudness_carry_kernel, row_grid, dim3(64), 0, s, lens_dev, R, l.hop, l.C, f, static_cast<const double*>(cs), entry);
+        hipLaunchKernelGGL(loudness_chunk_kernel<true>, chunk_grid, dim3(64), 0, s, x, stride, lens_dev, l.hop, l.C, f, true,
+                           static_cast<double*>(nullptr), static_cast<const double*>(entry), ysum);
+    }
+    hipLaunchKernelGGL(loudness_gate_kernel, row_grid, dim3(64), 0, s, lens_dev, R, l.hop, l.C, mode, target,
+                       std::isnan(peak_db) ? peak_db : std::pow(10.0, peak_db / 20.0), static_cast<const double*>(cs),
+                       static_cast<const double*>(ysum), stats, stats_out);
+    if (out) {
+        const bool wide = (xa | oa) % 16 == 0;
+        if (wide)
+            hipLaunchKernelGGL(loudness_gain_kernel<4>, dim3((unsigned)((stride / 4 + 255) / 256), (unsigned)R), dim3(256), 0, s, x, stride,
+                               lens_dev, static_cast<const double*>(stats), out);
+        else
+            hipLaunchKernelGGL(loudness_gain_kernel<1>, dim3((unsigned)((stride + 255) / 256), (unsigned)R), dim3(256), 0, s, x, stride,
+                               lens_dev, static_cast<const double*>(stats), out);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -3,6 +3,7 @@ allocates, and launches on torch's current HIP stream.  PyTorch is plumbing here
 torch.distributed); every FLOP of the NOMAD path runs in libnomad_hip.so."""
 from __future__ import annotations
 
+import math
 import os
 
 import ctypes as C
@@ -646,6 +647,59 @@ class Engine:
                                                    ir.shape[1], (C.c_int * G)(*ir_lens), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                    self._stream()), "nomad_degrade_convolve")
         return out, [n for n in lens for _ in range(G)]
+
+    @staticmethod
+    def check_normalize(target, kind, peak_db, sample_rate):
+        """The arguments of ``degrade_normalize`` that need no GPU -> (mode, target, peak_db as the C ABI takes them)."""
+        if kind not in _lib.LOUDNESS_MODE:
+            raise ValueError(f"kind must be 'ebu', 'rms' or 'peak', got {kind!r}")
+        target = float(target)
+        if not math.isfinite(target):
+            raise ValueError(f"the target level must be finite, got {target}")
+        peak = float("nan") if peak_db is None else float(peak_db)
+        if peak_db is not None and not math.isfinite(peak):
+            raise ValueError(f"peak_db must be finite or None, got {peak_db}")
+        sample_rate = int(sample_rate)
+        if not 8000 <= sample_rate <= 192000 or sample_rate % 10:
+            raise ValueError(f"sample_rate must be a multiple of 10 in 8000 .. 192000, got {sample_rate}")
+        return _lib.LOUDNESS_MODE[kind], target, peak, sample_rate
+
+    def degrade_normalize(self, waves=None, lengths=None, packed: Optional[Tuple[torch.Tensor, list]] = None, target: float = -23.0,
+                          kind: str = "ebu", peak_db: Optional[float] = None, sample_rate: int = 16000, inplace: bool = False,
+                          measure_only: bool = False):
+        """Loudness of every row and the linear gain that brings it to ``target`` -> (rows (R, stride) fp32 on the device or None,
+        lengths, stats (R, 4) float64 on the device = level, sample peak, applied gain, blocks past both gates).  kind "ebu": the
+        level is the BS.1770-4 integrated loudness in LUFS (K-weighting in float64, 400 ms blocks every 100 ms, the -70 LUFS and
+        -10 LU gates); "rms" / "peak": dBFS - ffmpeg-normalize's three.  peak_db: a ceiling for the SAMPLE peak after the gain.  A
+        row without a level (silence, under 400 ms for "ebu") is copied unchanged.  waves / lengths as ``degrade_noise`` takes
+        them, or packed = (device buffer, lengths) as the degradations return it; inplace: write into that buffer (what feeds
+        ``embed_ragged(packed=...)`` is then normalised with no copy); measure_only: statistics alone, rows None.  The linear gain of
+        ffmpeg's loudnorm: no dynamic mode, loudness range or true-peak limiter (``nomad_degrade_normalize``)."""
+        mode, target, peak, sample_rate = self.check_normalize(target, kind, peak_db, sample_rate)
+        if packed is not None:
+            if waves is not None or lengths is not None:
+                raise ValueError("packed goes without waves and lengths")
+            buf, lens = packed
+            self._check_dev(buf, "packed rows")
+            if buf.dim() != 2 or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.shape[1] % 4 or len(lens) != buf.shape[0]:
+                raise ValueError("packed must be a contiguous (R, stride) fp32 device buffer, stride a multiple of 4, with R lengths")
+        elif lengths is not None:
+            buf, lens = self.pack_ragged(waves, lengths)
+            if buf.shape[1] % 4 or not buf.is_contiguous() or buf.dtype != torch.float32:
+                buf, lens = self._pack([buf[i, :n] for i, n in enumerate(lens)])
+        else:
+            buf, lens = self._pack(waves)
+        lens = [int(n) for n in lens]
+        R, stride = buf.shape
+        if measure_only and inplace:
+            raise ValueError("measure_only writes no rows: it goes without inplace")
+        out = None if measure_only else buf if inplace else torch.empty(R, stride, dtype=torch.float32, device=self.device)
+        stats = torch.empty(R, 4, dtype=torch.float64, device=self.device)
+        ws = self._workspace(int(self.lib.nomad_degrade_normalize_scratch_bytes(R, stride, sample_rate)))
+        _lib.check(self.lib.nomad_degrade_normalize(self.ctx, buf.data_ptr(), R, stride, (C.c_int * R)(*lens), sample_rate, mode, target, peak,
+                                                    _ptr(out), stats.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_degrade_normalize")
+        return out, lens, stats
 
     def cdist(self, a: torch.Tensor, b: torch.Tensor, want_matrix: bool = True):
         """a (Na,D), b (Nb,D) fp32 on the GPU, D a multiple of 4 up to 4096 -> (dist (Na,Nb) float64 or None, mean (Na,)

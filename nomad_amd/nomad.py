@@ -1647,9 +1647,9 @@ class Nomad:
         kind "noise": ``levels`` are target SNRs in dB and ``noise`` a 1-D signal, tiled or cut to each clip:
         ``x + alpha s`` with ``alpha = (rms(x) / 10^(snr / 10)) / rms(s)`` - the reference's ``utils/degradations.py`` formula as it
         stands.  kind "clip": ``levels`` are clip factors in percent (0 .. 100): samples are clamped to the clip's own percentiles
-        ``cf / 2`` and ``100 - cf / 2`` (numpy's linear rule, exact order statistics).  Neither is followed by the loudness
-        normalisation the reference's rendering scripts apply, and codecs are not offered; reverberation is ``convolve``.  No
-        gradient."""
+        ``cf / 2`` and ``100 - cf / 2`` (numpy's linear rule, exact order statistics).  Both change the level with the
+        degradation; the loudness normalisation the reference's rendering scripts apply afterwards is ``normalize`` (or
+        ``intensity_sweep(normalize=...)``).  Codecs are not offered; reverberation is ``convolve``.  No gradient."""
         if kind not in ("noise", "clip"):
             raise ValueError(f"kind must be 'noise' or 'clip', got {kind!r}")
         if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
@@ -1672,7 +1672,8 @@ class Nomad:
         length (``lengths`` comes back repeated G times; every row is zero behind its length).  wav (B,1,N) or (B,N); lengths: the
         clips' exact lengths (any length from 1 sample); irs: a list of 1 .. 64 1-D responses of 1 .. 65536 taps each, or a (G,L)
         tensor with optional ``ir_lengths`` - measured rooms, or ``synthetic_rir``.  For a fixed setting a reverberator is this
-        filter; sox's parameters, the loudness normalisation of the reference's rendering scripts and codecs are not offered.  fp32
+        filter; sox's parameters and codecs are not offered, the loudness normalisation of the reference's rendering scripts is
+        ``normalize`` (a room adds its tail's energy).  fp32
         products and sums (``nomad_degrade_convolve``); a row does not depend on the batch it is made in.  No gradient."""
         if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
             raise ValueError(f"wav must be (B,1,N) or (B,N), got {tuple(getattr(wav, 'shape', ()))}")
@@ -1686,6 +1687,38 @@ class Nomad:
         x = (x.squeeze(1) if x.dim() == 3 else x).contiguous()
         lens = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)] if lengths is not None else [x.shape[1]] * x.shape[0]
         return self.engine.degrade_convolve(x, irs, lengths=lens, ir_lengths=ir_lengths)
+
+    def _rows_for_normalize(self, wav, lengths, what: str):
+        """(B,1,N) / (B,N) clips and their lengths as a device tensor and a list, for ``loudness`` and ``normalize``."""
+        if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+            raise ValueError(f"wav must be (B,1,N) or (B,N), got {tuple(getattr(wav, 'shape', ()))}")
+        if wav.requires_grad:
+            raise ValueError(f"{what} produces no gradient (the degradations have no backward): pass tensors that do not require one")
+        x = wav.detach().to(self.engine.device, torch.float32)
+        x = (x.squeeze(1) if x.dim() == 3 else x).contiguous()
+        lens = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)] if lengths is not None else [x.shape[1]] * x.shape[0]
+        return x, lens
+
+    def loudness(self, wav, lengths=None, kind: str = "ebu"):
+        """The level of every clip, measured on the GPU -> (R,) float64 on the device.  kind "ebu": ITU-R BS.1770-4 integrated
+        loudness in LUFS at 16 kHz, one channel (K-weighting, 400 ms blocks, absolute gate at -70 LUFS, relative gate 10 LU under
+        the gated mean); -inf for silence and for clips under 400 ms.  "rms" / "peak": dBFS of the clip's rms and of its SAMPLE peak
+        (not the oversampled true peak).  wav (B,1,N) or (B,N), lengths: the clips' exact lengths."""
+        Engine.check_normalize(0.0, kind, None, 16000)
+        x, lens = self._rows_for_normalize(wav, lengths, "loudness")
+        return self.engine.degrade_normalize(x, lengths=lens, kind=kind, measure_only=True)[2][:, 0]
+
+    def normalize(self, wav, target: float = -23.0, kind: str = "ebu", lengths=None, peak_db=None):
+        """Clips brought to one level on the GPU, as ``ffmpeg-normalize -nt <kind> -t <target>`` does to the reference's rendered
+        files (its default: EBU R128, -23 LUFS) -> (rows (R, stride) fp32 on the GPU, lengths, stats (R, 4) float64 on the GPU =
+        measured level, sample peak, applied gain, blocks past both gates).  The rows are packed as ``degrade`` returns them (zero
+        behind each length) and go into ``score`` / ``embed_ragged(packed=...)``.  Each clip is scaled by ONE gain
+        ``10^((target - level) / 20)``, lowered where needed so that the sample peak stays at ``peak_db`` dBFS; a clip without a
+        level (silence; under 400 ms for "ebu") is returned unchanged.  This is the linear mode of ffmpeg's ``loudnorm``: its
+        dynamic mode, loudness-range target and true-peak limiter are not offered.  No gradient."""
+        Engine.check_normalize(target, kind, peak_db, 16000)
+        x, lens = self._rows_for_normalize(wav, lengths, "normalize")
+        return self.engine.degrade_normalize(x, lengths=lens, target=target, kind=kind, peak_db=peak_db)
 
     def _clean_batches(self, clean, lengths, budget: int):
         """The clean clips of ``intensity_sweep`` as packed device batches of at most ``budget`` samples each (one clip at least):
@@ -1725,7 +1758,8 @@ class Nomad:
             lo = hi
 
     def intensity_sweep(self, clean, references, noise=None, snr_db=None, clip_factor=None, lengths=None, k=None,
-                        max_batch_samples: int = 256 * 64000, rt60_s=None, rir_seed: int = 0, drr_db: float = 0.0):
+                        max_batch_samples: int = 256 * 64000, rt60_s=None, rir_seed: int = 0, drr_db: float = 0.0,
+                        normalize=None, normalize_kind: str = "ebu"):
         """Does the score rank the strength of a degradation?  The reference's ``intensity`` experiment without rendered files: the
         clean clips are degraded on the GPU (``degrade``) at every level, embedded and scored against ``references`` ((Nr,256), as
         ``score`` takes them); -> {"NOISE": {...}, "CLIP": {...}, "REVERB": {...}}, a degradation whose levels are None being left out.  Each entry is
@@ -1738,9 +1772,17 @@ class Nomad:
         nearest-reference score of ``score(k=...)``.  rt60_s: reverberation times in seconds, each in (0, 4.096]: the clips are
         convolved (``convolve``) with ``synthetic_rir(rt60, rir_seed, drr_db)`` - a synthetic diffuse room, NOT sox's reverb -
         and ``Condition`` is the RT60; whether the score ranks it is not claimed.  The clean audio is uploaded once per batch; batches are cut so that the
-        G-fold degraded rows stay within ``max_batch_samples`` samples."""
+        G-fold degraded rows stay within ``max_batch_samples`` samples.
+
+        normalize: None - the degraded rows are scored at whatever level the degradation left them (noise at 0 dB SNR is 3 dB
+        louder than the clip, a 40 % clip factor several dB quieter).  A number: every degraded row is brought to that level in
+        place before it is embedded (``normalize``; ``normalize_kind`` "ebu" = LUFS as the reference's ``ffmpeg-normalize`` step,
+        -23 being its default, or "rms" / "peak" in dBFS), so that the score ranks the degradation at equal loudness; each entry
+        then also has ``gain_db``, the (N G,) float64 gains applied, in row order."""
         from .train import intensity_stats
         check_references(references)
+        if normalize is not None:
+            Engine.check_normalize(normalize, normalize_kind, None, 16000)
         k = check_k(k, references.shape[0]) if k is not None else None
         if snr_db is None and clip_factor is None and rt60_s is None:
             raise ValueError("intensity_sweep needs snr_db, clip_factor or both, or rt60_s")
@@ -1760,13 +1802,16 @@ class Nomad:
         refs = references.detach().to(eng.device, torch.float32).contiguous()
         if noise is not None:
             noise = torch.as_tensor(noise, dtype=torch.float32).reshape(-1).to(eng.device)
-        rows = {name: ([], [], []) for name, _, _ in sweeps}      # row names, levels, embeddings in flight
+        rows = {name: ([], [], [], []) for name, _, _ in sweeps}      # row names, levels, embeddings in flight, gains in flight
         budget = max(1, int(max_batch_samples) // max(len(levels) for _, _, levels in sweeps))
         for names, buf, lens in self._clean_batches(clean, lengths, budget):
             for name, kind, levels in sweeps:
                 if kind == "reverb" and isinstance(rirs, list):
                     rirs = eng.pack_responses(rirs)      # packed and uploaded once, with the first batch
                 out, lens_rep, _ = self._degrade_packed(buf, lens, kind, levels, rirs if kind == "reverb" else noise)
+                if normalize is not None:
+                    _, _, stats = eng.degrade_normalize(packed=(out, lens_rep), target=normalize, kind=normalize_kind, inplace=True)
+                    rows[name][3].append(eng.fetch_async(stats))
                 emb = eng.embed_ragged(None, precision=self._window_precision(sum(lens_rep)), packed=(out, lens_rep))
                 rows[name][0].extend(f"{n}|{name}_{g}" for n in names for g in range(len(levels)))
                 rows[name][1].extend(levels * len(names))
@@ -1774,7 +1819,7 @@ class Nomad:
         ref_df = pd.DataFrame(refs.cpu().numpy())
         results = {}
         for name, _, _ in sweeps:
-            row_names, conds, fetches = rows[name]
+            row_names, conds, fetches, gains = rows[name]
             if not row_names:
                 raise ValueError("intensity_sweep: no clean clip to degrade")
             df_emb = pd.concat([pd.DataFrame({"filepath_deg": row_names}),
@@ -1789,6 +1834,9 @@ class Nomad:
 
             results[name] = intensity_stats(df_emb, deg_data, ref_df, nmr_mean, name)
             results[name]["scores"] = scores["rows"]
+            if normalize is not None:
+                with np.errstate(divide="ignore"):
+                    results[name]["gain_db"] = 20.0 * np.log10(np.concatenate([f.result() for f in gains])[:, 2])
         return results
 
     def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor, lengths=None) -> "GraphedLoss":

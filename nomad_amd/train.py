@@ -690,8 +690,10 @@ class Training:
         With the config key ``degrade_on_device: {clean: <dir|csv>, noise: <wav>, snr_db: [...], clip: [...], rt60: [...]}`` (not a
         reference key) no rendered files and no ``test_mono_data`` are needed: the clean files are degraded on the GPU at the listed levels
         (``Nomad.intensity_sweep``: additive noise at an SNR, percentile clipping and - ``rt60``, in seconds - convolution with
-        ``synthetic_rir`` rooms, without the loudness normalisation of the reference's rendering scripts) and the result has the
-        same shape, with the degradations ``NOISE``, ``CLIP`` and ``REVERB``."""
+        ``synthetic_rir`` rooms) and the result has the same shape, with the degradations ``NOISE``, ``CLIP`` and ``REVERB``.  A
+        further key ``normalize: -23`` brings every degraded row to that BS.1770 loudness in LUFS before it is scored, as the
+        ``ffmpeg-normalize`` step of the reference's rendering scripts does (its linear gain only; no codecs); without the key the
+        rows keep the level the degradation left them."""
         import pandas as pd
         on_device = self.config.get("degrade_on_device")
         if on_device and self.config.get("eval_w2v"):
@@ -706,7 +708,8 @@ class Training:
                 on_device["clean"], torch.from_numpy(_emb_values(ref_embeddings)),
                 noise=self.nomad.load_processing(noise).reshape(-1) if noise is not None else None,
                 snr_db=on_device.get("snr_db"), clip_factor=on_device.get("clip"),
-                **({"rt60_s": on_device["rt60"]} if on_device.get("rt60") is not None else {}))
+                **({"rt60_s": on_device["rt60"]} if on_device.get("rt60") is not None else {}),
+                **({"normalize": on_device["normalize"]} if on_device.get("normalize") is not None else {}))
             for res in results.values():
                 res["ref_embeddings"] = ref_embeddings
             return results
