@@ -35,6 +35,28 @@
  * scratch comes from the caller-provided workspace (size from nomad_workspace_bytes).  A context
  * is bound to one device and is not re-entrant.  The library has no CPU fallback: without a
  * gfx950 device nomad_create fails with NOMAD_ERR_NO_DEVICE.
+ *
+ * Calling contract (what every entry point that takes a nomad_stream_t keeps; tests/test_gpu_stream_order.py and the
+ * unaligned cases of tests/test_gpu_degrade.py, test_gpu_convolve.py and test_gpu_loudness.py hold the library to it):
+ *   Stream.  ALL device work of a call - kernels, memsets, the copy of its host arrays - is queued on the stream the caller
+ *     passes, in order: it reads its inputs behind whatever the caller queued there before, and whatever the caller queues there
+ *     afterwards sees its outputs.  Nothing is launched on the legacy default stream or on a stream of the library's own; the only
+ *     exceptions are one-time preparation (nomad_create, nomad_enable_*, nomad_train_enable), which synchronises the device
+ *     before it returns.  (nomad_amd.Engine's two-stream batch split is host-layer code: it joins its side stream to the
+ *     caller's stream on both sides of the call.)
+ *   Host arrays.  Every `*_host` array - lengths, levels and SNRs, response lengths, span tables, loss weights and frame counts -
+ *     is consumed before the call returns: the caller may overwrite or free it at once, while the stream still has the call's
+ *     work ahead of it.  The library keeps its own copy in one of three rings of 16 slots per context (ragged metadata and span
+ *     tables; weighted-loss metadata; degradation metadata) until the asynchronous copy has run, so at most 16 such calls of
+ *     one family may be queued on a context without the stream having caught up (a span call takes two slots); the 17th
+ *     reuses the first one's slot.
+ *   Alignment.  Device pointers are expected 16-byte aligned: what hipMalloc and torch's allocator return, and any slice of
+ *     whole rows of such a buffer whose row is a multiple of 16 bytes (packed ragged rows: stride % 4 == 0; embeddings; layer
+ *     outputs).  Two exceptions need only the 4-byte alignment of a float: a [B][n_samples] waveform batch may be passed
+ *     from any whole row on, whatever n_samples is (the front end reads samples one by one); and the sample rows of the four
+ *     degradation calls - x_dev, out_dev, noise_dev and ir_dev of nomad_degrade_noise / _clip / _convolve / _normalize - which
+ *     are read and written sample by sample (convolve and normalize move 16 bytes at a time only where they find the addresses
+ *     aligned).  Workspaces, scratch and float64 statistics are always 16-byte aligned.
  */
 #ifndef NOMAD_HIP_H
 #define NOMAD_HIP_H

@@ -57,6 +57,25 @@ class Guards:
         item = torch.empty((), dtype=dtype).element_size()
         return self.empty_bytes(n * item, device, guard, name).view(dtype).view(shape)
 
+    def empty_at(self, shape, offset: int, dtype=torch.float32, device=None, guard: int = OUT_GUARD, name: str = "tensor") -> torch.Tensor:
+        """``empty`` whose first element lies ``offset`` elements (0 .. 3) behind the allocation's own (at least 64-byte) boundary:
+        with an offset of 1 or 3 floats the address is aligned to 4 bytes and nothing wider, with 2 to 8 bytes.  The ``offset``
+        elements in front of it and the ``4 - offset`` behind it carry the pattern and are checked as part of the two guards."""
+        assert 0 <= offset <= 3 and guard % 256 == 0
+        shape = tuple(int(s) for s in shape)
+        n = 1
+        for s in shape:
+            n *= s
+        item = torch.empty((), dtype=dtype).element_size()
+        pre, nbytes, post = guard + offset * item, n * item, guard + (4 - offset) * item
+        buf = torch.empty(pre + nbytes + post, dtype=torch.uint8, device=device)
+        buf[:pre].fill_(PATTERN)
+        buf[pre + nbytes:].fill_(PATTERN)
+        self.items.append(_Guarded(name, buf, pre, nbytes, post))
+        out = buf[pre:pre + nbytes].view(dtype).view(shape)
+        assert out.data_ptr() % 16 == offset * item % 16
+        return out
+
     def damaged(self):
         """[(name, side, bytes changed, first changed offset within the guard)] over every guarded allocation."""
         if any(g.buf.is_cuda for g in self.items):

@@ -52,17 +52,19 @@ def _rows(arrays, stride):
 class _Call:
     """One ABI call in guarded buffers; the arguments can be overridden one by one (the refusals)."""
 
-    def __init__(self, engine, clips, irs):
+    def __init__(self, engine, clips, irs, stride=None, x_off=0, ir_off=0, out_off=0):
+        """x_off / ir_off / out_off: the rows begin that many floats (0 .. 3) behind a 256-byte boundary (``guard.Guards.empty_at``):
+        base addresses aligned to 4 or 8 bytes only.  The workspace stays aligned."""
         self.engine, self.B, self.G = engine, len(clips), len(irs)
         self.lens, self.ir_lens = [int(c.shape[0]) for c in clips], [int(h.shape[0]) for h in irs]
-        self.stride, self.ir_stride = (max(self.lens) + 3) // 4 * 4, (max(self.ir_lens) + 3) // 4 * 4
+        self.stride, self.ir_stride = stride or (max(self.lens) + 3) // 4 * 4, (max(self.ir_lens) + 3) // 4 * 4
         dev = engine.device
         self.guards = g = guard.Guards()
-        self.x = g.empty((self.B, self.stride), device=dev, name="x")
+        self.x = g.empty_at((self.B, self.stride), x_off, device=dev, name="x")
         self.x.copy_(torch.from_numpy(_rows(clips, self.stride)))
-        self.ir = g.empty((self.G, self.ir_stride), device=dev, name="ir")
+        self.ir = g.empty_at((self.G, self.ir_stride), ir_off, device=dev, name="ir")
         self.ir.copy_(torch.from_numpy(_rows(irs, self.ir_stride)))
-        self.out = g.empty((self.B * self.G, self.stride), device=dev, name="out")
+        self.out = g.empty_at((self.B * self.G, self.stride), out_off, device=dev, name="out")
         self.out.fill_(float("nan"))
         self.ws_bytes = int(engine.lib.nomad_degrade_convolve_scratch_bytes(self.B, self.G))
         self.ws = g.empty_bytes(max(self.ws_bytes, 256), dev, 1 << 16, "workspace")
@@ -88,8 +90,8 @@ class _Call:
         return out
 
 
-def _convolve(engine, clips, irs):
-    call = _Call(engine, clips, irs)
+def _convolve(engine, clips, irs, **kw):
+    call = _Call(engine, clips, irs, **kw)
     rc = call.run()
     assert rc == 0, engine.lib.nomad_last_error()
     return call.results()
@@ -199,6 +201,33 @@ def test_non_finite_values_stay_in_their_rows(engine):
     for b, n in enumerate((4099, 9001)):
         assert not np.isfinite(out[b, 1, k:n]).any(), f"clip {b}: an infinite tap reaches every output from its index on"
         assert np.array_equal(_bits(out[b, 0]), _bits(clean[b, 0])), "the other response's rows are those of the clean call"
+
+
+# (x offset, out offset, response offset) in floats: together, separately, and every residue of 16 bytes on each pointer
+OFFSETS = [(1, 1, 1), (2, 2, 2), (3, 3, 3), (1, 0, 0), (0, 3, 0), (0, 0, 2), (2, 1, 3)]
+
+
+@pytest.mark.parametrize("offs", OFFSETS, ids=lambda o: "x%d-out%d-ir%d" % o)
+def test_rows_at_unaligned_addresses_have_the_bits_of_the_aligned_call(engine, offs):
+    """The kernel stores four outputs at once only where the output's base is 16-byte aligned and the four lie inside the length,
+    else one by one; it reads samples and taps one by one.  Rows whose base is aligned to a float and nothing wider therefore give
+    the aligned call's bits.  Lengths 4093 / 4096 / 4099 at a stride of 4100: the last vector store of a row ends 1 / 0 samples
+    in front of the length or the row ends in the second tile (3 outputs of it), and the zeros behind a length reach up to the
+    guard, which begins at the very next float.  The reference is np.convolve in float64 on integers (exact in any order)."""
+    xo, oo, io = offs
+    clips = [_ints(n, 8, 60 + n) for n in (4093, 4096, 4099)]
+    irs = [_ints(L, 4, 70 + L) for L in (1, 17, CHUNK + 1, 1000)]
+    if "aligned" not in _CACHE:
+        _CACHE["aligned"] = _convolve(engine, clips, irs, stride=4100)
+    want = _CACHE["aligned"]
+    call = _Call(engine, clips, irs, stride=4100, x_off=xo, ir_off=io, out_off=oo)
+    assert call.x.data_ptr() % 16 == 4 * xo and call.out.data_ptr() % 16 == 4 * oo and call.ir.data_ptr() % 16 == 4 * io
+    assert call.run() == 0, engine.lib.nomad_last_error()
+    out = call.results()      # guards, zeros behind every length
+    assert out.shape == (3, 4, 4100) and np.array_equal(_bits(out), _bits(want)), "the bits of the aligned call"
+    for b, x in enumerate(clips):
+        for g, h in enumerate(irs):
+            assert np.array_equal(out[b, g, :x.shape[0]].astype(np.float64), _ref64(x, h)), (x.shape[0], h.shape[0])
 
 
 def test_invalid_arguments_return_a_status_and_a_message_and_touch_nothing(engine):

@@ -62,7 +62,9 @@ def _same(a, b):
 class _Call:
     """One ABI call in guarded buffers: input rows padded with NaN, outputs and workspace filled with NaN bytes."""
 
-    def __init__(self, engine, clips, G, stats_shape, stride=None, ws_bytes=None):
+    def __init__(self, engine, clips, G, stats_shape, stride=None, ws_bytes=None, x_off=0, out_off=0):
+        """x_off / out_off: the rows begin that many floats (0 .. 3) behind a 256-byte boundary (``guard.Guards.empty_at``): base
+        addresses aligned to 4 or 8 bytes only.  Statistics and workspace stay aligned."""
         self.engine, self.clips, self.G = engine, clips, G
         self.B = len(clips)
         self.lens = [int(c.shape[0]) for c in clips]
@@ -72,9 +74,9 @@ class _Call:
         host = np.full((self.B, self.stride), np.nan, dtype=np.float32)
         for b, c in enumerate(clips):
             host[b, :min(self.lens[b], self.stride)] = c[:self.stride]
-        self.x = g.empty((self.B, self.stride), device=dev, name="x")
+        self.x = g.empty_at((self.B, self.stride), x_off, device=dev, name="x")
         self.x.copy_(torch.from_numpy(host))
-        self.out = g.empty((self.B * G, self.stride), device=dev, name="out")
+        self.out = g.empty_at((self.B * G, self.stride), out_off, device=dev, name="out")
         self.out.fill_(float("nan"))
         self.stats = g.empty(stats_shape, dtype=torch.float64, device=dev, name="stats")
         self.stats.fill_(float("nan"))
@@ -101,9 +103,10 @@ def _clip(engine, clips, levels, **kw):
     return rc, c
 
 
-def _noise(engine, clips, noise, levels, **kw):
+def _noise(engine, clips, noise, levels, noise_off=0, **kw):
     c = _Call(engine, clips, len(levels), (len(clips), len(levels)), **kw)
-    nz = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).to(engine.device)
+    nz = c.guards.empty_at((len(noise),), noise_off, device=engine.device, name="noise")
+    nz.copy_(torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)))
     rc = engine.lib.nomad_degrade_noise(engine.ctx, *c.args(), nz.data_ptr(), nz.numel(), (C.c_double * len(levels))(*levels), len(levels),
                                         c.out.data_ptr(), c.stats.data_ptr(), *c.tail())
     torch.cuda.synchronize()
@@ -220,6 +223,44 @@ def test_noise_special_inputs_and_silence_give_what_ieee_gives(engine):
     _, g1 = _noise(engine, [clips[1]], noise, SNR_LEVELS, stride=1028)
     o7, _ = g1.results()
     assert np.array_equal(_bits(o1[0, 0]), _bits(o7[0, 2])), "G = 1 gives the row of the sweep"
+
+
+# ---- rows at addresses that are aligned to 4 or 8 bytes only ------------------------------------------------------------------------
+# (x offset, out offset, noise offset) in floats: together, separately, and every residue of 16 bytes on each pointer
+OFFSETS = [(1, 1, 1), (2, 2, 2), (3, 3, 3), (1, 0, 0), (0, 3, 0), (0, 0, 2), (2, 1, 3)]
+
+
+@pytest.mark.parametrize("offs", OFFSETS, ids=lambda o: "x%d-out%d-aux%d" % o)
+def test_rows_at_unaligned_addresses_have_the_bits_of_the_aligned_call(engine, offs):
+    """Both calls read and write sample by sample, so rows whose base is aligned to a float and nothing wider give the aligned
+    call's bits - thresholds, alphas and rows -, zeros behind each length, and leave the guards (which begin at the very next
+    float on either side) intact.  The header's calling contract promises it."""
+    xo, oo, no = offs
+    clips = _pcm_clips()
+    noise = _pcm(4099, 901) * np.float32(0.3)
+    key = ("aligned", "pcm")
+    if key not in _REF:
+        rc, call = _clip(engine, clips, CLIP_LEVELS)
+        assert rc == 0
+        rn, calln = _noise(engine, clips, noise, SNR_LEVELS)
+        assert rn == 0
+        _REF[key] = (call.results(), calln.results())
+    (out_c, thr), (out_n, alpha) = _REF[key]
+    rc, call = _clip(engine, clips, CLIP_LEVELS, x_off=xo, out_off=oo)
+    assert rc == 0, engine.lib.nomad_last_error()
+    assert call.x.data_ptr() % 16 == 4 * xo and call.out.data_ptr() % 16 == 4 * oo
+    got, gthr = call.results()
+    assert np.array_equal(_bits(gthr), _bits(thr)), "clip thresholds"
+    assert np.array_equal(_bits(got), _bits(out_c)), "clipped rows (zeros behind the lengths included)"
+    for b, n in enumerate(LENS):
+        assert not got[b, :, n:].any() and not np.isnan(got[b, :, n:]).any(), f"clip {b}: rows are zero behind the length"
+    rc, call = _noise(engine, clips, noise, SNR_LEVELS, noise_off=no, x_off=xo, out_off=oo)
+    assert rc == 0, engine.lib.nomad_last_error()
+    got, galpha = call.results()
+    assert np.array_equal(_bits(galpha), _bits(alpha)), "noise alphas"
+    assert np.array_equal(_bits(got), _bits(out_n)), "noisy rows (zeros behind the lengths included)"
+    for b, n in enumerate(LENS):
+        assert not got[b, :, n:].any() and not np.isnan(got[b, :, n:]).any(), f"clip {b}: rows are zero behind the length"
 
 
 # ---- argument errors -------------------------------------------------------------------------------------------------------------

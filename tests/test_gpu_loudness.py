@@ -63,7 +63,9 @@ def _bits(a):
 class _Call:
     """One ABI call in guarded buffers: input rows NaN behind their length, outputs NaN-filled, workspace 0xFF."""
 
-    def __init__(self, engine, rows, fs=16000, inplace=False, stride=None):
+    def __init__(self, engine, rows, fs=16000, inplace=False, stride=None, x_off=0, out_off=0):
+        """x_off / out_off: the rows begin that many floats (0 .. 3) behind a 256-byte boundary (``guard.Guards.empty_at``): base
+        addresses aligned to 4 or 8 bytes only (in place: x_off for both).  Statistics and workspace stay aligned."""
         self.engine, self.rows, self.fs = engine, rows, fs
         self.R = len(rows)
         self.lens = [int(r.shape[0]) for r in rows]
@@ -73,9 +75,9 @@ class _Call:
         host = np.full((self.R, self.stride), np.nan, dtype=np.float32)
         for r, x in enumerate(rows):
             host[r, :min(self.lens[r], self.stride)] = x[:self.stride]
-        self.x = g.empty((self.R, self.stride), device=dev, name="x")
+        self.x = g.empty_at((self.R, self.stride), x_off, device=dev, name="x")
         self.x.copy_(torch.from_numpy(host))
-        self.out = self.x if inplace else g.empty((self.R, self.stride), device=dev, name="out")
+        self.out = self.x if inplace else g.empty_at((self.R, self.stride), out_off, device=dev, name="out")
         if not inplace:
             self.out.fill_(NAN)
         self.stats = g.empty((self.R, 4), dtype=torch.float64, device=dev, name="stats")
@@ -162,6 +164,55 @@ def test_a_row_has_the_bits_of_its_own_call(engine, batch):
         assert one.run() == 0
         o1, s1 = one.results()
         assert np.array_equal(_bits(s1[0]), _bits(stats[r])) and np.array_equal(_bits(o1[0, :n]), _bits(out[r, :n])), (batch, r, s1[0], stats[r])
+
+
+# (x offset, out offset) in floats: together and separately - one misaligned pointer is enough to leave the 16-byte gain kernel
+OFFSETS = [(1, 1), (2, 2), (3, 3), (1, 0), (0, 3), (2, 1)]
+
+
+def _aligned_rows():
+    return [L.pcm_noise(16777, 51), L.pcm_noise(8001, 52), L.sine(16777, 16000), L.pcm_noise(6399, 53)]
+
+
+def _aligned_ref(engine, kind, target):
+    if ("aligned", kind) not in _REF:
+        call = _Call(engine, _aligned_rows())
+        assert call.run(kind, target) == 0
+        _REF["aligned", kind] = call.results()
+    return _REF["aligned", kind]
+
+
+@pytest.mark.parametrize("kind,target", [("ebu", -23.0), ("peak", -1.0)])
+@pytest.mark.parametrize("offs", OFFSETS, ids=lambda o: "x%d-out%d" % o)
+def test_rows_at_unaligned_addresses_have_the_bits_of_the_aligned_call(engine, offs, kind, target):
+    """The gain pass moves 16 bytes per thread where both rows' bases are 16-byte aligned and one sample per thread otherwise
+    (``loudness_gain_kernel<1>``); the two walks read sample by sample.  Rows of 16777 and 8001 samples (no multiple of 4: the last
+    group of four straddles the length) at a stride of 16780 whose base is aligned to a float and nothing wider: the statistics
+    and the rows of the aligned call, bit for bit, zeros behind each length, guards intact (they begin at the very next float) -
+    out of place, in place and measuring alone."""
+    xo, oo = offs
+    rows = _aligned_rows()
+    out, stats = _aligned_ref(engine, kind, target)
+    call = _Call(engine, rows, x_off=xo, out_off=oo)
+    assert call.x.data_ptr() % 16 == 4 * xo and call.out.data_ptr() % 16 == 4 * oo
+    assert call.run(kind, target) == 0, engine.lib.nomad_last_error()
+    got, gstats = call.results()
+    assert np.array_equal(_bits(gstats), _bits(stats)), "statistics"
+    assert np.array_equal(_bits(got), _bits(out)), "rows (zeros behind the lengths included)"
+    for r, x in enumerate(rows):
+        n = x.shape[0]
+        assert np.array_equal(_bits(got[r, :n]), _bits(L.apply(x, gstats[r, 2]))), (r, "the row is not float32(float64(x) gain)")
+        assert not got[r, n:].any() and not np.isnan(got[r, n:]).any(), f"row {r}: not zero behind the length"
+    if xo:
+        inplace = _Call(engine, rows, inplace=True, x_off=xo)
+        assert inplace.out.data_ptr() == inplace.x.data_ptr() and inplace.x.data_ptr() % 16 == 4 * xo
+        assert inplace.run(kind, target) == 0
+        got3, stats3 = inplace.results()
+        assert np.array_equal(_bits(got3), _bits(out)) and np.array_equal(_bits(stats3), _bits(stats)), "in place"
+        only = _Call(engine, rows, x_off=xo, out_off=oo)
+        assert only.run(kind, target, out=False) == 0
+        got4, stats4 = only.results()
+        assert np.isnan(got4).all() and np.array_equal(_bits(stats4), _bits(stats)), "measure only"
 
 
 def test_the_ceiling_lowers_the_gain_exactly(engine):

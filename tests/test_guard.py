@@ -31,6 +31,22 @@ def test_write_one_before_is_reported():
     assert len(bad) == 1 and bad[0][:2] == ("emb", "before") and bad[0][3] >= guard.OUT_GUARD - 4
 
 
+@pytest.mark.parametrize("offset", [0, 1, 2, 3])
+def test_a_view_at_an_element_offset_is_guarded_from_the_very_next_element(offset):
+    """``empty_at``: the tensor begins ``offset`` floats behind an aligned address, and the float in front of it and the float
+    behind it already belong to the guards."""
+    g = guard.Guards()
+    t = g.empty_at((3, 5), offset, torch.float32, "cpu", name="rows")
+    assert t.shape == (3, 5) and t.is_contiguous() and t.data_ptr() % 16 == 4 * offset
+    t.fill_(2.0)
+    assert g.damaged() == []
+    _outside(t, -1).fill_(0.0)
+    assert [b[:3] for b in g.damaged()] == [("rows", "before", 4)] and g.damaged()[0][3] == guard.OUT_GUARD + 4 * offset - 4
+    _outside(t, -1).view(torch.uint8).fill_(guard.PATTERN)
+    _outside(t, t.numel()).fill_(0.0)
+    assert g.damaged() == [("rows", "after", 4, 0)]
+
+
 def test_bytes_equal_to_the_pattern_are_invisible_only_if_they_match():
     """The check compares bytes with the pattern: a float whose bytes are the pattern's (the one value that escapes) is not
     something a kernel produces; 0, NaN and any ordinary value are seen."""
