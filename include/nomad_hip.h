@@ -24,6 +24,8 @@
  *   nomad_degrade_noise / _clip    noise at a target SNR and percentile clipping of src/utils/degradations.py (:30-68, :70-83), G levels
  *                                  per clip, written as the packed batch nomad_embed_ragged reads
  *   nomad_degrade_convolve         every clip convolved with G impulse responses (reverberation as a causal FIR filter), same layout
+ *   nomad_degrade_reverb           sox's `reverb P` of src/utils/degradations.py (:97-101) as comb and all-pass recurrences, G reverberance
+ *                                  levels per clip, same layout (restated from memory of sox 14.4; not checked against the binary)
  *   nomad_degrade_normalize        BS.1770-4 loudness (or rms / peak level) of packed rows and the linear gain to a target, in place:
  *                                  the ffmpeg-normalize step of audio_degrader_training.py / audio_degrader_test.py
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
@@ -53,8 +55,8 @@
  *   Alignment.  Device pointers are expected 16-byte aligned: what hipMalloc and torch's allocator return, and any slice of
  *     whole rows of such a buffer whose row is a multiple of 16 bytes (packed ragged rows: stride % 4 == 0; embeddings; layer
  *     outputs).  Two exceptions need only the 4-byte alignment of a float: a [B][n_samples] waveform batch may be passed
- *     from any whole row on, whatever n_samples is (the front end reads samples one by one); and the sample rows of the four
- *     degradation calls - x_dev, out_dev, noise_dev and ir_dev of nomad_degrade_noise / _clip / _convolve / _normalize - which
+ *     from any whole row on, whatever n_samples is (the front end reads samples one by one); and the sample rows of the five
+ *     degradation calls - x_dev, out_dev, noise_dev and ir_dev of nomad_degrade_noise / _clip / _convolve / _reverb / _normalize - which
  *     are read and written sample by sample (convolve and normalize move 16 bytes at a time only where they find the addresses
  *     aligned).  Workspaces, scratch and float64 statistics are always 16-byte aligned.
  */
@@ -785,6 +787,69 @@ size_t nomad_degrade_normalize_scratch_bytes(int R, int stride, int sample_rate)
 int nomad_degrade_normalize(nomad_ctx* ctx, const float* x_dev, int R, int stride, const int* lens_host, int sample_rate, int mode,
                             double target, double peak_db, float* out_dev, double* stats_out_dev, void* ws_dev, size_t ws_bytes,
                             nomad_stream_t stream);
+
+/* ---- sox-style reverb on packed clips: the Freeverb comb and all-pass recurrences, G reverberance levels per clip --------
+ * The reference renders its REVERB conditions with sox's `reverb P` (src/utils/degradations.py), P = reverberance in 0 .. 100.
+ * nomad_degrade_convolve above cannot stand in for it: at P = 100 the comb feedback is 0.98 on loops of about 500 samples, and
+ * after 65536 taps the response has fallen by only about 25 dB.  This call runs the reverberator itself.
+ *
+ * WHAT THIS IS NOT: a port checked against sox.  The algorithm below is restated from memory of sox 14.4 reverb.c; neither sox
+ * nor torchaudio was available where it was written, so its agreement with the sox binary has never been measured.  The text
+ * below is the definition, and tests/freeverb_ref.py restates it sample by sample.
+ *
+ * Parameters (sox's names; range; sox's default): reverberance[g] 0 .. 100 (50), hf_damping 0 .. 100 (50), room_scale 0 .. 100 (100),
+ * stereo_depth 0 .. 100 (100), pre_delay_ms 0 .. 500 (0), wet_gain_db -10 .. 10 (0), wet_only 0 / 1 (0).  fs = sample_rate.
+ * All of the following is float64:
+ *   a = -1 / ln(1 - 0.3);  b = 100 / (ln(1 - 0.98) a + 1);  feedback = 1 - exp((reverberance - b) / (a b))
+ *   damp = hf_damping / 100 * 0.3 + 0.2;  gain = 10^(wet_gain_db / 20) * 0.015
+ *   scale = room_scale / 100 * 0.9 + 0.1;  depth = stereo_depth / 100;  r = fs * (1 / 44100.)
+ *   pre = (int)(pre_delay_ms / 1000 * fs + 0.5)
+ *   comb lengths {1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617};  all-pass {225, 341, 441, 556};  stereo adjust 12
+ *   channels c = 0 .. ceil(depth):  off = c * depth, its sign flipping after EVERY filter, combs first, then the all-passes:
+ *       comb i:      D = (int)(scale * r * (len_i + 12 * off) + 0.5);  off = -off
+ *       all-pass j:  D = (int)(        r * (len_j + 12 * off) + 0.5);  off = -off      (not scaled by the room)
+ * (16 kHz, defaults: channel 0 combs 405 431 463 492 516 541 565 587, all-passes 82 124 160 202; channel 1 combs 409 427 468 488 520
+ * 537 569 582, all-passes 86 119 164 197; feedback 0.3 at reverberance 0, 0.8816784043380077 at 50, 0.98 at 100.)
+ * Per channel and sample t, in = x[t - pre] (0 before the start), every delay line and store starting at zero:
+ *   acc = 0;  for i = 7 down to 0:  o = line_i[t - D_i];  store_i = o + (store_i - o) * damp;
+ *                                    line_i[t] = in + store_i * feedback;  acc += o
+ *   for j = 3 down to 0:  o = ap_j[t - D_j];  ap_j[t] = acc + o * 0.5;  acc = o - acc
+ *   wet_c[t] = acc * gain
+ * The clip is mono and so is the row: y[t] = (1 - wet_only) x[t] + mean_c wet_c[t] (two channels: 0.5 (wet_0 + wet_1); stereo_depth = 0:
+ * one channel), cut to the clip's length - no tail, as nomad_degrade_convolve.  With clamp != 0 the result is limited as sox's sample
+ * conversion does, v > 1 ? 1 : v < -1 ? -1 : v (a NaN stays a NaN); then ONE rounding to fp32.
+ *
+ * x_dev is [B][stride] fp32 with lens_host as above (nothing behind a length is read); out_dev is [B G][stride] fp32, row b G + g
+ * being clip b at params->reverberance[g], zeros from its length to the stride; the other parameters are shared by the call.
+ * How it runs (csrc/reverb.hip.h): a workgroup per (row, channel), a wave per comb with its delay line as a ring in LDS, time in
+ * tiles of T = min(64, the call's shortest delay) samples - one per lane - inside which only the one-pole `store` is a chain: a
+ * fixed-order scan across the lanes; a ninth wave adds the combs' outputs in the order 7 .. 0 and runs the all-passes; the wet
+ * signal of each channel goes to the workspace as float64 and a second kernel mixes, limits and rounds.  State and arithmetic are
+ * float64, there are no atomics, and every order is fixed by the clip's length and the shared parameters: row b G + g has the bits of
+ * the clip's own B = 1, G = 1 call.  Against the sample-by-sample recurrence the scan reassociates (a few units of 2^-53 per
+ * sample, amplified by at most 1 / (1 - feedback) <= 50).
+ * Non-finite input: a non-finite sample at position p of clip b makes every row of b non-finite at p (and, through the loops,
+ * possibly anywhere from there on); outputs at indices below p - p % 64 keep the bits of the clean run; no row of another clip
+ * changes; zeros stay behind every length.  (With clamp != 0 it is a NaN that stays: an infinite value is limited to +-1 like any
+ * other value beyond the range, as the formula above says.)
+ * Contract as the degradations above: asynchronous, no allocation, deterministic, the caller's stream; the lengths and the
+ * parameters are copied (the struct is read during the call, the tables go into the workspace ahead of the kernels), so both host
+ * objects may die on return.  Workspace: nomad_degrade_reverb_scratch_bytes(B, stride, G, sample_rate) bytes (0 for arguments the
+ * call would refuse) = two small tables + 16 bytes per output sample, written before it is read.  Argument errors return before
+ * anything is queued.
+ * NOMAD_ERR_INVALID: a NULL pointer, G outside 1 .. 64, B outside 1 .. 65535, stride not a positive multiple of 4 or shorter than a
+ * length, a length < 1, a parameter outside its range above or not finite, sample_rate outside 8000 .. 48000, out_dev overlapping
+ * x_dev.  NOMAD_ERR_WORKSPACE: ws_bytes too small.
+ */
+typedef struct {
+    int G;
+    double reverberance[64];
+    double hf_damping, room_scale, stereo_depth, pre_delay_ms, wet_gain_db;
+    int wet_only, clamp, sample_rate;
+} nomad_reverb_params;
+size_t nomad_degrade_reverb_scratch_bytes(int B, int stride, int G, int sample_rate);
+int nomad_degrade_reverb(nomad_ctx* ctx, const float* x_dev, int B, int stride, const int* lens_host, const nomad_reverb_params* params_host,
+                         float* out_dev, void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
 
 /* ---- bf16 path (BASELINE config C5: long-form clips) ---------------------------------------- */
 /*

@@ -9,7 +9,8 @@ the files shard across the ranks (RCCL all-gather of the embeddings, ``Nomad.pre
 (``Nomad.predict_spans``, ``spans.csv``).
 
 ``--sweep`` (one process): ``--deg`` holds CLEAN files, which are degraded on the GPU at every level of ``--snr-db`` (with ``--noise
-FILE``), ``--clip`` and / or ``--rt60`` (synthetic rooms, ``nomad_amd.nomad.synthetic_rir``) and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level.  ``--normalize [LUFS]`` brings every
+FILE``), ``--clip`` and / or ``--rt60`` (synthetic rooms, ``nomad_amd.nomad.synthetic_rir``) or ``--reverb`` (sox's reverb at its reverberance
+levels, ``Nomad.reverb``) and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level.  ``--normalize [LUFS]`` brings every
 degraded clip to one BS.1770 loudness first (bare: -23), as the reference's ``ffmpeg-normalize`` step does."""
 import argparse
 import os
@@ -39,7 +40,7 @@ def sweep(nomad, a):
     refs = nomad.get_embeddings(a.nmr).set_index("filename")
     refs = torch.from_numpy(refs.to_numpy(dtype="float32").copy())
     noise = nomad.load_processing(a.noise).reshape(-1) if a.noise is not None else None
-    reverb = {"rt60_s": a.rt60} if a.rt60 is not None else {}
+    reverb = {"rt60_s": a.rt60} if a.rt60 is not None else {"reverberance": a.reverb} if a.reverb is not None else {}
     if a.normalize is not None:
         reverb["normalize"] = a.normalize
     results = nomad.intensity_sweep(a.deg, refs, noise=noise, snr_db=a.snr_db, clip_factor=a.clip, k=a.knn, **reverb)
@@ -84,13 +85,17 @@ def main(argv=None):
                     help="score what is not silent: one score per test file over the frames within DB dB of its loudest frame (an "
                          "energy gate, not a speech detector; predict_spans)")
     ap.add_argument("--sweep", action="store_true",
-                    help="--deg holds CLEAN files: degrade them on the GPU at every level of --snr-db / --clip / --rt60, score the result against "
+                    help="--deg holds CLEAN files: degrade them on the GPU at every level of --snr-db / --clip / --rt60 / --reverb, score the result against "
                          "--nmr and report how well the score ranks the levels (nomad_intensity.csv, Nomad.intensity_sweep)")
     ap.add_argument("--noise", type=str, default=None, metavar="FILE", help="--sweep: the noise recording mixed in at --snr-db")
     ap.add_argument("--snr-db", dest="snr_db", type=_levels, default=None, metavar="A,B,...", help="--sweep: target SNRs in dB")
     ap.add_argument("--clip", type=_levels, default=None, metavar="A,B,...", help="--sweep: clip factors, percent of samples clipped")
     ap.add_argument("--rt60", type=_levels, default=None, metavar="A,B,...",
-                    help="--sweep: reverberation times in seconds (synthetic diffuse rooms, not sox's reverb), each in (0, 4.096]")
+                    help="--sweep: reverberation times in seconds (synthetic diffuse rooms, not sox's reverb: that is --reverb), each in "
+                         "(0, 4.096]")
+    ap.add_argument("--reverb", type=_levels, default=None, metavar="A,B,...",
+                    help="--sweep: sox's reverb (its comb and all-pass reverberator, the reference's REVERB degradation) at these "
+                         "reverberance levels, each in 0 .. 100, sox's defaults otherwise; excludes --rt60")
     ap.add_argument("--normalize", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS",
                     help="--sweep: bring every degraded clip to this BS.1770 integrated loudness before it is scored (bare: -23, EBU R128, "
                          "what the reference's ffmpeg-normalize step does), so that the score ranks the degradation at equal loudness")
@@ -101,6 +106,10 @@ def main(argv=None):
         ap.error("--noise, --snr-db and --clip go with --sweep")
     if not a.sweep and a.rt60 is not None:
         ap.error("--rt60 goes with --sweep")
+    if not a.sweep and a.reverb is not None:
+        ap.error("--reverb goes with --sweep")
+    if a.reverb is not None and a.rt60 is not None:
+        ap.error("--reverb and --rt60 exclude each other: both fill the REVERB rows")
     if a.normalize is not None:
         if not a.sweep:
             ap.error("--normalize goes with --sweep")
@@ -119,17 +128,19 @@ def main(argv=None):
     if a.sweep:
         if a.window is not None:
             ap.error("--sweep scores whole clips: it does not go with --window")
-        if a.snr_db is None and a.clip is None and a.rt60 is None:
-            ap.error("--sweep needs levels: --snr-db (with --noise), --clip or both, or --rt60")
+        if a.snr_db is None and a.clip is None and a.rt60 is None and a.reverb is None:
+            ap.error("--sweep needs levels: --snr-db (with --noise), --clip or both, or --rt60, or --reverb")
         if (a.snr_db is None) != (a.noise is None):
             ap.error("--noise and --snr-db go together")
-        for name, levels in (("--snr-db", a.snr_db), ("--clip", a.clip), ("--rt60", a.rt60)):
+        for name, levels in (("--snr-db", a.snr_db), ("--clip", a.clip), ("--rt60", a.rt60), ("--reverb", a.reverb)):
             if levels is not None and not 1 <= len(levels) <= 64:
                 ap.error(f"{name} takes 1 to 64 levels, got {len(levels)}")
         if a.clip is not None and not all(0.0 <= v <= 100.0 for v in a.clip):
             ap.error(f"--clip takes percentages from 0 to 100, got {a.clip}")
         if a.rt60 is not None and not all(0.0 < v <= 4.096 for v in a.rt60):
             ap.error(f"--rt60 takes seconds above 0 up to 4.096, got {a.rt60}")
+        if a.reverb is not None and not all(0.0 <= v <= 100.0 for v in a.reverb):
+            ap.error(f"--reverb takes reverberance levels from 0 to 100, got {a.reverb}")
     if a.knn is not None and not 1 <= a.knn <= 64:
         ap.error(f"--knn takes a number of references from 1 to 64, got {a.knn}")
     world = int(os.environ.get("WORLD_SIZE", "1"))

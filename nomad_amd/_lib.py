@@ -30,6 +30,13 @@ class WavInfo(C.Structure):
                 ("frames", C.c_longlong), ("data_offset", C.c_longlong)]
 
 
+class ReverbParams(C.Structure):
+    """nomad_reverb_params (include/nomad_hip.h): the G reverberance levels of one nomad_degrade_reverb call and what they share."""
+    _fields_ = [("G", C.c_int), ("reverberance", C.c_double * 64), ("hf_damping", C.c_double), ("room_scale", C.c_double),
+                ("stereo_depth", C.c_double), ("pre_delay_ms", C.c_double), ("wet_gain_db", C.c_double), ("wet_only", C.c_int),
+                ("clamp", C.c_int), ("sample_rate", C.c_int)]
+
+
 # name -> (restype, argtypes): the complete export list of include/nomad_hip.h
 SIGNATURES = {
     "nomad_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Weights)]),
@@ -63,6 +70,9 @@ SIGNATURES = {
     "nomad_degrade_convolve_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "nomad_degrade_convolve": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, C.c_int, C.c_int, C.POINTER(C.c_int),
                                          _fp, _fp, C.c_size_t, _fp]),
+    "nomad_degrade_reverb_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nomad_degrade_reverb": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(ReverbParams), _fp, _fp, C.c_size_t,
+                                       _fp]),
     "nomad_degrade_normalize_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nomad_degrade_normalize": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_double, C.c_double,
                                           _fp, _fp, _fp, C.c_size_t, _fp]),

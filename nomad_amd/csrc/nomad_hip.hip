@@ -27,6 +27,7 @@
 #include "backward.hip.h"
 #include "degrade.hip.h"
 #include "degrade_convolve.hip.h"
+#include "reverb.hip.h"
 #include "loudness.hip.h"
 #include "frontend.hip.h"
 #include "gemm_bf16.hip.h"
@@ -4077,6 +4078,94 @@ int nomad_degrade_normalize(nomad_ctx* c, const float* x, int R, int stride, con
             hipLaunchKernelGGL(loudness_gain_kernel<1>, dim3((unsigned)((stride + 255) / 256), (unsigned)R), dim3(256), 0, s, x, stride,
                                lens_dev, static_cast<const double*>(stats), out);
     }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- sox-style reverb: comb and all-pass recurrences (reverb.hip.h) ----
+// Scratch: [lengths: B int32, to 256 bytes | feedback: G float64, to 256 bytes | wet [2][B G][stride] float64].
+struct ReverbLayout {
+    size_t feedback, wet, plane, total;   // plane: doubles per channel
+};
+static ReverbLayout reverb_layout(int B, int stride, int G) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    ReverbLayout l;
+    l.feedback = up(sizeof(int) * (size_t)B);
+    l.wet = l.feedback + up(sizeof(double) * (size_t)G);
+    l.plane = (size_t)B * (size_t)G * (size_t)stride;
+    l.total = l.wet + 2 * sizeof(double) * l.plane;
+    return l;
+}
+static bool reverb_shape_ok(int B, int stride, int G, int sample_rate) {
+    return B >= 1 && B <= 65535 && G >= 1 && G <= kReverbMaxLevels && stride >= 4 && stride % 4 == 0 && sample_rate >= 8000 &&
+           sample_rate <= 48000;
+}
+
+size_t nomad_degrade_reverb_scratch_bytes(int B, int stride, int G, int sample_rate) {
+    if (!reverb_shape_ok(B, stride, G, sample_rate)) {
+        (void)fail(NOMAD_ERR_INVALID,
+                   "nomad_degrade_reverb_scratch_bytes: bad argument (B=%d: 1 .. 65535, stride=%d: a positive multiple of 4, G=%d: 1 .. %d, "
+                   "sample_rate=%d: 8000 .. 48000)", B, stride, G, kReverbMaxLevels, sample_rate);
+        return 0;
+    }
+    return reverb_layout(B, stride, G).total;
+}
+
+int nomad_degrade_reverb(nomad_ctx* c, const float* x, int B, int stride, const int* lens, const nomad_reverb_params* params, float* out,
+                         void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_degrade_reverb";
+    if (!c || !x || !lens || !params || !out || !ws)
+        return fail(NOMAD_ERR_INVALID, "%s: a NULL context, input, lengths, parameters, output or workspace", who);
+    const nomad_reverb_params q = *params;   // the caller's struct is read here and never again
+    const int G = q.G;
+    if (G < 1 || G > kReverbMaxLevels) return fail(NOMAD_ERR_INVALID, "%s: G=%d levels, 1 .. %d are supported", who, G, kReverbMaxLevels);
+    if (B < 1 || B > 65535) return fail(NOMAD_ERR_INVALID, "%s: B=%d clips, 1 .. 65535 are supported", who, B);
+    if (stride < 4 || stride % 4) return fail(NOMAD_ERR_INVALID, "%s: stride=%d is not a positive multiple of 4", who, stride);
+    if (q.sample_rate < 8000 || q.sample_rate > 48000)
+        return fail(NOMAD_ERR_INVALID, "%s: sample_rate=%d, 8000 .. 48000 is supported", who, q.sample_rate);
+    auto in_range = [](double v, double lo, double hi) { return std::isfinite(v) && v >= lo && v <= hi; };
+    for (int g = 0; g < G; ++g)
+        if (!in_range(q.reverberance[g], 0.0, 100.0))
+            return fail(NOMAD_ERR_INVALID, "%s: reverberance[%d]=%g, 0 .. 100 is supported", who, g, q.reverberance[g]);
+    if (!in_range(q.hf_damping, 0.0, 100.0) || !in_range(q.room_scale, 0.0, 100.0) || !in_range(q.stereo_depth, 0.0, 100.0))
+        return fail(NOMAD_ERR_INVALID, "%s: hf_damping=%g, room_scale=%g, stereo_depth=%g: each 0 .. 100", who, q.hf_damping, q.room_scale,
+                    q.stereo_depth);
+    if (!in_range(q.pre_delay_ms, 0.0, 500.0)) return fail(NOMAD_ERR_INVALID, "%s: pre_delay_ms=%g, 0 .. 500 is supported", who, q.pre_delay_ms);
+    if (!in_range(q.wet_gain_db, -10.0, 10.0)) return fail(NOMAD_ERR_INVALID, "%s: wet_gain_db=%g, -10 .. 10 is supported", who, q.wet_gain_db);
+    if ((q.wet_only != 0 && q.wet_only != 1) || (q.clamp != 0 && q.clamp != 1))
+        return fail(NOMAD_ERR_INVALID, "%s: wet_only=%d and clamp=%d are 0 or 1", who, q.wet_only, q.clamp);
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 1 || lens[b] > stride)
+            return fail(NOMAD_ERR_INVALID, "%s: clip %d has length %d, 1 .. stride=%d are supported", who, b, lens[b], stride);
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(x), oa = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t xbytes = sizeof(float) * (size_t)B * (size_t)stride, obytes = xbytes * (size_t)G;
+    if (oa < xa + xbytes && xa < oa + obytes) return fail(NOMAD_ERR_INVALID, "%s: the output overlaps the input", who);
+    const ReverbPlan plan = reverb_plan(q.hf_damping, q.room_scale, q.stereo_depth, q.pre_delay_ms, q.wet_gain_db, q.wet_only, q.clamp, q.sample_rate);
+    const size_t lds = sizeof(double) * (size_t)plan.lds_doubles;
+    if (plan.tile < 1 || lds > kReverbLdsMax)
+        return fail(NOMAD_ERR_INVALID, "%s: delays from %d samples, %zu bytes of delay lines: outside what a workgroup holds", who, plan.tile, lds);
+    const ReverbLayout l = reverb_layout(B, stride, G);
+    if (ws_bytes < l.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    if (lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(reverb_wet_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    // the lengths and the levels' feedback, staged in the context's ring and copied ahead of the kernels
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(l.wet, 0);
+    memcpy(staged.data(), lens, sizeof(int) * (size_t)B);
+    double* fb = reinterpret_cast<double*>(staged.data() + l.feedback);
+    for (int g = 0; g < G; ++g) fb[g] = reverb_feedback(q.reverberance[g]);
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), l.wet, hipMemcpyHostToDevice, s));
+    double samples = 0.0;
+    for (int b = 0; b < B; ++b) samples += lens[b];
+    Scope sc(c, s, NOMAD_K_ROW, samples * G * plan.channels * (kReverbCombs * 7.0 + kReverbAllpass * 3.0 + 1.0));
+    const int* lens_dev = reinterpret_cast<const int*>(w);
+    double* wet = reinterpret_cast<double*>(w + l.wet);
+    hipLaunchKernelGGL(reverb_wet_kernel, dim3((unsigned)(B * G), (unsigned)plan.channels), dim3(kReverbThreads), lds, s, x, stride, lens_dev,
+                       reinterpret_cast<const double*>(w + l.feedback), G, plan, wet);
+    hipLaunchKernelGGL(reverb_mix_kernel, dim3((unsigned)(B * G)), dim3(256), 0, s, x, stride, lens_dev, G, static_cast<const double*>(wet),
+                       l.plane, plan, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -648,6 +648,54 @@ class Engine:
                                                    self._stream()), "nomad_degrade_convolve")
         return out, [n for n in lens for _ in range(G)]
 
+    REVERB_RANGES = {"reverberance": (0.0, 100.0), "hf_damping": (0.0, 100.0), "room_scale": (0.0, 100.0), "stereo_depth": (0.0, 100.0),
+                     "pre_delay_ms": (0.0, 500.0), "wet_gain_db": (-10.0, 10.0)}
+
+    @staticmethod
+    def check_reverb(reverberance, hf_damping=50, room_scale=100, stereo_depth=100, pre_delay_ms=0, wet_gain_db=0, wet_only=False,
+                     clamp=True, sample_rate=16000):
+        """The arguments of ``degrade_reverb`` that need no GPU -> the ``nomad_reverb_params`` struct the C ABI takes."""
+        levels = [float(v) for v in (reverberance.tolist() if hasattr(reverberance, "tolist") else
+                                     reverberance if isinstance(reverberance, (list, tuple)) else [reverberance])]
+        if not 1 <= len(levels) <= 64:
+            raise ValueError(f"degrade_reverb takes 1 .. 64 reverberance levels per call, got {len(levels)}")
+        shared = dict(hf_damping=float(hf_damping), room_scale=float(room_scale), stereo_depth=float(stereo_depth),
+                      pre_delay_ms=float(pre_delay_ms), wet_gain_db=float(wet_gain_db))
+        for name, values in [("reverberance", levels)] + [(k, [v]) for k, v in shared.items()]:
+            lo, hi = Engine.REVERB_RANGES[name]
+            for v in values:
+                if not (math.isfinite(v) and lo <= v <= hi):
+                    raise ValueError(f"{name} must be finite and in {lo:g} .. {hi:g}, got {v}")
+        sample_rate = int(sample_rate)
+        if not 8000 <= sample_rate <= 48000:
+            raise ValueError(f"sample_rate must be in 8000 .. 48000, got {sample_rate}")
+        params = _lib.ReverbParams(G=len(levels), wet_only=int(bool(wet_only)), clamp=int(bool(clamp)), sample_rate=sample_rate, **shared)
+        params.reverberance[:len(levels)] = levels
+        return params
+
+    def degrade_reverb(self, waves, reverberance, lengths=None, hf_damping=50, room_scale=100, stereo_depth=100, pre_delay_ms=0,
+                       wet_gain_db=0, wet_only=False, clamp=True, sample_rate=16000):
+        """Sox-style reverb (``sox ... reverb P``: Freeverb's eight combs and four all-passes per channel) at G reverberance levels,
+        0 .. 100, the other parameters - sox's names, ranges and defaults - shared: waves as ``degrade_noise`` takes them -> (out
+        (B G, stride) fp32 on the device, lengths repeated G times): row b G + g is clip b at reverberance[g], the two output
+        channels averaged, cut to the clip's length and zero behind it; ``(out, lengths)`` goes into ``embed_ragged(packed=...)``
+        without another copy.  The recurrences run in float64 with one rounding to fp32 (``nomad_degrade_reverb``; include/nomad_hip.h
+        states the algorithm, which is restated from memory of sox 14.4 and has not been checked against the sox binary)."""
+        params = self.check_reverb(reverberance, hf_damping, room_scale, stereo_depth, pre_delay_ms, wet_gain_db, wet_only, clamp, sample_rate)
+        if lengths is not None:
+            buf, lens = self.pack_ragged(waves, lengths)
+            if buf.shape[1] % 4:     # a padded tensor whose row stride is no multiple of 4: through the packer after all
+                buf, lens = self._pack([buf[i, :n] for i, n in enumerate(lens)])
+        else:
+            buf, lens = self._pack(waves)
+        B, stride = buf.shape
+        G = params.G
+        out = torch.empty(B * G, stride, dtype=torch.float32, device=self.device)
+        ws = self._workspace(int(self.lib.nomad_degrade_reverb_scratch_bytes(B, stride, G, params.sample_rate)))
+        _lib.check(self.lib.nomad_degrade_reverb(self.ctx, buf.data_ptr(), B, stride, (C.c_int * B)(*lens), C.byref(params), out.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), self._stream()), "nomad_degrade_reverb")
+        return out, [n for n in lens for _ in range(G)]
+
     @staticmethod
     def check_normalize(target, kind, peak_db, sample_rate):
         """The arguments of ``degrade_normalize`` that need no GPU -> (mode, target, peak_db as the C ABI takes them)."""

@@ -1004,8 +1004,9 @@ def synthetic_rir(rt60_s, seed: int = 0, drr_db: float = 0.0) -> np.ndarray:
     ``h[0] = 1`` and, from tap 1 on, Gaussian noise (``np.random.RandomState(seed).standard_normal(L)``; its first value is not used)
     under an envelope that has fallen by 60 dB at ``rt60_s``, ``10^(-3 k / (rt60_s 16000))``, scaled so that the tail's energy is
     ``10^(-drr_db / 10)`` - ``drr_db`` is the direct-to-reverberant ratio.  rt60_s: finite, in (0, 4.096] seconds.  This is NOT
-    sox's reverb (Freeverb: comb and all-pass filters with its own parameters), which the reference's renderings use: it is a
-    stand-in with a stated RT60 for sweeps and augmentation; measured responses go into ``convolve`` as they are."""
+    sox's reverb (Freeverb: comb and all-pass filters with its own parameters), which the reference's renderings use - that one is
+    ``Nomad.reverb``: it is a stand-in with a stated RT60 for sweeps and augmentation; measured responses go into ``convolve`` as
+    they are."""
     rt60_s, drr_db = float(rt60_s), float(drr_db)
     if not (math.isfinite(rt60_s) and 0.0 < rt60_s <= 4.096):
         raise ValueError(f"rt60_s must be finite and in (0, 4.096] seconds, got {rt60_s}")
@@ -1632,9 +1633,11 @@ class Nomad:
     # ---- degradations on the device ----------------------------------------------------------------------------------
     def _degrade_packed(self, buf, lens, kind: str, levels, noise):
         """One degradation of a packed device batch -> (rows (B G, stride), lengths repeated G times, alpha or thresholds or None);
-        kind "reverb": ``noise`` holds the responses."""
+        kind "reverb": ``noise`` holds the responses; kind "freeverb" (sox's reverb at ``levels``): the shared parameters, a dict."""
         if kind == "reverb":
             return self.engine.degrade_convolve(buf, noise, lengths=lens) + (None,)
+        if kind == "freeverb":
+            return self.engine.degrade_reverb(buf, levels, lengths=lens, **(noise or {})) + (None,)
         if kind == "noise":
             return self.engine.degrade_noise(buf, noise, levels, lengths=lens)
         return self.engine.degrade_clip(buf, levels, lengths=lens)
@@ -1649,7 +1652,8 @@ class Nomad:
         stands.  kind "clip": ``levels`` are clip factors in percent (0 .. 100): samples are clamped to the clip's own percentiles
         ``cf / 2`` and ``100 - cf / 2`` (numpy's linear rule, exact order statistics).  Both change the level with the
         degradation; the loudness normalisation the reference's rendering scripts apply afterwards is ``normalize`` (or
-        ``intensity_sweep(normalize=...)``).  Codecs are not offered; reverberation is ``convolve``.  No gradient."""
+        ``intensity_sweep(normalize=...)``).  Codecs are not offered; reverberation is ``convolve`` (impulse responses) or ``reverb``
+        (sox's reverberator).  No gradient."""
         if kind not in ("noise", "clip"):
             raise ValueError(f"kind must be 'noise' or 'clip', got {kind!r}")
         if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
@@ -1672,7 +1676,7 @@ class Nomad:
         length (``lengths`` comes back repeated G times; every row is zero behind its length).  wav (B,1,N) or (B,N); lengths: the
         clips' exact lengths (any length from 1 sample); irs: a list of 1 .. 64 1-D responses of 1 .. 65536 taps each, or a (G,L)
         tensor with optional ``ir_lengths`` - measured rooms, or ``synthetic_rir``.  For a fixed setting a reverberator is this
-        filter; sox's parameters and codecs are not offered, the loudness normalisation of the reference's rendering scripts is
+        filter; sox's parameters are ``reverb``'s, codecs are not offered, the loudness normalisation of the reference's rendering scripts is
         ``normalize`` (a room adds its tail's energy).  fp32
         products and sums (``nomad_degrade_convolve``); a row does not depend on the batch it is made in.  No gradient."""
         if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
@@ -1687,6 +1691,20 @@ class Nomad:
         x = (x.squeeze(1) if x.dim() == 3 else x).contiguous()
         lens = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)] if lengths is not None else [x.shape[1]] * x.shape[0]
         return self.engine.degrade_convolve(x, irs, lengths=lens, ir_lengths=ir_lengths)
+
+    def reverb(self, wav, reverberance, lengths=None, **params):
+        """Sox-style reverberant copies of clean clips, made on the GPU - the reference's REVERB degradation (``sox ... reverb P``,
+        ``utils/degradations.py``) at its own condition values: -> (clips (B G, stride) fp32 on the GPU, lengths): row ``b G + g``
+        is clip ``b`` at ``reverberance[g]`` (0 .. 100, 1 .. 64 levels), the reverberator's two channels averaged, cut to the clip's
+        length (``lengths`` comes back repeated G times; every row is zero behind its length).  wav (B,1,N) or (B,N); lengths: the
+        clips' exact lengths.  params, shared by the levels, are sox's: ``hf_damping=50, room_scale=100, stereo_depth=100,
+        pre_delay_ms=0, wet_gain_db=0, wet_only=False`` plus ``clamp=True`` (limit to [-1, 1] as sox's sample conversion does) and
+        ``sample_rate=16000``.  The comb and all-pass recurrences run in float64 (``nomad_degrade_reverb``); a row does not depend on
+        the batch it is made in.  The algorithm is restated from memory of sox 14.4 and has NOT been checked against the sox binary.
+        No gradient."""
+        Engine.check_reverb(reverberance, **params)
+        x, lens = self._rows_for_normalize(wav, lengths, "reverb")
+        return self.engine.degrade_reverb(x, reverberance, lengths=lens, **params)
 
     def _rows_for_normalize(self, wav, lengths, what: str):
         """(B,1,N) / (B,N) clips and their lengths as a device tensor and a list, for ``loudness`` and ``normalize``."""
@@ -1759,7 +1777,7 @@ class Nomad:
 
     def intensity_sweep(self, clean, references, noise=None, snr_db=None, clip_factor=None, lengths=None, k=None,
                         max_batch_samples: int = 256 * 64000, rt60_s=None, rir_seed: int = 0, drr_db: float = 0.0,
-                        normalize=None, normalize_kind: str = "ebu"):
+                        normalize=None, normalize_kind: str = "ebu", reverberance=None, reverb_params=None):
         """Does the score rank the strength of a degradation?  The reference's ``intensity`` experiment without rendered files: the
         clean clips are degraded on the GPU (``degrade``) at every level, embedded and scored against ``references`` ((Nr,256), as
         ``score`` takes them); -> {"NOISE": {...}, "CLIP": {...}, "REVERB": {...}}, a degradation whose levels are None being left out.  Each entry is
@@ -1770,8 +1788,10 @@ class Nomad:
         clean: a (B,1,N) / (B,N) tensor (with ``lengths``), a list of 1-D clips, a directory of wav files or a csv file with a
         ``filename`` column (the file pipeline of ``get_embeddings``).  snr_db needs ``noise``, a 1-D signal at 16 kHz.  k: the
         nearest-reference score of ``score(k=...)``.  rt60_s: reverberation times in seconds, each in (0, 4.096]: the clips are
-        convolved (``convolve``) with ``synthetic_rir(rt60, rir_seed, drr_db)`` - a synthetic diffuse room, NOT sox's reverb -
-        and ``Condition`` is the RT60; whether the score ranks it is not claimed.  The clean audio is uploaded once per batch; batches are cut so that the
+        convolved (``convolve``) with ``synthetic_rir(rt60, rir_seed, drr_db)`` - a synthetic diffuse room, NOT sox's reverb (that is ``reverberance``) -
+        and ``Condition`` is the RT60; whether the score ranks it is not claimed.  reverberance: sox's reverb itself (``reverb``)
+        at these levels, 0 .. 100 - the reference's REVERB conditions - with ``reverb_params`` (a dict of ``reverb``'s shared
+        parameters, or None) and ``Condition`` the reverberance; it fills the same ``REVERB`` entry, so it goes without rt60_s.  The clean audio is uploaded once per batch; batches are cut so that the
         G-fold degraded rows stay within ``max_batch_samples`` samples.
 
         normalize: None - the degraded rows are scored at whatever level the degradation left them (noise at 0 dB SNR is 3 dB
@@ -1784,19 +1804,27 @@ class Nomad:
         if normalize is not None:
             Engine.check_normalize(normalize, normalize_kind, None, 16000)
         k = check_k(k, references.shape[0]) if k is not None else None
-        if snr_db is None and clip_factor is None and rt60_s is None:
-            raise ValueError("intensity_sweep needs snr_db, clip_factor or both, or rt60_s")
+        if rt60_s is not None and reverberance is not None:
+            raise ValueError("rt60_s and reverberance both fill the REVERB entry: pass one of them")
+        if reverb_params is not None and reverberance is None:
+            raise ValueError("reverb_params go with reverberance")
+        if reverberance is not None:
+            Engine.check_reverb(np.asarray(reverberance, dtype=np.float64).reshape(-1), **(reverb_params or {}))
+        if snr_db is None and clip_factor is None and rt60_s is None and reverberance is None:
+            raise ValueError("intensity_sweep needs snr_db, clip_factor or both, or rt60_s, or reverberance")
         if snr_db is not None and noise is None:
             raise ValueError("snr_db needs a noise signal: pass noise=")
         if references.requires_grad or (torch.is_tensor(noise) and noise.requires_grad):
             raise ValueError("intensity_sweep produces no gradient (the degradations have no backward): pass tensors that do not require one")
         sweeps = [(name, kind, [float(v) for v in np.asarray(levels, dtype=np.float64).reshape(-1)])
-                  for name, kind, levels in (("NOISE", "noise", snr_db), ("CLIP", "clip", clip_factor), ("REVERB", "reverb", rt60_s))
+                  for name, kind, levels in (("NOISE", "noise", snr_db), ("CLIP", "clip", clip_factor), ("REVERB", "reverb", rt60_s),
+                                             ("REVERB", "freeverb", reverberance))
                   if levels is not None]
         for name, _, levels in sweeps:
             if not 1 <= len(levels) <= 64:
                 raise ValueError(f"{name}: 1 .. 64 levels per sweep, got {len(levels)}")
         rirs = [torch.from_numpy(synthetic_rir(v, rir_seed, drr_db)) for v in sweeps[-1][2]] if rt60_s is not None else None
+        sox_params = dict(reverb_params or {})
         self._need_whole_encoder(self.engine)
         eng = self.engine
         refs = references.detach().to(eng.device, torch.float32).contiguous()
@@ -1808,7 +1836,8 @@ class Nomad:
             for name, kind, levels in sweeps:
                 if kind == "reverb" and isinstance(rirs, list):
                     rirs = eng.pack_responses(rirs)      # packed and uploaded once, with the first batch
-                out, lens_rep, _ = self._degrade_packed(buf, lens, kind, levels, rirs if kind == "reverb" else noise)
+                out, lens_rep, _ = self._degrade_packed(buf, lens, kind, levels,
+                                                        rirs if kind == "reverb" else sox_params if kind == "freeverb" else noise)
                 if normalize is not None:
                     _, _, stats = eng.degrade_normalize(packed=(out, lens_rep), target=normalize, kind=normalize_kind, inplace=True)
                     rows[name][3].append(eng.fetch_async(stats))

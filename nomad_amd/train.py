@@ -687,10 +687,12 @@ class Training:
         """``intensity`` (train_triplet.py:344-401): per degradation, the rank correlation of the mean distance with the
         degradation's level.  -> {degradation: {table, SRCC, embeddings, ref_embeddings}}.
 
-        With the config key ``degrade_on_device: {clean: <dir|csv>, noise: <wav>, snr_db: [...], clip: [...], rt60: [...]}`` (not a
+        With the config key ``degrade_on_device: {clean: <dir|csv>, noise: <wav>, snr_db: [...], clip: [...], rt60: [...], reverb: [...]}`` (not a
         reference key) no rendered files and no ``test_mono_data`` are needed: the clean files are degraded on the GPU at the listed levels
         (``Nomad.intensity_sweep``: additive noise at an SNR, percentile clipping and - ``rt60``, in seconds - convolution with
-        ``synthetic_rir`` rooms) and the result has the same shape, with the degradations ``NOISE``, ``CLIP`` and ``REVERB``.  A
+        ``synthetic_rir`` rooms, which is NOT sox's reverb - or ``reverb``, the reference's own condition values: sox's reverb at these
+        reverberance levels, 0 .. 100, ``Nomad.reverb``; one of the two) and the result has the same shape, with the degradations
+        ``NOISE``, ``CLIP`` and ``REVERB``.  A
         further key ``normalize: -23`` brings every degraded row to that BS.1770 loudness in LUFS before it is scored, as the
         ``ffmpeg-normalize`` step of the reference's rendering scripts does (its linear gain only; no codecs); without the key the
         rows keep the level the degradation left them."""
@@ -709,6 +711,7 @@ class Training:
                 noise=self.nomad.load_processing(noise).reshape(-1) if noise is not None else None,
                 snr_db=on_device.get("snr_db"), clip_factor=on_device.get("clip"),
                 **({"rt60_s": on_device["rt60"]} if on_device.get("rt60") is not None else {}),
+                **({"reverberance": on_device["reverb"]} if on_device.get("reverb") is not None else {}),
                 **({"normalize": on_device["normalize"]} if on_device.get("normalize") is not None else {}))
             for res in results.values():
                 res["ref_embeddings"] = ref_embeddings
