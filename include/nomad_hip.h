@@ -28,6 +28,9 @@
  *                                  levels per clip, same layout (restated from memory of sox 14.4; not checked against the binary)
  *   nomad_degrade_normalize        BS.1770-4 loudness (or rms / peak level) of packed rows and the linear gain to a target, in place:
  *                                  the ffmpeg-normalize step of audio_degrader_training.py / audio_degrader_test.py
+ *   nomad_gammatone / nomad_nsim   gammatone spectrograms of packed rows and the NSIM of each degraded row with its clean clip: the
+ *                                  similarity src/utils/nsim_triplet_sampling.py samples triplets from (modelled on ViSQOL's speech mode
+ *                                  from memory; not checked against the binary)
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
  *
@@ -850,6 +853,74 @@ typedef struct {
 size_t nomad_degrade_reverb_scratch_bytes(int B, int stride, int G, int sample_rate);
 int nomad_degrade_reverb(nomad_ctx* ctx, const float* x_dev, int B, int stride, const int* lens_host, const nomad_reverb_params* params_host,
                          float* out_dev, void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
+
+/* ---- gammatone spectrograms of packed rows and their NSIM: the similarity the reference's triplets are sampled from ----------
+ * The reference runs ViSQOL over every (clean, degraded) pair and builds its (Anchor, Positive, Negative) rows from the pairs' NSIM
+ * (src/utils/nsim_triplet_sampling.py).  These calls compute a gammatone-spectrogram NSIM over the packed rows the nomad_degrade_*
+ * calls write, so that triplets can be mined with nothing rendered to disk.
+ *
+ * WHAT THIS IS NOT: a port checked against ViSQOL.  The measure below is modelled on what ViSQOL's speech mode is remembered to do
+ * (Slaney's ERB gammatone bank, 80 ms frames every 20 ms with the filter state reset per frame, dB floors, a 3 x 3 NSIM window);
+ * ViSQOL was not available where it was written, so its agreement with the ViSQOL binary has never been measured.  The text
+ * below is the definition, and tests/nsim_ref.py restates it.  ViSQOL's patch search, time alignment and voice-activity gate are
+ * left out: the rows this is made for are sample-aligned with their clean clip by construction, so one similarity map covers the
+ * whole clip; files with codec delay are outside what it claims.  No gradient, no MOS mapping.
+ *
+ * Rows are fp32, mono, at fs = sample_rate samples per second, fs in 16000 .. 48000 and a multiple of 50.  Everything below is float64.
+ * Bank: N = 21 bands.  With EarQ = 9.26449, minBW = 24.7, lo = 50, hi = 8000:
+ *   cf_i = -EarQ minBW + exp(i (log(lo + EarQ minBW) - log(hi + EarQ minBW)) / N) (hi + EarQ minBW) for i = 1 .. N; band 0 is the
+ *   lowest (i = N, 50 Hz), band 20 the highest (i = 1).
+ *   T = 1 / fs, ERB = cf / EarQ + minBW, B = 1.019 2 pi ERB, c = cos(2 pi cf T), s = sin(2 pi cf T), e = exp(B T).
+ *   Four second-order sections with the common denominator [1, -2 c / e, exp(-2 B T)] and the numerators [T, A1k, 0],
+ *   A1k = -(2 T c / e +- 2 sqrt(3 +- 2^1.5) T s / e) / 2 in the order (+,+), (-,+), (+,-), (-,-): the first sign is the one in front
+ *   of the square root, the second the one inside it.  The gain g is the magnitude of the product of the four sections' responses at
+ *   z = exp(j 2 pi cf T), formed on the host in complex float64; it is divided into the first section's two numerator coefficients
+ *   on the host.  Each section runs as transposed direct form II: y = b0 x + z1; z1 = b1 x - a1 y + z2; z2 = -a2 y.  All
+ *   coefficients are formed on the host, once per call.
+ * Spectrogram: W = 0.08 fs = 4 H, H = 0.02 fs.  A row of n >= W samples has F = (n - W) / H + 1 whole frames (integer division;
+ *   nomad_gammatone_frames(n, fs), <= 0 for a shorter row or a rate outside the range); a trailing partial frame is in none.  For
+ *   frame t and band b the four sections run over samples [t H, t H + W) from the zero state, section k fed by section k - 1, and
+ *   S[t][b] = sqrt((sum_i y_i^2) / W), the sum taken in time order.  Frames are packed clip after clip as [sum F_r][21] doubles,
+ *   as nomad_frame_energy packs its frames.
+ * NSIM of a clean spectrogram R and a degraded one D with the same F: eps = 2^-52; X = 10 log10(max(S, eps)); the absolute floor
+ *   X = max(X, -45); for each frame X_t = max(X_t, p_t - 45), p_t the largest value of frame t in either spectrogram; then the
+ *   smallest value left in either is subtracted from both.  The window is w = [[0.0113, 0.0838, 0.0113], [0.0838, 0.6193, 0.0838],
+ *   [0.0113, 0.0838, 0.0113]], applied with the edges replicated so that the map stays F x 21, its nine terms added row by row:
+ *   frames t - 1, t, t + 1 outside, bands b - 1, b, b + 1 inside.  mu = w * X; variance = w * X^2 - mu^2 clamped at 0, sigma its
+ *   square root; covariance = w * (R D) - mu_R mu_D.  C1 = (0.01 L)^2 and C3 = (0.03 L)^2 / 2 with the intensity range L a call
+ *   parameter (1.0 where a caller has no reason for another).  The map is
+ *   (2 mu_R mu_D + C1) / (mu_R^2 + mu_D^2 + C1) * ((cov + C3) / (sigma_R sigma_D + C3)).
+ *   A band's value is the mean of its column over the F frames, added in ascending order (a sequential walk); the row's NSIM is the
+ *   mean of the 21 band values, added in ascending order.
+ * Non-finite samples: a non-finite sample makes every frame that holds it NaN; every max and min above is formed so that a NaN
+ *   sticks, so that row's NSIM and band values are NaN, and no other row changes a bit.  A silent pair gives exactly 1.
+ *
+ *   nomad_gammatone   x_dev [R][stride] fp32, row r in its first lens_host[r] samples (HOST array; nothing behind a length is read,
+ *                     rows need 4-byte alignment only) -> spec_out_dev [sum F_r][21] float64.  A (frame, band) value depends on its
+ *                     own W samples and the rate alone: a row has the bits of its own R = 1 call whatever the batch, the stride
+ *                     and the base alignment.  csrc/nsim.hip.h states how the work is laid out (a lane per (frame, band), a
+ *                     workgroup's span of samples staged in LDS once, the cascade skewed by one sample per section).
+ *   nomad_nsim        spec_ref_dev [sum F_b][21] (B clean clips), spec_deg_dev [G sum F_b][21]: degraded row b G + g belongs to clean
+ *                     clip b and has its F_b = frames_host[b] frames, rows packed in that order -> nsim_out_dev [B G], bands_out_dev
+ *                     [B G][21] or NULL (the scores keep their bits).  One workgroup per degraded row; a row has the bits of its
+ *                     own B = 1, G = 1 call.
+ * Contract as the degradations above: asynchronous on the caller's stream, no allocation, deterministic, no atomics; the host
+ * tables (lengths or frame counts, their prefix sums, the bank) are copied into the workspace ahead of the kernels, so the host
+ * arrays may die on return; workspace nomad_gammatone_scratch_bytes(R, stride, sample_rate) / nomad_nsim_scratch_bytes(B, G,
+ * total_frames = sum F_b) bytes (0 for arguments the call would refuse), written before it is read.  Argument errors return before
+ * anything is queued.
+ * NOMAD_ERR_INVALID: a NULL pointer other than bands_out_dev, R or B outside 1 .. 65535, G outside 1 .. 64, a stride that is not a
+ * positive multiple of 4 or is shorter than a length, a length below one frame, a rate outside the range above, a frame count
+ * below 1, an intensity range that is not finite and positive.  NOMAD_ERR_WORKSPACE: ws_bytes too small.
+ */
+int nomad_gammatone_frames(int n_samples, int sample_rate);
+size_t nomad_gammatone_scratch_bytes(int R, int stride, int sample_rate);
+int nomad_gammatone(nomad_ctx* ctx, const float* x_dev, int R, int stride, const int* lens_host, int sample_rate, double* spec_out_dev,
+                    void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
+size_t nomad_nsim_scratch_bytes(int B, int G, long long total_frames);
+int nomad_nsim(nomad_ctx* ctx, const double* spec_ref_dev, const double* spec_deg_dev, int B, int G, const int* frames_host /* [B] */,
+               double intensity_range, double* nsim_out_dev /* [B G] */, double* bands_out_dev /* [B G][21] or NULL */, void* ws_dev,
+               size_t ws_bytes, nomad_stream_t stream);
 
 /* ---- bf16 path (BASELINE config C5: long-form clips) ---------------------------------------- */
 /*

@@ -11,7 +11,9 @@ the files shard across the ranks (RCCL all-gather of the embeddings, ``Nomad.pre
 ``--sweep`` (one process): ``--deg`` holds CLEAN files, which are degraded on the GPU at every level of ``--snr-db`` (with ``--noise
 FILE``), ``--clip`` and / or ``--rt60`` (synthetic rooms, ``nomad_amd.nomad.synthetic_rir``) or ``--reverb`` (sox's reverb at its reverberance
 levels, ``Nomad.reverb``) and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level.  ``--normalize [LUFS]`` brings every
-degraded clip to one BS.1770 loudness first (bare: -23), as the reference's ``ffmpeg-normalize`` step does."""
+degraded clip to one BS.1770 loudness first (bare: -23), as the reference's ``ffmpeg-normalize`` step does.  ``--nsim`` adds an ``NSIM``
+column: the mean gammatone NSIM (``Nomad.nsim``) of the same rows with their clean clips, the similarity the model was trained to
+order, next to the score."""
 import argparse
 import os
 
@@ -43,11 +45,17 @@ def sweep(nomad, a):
     reverb = {"rt60_s": a.rt60} if a.rt60 is not None else {"reverberance": a.reverb} if a.reverb is not None else {}
     if a.normalize is not None:
         reverb["normalize"] = a.normalize
+    if a.nsim:
+        reverb["nsim"] = True
     results = nomad.intensity_sweep(a.deg, refs, noise=noise, snr_db=a.snr_db, clip_factor=a.clip, k=a.knn, **reverb)
     parts = []
     for name, res in results.items():
         t = res["table"].sort_values(by="Condition")
-        parts.append(pd.DataFrame({"Degradation": name, "Condition": t["Condition"].to_numpy(), "NOMAD": t["Distance"].to_numpy()}))
+        part = pd.DataFrame({"Degradation": name, "Condition": t["Condition"].to_numpy(), "NOMAD": t["Distance"].to_numpy()})
+        if a.nsim:     # the rows' mean per level, in the table's order
+            mean = pd.DataFrame({"Condition": res["conditions"], "NSIM": res["nsim"]}).groupby("Condition")["NSIM"].mean()
+            part["NSIM"] = mean.reindex(part["Condition"]).to_numpy()
+        parts.append(part)
         print(f"{name}: SRCC of the mean NOMAD score with the level = {res['SRCC']:.3f}")
     table = pd.concat(parts, ignore_index=True)
     if a.results_path is None:      # as predict names its files
@@ -99,6 +107,9 @@ def main(argv=None):
     ap.add_argument("--normalize", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS",
                     help="--sweep: bring every degraded clip to this BS.1770 integrated loudness before it is scored (bare: -23, EBU R128, "
                          "what the reference's ffmpeg-normalize step does), so that the score ranks the degradation at equal loudness")
+    ap.add_argument("--nsim", action="store_true",
+                    help="--sweep: add an NSIM column, the mean gammatone NSIM of the same degraded rows with their clean clips (Nomad.nsim; "
+                         "this project's measure, not ViSQOL's); every clean file then needs 80 ms")
     a = ap.parse_args(argv)
     if a.hop is not None and a.window is None:
         ap.error("--hop goes with --window")
@@ -110,6 +121,8 @@ def main(argv=None):
         ap.error("--reverb goes with --sweep")
     if a.reverb is not None and a.rt60 is not None:
         ap.error("--reverb and --rt60 exclude each other: both fill the REVERB rows")
+    if a.nsim and not a.sweep:
+        ap.error("--nsim goes with --sweep")
     if a.normalize is not None:
         if not a.sweep:
             ap.error("--normalize goes with --sweep")

@@ -76,6 +76,11 @@ SIGNATURES = {
     "nomad_degrade_normalize_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nomad_degrade_normalize": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_double, C.c_double,
                                           _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_gammatone_frames": (C.c_int, [C.c_int, C.c_int]),
+    "nomad_gammatone_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nomad_gammatone": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_nsim_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_longlong]),
+    "nomad_nsim": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, _fp, _fp, _fp, C.c_size_t, _fp]),
     "nomad_embed_features": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "nomad_embed_features_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp,
                                               C.c_size_t, _fp]),

@@ -29,6 +29,7 @@
 #include "degrade_convolve.hip.h"
 #include "reverb.hip.h"
 #include "loudness.hip.h"
+#include "nsim.hip.h"
 #include "frontend.hip.h"
 #include "gemm_bf16.hip.h"
 #include "gemm_bf16_8phase.hip.h"
@@ -4166,6 +4167,129 @@ int nomad_degrade_reverb(nomad_ctx* c, const float* x, int B, int stride, const 
                        reinterpret_cast<const double*>(w + l.feedback), G, plan, wet);
     hipLaunchKernelGGL(reverb_mix_kernel, dim3((unsigned)(B * G)), dim3(256), 0, s, x, stride, lens_dev, G, static_cast<const double*>(wet),
                        l.plane, plan, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- gammatone spectrograms and NSIM (nsim.hip.h) ----
+int nomad_gammatone_frames(int n_samples, int sample_rate) {
+    if (!gammatone_rate_ok(sample_rate)) return 0;
+    const int H = sample_rate / 50, W = 4 * H;
+    return n_samples < W ? 0 : (n_samples - W) / H + 1;
+}
+
+// Scratch: [lengths: R int32, to 256 bytes | frame prefix sums: R + 1 int64, to 256 bytes | the bank: [21][10] float64].
+struct GammatoneLayout {
+    size_t fpref, coef, total;
+};
+static GammatoneLayout gammatone_layout(int R) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    GammatoneLayout l;
+    l.fpref = up(sizeof(int) * (size_t)R);
+    l.coef = l.fpref + up(sizeof(long long) * ((size_t)R + 1));
+    l.total = l.coef + up(sizeof(double) * kGammatoneCoefs * kGammatoneBands);
+    return l;
+}
+
+size_t nomad_gammatone_scratch_bytes(int R, int stride, int sample_rate) {
+    if (R < 1 || R > 65535 || stride < 4 || stride % 4 || !gammatone_rate_ok(sample_rate)) {
+        (void)fail(NOMAD_ERR_INVALID,
+                   "nomad_gammatone_scratch_bytes: bad argument (R=%d: 1 .. 65535, stride=%d: a positive multiple of 4, sample_rate=%d: a multiple "
+                   "of 50 in %d .. %d)", R, stride, sample_rate, kGammatoneMinRate, kGammatoneMaxRate);
+        return 0;
+    }
+    return gammatone_layout(R).total;
+}
+
+int nomad_gammatone(nomad_ctx* c, const float* x, int R, int stride, const int* lens, int sample_rate, double* spec, void* ws,
+                    size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_gammatone";
+    if (!c || !x || !lens || !spec || !ws) return fail(NOMAD_ERR_INVALID, "%s: a NULL context, input, lengths, output or workspace", who);
+    if (R < 1 || R > 65535) return fail(NOMAD_ERR_INVALID, "%s: R=%d rows, 1 .. 65535 are supported", who, R);
+    if (stride < 4 || stride % 4) return fail(NOMAD_ERR_INVALID, "%s: stride=%d is not a positive multiple of 4", who, stride);
+    if (!gammatone_rate_ok(sample_rate))
+        return fail(NOMAD_ERR_INVALID, "%s: sample_rate=%d, a multiple of 50 in %d .. %d is supported", who, sample_rate, kGammatoneMinRate,
+                    kGammatoneMaxRate);
+    const int H = sample_rate / 50, W = 4 * H;
+    int max_f = 0;
+    for (int r = 0; r < R; ++r) {
+        if (lens[r] < W || lens[r] > stride)
+            return fail(NOMAD_ERR_INVALID, "%s: row %d has length %d, one frame of %d samples .. stride=%d are supported", who, r, lens[r], W, stride);
+        const int f = (lens[r] - W) / H + 1;
+        max_f = f > max_f ? f : max_f;
+    }
+    const GammatoneLayout l = gammatone_layout(R);
+    if (ws_bytes < l.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(l.total, 0);
+    memcpy(staged.data(), lens, sizeof(int) * (size_t)R);
+    long long* fp = reinterpret_cast<long long*>(staged.data() + l.fpref);
+    for (int r = 0; r < R; ++r) fp[r + 1] = fp[r] + ((lens[r] - W) / H + 1);
+    const double frames = (double)fp[R];
+    gammatone_bank(sample_rate, reinterpret_cast<double*>(staged.data() + l.coef), nullptr);
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), l.total, hipMemcpyHostToDevice, s));
+    Scope sc(c, s, NOMAD_K_ROW, 2.0 * 16.0 * frames * kGammatoneBands * W);
+    const size_t lds = sizeof(float) * (size_t)(kGammatoneBlockFrames + 3) * (size_t)(H + 1);   // at most 57 660 bytes (48 kHz)
+    hipLaunchKernelGGL(gammatone_frames_kernel, dim3((unsigned)((max_f + kGammatoneBlockFrames - 1) / kGammatoneBlockFrames), (unsigned)R),
+                       dim3(256), lds, s, x, stride, reinterpret_cast<const int*>(w), reinterpret_cast<const long long*>(w + l.fpref),
+                       reinterpret_cast<const double*>(w + l.coef), H, spec);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Scratch: [frames: B int32, to 256 bytes | frame prefix sums: B + 1 int64, to 256 bytes | planes [3][G total_frames][21] float64].
+struct NsimLayout {
+    size_t fpref, planes, total;
+};
+static NsimLayout nsim_layout(int B, int G, long long total_frames) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    NsimLayout l;
+    l.fpref = up(sizeof(int) * (size_t)B);
+    l.planes = l.fpref + up(sizeof(long long) * ((size_t)B + 1));
+    l.total = l.planes + 3 * sizeof(double) * (size_t)G * (size_t)total_frames * kGammatoneBands;
+    return l;
+}
+
+size_t nomad_nsim_scratch_bytes(int B, int G, long long total_frames) {
+    if (B < 1 || B > 65535 || G < 1 || G > 64 || total_frames < B || total_frames > (1ll << 31)) {
+        (void)fail(NOMAD_ERR_INVALID, "nomad_nsim_scratch_bytes: bad argument (B=%d: 1 .. 65535, G=%d: 1 .. 64, total_frames=%lld: B .. 2^31)", B, G,
+                   total_frames);
+        return 0;
+    }
+    return nsim_layout(B, G, total_frames).total;
+}
+
+int nomad_nsim(nomad_ctx* c, const double* spec_ref, const double* spec_deg, int B, int G, const int* frames, double intensity_range,
+               double* nsim_out, double* bands_out, void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_nsim";
+    if (!c || !spec_ref || !spec_deg || !frames || !nsim_out || !ws)
+        return fail(NOMAD_ERR_INVALID, "%s: a NULL context, spectrogram, frame counts, output or workspace", who);
+    if (B < 1 || B > 65535) return fail(NOMAD_ERR_INVALID, "%s: B=%d clips, 1 .. 65535 are supported", who, B);
+    if (G < 1 || G > 64) return fail(NOMAD_ERR_INVALID, "%s: G=%d rows per clip, 1 .. 64 are supported", who, G);
+    if (!std::isfinite(intensity_range) || !(intensity_range > 0.0))
+        return fail(NOMAD_ERR_INVALID, "%s: the intensity range must be finite and positive, got %g", who, intensity_range);
+    long long total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (frames[b] < 1) return fail(NOMAD_ERR_INVALID, "%s: clip %d has %d frames, at least 1 is needed", who, b, frames[b]);
+        total += frames[b];
+    }
+    if (total > (1ll << 31)) return fail(NOMAD_ERR_INVALID, "%s: %lld frames in all, at most 2^31 are supported", who, total);
+    const NsimLayout l = nsim_layout(B, G, total);
+    if (ws_bytes < l.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(l.planes, 0);
+    memcpy(staged.data(), frames, sizeof(int) * (size_t)B);
+    long long* fp = reinterpret_cast<long long*>(staged.data() + l.fpref);
+    for (int b = 0; b < B; ++b) fp[b + 1] = fp[b] + frames[b];
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), l.planes, hipMemcpyHostToDevice, s));
+    const double C1 = (0.01 * intensity_range) * (0.01 * intensity_range), C3 = (0.03 * intensity_range) * (0.03 * intensity_range) / 2.0;
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(nsim_kernel, dim3((unsigned)(B * G)), dim3(256), 0, s, spec_ref, spec_deg, G, reinterpret_cast<const int*>(w),
+                       reinterpret_cast<const long long*>(w + l.fpref), total, C1, C3, reinterpret_cast<double*>(w + l.planes), nsim_out, bands_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

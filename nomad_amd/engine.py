@@ -749,6 +749,101 @@ class Engine:
                    "nomad_degrade_normalize")
         return out, lens, stats
 
+    def _scratch_size(self, fn, what, *args) -> int:
+        """Bytes from a ``*_scratch_bytes`` helper that returns the size itself: 0 is its refusal, raised as ``_size`` raises one."""
+        n = int(fn(*args))
+        if n == 0:
+            _lib.check(_lib.NOMAD_ERR_INVALID, what)
+        return n
+
+    def _rows(self, waves, lengths, packed):
+        """``packed`` = (device (R, stride) fp32 buffer, lengths) as the degradations return it, used as it is; or waves / lengths
+        as ``degrade_noise`` takes them -> (buffer, lengths)."""
+        if packed is not None:
+            if waves is not None or lengths is not None:
+                raise ValueError("packed goes without waves and lengths")
+            buf, lens = packed
+            self._check_dev(buf, "packed rows")
+            if buf.dim() != 2 or buf.shape[1] % 4 or len(lens) != buf.shape[0]:
+                raise ValueError("packed must be a contiguous (R, stride) fp32 device buffer, stride a multiple of 4, with R lengths")
+        elif lengths is not None:
+            buf, lens = self.pack_ragged(waves, lengths)
+            if buf.shape[1] % 4 or not buf.is_contiguous() or buf.dtype != torch.float32:
+                buf, lens = self._pack([buf[i, :n] for i, n in enumerate(lens)])
+        else:
+            buf, lens = self._pack(waves)
+        return buf, [int(n) for n in lens]
+
+    NSIM_BANDS = 21
+
+    @staticmethod
+    def gammatone_frames(n_samples: int, sample_rate: int = 16000) -> int:
+        """Whole 80 ms frames every 20 ms of a row of n_samples (``nomad_gammatone_frames``), 0 for a shorter row."""
+        H = int(sample_rate) // 50
+        return 0 if n_samples < 4 * H else (int(n_samples) - 4 * H) // H + 1
+
+    @staticmethod
+    def check_gammatone(sample_rate):
+        sample_rate = int(sample_rate)
+        if not 16000 <= sample_rate <= 48000 or sample_rate % 50:
+            raise ValueError(f"sample_rate must be a multiple of 50 in 16000 .. 48000, got {sample_rate}")
+        return sample_rate
+
+    def gammatone(self, waves=None, lengths=None, packed: Optional[Tuple[torch.Tensor, list]] = None, sample_rate: int = 16000):
+        """Gammatone spectrogram of every row: 21 ERB bands from 50 Hz to 8 kHz, 80 ms frames every 20 ms with the filter state
+        reset per frame, float64 -> (spec (sum F_r, 21) float64 on the device, frames [F_r]): the rows' frames packed row after
+        row, S[t][b] = the band's RMS over the frame.  waves / lengths as ``degrade_noise`` takes them, or packed = (device
+        buffer, lengths) as the degradations return it (no copy).  Every row needs one whole frame.  Modelled on ViSQOL's
+        speech mode from memory, not checked against it; include/nomad_hip.h states the measure (``nomad_gammatone``)."""
+        sample_rate = self.check_gammatone(sample_rate)
+        buf, lens = self._rows(waves, lengths, packed)
+        R, stride = buf.shape
+        frames = [self.gammatone_frames(n, sample_rate) for n in lens]
+        if min(frames) < 1:
+            raise ValueError(f"a row of {min(lens)} samples is shorter than one frame of {sample_rate // 50 * 4}")
+        spec = torch.empty(sum(frames), self.NSIM_BANDS, dtype=torch.float64, device=self.device)
+        ws = self._workspace(self._scratch_size(self.lib.nomad_gammatone_scratch_bytes, "nomad_gammatone_scratch_bytes", R, stride, sample_rate))
+        _lib.check(self.lib.nomad_gammatone(self.ctx, buf.data_ptr(), R, stride, (C.c_int * R)(*lens), sample_rate, spec.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), self._stream()), "nomad_gammatone")
+        return spec, frames
+
+    def nsim_of_spectrograms(self, spec_ref: torch.Tensor, spec_deg: torch.Tensor, frames, G: int, intensity_range: float = 1.0,
+                             want_bands: bool = True):
+        """``nomad_nsim`` on spectrograms ``gammatone`` made: spec_ref (sum F_b, 21) of B clean clips, spec_deg (G sum F_b, 21) of
+        their B G degraded rows (row b G + g belongs to clip b), frames [F_b] -> (nsim (B, G) float64, bands (B, G, 21) or None)."""
+        frames = [int(f) for f in frames]
+        B, G, total = len(frames), int(G), sum(frames)
+        intensity_range = float(intensity_range)
+        if not (math.isfinite(intensity_range) and intensity_range > 0.0):
+            raise ValueError(f"intensity_range must be finite and positive, got {intensity_range}")
+        for t, rows, name in ((spec_ref, total, "spec_ref"), (spec_deg, G * total, "spec_deg")):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                    and tuple(t.shape) == (rows, self.NSIM_BANDS)):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape ({rows}, {self.NSIM_BANDS}) on {self.device}")
+        nsim = torch.empty(B, G, dtype=torch.float64, device=self.device)
+        bands = torch.empty(B, G, self.NSIM_BANDS, dtype=torch.float64, device=self.device) if want_bands else None
+        ws = self._workspace(self._scratch_size(self.lib.nomad_nsim_scratch_bytes, "nomad_nsim_scratch_bytes", B, G, total))
+        _lib.check(self.lib.nomad_nsim(self.ctx, spec_ref.data_ptr(), spec_deg.data_ptr(), B, G, (C.c_int * B)(*frames), intensity_range,
+                                       nsim.data_ptr(), _ptr(bands), ws.data_ptr(), ws.numel(), self._stream()), "nomad_nsim")
+        return nsim, bands
+
+    def nsim(self, clean, degraded, G: int, intensity_range: float = 1.0, sample_rate: int = 16000, want_bands: bool = True):
+        """NSIM of every degraded row with its clean clip -> (nsim (B, G) float64 on the device, bands (B, G, 21) or None): clean
+        and degraded are (device buffer, lengths) pairs as ``degrade_normalize`` takes ``packed`` - B clean rows, and B G degraded
+        rows of which row b G + g belongs to clip b and has its length, i.e. what any ``degrade_*`` call returns, without a copy.
+        1 for identical rows, falling with the degradation; the clean spectrograms are computed once (``gammatone`` twice, then
+        ``nomad_nsim``).  Not ViSQOL's number: include/nomad_hip.h states the measure."""
+        cbuf, clens = self._rows(None, None, clean)
+        dbuf, dlens = self._rows(None, None, degraded)
+        G = int(G)
+        if not 1 <= G <= 64:
+            raise ValueError(f"nsim takes 1 .. 64 degraded rows per clean clip, got {G}")
+        if dlens != [n for n in clens for _ in range(G)]:
+            raise ValueError("degraded must hold G rows per clean clip, row b G + g with the length of clip b")
+        spec_ref, frames = self.gammatone(packed=(cbuf, clens), sample_rate=sample_rate)
+        spec_deg, _ = self.gammatone(packed=(dbuf, dlens), sample_rate=sample_rate)
+        return self.nsim_of_spectrograms(spec_ref, spec_deg, frames, G, intensity_range, want_bands)
+
     def cdist(self, a: torch.Tensor, b: torch.Tensor, want_matrix: bool = True):
         """a (Na,D), b (Nb,D) fp32 on the GPU, D a multiple of 4 up to 4096 -> (dist (Na,Nb) float64 or None, mean (Na,)
         float64): ``pairwise`` for rows of any width (the same bits at D = 256)."""

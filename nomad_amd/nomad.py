@@ -1738,6 +1738,97 @@ class Nomad:
         x, lens = self._rows_for_normalize(wav, lengths, "normalize")
         return self.engine.degrade_normalize(x, lengths=lens, target=target, kind=kind, peak_db=peak_db)
 
+    def nsim(self, degraded, clean, lengths=None, bands: bool = False, intensity_range: float = 1.0):
+        """The gammatone-spectrogram NSIM of degraded clips with their clean clips, computed on the GPU: the similarity the
+        reference takes from ViSQOL before it samples triplets -> (B, G) float64 on the GPU, 1 for identical clips and falling with
+        the degradation (with ``bands``: also the (B, G, 21) per-band values whose mean it is).  clean (B,1,N) or (B,N) with
+        ``lengths``, the clips' exact lengths (at least 80 ms each); degraded: a tensor of clean's shape (G = 1), or the packed
+        ``(rows, lengths)`` that ``degrade`` / ``convolve`` / ``reverb`` / ``normalize`` return for these clips - row ``b G + g``
+        belongs to clip ``b`` - which is used without a copy.  21 ERB bands from 50 Hz to 8 kHz, 80 ms frames every 20 ms, dB
+        floors, a 3 x 3 window over one similarity map of the whole clip: the rows must be sample-aligned with their clean clip (no
+        patch search, no time alignment, no voice-activity gate, no MOS mapping).  Modelled on ViSQOL's speech mode from memory
+        and NOT checked against the ViSQOL binary; include/nomad_hip.h states the measure.  No gradient."""
+        x, lens = self._rows_for_normalize(clean, lengths, "nsim")
+        eng = self.engine
+        cbuf, clens = eng._rows(x, lens, None)
+        if isinstance(degraded, tuple):
+            dbuf, dlens = degraded
+            dlens = [int(n) for n in dlens]
+            if not torch.is_tensor(dbuf) or dbuf.dim() != 2 or len(dlens) != dbuf.shape[0] or len(dlens) % len(clens) or not dlens:
+                raise ValueError("degraded must be (rows (B G, stride), lengths) as degrade returns them, G rows per clean clip")
+            G = len(dlens) // len(clens)
+        else:
+            if not torch.is_tensor(degraded) or tuple(degraded.shape) != tuple(clean.shape):
+                raise ValueError("degraded must have clean's shape, or be the (rows, lengths) a degradation returned")
+            d, _ = self._rows_for_normalize(degraded, lengths, "nsim")
+            dbuf, dlens = eng._rows(d, lens, None)
+            G = 1
+        score, per_band = eng.nsim((cbuf, clens), (dbuf, dlens), G, intensity_range=intensity_range, want_bands=bands)
+        return (score, per_band) if bands else score
+
+    def mine_triplets(self, clean, noise=None, snr_db=None, clip_factor=None, reverberance=None, normalize=-23.0, lengths=None,
+                      N: int = 3, hard_sampling: bool = False, margin: float = 0.05, seed=0):
+        """From clean clips to (Anchor, Positive, Negative) batches with nothing rendered to disk - the reference's data
+        preparation (degrade, ``ffmpeg-normalize``, ViSQOL's NSIM, ``nsim_triplet_sampling.py``) on the GPU.  The clips are
+        degraded at every given level (``snr_db`` with ``noise``, ``clip_factor``, ``reverberance``: the C conditions, in that
+        order); with ``normalize`` (LUFS, None: not at all) every degraded row and a copy of the clean clip are brought to that
+        loudness; the NSIM of every degraded row is taken against the UN-normalised clean clip, as the reference hands ViSQOL
+        its original wav; the (B, C) table makes one round trip to the host, where ``triplets.create_triplets`` samples up to N
+        triplets per clip (``hard_sampling``, ``margin``, ``seed``: its arguments); the three branches are gathered on the GPU.
+
+        -> (anchor, positive, negative, info): each branch a ``(rows (K, stride) fp32 on the GPU, lengths)`` pair as
+        ``forward_triplet`` / ``embed_ragged(packed=...)`` take them, K <= B N; ``info`` = {"nsim": the (B, C) float64 table,
+        "conditions": [(kind, level)] per column, "triplets": ``create_triplets``' index table (member C is the clean clip),
+        "dropped": its count of draws that gave no row}.  The NSIM is this project's (``nsim``), not ViSQOL's.  No gradient."""
+        from .triplets import create_triplets
+        x, lens = self._rows_for_normalize(clean, lengths, "mine_triplets")
+        if snr_db is not None and noise is None:
+            raise ValueError("snr_db needs a noise signal: pass noise=")
+        if torch.is_tensor(noise) and noise.requires_grad:
+            raise ValueError("mine_triplets produces no gradient: pass tensors that do not require one")
+        sweeps = [(kind, [float(v) for v in np.asarray(levels, dtype=np.float64).reshape(-1)])
+                  for kind, levels in (("noise", snr_db), ("clip", clip_factor), ("freeverb", reverberance)) if levels is not None]
+        if not sweeps:
+            raise ValueError("mine_triplets needs snr_db, clip_factor or reverberance")
+        for kind, levels in sweeps:
+            if not 1 <= len(levels) <= 64:
+                raise ValueError(f"{kind}: 1 .. 64 levels, got {len(levels)}")
+        if normalize is not None:
+            Engine.check_normalize(normalize, "ebu", None, 16000)
+        eng = self.engine
+        buf, lens = eng._rows(x, lens, None)
+        B, stride = buf.shape
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).reshape(-1).to(eng.device)
+        spec_ref, frames = eng.gammatone(packed=(buf, lens))
+        members, scores = [], []
+        for kind, levels in sweeps:
+            out, lens_rep, _ = self._degrade_packed(buf, lens, kind, levels, noise if kind == "noise" else None)
+            if normalize is not None:
+                eng.degrade_normalize(packed=(out, lens_rep), target=normalize, inplace=True)
+            spec_deg, _ = eng.gammatone(packed=(out, lens_rep))
+            scores.append(eng.nsim_of_spectrograms(spec_ref, spec_deg, frames, len(levels), want_bands=False)[0])
+            members.append(out.view(B, len(levels), stride))
+        if normalize is not None:
+            clean_member = eng.degrade_normalize(packed=(buf, lens), target=normalize)[0]
+        else:                     # the clean member is zero behind its length like every other row
+            clean_member = buf.clone()
+            for b, n in enumerate(lens):
+                clean_member[b, n:] = 0.0
+        members.append(clean_member.view(B, 1, stride))
+        table = torch.cat(scores, dim=1).cpu().numpy()        # the one round trip
+        triplets, dropped = create_triplets(table, N=N, hard_sampling=hard_sampling, margin=margin, rng=seed)
+        bank = torch.cat(members, dim=1)
+        C1 = bank.shape[1]
+        bank = bank.view(B * C1, stride)
+        branch_lens = [lens[b] for b in triplets["clip"]]
+        branches = []
+        for key in ("anchor", "positive", "negative"):
+            idx = torch.from_numpy(triplets["clip"] * C1 + triplets[key]).to(eng.device)
+            branches.append((bank.index_select(0, idx), list(branch_lens)))
+        info = {"nsim": table, "conditions": [(kind, v) for kind, levels in sweeps for v in levels], "triplets": triplets, "dropped": dropped}
+        return branches[0], branches[1], branches[2], info
+
     def _clean_batches(self, clean, lengths, budget: int):
         """The clean clips of ``intensity_sweep`` as packed device batches of at most ``budget`` samples each (one clip at least):
         yields (names, buffer, lengths)."""
@@ -1777,7 +1868,7 @@ class Nomad:
 
     def intensity_sweep(self, clean, references, noise=None, snr_db=None, clip_factor=None, lengths=None, k=None,
                         max_batch_samples: int = 256 * 64000, rt60_s=None, rir_seed: int = 0, drr_db: float = 0.0,
-                        normalize=None, normalize_kind: str = "ebu", reverberance=None, reverb_params=None):
+                        normalize=None, normalize_kind: str = "ebu", reverberance=None, reverb_params=None, nsim: bool = False):
         """Does the score rank the strength of a degradation?  The reference's ``intensity`` experiment without rendered files: the
         clean clips are degraded on the GPU (``degrade``) at every level, embedded and scored against ``references`` ((Nr,256), as
         ``score`` takes them); -> {"NOISE": {...}, "CLIP": {...}, "REVERB": {...}}, a degradation whose levels are None being left out.  Each entry is
@@ -1798,7 +1889,11 @@ class Nomad:
         louder than the clip, a 40 % clip factor several dB quieter).  A number: every degraded row is brought to that level in
         place before it is embedded (``normalize``; ``normalize_kind`` "ebu" = LUFS as the reference's ``ffmpeg-normalize`` step,
         -23 being its default, or "rms" / "peak" in dBFS), so that the score ranks the degradation at equal loudness; each entry
-        then also has ``gain_db``, the (N G,) float64 gains applied, in row order."""
+        then also has ``gain_db``, the (N G,) float64 gains applied, in row order.
+
+        nsim: each entry also gets ``nsim``, the (N G,) float64 NSIM of every scored row with its clean clip (``nsim``: this
+        project's gammatone measure, one more call over the same rows; the clean clip is taken as it is, the degraded row as it
+        is scored), in row order - the similarity the model was trained to order, next to the score.  Every clip then needs 80 ms."""
         from .train import intensity_stats
         check_references(references)
         if normalize is not None:
@@ -1830,9 +1925,10 @@ class Nomad:
         refs = references.detach().to(eng.device, torch.float32).contiguous()
         if noise is not None:
             noise = torch.as_tensor(noise, dtype=torch.float32).reshape(-1).to(eng.device)
-        rows = {name: ([], [], [], []) for name, _, _ in sweeps}      # row names, levels, embeddings in flight, gains in flight
+        rows = {name: ([], [], [], [], []) for name, _, _ in sweeps}  # row names, levels, embeddings, gains and NSIM in flight
         budget = max(1, int(max_batch_samples) // max(len(levels) for _, _, levels in sweeps))
         for names, buf, lens in self._clean_batches(clean, lengths, budget):
+            spec_ref, frames = eng.gammatone(packed=(buf, lens)) if nsim else (None, None)
             for name, kind, levels in sweeps:
                 if kind == "reverb" and isinstance(rirs, list):
                     rirs = eng.pack_responses(rirs)      # packed and uploaded once, with the first batch
@@ -1841,6 +1937,10 @@ class Nomad:
                 if normalize is not None:
                     _, _, stats = eng.degrade_normalize(packed=(out, lens_rep), target=normalize, kind=normalize_kind, inplace=True)
                     rows[name][3].append(eng.fetch_async(stats))
+                if nsim:
+                    spec_deg, _ = eng.gammatone(packed=(out, lens_rep))
+                    rows[name][4].append(eng.fetch_async(eng.nsim_of_spectrograms(spec_ref, spec_deg, frames, len(levels),
+                                                                                  want_bands=False)[0].reshape(-1)))
                 emb = eng.embed_ragged(None, precision=self._window_precision(sum(lens_rep)), packed=(out, lens_rep))
                 rows[name][0].extend(f"{n}|{name}_{g}" for n in names for g in range(len(levels)))
                 rows[name][1].extend(levels * len(names))
@@ -1848,7 +1948,7 @@ class Nomad:
         ref_df = pd.DataFrame(refs.cpu().numpy())
         results = {}
         for name, _, _ in sweeps:
-            row_names, conds, fetches, gains = rows[name]
+            row_names, conds, fetches, gains, sims = rows[name]
             if not row_names:
                 raise ValueError("intensity_sweep: no clean clip to degrade")
             df_emb = pd.concat([pd.DataFrame({"filepath_deg": row_names}),
@@ -1866,6 +1966,9 @@ class Nomad:
             if normalize is not None:
                 with np.errstate(divide="ignore"):
                     results[name]["gain_db"] = 20.0 * np.log10(np.concatenate([f.result() for f in gains])[:, 2])
+            if nsim:
+                results[name]["nsim"] = np.concatenate([f.result() for f in sims])
+                results[name]["conditions"] = np.asarray(conds, dtype=np.float64)
         return results
 
     def graphed_loss(self, estimate: torch.Tensor, clean: torch.Tensor, lengths=None) -> "GraphedLoss":

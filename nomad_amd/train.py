@@ -37,6 +37,13 @@ Differences, on purpose:
   validation embeds through nomad_embed_ragged - the arithmetic ``predict`` and the evaluation experiments score the model
   with, and no time spent on padded frames.  ``freeze_convnet: False`` is refused with it (the conv extractor's parameter
   gradients need equal-length batches).
+* ``triplets_on_device`` (not a reference key): ``{clean: <dir|csv>, valid_clean: <dir|csv>, noise: <wav>, snr_db: [...], clip:
+  [...], reverb: [...], normalize: -23, N: 3, hard_sampling: false, sampling_margin: 0.05}``.  With it ``train_df`` / ``valid_df``
+  are not read: a step takes ``train_bs // N`` clean clips, degrades them on the GPU at every listed level, takes each degraded
+  row's NSIM with its clean clip, samples up to ``train_bs`` triplets by the reference's rule (``Nomad.mine_triplets``: the
+  reference's offline ffmpeg / sox / ViSQOL / pandas preparation with nothing rendered to disk; the NSIM is this project's
+  gammatone measure, not ViSQOL's) and runs the exact-length step on them.  It requires ``pad_mode: exact``.  Validation mines with
+  one fixed seed per batch, the same in every epoch, so successive epochs are comparable.
 * model.train() regularisation (fairseq BASE config: dropout 0.1, attention_dropout 0.1, dropout_input 0.1,
   encoder_layerdrop 0.05) uses the engine's counter-based masks; torch's RNG stream of the reference's device cannot
   be reproduced on any other device, so runs are statistically, not bit-wise, equivalent to the reference's.
@@ -70,6 +77,78 @@ def check_pad_mode(config) -> str:
         raise ValueError("pad_mode 'exact' needs freeze_convnet: True: the conv feature extractor's parameter gradients are built for "
                          "equal-length batches only")
     return mode
+
+MINING_DEFAULTS = dict(clean=None, valid_clean=None, noise=None, snr_db=None, clip=None, reverb=None, normalize=-23.0, N=3,
+                       hard_sampling=False, sampling_margin=0.05)
+
+
+def check_triplets_on_device(config, pad_mode: str) -> Optional[dict]:
+    """The config's ``triplets_on_device`` (module docstring) with its defaults filled in, or None without the key.  Needs no GPU."""
+    raw = config.get("triplets_on_device")
+    if raw is None:
+        return None
+    if not isinstance(raw, dict):
+        raise ValueError("triplets_on_device must be a mapping (clean, valid_clean, noise, snr_db, clip, reverb, normalize, N, ...)")
+    unknown = sorted(set(raw) - set(MINING_DEFAULTS))
+    if unknown:
+        raise ValueError(f"triplets_on_device: unknown keys {unknown}; known: {sorted(MINING_DEFAULTS)}")
+    if pad_mode != "exact":
+        raise ValueError("triplets_on_device requires pad_mode: exact (mined triplets are packed rows with their exact lengths; "
+                         f"the config has pad_mode: {pad_mode})")
+    m = dict(MINING_DEFAULTS, **raw)
+    if not m["clean"] or not m["valid_clean"]:
+        raise ValueError("triplets_on_device needs clean and valid_clean: a directory of wav files or a csv with a filename column")
+    if m["snr_db"] is None and m["clip"] is None and m["reverb"] is None:
+        raise ValueError("triplets_on_device needs at least one of snr_db, clip and reverb (lists of levels)")
+    if m["snr_db"] is not None and not m["noise"]:
+        raise ValueError("triplets_on_device: snr_db needs noise: <wav>")
+    m["N"] = int(m["N"])
+    if m["N"] < 1 or int(config.get("train_bs", m["N"])) < m["N"] or int(config.get("val_bs", m["N"])) < m["N"]:
+        raise ValueError(f"triplets_on_device: N = {m['N']} must be at least 1 and at most train_bs and val_bs")
+    return m
+
+
+class MinedTriplets:
+    """What ``Training`` iterates in place of a DataLoader with ``triplets_on_device``: batches of ``batch_size // N`` clean files,
+    each turned into up to ``batch_size`` triplets on the GPU (``Nomad.mine_triplets``) -> (A, P, N) as ``_step_exact`` takes them.
+    shuffle: a new order of the files and new draws in every pass; otherwise file order and one fixed seed per batch, the same in
+    every pass.  A batch whose draws all dropped is passed over."""
+
+    def __init__(self, nomad: Nomad, files, mining: dict, batch_size: int, shuffle: bool, seed: int = SEED, trim: bool = False):
+        self.nomad, self.mining, self.shuffle, self.trim = nomad, mining, shuffle, trim
+        self.files = sorted(str(f) for f in files)     # (a directory lists in no fixed order)
+        if not self.files:
+            raise ValueError("triplets_on_device: no clean file to mine from")
+        self.clips = max(1, int(batch_size) // mining["N"])
+        self.noise = load_processing(mining["noise"])[0] if mining["noise"] else None
+        self._rng = np.random.RandomState(seed)
+        self._seed = seed
+        self.last_info = None
+
+    def __len__(self):
+        return (len(self.files) + self.clips - 1) // self.clips
+
+    def mine(self, paths, seed):
+        """The clean files ``paths`` -> (A, P, N, info) of ``Nomad.mine_triplets``."""
+        wavs = [load_processing(p, trim=self.trim)[0] for p in paths]
+        lens = [int(w.shape[0]) for w in wavs]
+        rows = torch.zeros(len(wavs), max(lens), dtype=torch.float32)
+        for i, w in enumerate(wavs):
+            rows[i, :lens[i]] = w
+        m = self.mining
+        return self.nomad.mine_triplets(rows, noise=self.noise, snr_db=m["snr_db"], clip_factor=m["clip"], reverberance=m["reverb"],
+                                        normalize=m["normalize"], lengths=lens, N=m["N"], hard_sampling=bool(m["hard_sampling"]),
+                                        margin=float(m["sampling_margin"]), seed=seed)
+
+    def __iter__(self):
+        order = self._rng.permutation(len(self.files)) if self.shuffle else np.arange(len(self.files))
+        for k, lo in enumerate(range(0, len(order), self.clips)):
+            seed = int(self._rng.randint(0, 2 ** 31 - 1)) if self.shuffle else self._seed + k
+            A, P, N, info = self.mine([self.files[i] for i in order[lo:lo + self.clips]], seed)
+            self.last_info = info
+            if len(A[1]):
+                yield A, P, N
+
 
 # fairseq wav2vec 2.0 BASE pre-training config (what wav2vec_small.pt carries in its cfg)
 W2V_BASE_REGULARISATION = dict(dropout=0.1, attention_dropout=0.1, dropout_input=0.1, encoder_layerdrop=0.05)
@@ -365,6 +444,7 @@ class Training:
             with open(config_file) as file:
                 self.config = yaml.load(file, Loader=yaml.FullLoader)
         self.pad_mode = check_pad_mode(self.config)   # (a config error is reported as one, with or without a GPU)
+        self.mining = check_triplets_on_device(self.config, self.pad_mode)
         if not torch.cuda.is_available():
             raise RuntimeError("nomad_amd.train needs an MI355X: the engine has no CPU path")
         self.DEVICE = torch.device("cuda", device)
@@ -415,21 +495,32 @@ class Training:
         self.merge_branches = merge_branches     # A/P/N as one 3B-clip launch sequence when their padded lengths agree
         if self.config["experiment_name"] == "Training":
             self.current_level = self.config.get("current_level")
-            g = torch.Generator()
-            g.manual_seed(SEED)
-            self.train_set = TripletDataset(self.config, data_mode="train_df", level=self.current_level)
-            self.train_sampler = None
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-                self.train_sampler = torch.utils.data.distributed.DistributedSampler(
-                    self.train_set, num_replicas=dist.get_world_size(group), rank=dist.get_rank(group), shuffle=True, seed=SEED)
-            self.train_loader = torch.utils.data.DataLoader(
-                self.train_set, batch_size=self.config["train_bs"], shuffle=self.train_sampler is None,
-                sampler=self.train_sampler, num_workers=self.config["num_workers"],
-                collate_fn=self.train_set.collate_fn, generator=g, pin_memory=True)
-            self.valid_set = TripletDataset(self.config, data_mode="valid_df", level=self.current_level)
-            self.valid_loader = torch.utils.data.DataLoader(
-                self.valid_set, batch_size=self.config["val_bs"], shuffle=False, num_workers=self.config["num_workers"],
-                collate_fn=self.valid_set.collate_fn, pin_memory=True)
+            if self.mining is not None:
+                # triplets mined on the GPU from clean files (module docstring): train_df / valid_df are not read
+                from .nomad import _file_table
+                miner = Nomad.from_engine(self.engine)
+                trim = bool(self.config.get("trim", False))
+                self.train_sampler = None
+                self.train_loader = MinedTriplets(miner, _file_table(str(self.mining["clean"]))["filename"], self.mining,
+                                                  self.config["train_bs"], shuffle=True, trim=trim)
+                self.valid_loader = MinedTriplets(miner, _file_table(str(self.mining["valid_clean"]))["filename"], self.mining,
+                                                  self.config["val_bs"], shuffle=False, trim=trim)
+            else:
+                g = torch.Generator()
+                g.manual_seed(SEED)
+                self.train_set = TripletDataset(self.config, data_mode="train_df", level=self.current_level)
+                self.train_sampler = None
+                if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+                    self.train_sampler = torch.utils.data.distributed.DistributedSampler(
+                        self.train_set, num_replicas=dist.get_world_size(group), rank=dist.get_rank(group), shuffle=True, seed=SEED)
+                self.train_loader = torch.utils.data.DataLoader(
+                    self.train_set, batch_size=self.config["train_bs"], shuffle=self.train_sampler is None,
+                    sampler=self.train_sampler, num_workers=self.config["num_workers"],
+                    collate_fn=self.train_set.collate_fn, generator=g, pin_memory=True)
+                self.valid_set = TripletDataset(self.config, data_mode="valid_df", level=self.current_level)
+                self.valid_loader = torch.utils.data.DataLoader(
+                    self.valid_set, batch_size=self.config["val_bs"], shuffle=False, num_workers=self.config["num_workers"],
+                    collate_fn=self.valid_set.collate_fn, pin_memory=True)
             self.margin = float(self.config["margin"])
             # train_triplet.py:96-107: Adam; with freeze_convnet the pretrained parameters at 1e-5 and embedding_layer at
             # `lr`, otherwise the optimiser is not overwritten and every parameter runs at `lr`
