@@ -31,6 +31,8 @@
  *   nomad_gammatone / nomad_nsim   gammatone spectrograms of packed rows and the NSIM of each degraded row with its clean clip: the
  *                                  similarity src/utils/nsim_triplet_sampling.py samples triplets from (modelled on ViSQOL's speech mode
  *                                  from memory; not checked against the binary)
+ *   nomad_align_delay / _shift     the delay of every degraded row against its clean clip (the largest cross-correlation over integer
+ *                                  lags) and the rows moved by it: what files with codec delay need ahead of nomad_nsim
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
  *   nomad_l1_loss                  NomadLoss.forward (nomad.py:267-282)
  *
@@ -862,9 +864,12 @@ int nomad_degrade_reverb(nomad_ctx* ctx, const float* x_dev, int B, int stride, 
  * WHAT THIS IS NOT: a port checked against ViSQOL.  The measure below is modelled on what ViSQOL's speech mode is remembered to do
  * (Slaney's ERB gammatone bank, 80 ms frames every 20 ms with the filter state reset per frame, dB floors, a 3 x 3 NSIM window);
  * ViSQOL was not available where it was written, so its agreement with the ViSQOL binary has never been measured.  The text
- * below is the definition, and tests/nsim_ref.py restates it.  ViSQOL's patch search, time alignment and voice-activity gate are
- * left out: the rows this is made for are sample-aligned with their clean clip by construction, so one similarity map covers the
- * whole clip; files with codec delay are outside what it claims.  No gradient, no MOS mapping.
+ * below is the definition, and tests/nsim_ref.py restates it.  ViSQOL's patch search and voice-activity gate are left out, and
+ * these two calls align nothing: one similarity map covers the whole clip, so the rows must be sample-aligned with their clean clip.
+ * The rows the degradations make are, by construction; rows with ONE constant delay of whole samples (a codec round trip, a model
+ * with latency) are brought there by nomad_align_delay / nomad_align_shift below.  Still outside what is claimed: delays that change
+ * inside a file (clock drift, dropped packets), sub-sample delays, and agreement with ViSQOL's own aligner, which has not been
+ * measured.  No gradient, no MOS mapping.
  *
  * Rows are fp32, mono, at fs = sample_rate samples per second, fs in 16000 .. 48000 and a multiple of 50.  Everything below is float64.
  * Bank: N = 21 bands.  With EarQ = 9.26449, minBW = 24.7, lo = 50, hi = 8000:
@@ -921,6 +926,55 @@ size_t nomad_nsim_scratch_bytes(int B, int G, long long total_frames);
 int nomad_nsim(nomad_ctx* ctx, const double* spec_ref_dev, const double* spec_deg_dev, int B, int G, const int* frames_host /* [B] */,
                double intensity_range, double* nsim_out_dev /* [B G] */, double* bands_out_dev /* [B G][21] or NULL */, void* ws_dev,
                size_t ws_bytes, nomad_stream_t stream);
+
+/* ---- time alignment: the delay of every degraded row against its clean clip, and the rows moved by it ----------------------
+ * A codec round trip (the reference's MP3, Opus and Vorbis conditions), a model with latency or a recording through a device shifts
+ * and pads a file by hundreds to thousands of samples; nomad_nsim on such a row compares frames that do not belong together.
+ * clean_dev is [B][stride] fp32, clip b in its first lens_host[b] = n_b samples; deg_dev is [B G][deg_stride] fp32, row r = b G + g
+ * belongs to clip b and has its OWN length deg_lens_host[r] = m_r, which may differ from n_b.  Nothing behind a length is read
+ * (anything, NaN included, may stand there); rows need 4-byte alignment only and the strides need not be multiples of 4.
+ *
+ * Definition.  For every integer lag d in [-D, D], D = max_delay (0 .. 16384 samples, 1.024 s at 16 kHz):
+ *   c_r[d] = sum over i with 0 <= i < n_b and 0 <= i + d < m_r of x_b[i] y_r[i + d].
+ * d > 0 means the degraded row is late.  A lag with no overlap gives exactly 0.
+ * Arithmetic and order: fp32 products and fp32 chains on the matrix cores (v_mfma_f32_16x16x4_f32), no rounding skipped or added.
+ * With t = i + 16 j, j = ((d + D) mod 256) / 16, one chain covers the terms whose t lies in one SLICE [4096 k, 4096 (k + 1)), t
+ * ascending; the slices of a lag are then added in float64 in ascending order - eight at a time inside a workgroup, then the
+ * groups of eight, again ascending, by a second launch without atomics.  Products with a padding zero are formed and add +-0.  The
+ * order depends on (n_b, m_r, D) and the lag alone: row r of any batch has the bits of its own B = 1, G = 1 call, whatever the
+ * strides and the base alignment.  Integer-valued inputs whose sums stay below 2^24 per slice give the exact sums; otherwise
+ *   |c - exact| <= (4096 + 8) 2^-24 sum |x_b[i]| |y_r[i + d]|   (the running-error bound of the chains; underflow aside).
+ * Selection: delay_out_dev[r] is the lag of the largest c_r[d] - the sign counts, there is no normalisation by the overlap -,
+ * ties going to the smaller |d|, then to the non-negative lag; peak_out_dev[r] is that c_r[d].  A silent row ties everywhere and gets
+ * 0.  If any c_r[d] is NaN the delay is 0 and the peak NaN.  corr_out_dev, if not NULL, receives every c_r[d] as [B G][2 D + 1]
+ * float64, lag -D first; delay and peak keep their bits without it.
+ * Non-finite samples: a NaN sample that some lag reaches makes c_r NaN there (and, against padding zeros, at up to 255 further
+ * lags), so the row's (for a clean clip: its G rows') delay is 0 and its peak NaN; an infinite sample does the same wherever it
+ * meets a zero - a padding zero included (0 x inf) - or an infinity of the other sign.  No other row changes a bit.
+ *
+ *   nomad_align_shift   out[r][i] = y_r[i + delay_dev[r]] for 0 <= i < out_lens_host[r] and 0 <= i + delay_dev[r] < m_r, 0 otherwise and
+ *                       from out_lens_host[r] to out_stride; R rows of deg_stride, out_dev [R][out_stride].  delay_dev is read from
+ *                       DEVICE memory (nomad_align_delay's output, no host round trip; any int is taken).  A copy: the samples keep
+ *                       their bits.  With out_lens_host[r] = n_b the result is a packed batch nomad_gammatone / nomad_embed_ragged read.
+ *
+ * NOT offered: sub-sample delays, clock drift, per-patch re-alignment, a polarity search (an inverted row finds some other lag), a
+ * gradient.  How close the delays are to those of ViSQOL's aligner has not been measured.
+ * Contract as the degradations above: asynchronous on the caller's stream, no allocation, deterministic, no atomics; the host
+ * tables are copied into the workspace ahead of the kernels, so the host arrays may die on return; workspace
+ * nomad_align_scratch_bytes(B, G, stride, deg_stride, max_delay) bytes (0 for arguments the call would refuse; it covers a
+ * nomad_align_shift of the same B G rows, which needs 2 x (4 R rounded up to 256) bytes), written before it is read.  Argument
+ * errors return before anything is queued.
+ * NOMAD_ERR_INVALID: a NULL pointer other than corr_out_dev, B outside 1 .. 65535 (R outside 1 .. 65535 x 64), G outside 1 .. 64,
+ * max_delay outside 0 .. 16384, a length below 1, a stride shorter than a length (or above 2^30).  NOMAD_ERR_WORKSPACE: ws_bytes too
+ * small.
+ */
+size_t nomad_align_scratch_bytes(int B, int G, int stride, int deg_stride, int max_delay);
+int nomad_align_delay(nomad_ctx* ctx, const float* clean_dev, int B, int stride, const int* lens_host, const float* deg_dev, int G,
+                      int deg_stride, const int* deg_lens_host /* [B G] */, int max_delay, int* delay_out_dev /* [B G] */,
+                      double* peak_out_dev /* [B G] */, double* corr_out_dev /* [B G][2 max_delay + 1] or NULL */, void* ws_dev,
+                      size_t ws_bytes, nomad_stream_t stream);
+int nomad_align_shift(nomad_ctx* ctx, const float* deg_dev, int R, int deg_stride, const int* deg_lens_host, const int* delay_dev,
+                      const int* out_lens_host, float* out_dev, int out_stride, void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
 
 /* ---- bf16 path (BASELINE config C5: long-form clips) ---------------------------------------- */
 /*

@@ -13,7 +13,10 @@ FILE``), ``--clip`` and / or ``--rt60`` (synthetic rooms, ``nomad_amd.nomad.synt
 levels, ``Nomad.reverb``) and scored against ``--nmr``: ``nomad_intensity.csv`` and the rank correlation of score and level.  ``--normalize [LUFS]`` brings every
 degraded clip to one BS.1770 loudness first (bare: -23), as the reference's ``ffmpeg-normalize`` step does.  ``--nsim`` adds an ``NSIM``
 column: the mean gammatone NSIM (``Nomad.nsim``) of the same rows with their clean clips, the similarity the model was trained to
-order, next to the score."""
+order, next to the score.
+
+``--nsim-pairs CSV [--max-delay S]`` (one process): the NSIM of every (``filepath_ref``, ``filepath_deg``) pair of CSV, the degraded
+file moved by its delay against the clean one first (``Nomad.nsim_files``, ``nsim_pairs.csv``)."""
 import argparse
 import os
 
@@ -110,7 +113,27 @@ def main(argv=None):
     ap.add_argument("--nsim", action="store_true",
                     help="--sweep: add an NSIM column, the mean gammatone NSIM of the same degraded rows with their clean clips (Nomad.nsim; "
                          "this project's measure, not ViSQOL's); every clean file then needs 80 ms")
+    ap.add_argument("--nsim-pairs", dest="nsim_pairs", type=str, default=None, metavar="CSV",
+                    help="NSIM of rendered files with their clean files, each pair time-aligned first: CSV has the columns filepath_ref and "
+                         "filepath_deg (the reference's degraded_data_visqol_format.csv); writes nsim_pairs.csv under --results_path "
+                         "(Nomad.nsim_files; this project's measure and delay search, not ViSQOL's).  Needs neither --nmr nor --deg")
+    ap.add_argument("--max-delay", dest="max_delay", type=float, default=None, metavar="S",
+                    help="--nsim-pairs: the largest delay searched, in seconds (default 0.25, at most 1.024)")
     a = ap.parse_args(argv)
+    if a.max_delay is not None and a.nsim_pairs is None:
+        ap.error("--max-delay goes with --nsim-pairs")
+    if a.nsim_pairs is not None:
+        if a.sweep or a.window is not None or a.spans is not None or a.active_db is not None or a.knn is not None:
+            ap.error("--nsim-pairs scores file pairs on its own: it does not go with --sweep, --window, --spans, --active-db or --knn")
+        if a.max_delay is not None and not 0.0 <= a.max_delay <= 1.024:
+            ap.error(f"--max-delay takes seconds from 0 to 1.024, got {a.max_delay}")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--nsim-pairs runs in one process")
+        nomad = Nomad(device=a.device, weights=a.weights, precision=a.precision)
+        table = nomad.nsim_files(a.nsim_pairs, max_delay_s=0.25 if a.max_delay is None else a.max_delay, results_path=a.results_path)
+        print("NSIM of the aligned pairs, printing the first 5 rows")
+        print(table.head())
+        return
     if a.hop is not None and a.window is None:
         ap.error("--hop goes with --window")
     if not a.sweep and (a.noise is not None or a.snr_db is not None or a.clip is not None):

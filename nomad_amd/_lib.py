@@ -81,6 +81,13 @@ SIGNATURES = {
     "nomad_gammatone": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "nomad_nsim_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_longlong]),
     "nomad_nsim": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_align_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # (the second host table of either call - the degraded lengths, the output lengths - goes in as an address like the device
+    # pointers: a ctypes int array is passed as it is)
+    "nomad_align_delay": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, C.c_int, C.c_int, _fp, C.c_int,
+                                    _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_align_shift": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp, _fp, C.c_int, _fp,
+                                    C.c_size_t, _fp]),
     "nomad_embed_features": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "nomad_embed_features_ragged": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp,
                                               C.c_size_t, _fp]),

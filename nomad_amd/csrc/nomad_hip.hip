@@ -30,6 +30,7 @@
 #include "reverb.hip.h"
 #include "loudness.hip.h"
 #include "nsim.hip.h"
+#include "align.hip.h"
 #include "frontend.hip.h"
 #include "gemm_bf16.hip.h"
 #include "gemm_bf16_8phase.hip.h"
@@ -4290,6 +4291,114 @@ int nomad_nsim(nomad_ctx* c, const double* spec_ref, const double* spec_deg, int
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
     hipLaunchKernelGGL(nsim_kernel, dim3((unsigned)(B * G)), dim3(256), 0, s, spec_ref, spec_deg, G, reinterpret_cast<const int*>(w),
                        reinterpret_cast<const long long*>(w + l.fpref), total, C1, C3, reinterpret_cast<double*>(w + l.planes), nsim_out, bands_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- time alignment: delay search and shift (align.hip.h) ----
+// Scratch: [clean lengths: B int32, to 256 bytes | degraded lengths: B G int32, to 256 bytes | parts [B G][pmax][2 D + 1] float64],
+// pmax = the parts of a clip as long as the stride.  nomad_align_shift uses the front of it: [degraded lengths | output lengths].
+struct AlignLayout {
+    int pmax;
+    size_t dlens, parts, total;
+};
+static size_t align_lens_bytes(long long rows) { return (sizeof(int) * (size_t)rows + 255) / 256 * 256; }
+static AlignLayout align_layout(int B, int G, int stride, int max_delay) {
+    AlignLayout l;
+    l.pmax = align_parts(stride);
+    l.dlens = align_lens_bytes(B);
+    l.parts = l.dlens + align_lens_bytes((long long)B * G);
+    l.total = l.parts + sizeof(double) * (size_t)B * (size_t)G * (size_t)l.pmax * (size_t)(2 * max_delay + 1);
+    const size_t shift = 2 * align_lens_bytes((long long)B * G);
+    l.total = l.total < shift ? shift : l.total;
+    return l;
+}
+constexpr int kAlignMaxStride = 1 << 30;
+
+size_t nomad_align_scratch_bytes(int B, int G, int stride, int deg_stride, int max_delay) {
+    if (B < 1 || B > 65535 || G < 1 || G > 64 || stride < 1 || stride > kAlignMaxStride || deg_stride < 1 || deg_stride > kAlignMaxStride ||
+        max_delay < 0 || max_delay > kAlignMaxDelay) {
+        (void)fail(NOMAD_ERR_INVALID,
+                   "nomad_align_scratch_bytes: bad argument (B=%d: 1 .. 65535, G=%d: 1 .. 64, stride=%d, deg_stride=%d: 1 .. 2^30, max_delay=%d: "
+                   "0 .. %d)", B, G, stride, deg_stride, max_delay, kAlignMaxDelay);
+        return 0;
+    }
+    return align_layout(B, G, stride, max_delay).total;
+}
+
+int nomad_align_delay(nomad_ctx* c, const float* clean, int B, int stride, const int* lens, const float* deg, int G, int deg_stride,
+                      const int* deg_lens, int max_delay, int* delay_out, double* peak_out, double* corr_out, void* ws, size_t ws_bytes,
+                      nomad_stream_t stream) {
+    const char* who = "nomad_align_delay";
+    if (!c || !clean || !lens || !deg || !deg_lens || !delay_out || !peak_out || !ws)
+        return fail(NOMAD_ERR_INVALID, "%s: a NULL context, clean rows, lengths, degraded rows, degraded lengths, delay or peak output or workspace", who);
+    if (B < 1 || B > 65535) return fail(NOMAD_ERR_INVALID, "%s: B=%d clips, 1 .. 65535 are supported", who, B);
+    if (G < 1 || G > 64) return fail(NOMAD_ERR_INVALID, "%s: G=%d rows per clip, 1 .. 64 are supported", who, G);
+    if (max_delay < 0 || max_delay > kAlignMaxDelay)
+        return fail(NOMAD_ERR_INVALID, "%s: max_delay=%d samples, 0 .. %d are supported", who, max_delay, kAlignMaxDelay);
+    if (stride < 1 || stride > kAlignMaxStride) return fail(NOMAD_ERR_INVALID, "%s: stride=%d, 1 .. 2^30 are supported", who, stride);
+    if (deg_stride < 1 || deg_stride > kAlignMaxStride)
+        return fail(NOMAD_ERR_INVALID, "%s: deg_stride=%d, 1 .. 2^30 are supported", who, deg_stride);
+    const long long R = (long long)B * G;
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 1 || lens[b] > stride)
+            return fail(NOMAD_ERR_INVALID, "%s: clip %d has length %d, 1 .. stride=%d are supported", who, b, lens[b], stride);
+    for (long long r = 0; r < R; ++r)
+        if (deg_lens[r] < 1 || deg_lens[r] > deg_stride)
+            return fail(NOMAD_ERR_INVALID, "%s: degraded row %lld has length %d, 1 .. deg_stride=%d are supported", who, r, deg_lens[r], deg_stride);
+    const AlignLayout l = align_layout(B, G, stride, max_delay);
+    const int nl = 2 * max_delay + 1, lag_blocks = (nl + kAlignTile - 1) / kAlignTile;
+    if (R * lag_blocks * l.pmax > 0x7fffffffLL)
+        return fail(NOMAD_ERR_INVALID, "%s: %lld workgroups, more than one launch holds", who, R * lag_blocks * l.pmax);
+    if (ws_bytes < l.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(l.parts, 0);
+    memcpy(staged.data(), lens, sizeof(int) * (size_t)B);
+    memcpy(staged.data() + l.dlens, deg_lens, sizeof(int) * (size_t)R);
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), l.parts, hipMemcpyHostToDevice, s));
+    const int* lens_dev = reinterpret_cast<const int*>(w);
+    double* parts = reinterpret_cast<double*>(w + l.parts);
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(align_corr_kernel, dim3((unsigned)(R * lag_blocks * l.pmax)), dim3(kAlignThreads), 0, s, clean, stride, lens_dev, deg,
+                       deg_stride, reinterpret_cast<const int*>(w + l.dlens), G, max_delay, lag_blocks, l.pmax, parts);
+    hipLaunchKernelGGL(align_select_kernel, dim3((unsigned)R), dim3(256), 0, s, static_cast<const double*>(parts), lens_dev, G, max_delay,
+                       l.pmax, delay_out, peak_out, corr_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int nomad_align_shift(nomad_ctx* c, const float* deg, int R, int deg_stride, const int* deg_lens, const int* delay, const int* out_lens,
+                      float* out, int out_stride, void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_align_shift";
+    if (!c || !deg || !deg_lens || !delay || !out_lens || !out || !ws)
+        return fail(NOMAD_ERR_INVALID, "%s: a NULL context, degraded rows, lengths, delays, output lengths, output or workspace", who);
+    if (R < 1 || R > 65535 * 64) return fail(NOMAD_ERR_INVALID, "%s: R=%d rows, 1 .. 65535 x 64 are supported", who, R);
+    if (deg_stride < 1 || deg_stride > kAlignMaxStride)
+        return fail(NOMAD_ERR_INVALID, "%s: deg_stride=%d, 1 .. 2^30 are supported", who, deg_stride);
+    if (out_stride < 1 || out_stride > kAlignMaxStride)
+        return fail(NOMAD_ERR_INVALID, "%s: out_stride=%d, 1 .. 2^30 are supported", who, out_stride);
+    for (int r = 0; r < R; ++r) {
+        if (deg_lens[r] < 1 || deg_lens[r] > deg_stride)
+            return fail(NOMAD_ERR_INVALID, "%s: degraded row %d has length %d, 1 .. deg_stride=%d are supported", who, r, deg_lens[r], deg_stride);
+        if (out_lens[r] < 1 || out_lens[r] > out_stride)
+            return fail(NOMAD_ERR_INVALID, "%s: output row %d has length %d, 1 .. out_stride=%d are supported", who, r, out_lens[r], out_stride);
+    }
+    const long long tiles = ((long long)out_stride + 255) / 256;
+    if (tiles * R > 0x7fffffffLL) return fail(NOMAD_ERR_INVALID, "%s: %lld workgroups, more than one launch holds", who, tiles * R);
+    const size_t tab = align_lens_bytes(R), need = 2 * tab;
+    if (ws_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(need, 0);
+    memcpy(staged.data(), deg_lens, sizeof(int) * (size_t)R);
+    memcpy(staged.data() + tab, out_lens, sizeof(int) * (size_t)R);
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), need, hipMemcpyHostToDevice, s));
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(align_shift_kernel, dim3((unsigned)(tiles * R)), dim3(256), 0, s, deg, deg_stride, reinterpret_cast<const int*>(w), delay,
+                       reinterpret_cast<const int*>(w + tab), (int)tiles, out, out_stride);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -844,6 +844,69 @@ class Engine:
         spec_deg, _ = self.gammatone(packed=(dbuf, dlens), sample_rate=sample_rate)
         return self.nsim_of_spectrograms(spec_ref, spec_deg, frames, G, intensity_range, want_bands)
 
+    ALIGN_MAX_DELAY = 16384
+
+    def _align_rows(self, clean, degraded, G, max_delay):
+        cbuf, clens = self._rows(None, None, clean)
+        dbuf, dlens = self._rows(None, None, degraded)
+        G, max_delay = int(G), int(max_delay)
+        if not 1 <= G <= 64:
+            raise ValueError(f"align takes 1 .. 64 degraded rows per clean clip, got {G}")
+        if not 0 <= max_delay <= self.ALIGN_MAX_DELAY:
+            raise ValueError(f"max_delay must be 0 .. {self.ALIGN_MAX_DELAY} samples, got {max_delay}")
+        if len(dlens) != G * len(clens) or not clens:
+            raise ValueError("degraded must hold G rows per clean clip, row b G + g belonging to clip b")
+        if min(clens) < 1 or min(dlens) < 1:
+            raise ValueError("every clean clip and every degraded row needs at least one sample")
+        return cbuf, clens, dbuf, dlens, G, max_delay
+
+    def align_delay(self, clean, degraded, G: int, max_delay: int, want_corr: bool = False):
+        """The delay of every degraded row against its clean clip -> (delay (B G,) int32, peak (B G,) float64, corr (B G, 2
+        max_delay + 1) float64 or None), all on the device: clean and degraded are (device buffer, lengths) pairs as ``nsim``
+        takes them, but the degraded lengths may be any positive values.  ``corr[r][d + max_delay]`` is the cross-correlation
+        ``sum_i x[i] y[i + d]``, the delay the lag of its largest value (d > 0: the row is late; ties to the smaller ``|d|``, then
+        to d >= 0; any NaN: delay 0, peak NaN).  fp32 products on the matrix cores, 4096 steps per chain, the chains added in
+        float64: include/nomad_hip.h states the order (``nomad_align_delay``)."""
+        cbuf, clens, dbuf, dlens, G, max_delay = self._align_rows(clean, degraded, G, max_delay)
+        B, R = len(clens), len(dlens)
+        delay = torch.empty(R, dtype=torch.int32, device=self.device)
+        peak = torch.empty(R, dtype=torch.float64, device=self.device)
+        corr = torch.empty(R, 2 * max_delay + 1, dtype=torch.float64, device=self.device) if want_corr else None
+        ws = self._workspace(self._scratch_size(self.lib.nomad_align_scratch_bytes, "nomad_align_scratch_bytes", B, G, cbuf.shape[1],
+                                                dbuf.shape[1], max_delay))
+        _lib.check(self.lib.nomad_align_delay(self.ctx, cbuf.data_ptr(), B, cbuf.shape[1], (C.c_int * B)(*clens), dbuf.data_ptr(), G,
+                                              dbuf.shape[1], (C.c_int * R)(*dlens), max_delay, delay.data_ptr(), peak.data_ptr(), _ptr(corr),
+                                              ws.data_ptr(), ws.numel(), self._stream()), "nomad_align_delay")
+        return delay, peak, corr
+
+    def align_shift(self, degraded, delay: torch.Tensor, out_lengths, out_stride: Optional[int] = None):
+        """Every degraded row moved by its delay: ``out[r][i] = y[r][i + delay[r]]`` inside the row, 0 outside and behind
+        ``out_lengths[r]`` -> (rows (R, out_stride) fp32 on the device, out_lengths).  ``delay`` is an int32 device tensor and is
+        read on the device (``nomad_align_shift``)."""
+        dbuf, dlens = self._rows(None, None, degraded)
+        R = len(dlens)
+        olens = [int(n) for n in out_lengths]
+        if not (torch.is_tensor(delay) and delay.is_cuda and delay.dtype == torch.int32 and delay.is_contiguous() and delay.numel() == R):
+            raise ValueError(f"delay must be a contiguous int32 tensor of {R} entries on {self.device}")
+        if len(olens) != R or min(olens) < 1 or min(dlens) < 1:
+            raise ValueError("out_lengths must hold one positive entry per degraded row")
+        stride = (max(olens) + 3) // 4 * 4 if out_stride is None else int(out_stride)
+        out = torch.empty(R, stride, dtype=torch.float32, device=self.device)
+        ws = self._workspace(2 * ((4 * R + 255) // 256 * 256))
+        _lib.check(self.lib.nomad_align_shift(self.ctx, dbuf.data_ptr(), R, dbuf.shape[1], (C.c_int * R)(*dlens), delay.data_ptr(),
+                                              (C.c_int * R)(*olens), out.data_ptr(), stride, ws.data_ptr(), ws.numel(), self._stream()),
+                   "nomad_align_shift")
+        return out, olens
+
+    def align(self, clean, degraded, G: int, max_delay: int):
+        """``align_delay`` then ``align_shift`` with no host round trip -> ((rows (B G, stride) fp32, clean lengths repeated G
+        times), delay (B G,) int32 on the device, peak (B G,) float64): row b G + g has clip b's length and stride, so the pair
+        goes into ``nsim`` / ``embed_ragged(packed=...)`` as a degradation's result does."""
+        cbuf, clens, dbuf, dlens, G, max_delay = self._align_rows(clean, degraded, G, max_delay)
+        delay, peak, _ = self.align_delay((cbuf, clens), (dbuf, dlens), G, max_delay)
+        rows = self.align_shift((dbuf, dlens), delay, [n for n in clens for _ in range(G)], out_stride=cbuf.shape[1])
+        return rows, delay, peak
+
     def cdist(self, a: torch.Tensor, b: torch.Tensor, want_matrix: bool = True):
         """a (Na,D), b (Nb,D) fp32 on the GPU, D a multiple of 4 up to 4096 -> (dist (Na,Nb) float64 or None, mean (Na,)
         float64): ``pairwise`` for rows of any width (the same bits at D = 256)."""

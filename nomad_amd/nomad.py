@@ -575,6 +575,37 @@ def _file_table(path) -> pd.DataFrame:
     raise Exception(f"Path {path} does not exist")
 
 
+def pairs_from_csv(table):
+    """The (clean, degraded) file pairs of ``nsim_files`` -> (clean paths, degraded paths): a csv path or a DataFrame with the
+    columns ``filepath_ref`` and ``filepath_deg`` - what the reference's data preparation writes as
+    ``degraded_data_visqol_format.csv``.  Other columns are ignored; the rows keep their order."""
+    if isinstance(table, (str, os.PathLike)):
+        if not os.path.isfile(table):
+            raise ValueError(f"File {table} does not exist")
+        table = pd.read_csv(table)
+    if not isinstance(table, pd.DataFrame):
+        raise ValueError("the pairs are a csv path or a DataFrame with the columns filepath_ref and filepath_deg")
+    missing = [c for c in ("filepath_ref", "filepath_deg") if c not in table.columns]
+    if missing:
+        raise ValueError(f"the pairs table lacks the column(s) {', '.join(missing)}: filepath_ref and filepath_deg are needed")
+    if len(table) == 0:
+        raise ValueError("the pairs table has no rows")
+    if table[["filepath_ref", "filepath_deg"]].isna().any().any():
+        raise ValueError("the pairs table has an empty filepath_ref or filepath_deg")
+    return [str(p) for p in table["filepath_ref"]], [str(p) for p in table["filepath_deg"]]
+
+
+def check_max_delay(max_delay_s, sample_rate: int = 16000) -> int:
+    """``max_delay_s`` of ``align`` / ``nsim`` / ``nsim_files`` -> whole samples: a finite number of seconds from 0 up to 16384
+    samples (1.024 s at 16 kHz), rounded to the nearest sample."""
+    if isinstance(max_delay_s, bool) or not isinstance(max_delay_s, (int, float, np.integer, np.floating)) or not math.isfinite(max_delay_s):
+        raise ValueError(f"max_delay_s must be a finite number of seconds, got {max_delay_s!r}")
+    samples = int(round(float(max_delay_s) * sample_rate))
+    if max_delay_s < 0 or samples > Engine.ALIGN_MAX_DELAY:
+        raise ValueError(f"max_delay_s must lie in 0 .. {Engine.ALIGN_MAX_DELAY / sample_rate} s ({Engine.ALIGN_MAX_DELAY} samples), got {max_delay_s}")
+    return samples
+
+
 class _CdistFn(torch.autograd.Function):
     """``Engine.cdist`` with a backward: (dist, mean) -> d / d a and d / d b through ``Engine.cdist_backward``."""
 
@@ -1738,16 +1769,77 @@ class Nomad:
         x, lens = self._rows_for_normalize(wav, lengths, "normalize")
         return self.engine.degrade_normalize(x, lengths=lens, target=target, kind=kind, peak_db=peak_db)
 
-    def nsim(self, degraded, clean, lengths=None, bands: bool = False, intensity_range: float = 1.0):
+    def _align_inputs(self, degraded, clean, lengths, degraded_lengths, max_delay_s, what: str):
+        """The arguments of ``align`` checked on the host -> (clean tensor, its lengths, degraded tensor, its lengths, G, max delay
+        in samples).  degraded: a (R,1,M) / (R,M) tensor of any width with ``degraded_lengths``, or a packed ``(rows, lengths)``."""
+        max_delay = check_max_delay(max_delay_s)
+        x, lens = self._rows_for_normalize(clean, lengths, what)
+        if isinstance(degraded, tuple):
+            if degraded_lengths is not None:
+                raise ValueError("degraded_lengths go with a tensor: packed (rows, lengths) have their own")
+            if len(degraded) != 2 or not torch.is_tensor(degraded[0]) or degraded[0].dim() != 2:
+                raise ValueError("degraded must be a (R,1,M) or (R,M) tensor, or packed (rows (R, stride), lengths)")
+            if degraded[0].requires_grad:
+                raise ValueError(f"{what} produces no gradient (the degradations have no backward): pass tensors that do not require one")
+            d, dlens = degraded[0].detach(), [int(n) for n in degraded[1]]
+        else:
+            d, dlens = self._rows_for_normalize(degraded, degraded_lengths, what)
+        if len(lens) != x.shape[0] or len(dlens) != d.shape[0]:
+            raise ValueError("lengths must hold one entry per clean clip, degraded_lengths one per degraded row")
+        if not dlens or len(dlens) % len(lens) or len(dlens) // len(lens) > 64:
+            raise ValueError(f"degraded must hold G rows per clean clip, G = 1 .. 64 (row b G + g belongs to clip b), got {len(dlens)} rows "
+                             f"for {len(lens)} clips")
+        if min(lens) < 1 or max(lens) > x.shape[1] or min(dlens) < 1 or max(dlens) > d.shape[1]:
+            raise ValueError("every length must lie in 1 .. the width of its tensor")
+        return x, lens, d, dlens, len(dlens) // len(lens), max_delay
+
+    def align(self, degraded, clean, lengths=None, degraded_lengths=None, max_delay_s: float = 0.25):
+        """Degraded clips brought into line with their clean clips on the GPU -> ((rows (B G, stride) fp32 on the GPU, lengths),
+        delay (B G,) int32 on the GPU, peak (B G,) float64): row ``b G + g`` is degraded row ``b G + g`` moved by its delay, cut or
+        zero-filled to clip ``b``'s length, so the pair goes straight into ``nsim``, ``score`` and ``embed_ragged(packed=...)``.
+        clean (B,1,N) or (B,N) with ``lengths``; degraded a tensor of ANY width with ``degraded_lengths`` (its own exact lengths),
+        or packed ``(rows, lengths)``; B G rows, G = 1 .. 64.  The delay is the lag, within ``max_delay_s`` (up to 1.024 s), of the
+        largest cross-correlation ``sum_i clean[i] degraded[i + d]`` - positive where the degraded clip is late - and ONE whole
+        number of samples per row: no sub-sample delays, no clock drift, no per-patch re-alignment, no polarity search; ``peak`` is
+        the correlation there (NaN, with a delay of 0, where a row or its clip holds a NaN).  include/nomad_hip.h states the
+        arithmetic (``nomad_align_delay``); agreement with ViSQOL's aligner has not been measured.  No gradient."""
+        x, lens, d, dlens, G, max_delay = self._align_inputs(degraded, clean, lengths, degraded_lengths, max_delay_s, "align")
+        eng = self.engine
+        return eng.align(eng._rows(x, lens, None), self._packed_rows(d, dlens), G, max_delay)
+
+    def _packed_rows(self, d, dlens):
+        """A checked (R, M) tensor and its lengths as a packed device pair (no copy where it already is one)."""
+        eng = self.engine
+        d = d.to(eng.device, torch.float32)
+        if d.shape[1] % 4 or not d.is_contiguous():
+            return eng._pack([d[i, :n] for i, n in enumerate(dlens)])
+        return eng._rows(None, None, (d, dlens))
+
+    def nsim(self, degraded, clean, lengths=None, bands: bool = False, intensity_range: float = 1.0, max_delay_s=None,
+             degraded_lengths=None):
         """The gammatone-spectrogram NSIM of degraded clips with their clean clips, computed on the GPU: the similarity the
         reference takes from ViSQOL before it samples triplets -> (B, G) float64 on the GPU, 1 for identical clips and falling with
         the degradation (with ``bands``: also the (B, G, 21) per-band values whose mean it is).  clean (B,1,N) or (B,N) with
         ``lengths``, the clips' exact lengths (at least 80 ms each); degraded: a tensor of clean's shape (G = 1), or the packed
         ``(rows, lengths)`` that ``degrade`` / ``convolve`` / ``reverb`` / ``normalize`` return for these clips - row ``b G + g``
         belongs to clip ``b`` - which is used without a copy.  21 ERB bands from 50 Hz to 8 kHz, 80 ms frames every 20 ms, dB
-        floors, a 3 x 3 window over one similarity map of the whole clip: the rows must be sample-aligned with their clean clip (no
-        patch search, no time alignment, no voice-activity gate, no MOS mapping).  Modelled on ViSQOL's speech mode from memory
-        and NOT checked against the ViSQOL binary; include/nomad_hip.h states the measure.  No gradient."""
+        floors, a 3 x 3 window over one similarity map of the whole clip (no patch search, no voice-activity gate, no MOS
+        mapping).  Time alignment: with ``max_delay_s=None`` there is none and the rows must be sample-aligned with their clean
+        clip, as everything the degradations make is.  With ``max_delay_s`` (seconds, up to 1.024) every row is first moved by its
+        delay against its clip (``align``: one whole-sample delay per row); the degraded rows may then have any lengths - a tensor
+        of another width takes ``degraded_lengths`` - and the (B, G) int32 delays are returned as one more, last result.
+        Modelled on ViSQOL's speech mode from memory and NOT checked against the ViSQOL binary, neither the measure nor the
+        delays; include/nomad_hip.h states both.  No gradient."""
+        if max_delay_s is not None:
+            x, lens, d, dlens, G, max_delay = self._align_inputs(degraded, clean, lengths, degraded_lengths, max_delay_s, "nsim")
+            eng = self.engine
+            crows = eng._rows(x, lens, None)
+            rows, delay, _ = eng.align(crows, self._packed_rows(d, dlens), G, max_delay)
+            score, per_band = eng.nsim(crows, rows, G, intensity_range=intensity_range, want_bands=bands)
+            delay = delay.view(len(lens), G)
+            return (score, per_band, delay) if bands else (score, delay)
+        if degraded_lengths is not None:
+            raise ValueError("degraded_lengths go with max_delay_s: without alignment a degraded row has its clean clip's length")
         x, lens = self._rows_for_normalize(clean, lengths, "nsim")
         eng = self.engine
         cbuf, clens = eng._rows(x, lens, None)
@@ -1765,6 +1857,64 @@ class Nomad:
             G = 1
         score, per_band = eng.nsim((cbuf, clens), (dbuf, dlens), G, intensity_range=intensity_range, want_bands=bands)
         return (score, per_band) if bands else score
+
+    def nsim_files(self, degraded, clean=None, max_delay_s: float = 0.25, results_path=None, max_batch_samples: int = 64 * 160000):
+        """The NSIM of rendered files with their clean files, each pair aligned first: files a codec, a device or another program
+        made, which are not sample-aligned with their source.  ``degraded`` and ``clean``: two lists of paths of one length; or
+        ``degraded`` alone: a csv path (or DataFrame) with the columns ``filepath_ref`` and ``filepath_deg``, the reference's
+        ``degraded_data_visqol_format.csv``.  -> a DataFrame ``filepath_ref, filepath_deg, delay_samples, delay_s, NSIM`` in the
+        pairs' order, written to ``nsim_pairs.csv`` under ``results_path`` if given.  The files go through the staged reader of
+        ``predict`` (mono, resampled to 16 kHz), pairs are batched up to ``max_batch_samples`` samples, and every pair is
+        ``nsim(max_delay_s=...)`` of its two files: the degraded file moved by ONE delay of whole samples (positive: it is late)
+        and cut or zero-filled to the clean file's length.  A pair whose clean file is under 80 ms gets NaN.  The NSIM is this
+        project's (``nsim``) and the delay search is not ViSQOL's either: neither has been checked against that binary."""
+        if clean is None:
+            ref_paths, deg_paths = pairs_from_csv(degraded)
+        else:
+            if isinstance(degraded, (str, os.PathLike)) or isinstance(clean, (str, os.PathLike)):
+                raise ValueError("nsim_files takes two lists of paths, or one csv with the columns filepath_ref and filepath_deg")
+            ref_paths, deg_paths = [str(p) for p in clean], [str(p) for p in degraded]
+            if len(ref_paths) != len(deg_paths) or not ref_paths:
+                raise ValueError(f"nsim_files needs as many clean files as degraded ones and at least one, got {len(ref_paths)} and {len(deg_paths)}")
+        max_delay = check_max_delay(max_delay_s)
+        eng = self.engine
+        paths = [p for pair in zip(ref_paths, deg_paths) for p in pair]      # file 2 k is pair k's clean file, 2 k + 1 its degraded one
+        delays, scores = np.zeros(len(ref_paths), dtype=np.int64), np.full(len(ref_paths), np.nan)
+        held, fetches = {}, []
+
+        def run(ks):
+            cbuf, clens = eng._pack([held[2 * k] for k in ks])
+            rows, delay, _ = eng.align((cbuf, clens), eng._pack([held[2 * k + 1] for k in ks]), 1, max_delay)
+            ok = [i for i, n in enumerate(clens) if Engine.gammatone_frames(n) >= 1]
+            sims = None
+            if ok:
+                pick = torch.as_tensor(ok, device=eng.device)
+                lens_ok = [clens[i] for i in ok]
+                sims = eng.nsim((cbuf[pick], lens_ok), (rows[0][pick], lens_ok), 1, want_bands=False)[0].reshape(-1)
+            fetches.append((ks, ok, eng.fetch_async(delay), eng.fetch_async(sims) if ok else None))
+            for k in ks:
+                del held[2 * k], held[2 * k + 1]
+
+        for idxs, packed, uploaded in _staged_batches(paths, lambda p: self.load_processing(p, trim=False), eng.pack_ragged_host,
+                                                      max_batch_samples, self.DECODE_THREADS, self.PIPELINE_BATCHES, self.NATIVE_WAV_THREADS,
+                                                      device=getattr(eng, "device", None)):
+            buf, lens = eng._pack(None, packed)
+            uploaded()
+            for r, i in enumerate(idxs):
+                held[i] = buf[r, :lens[r]]
+            ks = sorted(i // 2 for i in idxs if i % 2 and i - 1 in held)      # a pair is whole once its degraded file is here
+            if ks:
+                run(ks)
+        for ks, ok, delay, sims in fetches:
+            delays[ks] = delay.result()
+            if ok:
+                scores[[ks[i] for i in ok]] = sims.result()
+        df = pd.DataFrame({"filepath_ref": ref_paths, "filepath_deg": deg_paths, "delay_samples": delays, "delay_s": delays / 16000.0,
+                           "NSIM": scores})
+        if results_path is not None:
+            os.makedirs(results_path, exist_ok=True)
+            df.to_csv(os.path.join(results_path, "nsim_pairs.csv"), index=False)
+        return df
 
     def mine_triplets(self, clean, noise=None, snr_db=None, clip_factor=None, reverberance=None, normalize=-23.0, lengths=None,
                       N: int = 3, hard_sampling: bool = False, margin: float = 0.05, seed=0):
