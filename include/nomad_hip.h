@@ -31,6 +31,8 @@
  *   nomad_gammatone / nomad_nsim   gammatone spectrograms of packed rows and the NSIM of each degraded row with its clean clip: the
  *                                  similarity src/utils/nsim_triplet_sampling.py samples triplets from (modelled on ViSQOL's speech mode
  *                                  from memory; not checked against the binary)
+ *   nomad_nsim_patches             the same similarity patch by patch: the clean clip's active patches, each searched for in the
+ *                                  degraded spectrogram, so that a delay may change inside a file and silence does not count
  *   nomad_align_delay / _shift     the delay of every degraded row against its clean clip (the largest cross-correlation over integer
  *                                  lags) and the rows moved by it: what files with codec delay need ahead of nomad_nsim
  *   nomad_wav_probe / _read_rows   torchaudio.load + channel mean + Resample of load_processing (nomad.py:196-205)
@@ -864,12 +866,13 @@ int nomad_degrade_reverb(nomad_ctx* ctx, const float* x_dev, int B, int stride, 
  * WHAT THIS IS NOT: a port checked against ViSQOL.  The measure below is modelled on what ViSQOL's speech mode is remembered to do
  * (Slaney's ERB gammatone bank, 80 ms frames every 20 ms with the filter state reset per frame, dB floors, a 3 x 3 NSIM window);
  * ViSQOL was not available where it was written, so its agreement with the ViSQOL binary has never been measured.  The text
- * below is the definition, and tests/nsim_ref.py restates it.  ViSQOL's patch search and voice-activity gate are left out, and
- * these two calls align nothing: one similarity map covers the whole clip, so the rows must be sample-aligned with their clean clip.
+ * below is the definition, and tests/nsim_ref.py restates it.  These two calls have no patch search and no voice-activity gate
+ * (nomad_nsim_patches below adds both, over whole frames), and
+ * they align nothing: one similarity map covers the whole clip, so the rows must be sample-aligned with their clean clip.
  * The rows the degradations make are, by construction; rows with ONE constant delay of whole samples (a codec round trip, a model
- * with latency) are brought there by nomad_align_delay / nomad_align_shift below.  Still outside what is claimed: delays that change
- * inside a file (clock drift, dropped packets), sub-sample delays, and agreement with ViSQOL's own aligner, which has not been
- * measured.  No gradient, no MOS mapping.
+ * with latency) are brought there by nomad_align_delay / nomad_align_shift below.  Delays that change inside a file (clock drift, dropped
+ * packets) are followed in steps of whole frames by nomad_nsim_patches.  Still outside what is claimed: sub-sample delays, and
+ * agreement with ViSQOL's own aligner, which has not been measured.  No gradient, no MOS mapping.
  *
  * Rows are fp32, mono, at fs = sample_rate samples per second, fs in 16000 .. 48000 and a multiple of 50.  Everything below is float64.
  * Bank: N = 21 bands.  With EarQ = 9.26449, minBW = 24.7, lo = 50, hi = 8000:
@@ -957,8 +960,8 @@ int nomad_nsim(nomad_ctx* ctx, const double* spec_ref_dev, const double* spec_de
  *                       DEVICE memory (nomad_align_delay's output, no host round trip; any int is taken).  A copy: the samples keep
  *                       their bits.  With out_lens_host[r] = n_b the result is a packed batch nomad_gammatone / nomad_embed_ragged read.
  *
- * NOT offered: sub-sample delays, clock drift, per-patch re-alignment, a polarity search (an inverted row finds some other lag), a
- * gradient.  How close the delays are to those of ViSQOL's aligner has not been measured.
+ * NOT offered: sub-sample delays, a per-patch re-alignment in the time domain (nomad_nsim_patches moves patches by whole frames of
+ * the spectrogram; clock drift is followed only so far), a polarity search (an inverted row finds some other lag), a gradient.  How close the delays are to those of ViSQOL's aligner has not been measured.
  * Contract as the degradations above: asynchronous on the caller's stream, no allocation, deterministic, no atomics; the host
  * tables are copied into the workspace ahead of the kernels, so the host arrays may die on return; workspace
  * nomad_align_scratch_bytes(B, G, stride, deg_stride, max_delay) bytes (0 for arguments the call would refuse; it covers a
@@ -975,6 +978,70 @@ int nomad_align_delay(nomad_ctx* ctx, const float* clean_dev, int B, int stride,
                       size_t ws_bytes, nomad_stream_t stream);
 int nomad_align_shift(nomad_ctx* ctx, const float* deg_dev, int R, int deg_stride, const int* deg_lens_host, const int* delay_dev,
                       const int* out_lens_host, float* out_dev, int out_stride, void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
+
+/* ---- patch-wise NSIM: a voice-activity gate on the clean clip and a search for every patch in the degraded row --------------
+ * nomad_nsim lays ONE map over the whole clip: a row whose delay changes inside the file (dropped or inserted frames, a device
+ * with its own clock, a concatenating model) gets a number that is too low, and silence counts like speech.  nomad_nsim_patches
+ * cuts the clean spectrogram into patches, keeps the active ones, finds for each where it best sits in the degraded spectrogram
+ * and averages the patches' similarities.
+ *
+ * WHAT THIS IS NOT: a port of ViSQOL.  Like the measure it extends it is modelled on what ViSQOL's speech mode is remembered to do;
+ * the text below is the definition, tests/patch_nsim_ref.py restates it, and its agreement with the ViSQOL binary has never been
+ * measured.  NOT offered: a time-domain fine alignment per patch, sub-sample delays, a polarity search, a MOS mapping, a gradient.
+ *
+ * Inputs, both from nomad_gammatone: spec_ref_dev [sum F_b][21] (B clean clips, F_b = frames_host[b]) and spec_deg_dev
+ * [sum over rows Fd_r][21]: degraded row r = b G + g belongs to clip b and has its OWN frame count Fd_r = deg_frames_host[r], shorter
+ * or longer than F_b, rows packed in that order; no nomad_align_shift has to come first.  Everything is float64.
+ * Parameters: patch in 1 .. 64 frames, search in 0 .. 128 frames, vad_ratio in (0, 1], min_active_frames in 1 .. patch,
+ *   intensity_range as in nomad_nsim.
+ * Activity, per clean clip: E_t = sum_b S[t][b]^2, bands ascending from 0, each product rounded and then added (no fused
+ *   multiply-add).  Frame t is active iff E_t >= vad_ratio * max_t E_t, the product rounded once, the maximum formed so that a NaN
+ *   sticks.  A silent clip is active everywhere (0 >= 0).
+ * Patches: clip b has P_b = F_b / patch patches (integer division; nomad_nsim_patch_count(F_b, patch)); patch p covers the clean
+ *   frames [s, s + patch) with s = p patch, trailing frames are in none.  Its candidate window in row r is
+ *   [lo, hi] = [max(s - search, 0), min(s + search, Fd_r - patch)].  The patch is KEPT for row r iff at least min_active_frames
+ *   of its frames are active and lo <= hi.
+ * Candidates: q_p[u] for u in [lo, hi] is nomad_nsim of the cut-out pair spec_ref[s .. s + patch) and spec_deg_r[u .. u + patch),
+ *   taken as two spectrograms of `patch` frames exactly as that call defines it: dB and absolute floor, the per-frame peak floor
+ *   over both, the minimum over both subtracted, the 3 x 3 window with its edges replicated at the PATCH's own edges, the
+ *   sequential band means, the mean of 21.  A candidate and its 21 band values have the BITS of a nomad_nsim call (B = 1, G = 1,
+ *   frames = patch) on the cut-outs.
+ * Selection, over the kept patches k = 0 .. K - 1 of a row in patch order (starts s_k, windows [lo_k, hi_k]): T_0[u] = q_0[u];
+ *   T_k[u] = T_{k-1}[a_k(u)] + q_k[u], where a_k(u) is the best u' in [lo_{k-1}, min(u, hi_{k-1})] under the order: larger T, then
+ *   smaller |u' - s_{k-1}|, then smaller u'.  The places of a chain so never decrease; lo_k and hi_k do not decrease in k, so
+ *   a chain always exists.  The row's chain ends at the best u of the last window under the same order and is traced back through a.
+ * Results per row: nsim = T_best / K; bands[j] = the chosen candidates' band values j added in ascending k, divided by K;
+ *   offsets[p] = u_p, the chosen place of patch p, -1 for a patch that is not kept; patch_nsim[p] = q_p[u_p], NaN where not kept.
+ *   K = 0 (a clip or a row shorter than a patch, nothing active enough) gives NaN, all offsets -1.  A silent pair gives exactly 1.
+ * Non-finite values: a NaN anywhere in a clean clip's spectrogram voids its G rows; a row one of whose candidates is NaN - a NaN
+ *   in a degraded frame inside some kept patch's window [lo, hi + patch) makes one - is void too: NaN results, offsets -1.  A NaN
+ *   outside every window is not seen.  No other row changes a bit.
+ *
+ *   nomad_nsim_patches  -> nsim_out_dev [B G]; bands_out_dev [B G][21], offsets_out_dev [B G][out_patches] int32, patch_nsim_out_dev
+ *                       [B G][out_patches], cand_out_dev [B G][out_patches][2 search + 1], each or NULL; out_patches >= every P_b and
+ *                       >= 1, entries from P_b on are -1 / NaN.  cand_out_dev receives every q_p[u] at column u - (s - search), NaN
+ *                       where there is no candidate (for a void row too).  The other outputs keep their bits with or without
+ *                       any optional output, and a row has the bits of its own B = 1, G = 1 call.  Three launches: the activity
+ *                       per clean clip, the candidates (one workgroup per row and patch; csrc/nsim_patches.hip.h states the
+ *                       layout), the selection per row.
+ * Contract as nomad_nsim: asynchronous on the caller's stream, no allocation, deterministic, no atomics; both host tables are
+ * copied into the workspace ahead of the kernels, so they may die on return; workspace nomad_nsim_patches_scratch_bytes(B, G,
+ * total_ref_frames = sum F_b, total_deg_frames = sum Fd_r, patch, search) bytes (0 for arguments the call would refuse), written
+ * before it is read.  Argument errors return before anything is queued.
+ * NOMAD_ERR_INVALID: a NULL context, spectrogram, table, nsim_out_dev or workspace; B outside 1 .. 65535, G outside 1 .. 64, patch
+ * outside 1 .. 64, search outside 0 .. 128, vad_ratio outside (0, 1] (a NaN included), min_active_frames outside 1 .. patch, an
+ * intensity range that is not finite and positive, a frame count below 1, out_patches below 1 or below a clip's P_b, more than
+ * 2^31 - 1 (row, patch) workgroups.  NOMAD_ERR_WORKSPACE: ws_bytes too small.
+ */
+int nomad_nsim_patch_count(int frames, int patch);
+size_t nomad_nsim_patches_scratch_bytes(int B, int G, long long total_ref_frames, long long total_deg_frames, int patch, int search);
+int nomad_nsim_patches(nomad_ctx* ctx, const double* spec_ref_dev, const double* spec_deg_dev, int B, int G,
+                       const int* frames_host /* [B] */, const int* deg_frames_host /* [B G] */, int patch, int search, double vad_ratio,
+                       int min_active_frames, double intensity_range, int out_patches /* >= every P_b, >= 1 */,
+                       double* nsim_out_dev /* [B G] */, double* bands_out_dev /* [B G][21] or NULL */,
+                       int* offsets_out_dev /* [B G][out_patches] or NULL */, double* patch_nsim_out_dev /* [B G][out_patches] or NULL */,
+                       double* cand_out_dev /* [B G][out_patches][2 search + 1] or NULL */, void* ws_dev, size_t ws_bytes,
+                       nomad_stream_t stream);
 
 /* ---- bf16 path (BASELINE config C5: long-form clips) ---------------------------------------- */
 /*

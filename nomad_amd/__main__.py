@@ -16,7 +16,9 @@ column: the mean gammatone NSIM (``Nomad.nsim``) of the same rows with their cle
 order, next to the score.
 
 ``--nsim-pairs CSV [--max-delay S]`` (one process): the NSIM of every (``filepath_ref``, ``filepath_deg``) pair of CSV, the degraded
-file moved by its delay against the clean one first (``Nomad.nsim_files``, ``nsim_pairs.csv``)."""
+file moved by its delay against the clean one first (``Nomad.nsim_files``, ``nsim_pairs.csv``).  With ``--patch S [--search S]
+[--vad-db DB]`` the NSIM is the patch-wise one (``Nomad.nsim_patches``): the clean file's active patches of S seconds, each searched
+for within ``--search`` seconds of its own place, and the table gains ``patches_kept``, ``offset_min_frames`` and ``offset_max_frames``."""
 import argparse
 import os
 
@@ -119,9 +121,20 @@ def main(argv=None):
                          "(Nomad.nsim_files; this project's measure and delay search, not ViSQOL's).  Needs neither --nmr nor --deg")
     ap.add_argument("--max-delay", dest="max_delay", type=float, default=None, metavar="S",
                     help="--nsim-pairs: the largest delay searched, in seconds (default 0.25, at most 1.024)")
+    ap.add_argument("--patch", type=float, default=None, metavar="S",
+                    help="--nsim-pairs: the patch-wise NSIM (Nomad.nsim_patches) with patches of S seconds (0.02 .. 1.28; ViSQOL's speech "
+                         "mode is remembered to use 0.4): the clean file's active patches, each searched for in the degraded file")
+    ap.add_argument("--search", type=float, default=None, metavar="S",
+                    help="--patch: how far from its own place a patch is searched for, in seconds (default 1.2, at most 2.56)")
+    ap.add_argument("--vad-db", dest="vad_db", type=float, default=None, metavar="DB",
+                    help="--patch: a clean frame is active within DB decibels of the file's loudest frame (default 40)")
     a = ap.parse_args(argv)
     if a.max_delay is not None and a.nsim_pairs is None:
         ap.error("--max-delay goes with --nsim-pairs")
+    if a.patch is not None and a.nsim_pairs is None:
+        ap.error("--patch goes with --nsim-pairs")
+    if (a.search is not None or a.vad_db is not None) and a.patch is None:
+        ap.error("--search and --vad-db go with --patch")
     if a.nsim_pairs is not None:
         if a.sweep or a.window is not None or a.spans is not None or a.active_db is not None or a.knn is not None:
             ap.error("--nsim-pairs scores file pairs on its own: it does not go with --sweep, --window, --spans, --active-db or --knn")
@@ -130,7 +143,10 @@ def main(argv=None):
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit("--nsim-pairs runs in one process")
         nomad = Nomad(device=a.device, weights=a.weights, precision=a.precision)
-        table = nomad.nsim_files(a.nsim_pairs, max_delay_s=0.25 if a.max_delay is None else a.max_delay, results_path=a.results_path)
+        patches = {}
+        if a.patch is not None:
+            patches = {"patch_s": a.patch, "search_s": 1.2 if a.search is None else a.search, "vad_db": 40.0 if a.vad_db is None else a.vad_db}
+        table = nomad.nsim_files(a.nsim_pairs, max_delay_s=0.25 if a.max_delay is None else a.max_delay, results_path=a.results_path, **patches)
         print("NSIM of the aligned pairs, printing the first 5 rows")
         print(table.head())
         return

@@ -30,6 +30,7 @@
 #include "reverb.hip.h"
 #include "loudness.hip.h"
 #include "nsim.hip.h"
+#include "nsim_patches.hip.h"
 #include "align.hip.h"
 #include "frontend.hip.h"
 #include "gemm_bf16.hip.h"
@@ -4291,6 +4292,137 @@ int nomad_nsim(nomad_ctx* c, const double* spec_ref, const double* spec_deg, int
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
     hipLaunchKernelGGL(nsim_kernel, dim3((unsigned)(B * G)), dim3(256), 0, s, spec_ref, spec_deg, G, reinterpret_cast<const int*>(w),
                        reinterpret_cast<const long long*>(w + l.fpref), total, C1, C3, reinterpret_cast<double*>(w + l.planes), nsim_out, bands_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- patch-wise NSIM (nsim_patches.hip.h) ----
+int nomad_nsim_patch_count(int frames, int patch) { return frames < 1 || patch < 1 || patch > kPatchMax ? 0 : frames / patch; }
+
+// Scratch, every part rounded up to 256 bytes: [clean frame counts: B int32 | degraded frame counts: B G int32 | clean frame prefix
+// sums: B + 1 int64 | degraded frame prefix sums: B G + 1 int64 | patch prefix sums: B + 1 int64 || E: total_ref float64 |
+// activity: total_ref int32 | kept: TP int32 | clipbad: B int32 | candidates [G TP][2 search + 1] float64 | back-pointers
+// [G TP][2 search + 1] int32 | link, pick: [G TP] int32 each].  TP = the patches of all clean clips; the size helper takes its
+// bound total_ref / patch.  The parts ahead of || come from the host.
+struct PatchLayout {
+    size_t dframes, fpref, dpref, ppref, E, active, kept, clipbad, cand, back, link, pick, total;
+};
+static PatchLayout patch_layout(int B, int G, long long total_ref, long long TP, int search) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t R = (size_t)B * (size_t)G, places = 2 * (size_t)search + 1, rp = (size_t)G * (size_t)(TP < 1 ? 1 : TP);
+    PatchLayout l;
+    l.dframes = up(sizeof(int) * (size_t)B);
+    l.fpref = l.dframes + up(sizeof(int) * R);
+    l.dpref = l.fpref + up(sizeof(long long) * ((size_t)B + 1));
+    l.ppref = l.dpref + up(sizeof(long long) * (R + 1));
+    l.E = l.ppref + up(sizeof(long long) * ((size_t)B + 1));
+    l.active = l.E + up(sizeof(double) * (size_t)total_ref);
+    l.kept = l.active + up(sizeof(int) * (size_t)total_ref);
+    l.clipbad = l.kept + up(sizeof(int) * (size_t)(TP < 1 ? 1 : TP));
+    l.cand = l.clipbad + up(sizeof(int) * (size_t)B);
+    l.back = l.cand + up(sizeof(double) * rp * places);
+    l.link = l.back + up(sizeof(int) * rp * places);
+    l.pick = l.link + up(sizeof(int) * rp);
+    l.total = l.pick + up(sizeof(int) * rp);
+    return l;
+}
+constexpr long long kPatchMaxFrames = 1ll << 31;
+
+size_t nomad_nsim_patches_scratch_bytes(int B, int G, long long total_ref_frames, long long total_deg_frames, int patch, int search) {
+    if (B < 1 || B > 65535 || G < 1 || G > 64 || total_ref_frames < B || total_ref_frames > kPatchMaxFrames ||
+        total_deg_frames < (long long)B * G || total_deg_frames > 64 * kPatchMaxFrames || patch < 1 || patch > kPatchMax || search < 0 ||
+        search > kPatchSearchMax) {
+        (void)fail(NOMAD_ERR_INVALID,
+                   "nomad_nsim_patches_scratch_bytes: bad argument (B=%d: 1 .. 65535, G=%d: 1 .. 64, total_ref_frames=%lld: B .. 2^31, "
+                   "total_deg_frames=%lld: B G .. 2^37, patch=%d: 1 .. %d, search=%d: 0 .. %d)", B, G, total_ref_frames, total_deg_frames, patch,
+                   kPatchMax, search, kPatchSearchMax);
+        return 0;
+    }
+    return patch_layout(B, G, total_ref_frames, total_ref_frames / patch, search).total;
+}
+
+int nomad_nsim_patches(nomad_ctx* c, const double* spec_ref, const double* spec_deg, int B, int G, const int* frames, const int* deg_frames,
+                       int patch, int search, double vad_ratio, int min_active_frames, double intensity_range, int out_patches,
+                       double* nsim_out, double* bands_out, int* offsets_out, double* patch_nsim_out, double* cand_out, void* ws,
+                       size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_nsim_patches";
+    if (!c || !spec_ref || !spec_deg || !frames || !deg_frames || !nsim_out || !ws)
+        return fail(NOMAD_ERR_INVALID, "%s: a NULL context, spectrogram, frame counts, output or workspace", who);
+    if (B < 1 || B > 65535) return fail(NOMAD_ERR_INVALID, "%s: B=%d clips, 1 .. 65535 are supported", who, B);
+    if (G < 1 || G > 64) return fail(NOMAD_ERR_INVALID, "%s: G=%d rows per clip, 1 .. 64 are supported", who, G);
+    if (patch < 1 || patch > kPatchMax) return fail(NOMAD_ERR_INVALID, "%s: patch=%d frames, 1 .. %d are supported", who, patch, kPatchMax);
+    if (search < 0 || search > kPatchSearchMax)
+        return fail(NOMAD_ERR_INVALID, "%s: search=%d frames, 0 .. %d are supported", who, search, kPatchSearchMax);
+    if (!(vad_ratio > 0.0 && vad_ratio <= 1.0)) return fail(NOMAD_ERR_INVALID, "%s: vad_ratio=%g, a value in (0, 1] is needed", who, vad_ratio);
+    if (min_active_frames < 1 || min_active_frames > patch)
+        return fail(NOMAD_ERR_INVALID, "%s: min_active_frames=%d, 1 .. patch=%d are supported", who, min_active_frames, patch);
+    if (!std::isfinite(intensity_range) || !(intensity_range > 0.0))
+        return fail(NOMAD_ERR_INVALID, "%s: the intensity range must be finite and positive, got %g", who, intensity_range);
+    const long long R = (long long)B * G;
+    long long total = 0, dtotal = 0, TP = 0;
+    int maxP = 0;
+    for (int b = 0; b < B; ++b) {
+        if (frames[b] < 1) return fail(NOMAD_ERR_INVALID, "%s: clip %d has %d frames, at least 1 is needed", who, b, frames[b]);
+        total += frames[b];
+        TP += frames[b] / patch;
+        maxP = frames[b] / patch > maxP ? frames[b] / patch : maxP;
+    }
+    for (long long r = 0; r < R; ++r) {
+        if (deg_frames[r] < 1) return fail(NOMAD_ERR_INVALID, "%s: degraded row %lld has %d frames, at least 1 is needed", who, r, deg_frames[r]);
+        dtotal += deg_frames[r];
+    }
+    if (total > kPatchMaxFrames || dtotal > 64 * kPatchMaxFrames)
+        return fail(NOMAD_ERR_INVALID, "%s: %lld clean and %lld degraded frames in all, at most 2^31 and 2^37 are supported", who, total, dtotal);
+    if (out_patches < 1 || out_patches < maxP)
+        return fail(NOMAD_ERR_INVALID, "%s: out_patches=%d, at least 1 and the %d patches of the longest clip are needed", who, out_patches, maxP);
+    if (R * (long long)(maxP < 1 ? 1 : maxP) > 0x7fffffffLL)
+        return fail(NOMAD_ERR_INVALID, "%s: %lld workgroups, more than one launch holds", who, R * (long long)maxP);
+    const PatchLayout l = patch_layout(B, G, total, TP, search);
+    if (ws_bytes < l.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    int W = 4;
+    size_t lds = sizeof(double) * (patch_staged_doubles(patch, search) + (size_t)W * patch_wave_doubles(patch));
+    if (lds > kPatchLdsMax) {
+        W = 2;
+        lds = sizeof(double) * (patch_staged_doubles(patch, search) + (size_t)W * patch_wave_doubles(patch));
+    }
+    if (lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(patch_candidates_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t sel_lds = sizeof(double) * ((size_t)(2 * kGammatoneBands + 2) * (size_t)patch + patch_wave_doubles(patch));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(l.E, 0);
+    memcpy(staged.data(), frames, sizeof(int) * (size_t)B);
+    memcpy(staged.data() + l.dframes, deg_frames, sizeof(int) * (size_t)R);
+    long long* fp = reinterpret_cast<long long*>(staged.data() + l.fpref);
+    long long* dp = reinterpret_cast<long long*>(staged.data() + l.dpref);
+    long long* pp = reinterpret_cast<long long*>(staged.data() + l.ppref);
+    for (int b = 0; b < B; ++b) {
+        fp[b + 1] = fp[b] + frames[b];
+        pp[b + 1] = pp[b] + frames[b] / patch;
+    }
+    for (long long r = 0; r < R; ++r) dp[r + 1] = dp[r] + deg_frames[r];
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), l.E, hipMemcpyHostToDevice, s));
+    const double C1 = (0.01 * intensity_range) * (0.01 * intensity_range), C3 = (0.03 * intensity_range) * (0.03 * intensity_range) / 2.0;
+    PatchTables tb;
+    tb.frames = reinterpret_cast<const int*>(w);
+    tb.dframes = reinterpret_cast<const int*>(w + l.dframes);
+    tb.fpref = reinterpret_cast<const long long*>(w + l.fpref);
+    tb.dpref = reinterpret_cast<const long long*>(w + l.dpref);
+    tb.ppref = reinterpret_cast<const long long*>(w + l.ppref);
+    tb.kept = reinterpret_cast<const int*>(w + l.kept);
+    tb.clipbad = reinterpret_cast<const int*>(w + l.clipbad);
+    double* cand = reinterpret_cast<double*>(w + l.cand);
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(patch_activity_kernel, dim3((unsigned)B), dim3(256), 0, s, spec_ref, tb.frames, tb.fpref, tb.ppref, patch, vad_ratio,
+                       min_active_frames, reinterpret_cast<double*>(w + l.E), reinterpret_cast<int*>(w + l.active),
+                       reinterpret_cast<int*>(w + l.kept), reinterpret_cast<int*>(w + l.clipbad));
+    if (maxP > 0)
+        hipLaunchKernelGGL(patch_candidates_kernel, dim3((unsigned)(R * maxP)), dim3(64 * W), lds, s, spec_ref, spec_deg, G, tb, patch, search,
+                           maxP, C1, C3, cand);
+    hipLaunchKernelGGL(patch_select_kernel, dim3((unsigned)R), dim3(256), sel_lds, s, spec_ref, spec_deg, G, tb, patch, search, C1, C3,
+                       static_cast<const double*>(cand), reinterpret_cast<int*>(w + l.back), reinterpret_cast<int*>(w + l.link),
+                       reinterpret_cast<int*>(w + l.pick), out_patches, nsim_out, bands_out, offsets_out, patch_nsim_out, cand_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

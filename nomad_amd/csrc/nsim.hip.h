@@ -193,6 +193,31 @@ __device__ __forceinline__ void nsim_window(const double* __restrict__ R, const 
     }
 }
 
+// The map at (t, band) from the floored planes with their minimum subtracted: what nsim_kernel and the patch search
+// (nsim_patches.hip.h) both evaluate, so that a patch candidate has the bits of a nomad_nsim call on the cut-out pair.
+__device__ __forceinline__ double nsim_cell(const double* __restrict__ R, const double* __restrict__ D, int F, int t, int band, double C1,
+                                            double C3) {
+    double mr, md, rr, dd, rd;
+    nsim_window(R, D, F, t, band, mr, md, rr, dd, rd);
+    double vr = rr - mr * mr, vd = dd - md * md;
+    vr = vr < 0.0 ? 0.0 : vr;   // a NaN is not below 0: it stays
+    vd = vd < 0.0 ? 0.0 : vd;
+    const double cov = rd - mr * md;
+    return (2.0 * mr * md + C1) / (mr * mr + md * md + C1) * ((cov + C3) / (sqrt(vr) * sqrt(vd) + C3));
+}
+
+// The two walks: a band's column of the map over the F frames in ascending order, and the 21 band values in ascending order.
+__device__ __forceinline__ double nsim_band_mean(const double* __restrict__ M, int F, int band) {
+    double acc = 0.0;
+    for (int t = 0; t < F; ++t) acc += M[(size_t)t * kGammatoneBands + band];
+    return acc / (double)F;
+}
+__device__ __forceinline__ double nsim_of_bands(const double* __restrict__ band_mean) {
+    double acc = 0.0;
+    for (int k = 0; k < kGammatoneBands; ++k) acc += band_mean[k];
+    return acc / (double)kGammatoneBands;
+}
+
 // Grid B G, 256 threads.  Degraded row j = b G + g: clean frames spec_ref[fpref[b] ..][21], its own spec_deg[G fpref[b] + g F_b ..][21];
 // planes: [3][G total][21] float64 at the row's own offset.  nsim[j], bands[j][21] (or null).
 __global__ __launch_bounds__(256) void nsim_kernel(const double* __restrict__ spec_ref, const double* __restrict__ spec_deg, int G,
@@ -255,27 +280,17 @@ __global__ __launch_bounds__(256) void nsim_kernel(const double* __restrict__ sp
     __syncthreads();
     for (int i = tid; i < n; i += 256) {
         const int t = i / kGammatoneBands, band = i % kGammatoneBands;
-        double mr, md, rr, dd, rd;
-        nsim_window(R, D, F, t, band, mr, md, rr, dd, rd);
-        double vr = rr - mr * mr, vd = dd - md * md;
-        vr = vr < 0.0 ? 0.0 : vr;   // a NaN is not below 0: it stays
-        vd = vd < 0.0 ? 0.0 : vd;
-        const double cov = rd - mr * md;
-        M[i] = (2.0 * mr * md + C1) / (mr * mr + md * md + C1) * ((cov + C3) / (sqrt(vr) * sqrt(vd) + C3));
+        M[i] = nsim_cell(R, D, F, t, band, C1, C3);
     }
     __syncthreads();
     if (tid < kGammatoneBands) {
-        double acc = 0.0;
-        for (int t = 0; t < F; ++t) acc += M[(size_t)t * kGammatoneBands + tid];
-        const double v = acc / (double)F;
+        const double v = nsim_band_mean(M, F, tid);
         band_mean[tid] = v;
         if (bands) bands[(size_t)j * kGammatoneBands + tid] = v;
     }
     __syncthreads();
     if (tid == 0) {
-        double acc = 0.0;
-        for (int k = 0; k < kGammatoneBands; ++k) acc += band_mean[k];
-        nsim[j] = acc / (double)kGammatoneBands;
+        nsim[j] = nsim_of_bands(band_mean);
     }
 }
 

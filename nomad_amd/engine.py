@@ -844,6 +844,79 @@ class Engine:
         spec_deg, _ = self.gammatone(packed=(dbuf, dlens), sample_rate=sample_rate)
         return self.nsim_of_spectrograms(spec_ref, spec_deg, frames, G, intensity_range, want_bands)
 
+    NSIM_PATCH_MAX, NSIM_SEARCH_MAX = 64, 128
+
+    @classmethod
+    def check_patches(cls, patch, search, vad_ratio, min_active_frames):
+        """The parameters of ``nsim_patches`` -> (patch, search, vad_ratio, min_active_frames) as the library takes them."""
+        patch, search, vad_ratio, min_active_frames = int(patch), int(search), float(vad_ratio), int(min_active_frames)
+        if not 1 <= patch <= cls.NSIM_PATCH_MAX:
+            raise ValueError(f"patch must be 1 .. {cls.NSIM_PATCH_MAX} frames, got {patch}")
+        if not 0 <= search <= cls.NSIM_SEARCH_MAX:
+            raise ValueError(f"search must be 0 .. {cls.NSIM_SEARCH_MAX} frames, got {search}")
+        if not 0.0 < vad_ratio <= 1.0:
+            raise ValueError(f"vad_ratio must lie in (0, 1], got {vad_ratio}")
+        if not 1 <= min_active_frames <= patch:
+            raise ValueError(f"min_active_frames must be 1 .. patch = {patch}, got {min_active_frames}")
+        return patch, search, vad_ratio, min_active_frames
+
+    def nsim_patches_of_spectrograms(self, spec_ref: torch.Tensor, spec_deg: torch.Tensor, frames, deg_frames, G: int, patch: int,
+                                     search: int, vad_ratio: float, min_active_frames: int, intensity_range: float = 1.0,
+                                     want_bands: bool = True, want_cand: bool = False):
+        """``nomad_nsim_patches`` on spectrograms ``gammatone`` made: spec_ref (sum F_b, 21) of B clean clips, spec_deg (sum Fd_r, 21)
+        of their B G degraded rows, row b G + g belonging to clip b and having its OWN frame count deg_frames[b G + g] -> a dict of
+        device tensors: nsim (B, G) float64, bands (B, G, 21) or None, offsets (B, G, P) int32 (the chosen place of every patch, -1
+        where it is not kept), patch_nsim (B, G, P) (NaN where not kept), cand (B, G, P, 2 search + 1) or None; P = the patches of
+        the longest clip, at least 1.  The clean clip's active patches (frame energy within vad_ratio of the clip's largest, at
+        least min_active_frames per patch of ``patch`` frames) are each searched for within ``search`` frames of their own place,
+        the places of a row never going back.  include/nomad_hip.h states the measure."""
+        frames, deg_frames = [int(f) for f in frames], [int(f) for f in deg_frames]
+        B, G = len(frames), int(G)
+        patch, search, vad_ratio, min_active_frames = self.check_patches(patch, search, vad_ratio, min_active_frames)
+        intensity_range = float(intensity_range)
+        if not (math.isfinite(intensity_range) and intensity_range > 0.0):
+            raise ValueError(f"intensity_range must be finite and positive, got {intensity_range}")
+        if not 1 <= G <= 64 or len(deg_frames) != B * G or not frames:
+            raise ValueError("deg_frames must hold G = 1 .. 64 entries per clean clip, row b G + g belonging to clip b")
+        if min(frames) < 1 or min(deg_frames) < 1:
+            raise ValueError("every clean clip and every degraded row needs at least one frame")
+        total, dtotal = sum(frames), sum(deg_frames)
+        for t, rows, name in ((spec_ref, total, "spec_ref"), (spec_deg, dtotal, "spec_deg")):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                    and tuple(t.shape) == (rows, self.NSIM_BANDS)):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape ({rows}, {self.NSIM_BANDS}) on {self.device}")
+        P = max(1, max(frames) // patch)
+        nsim = torch.empty(B, G, dtype=torch.float64, device=self.device)
+        bands = torch.empty(B, G, self.NSIM_BANDS, dtype=torch.float64, device=self.device) if want_bands else None
+        offsets = torch.empty(B, G, P, dtype=torch.int32, device=self.device)
+        patch_nsim = torch.empty(B, G, P, dtype=torch.float64, device=self.device)
+        cand = torch.empty(B, G, P, 2 * search + 1, dtype=torch.float64, device=self.device) if want_cand else None
+        ws = self._workspace(self._scratch_size(self.lib.nomad_nsim_patches_scratch_bytes, "nomad_nsim_patches_scratch_bytes", B, G, total,
+                                                dtotal, patch, search))
+        _lib.check(self.lib.nomad_nsim_patches(self.ctx, spec_ref.data_ptr(), spec_deg.data_ptr(), B, G, (C.c_int * B)(*frames),
+                                               (C.c_int * (B * G))(*deg_frames), patch, search, vad_ratio, min_active_frames, intensity_range,
+                                               P, nsim.data_ptr(), _ptr(bands), offsets.data_ptr(), patch_nsim.data_ptr(), _ptr(cand),
+                                               ws.data_ptr(), ws.numel(), self._stream()), "nomad_nsim_patches")
+        return {"nsim": nsim, "bands": bands, "offsets": offsets, "patch_nsim": patch_nsim, "cand": cand}
+
+    def nsim_patches(self, clean, degraded, G: int, patch: int, search: int, vad_ratio: float, min_active_frames: int,
+                     intensity_range: float = 1.0, sample_rate: int = 16000, want_bands: bool = True, want_cand: bool = False):
+        """Patch-wise NSIM of every degraded row with its clean clip: clean and degraded are (device buffer, lengths) pairs as
+        ``nsim`` takes them, but a degraded row may have any length of at least one frame (``gammatone`` twice, then
+        ``nsim_patches_of_spectrograms``, whose dict it returns with "frames" and "deg_frames" added)."""
+        cbuf, clens = self._rows(None, None, clean)
+        dbuf, dlens = self._rows(None, None, degraded)
+        G = int(G)
+        if not 1 <= G <= 64 or len(dlens) != G * len(clens) or not clens:
+            raise ValueError("degraded must hold G = 1 .. 64 rows per clean clip, row b G + g belonging to clip b")
+        self.check_patches(patch, search, vad_ratio, min_active_frames)
+        spec_ref, frames = self.gammatone(packed=(cbuf, clens), sample_rate=sample_rate)
+        spec_deg, dframes = self.gammatone(packed=(dbuf, dlens), sample_rate=sample_rate)
+        res = self.nsim_patches_of_spectrograms(spec_ref, spec_deg, frames, dframes, G, patch, search, vad_ratio, min_active_frames,
+                                                intensity_range, want_bands, want_cand)
+        res["frames"], res["deg_frames"] = frames, dframes
+        return res
+
     ALIGN_MAX_DELAY = 16384
 
     def _align_rows(self, clean, degraded, G, max_delay):

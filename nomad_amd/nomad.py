@@ -595,6 +595,26 @@ def pairs_from_csv(table):
     return [str(p) for p in table["filepath_ref"]], [str(p) for p in table["filepath_deg"]]
 
 
+def check_patch_params(patch_s, search_s=1.2, vad_db=40.0, min_active=1.0):
+    """The patch parameters of ``nsim_patches`` / ``nsim`` / ``nsim_files`` / ``mine_triplets`` -> (patch, search, vad_ratio,
+    min_active_frames) as ``nomad_nsim_patches`` takes them: seconds to frames of 20 ms (patch 1 .. 64, search 0 .. 128),
+    ``vad_ratio = 10 ** (-vad_db / 10)`` formed here and handed down as that double, ``max(1, ceil(min_active * patch))``."""
+    for name, v in (("patch_s", patch_s), ("search_s", search_s), ("vad_db", vad_db), ("min_active", min_active)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    patch, search = int(round(float(patch_s) * 50.0)), int(round(float(search_s) * 50.0))
+    if not 1 <= patch <= Engine.NSIM_PATCH_MAX:
+        raise ValueError(f"patch_s must lie in 0.02 .. {Engine.NSIM_PATCH_MAX / 50.0} s (1 .. {Engine.NSIM_PATCH_MAX} frames of 20 ms), got {patch_s}")
+    if search_s < 0 or search > Engine.NSIM_SEARCH_MAX:
+        raise ValueError(f"search_s must lie in 0 .. {Engine.NSIM_SEARCH_MAX / 50.0} s (0 .. {Engine.NSIM_SEARCH_MAX} frames of 20 ms), got {search_s}")
+    vad_ratio = 10.0 ** (-float(vad_db) / 10.0)
+    if vad_db < 0 or not vad_ratio > 0.0:
+        raise ValueError(f"vad_db must lie in 0 .. 3000 dB under the clip's loudest frame, got {vad_db}")
+    if not 0.0 < min_active <= 1.0:
+        raise ValueError(f"min_active must be a share of a patch's frames in (0, 1], got {min_active}")
+    return patch, search, vad_ratio, max(1, int(math.ceil(float(min_active) * patch)))
+
+
 def check_max_delay(max_delay_s, sample_rate: int = 16000) -> int:
     """``max_delay_s`` of ``align`` / ``nsim`` / ``nsim_files`` -> whole samples: a finite number of seconds from 0 up to 16384
     samples (1.024 s at 16 kHz), rounded to the nearest sample."""
@@ -1815,8 +1835,42 @@ class Nomad:
             return eng._pack([d[i, :n] for i, n in enumerate(dlens)])
         return eng._rows(None, None, (d, dlens))
 
+    def nsim_patches(self, degraded, clean, lengths=None, degraded_lengths=None, patch_s: float = 0.4, search_s: float = 1.2,
+                     vad_db: float = 40.0, min_active: float = 1.0, max_delay_s=None, intensity_range: float = 1.0):
+        """The patch-wise NSIM of degraded clips with their clean clips, on the GPU: the clean clip's spectrogram is cut into
+        patches of ``patch_s`` seconds, the ACTIVE ones are kept (a frame is active within ``vad_db`` dB of the clip's loudest
+        frame; a patch needs the share ``min_active`` of its frames active), each is searched for within ``search_s`` seconds of
+        its own place in the degraded spectrogram - the places of a row never going back -, and the patches' similarities are
+        averaged.  A delay that changes inside a file (dropped or inserted frames, a drifting clock) so costs one patch instead of
+        the whole score, and silence does not count.  -> a dict of device tensors: ``nsim`` (B, G) float64, ``bands`` (B, G, 21),
+        ``offsets`` (B, G, P) int32 (the degraded frame every patch was found at, -1 where it is not kept; patch p starts at clean
+        frame ``p * round(50 patch_s)``), ``patch_nsim`` (B, G, P) (NaN where not kept), ``kept`` (B, G) (the kept patches; a row
+        with none has NaN), and ``delay`` (B, G) int32 with ``max_delay_s``: the global alignment of ``align`` first, then the
+        patch search.  clean and degraded as ``align`` takes them; without ``max_delay_s`` a degraded row may be shorter or longer
+        than its clip (``degraded_lengths``, or packed rows).  Whole frames of 20 ms only: no fine alignment per patch, no
+        sub-sample delays, no polarity search, no MOS mapping, no gradient.  Modelled on ViSQOL's speech mode from memory and NOT
+        checked against the ViSQOL binary; include/nomad_hip.h states the measure (``nomad_nsim_patches``)."""
+        patch, search, vad_ratio, need = check_patch_params(patch_s, search_s, vad_db, min_active)
+        eng = self.engine
+        x, lens, d, dlens, G, max_delay = self._align_inputs(degraded, clean, lengths, degraded_lengths,
+                                                             0.0 if max_delay_s is None else max_delay_s, "nsim_patches")
+        one = 4 * (16000 // 50)
+        if min(lens) < one or min(dlens) < one:
+            raise ValueError(f"every clean clip and every degraded row needs one frame of {one} samples (80 ms)")
+        crows = eng._rows(x, lens, None)
+        drows = self._packed_rows(d, dlens)
+        delay = None
+        if max_delay_s is not None:
+            drows, delay, _ = eng.align(crows, drows, G, max_delay)
+        res = eng.nsim_patches(crows, drows, G, patch, search, vad_ratio, need, intensity_range=intensity_range)
+        out = {"nsim": res["nsim"], "bands": res["bands"], "offsets": res["offsets"], "patch_nsim": res["patch_nsim"],
+               "kept": (res["offsets"] >= 0).sum(dim=2)}
+        if delay is not None:
+            out["delay"] = delay.view(len(lens), G)
+        return out
+
     def nsim(self, degraded, clean, lengths=None, bands: bool = False, intensity_range: float = 1.0, max_delay_s=None,
-             degraded_lengths=None):
+             degraded_lengths=None, patch_s=None, search_s: float = 1.2, vad_db: float = 40.0, min_active: float = 1.0):
         """The gammatone-spectrogram NSIM of degraded clips with their clean clips, computed on the GPU: the similarity the
         reference takes from ViSQOL before it samples triplets -> (B, G) float64 on the GPU, 1 for identical clips and falling with
         the degradation (with ``bands``: also the (B, G, 21) per-band values whose mean it is).  clean (B,1,N) or (B,N) with
@@ -1829,7 +1883,14 @@ class Nomad:
         delay against its clip (``align``: one whole-sample delay per row); the degraded rows may then have any lengths - a tensor
         of another width takes ``degraded_lengths`` - and the (B, G) int32 delays are returned as one more, last result.
         Modelled on ViSQOL's speech mode from memory and NOT checked against the ViSQOL binary, neither the measure nor the
-        delays; include/nomad_hip.h states both.  No gradient."""
+        delays; include/nomad_hip.h states both.  No gradient.  With ``patch_s`` (seconds; ``search_s``, ``vad_db``, ``min_active``
+        as ``nsim_patches`` takes them) the score and the band values are the patch-wise ones of ``nsim_patches``, in the same
+        tuple; ``patch_s=None`` is every call as it was."""
+        if patch_s is not None:
+            res = self.nsim_patches(degraded, clean, lengths, degraded_lengths, patch_s, search_s, vad_db, min_active, max_delay_s,
+                                    intensity_range)
+            out = (res["nsim"],) + ((res["bands"],) if bands else ()) + ((res["delay"],) if max_delay_s is not None else ())
+            return out if len(out) > 1 else out[0]
         if max_delay_s is not None:
             x, lens, d, dlens, G, max_delay = self._align_inputs(degraded, clean, lengths, degraded_lengths, max_delay_s, "nsim")
             eng = self.engine
@@ -1858,7 +1919,8 @@ class Nomad:
         score, per_band = eng.nsim((cbuf, clens), (dbuf, dlens), G, intensity_range=intensity_range, want_bands=bands)
         return (score, per_band) if bands else score
 
-    def nsim_files(self, degraded, clean=None, max_delay_s: float = 0.25, results_path=None, max_batch_samples: int = 64 * 160000):
+    def nsim_files(self, degraded, clean=None, max_delay_s: float = 0.25, results_path=None, max_batch_samples: int = 64 * 160000,
+                   patch_s=None, search_s: float = 1.2, vad_db: float = 40.0, min_active: float = 1.0):
         """The NSIM of rendered files with their clean files, each pair aligned first: files a codec, a device or another program
         made, which are not sample-aligned with their source.  ``degraded`` and ``clean``: two lists of paths of one length; or
         ``degraded`` alone: a csv path (or DataFrame) with the columns ``filepath_ref`` and ``filepath_deg``, the reference's
@@ -1867,7 +1929,11 @@ class Nomad:
         ``predict`` (mono, resampled to 16 kHz), pairs are batched up to ``max_batch_samples`` samples, and every pair is
         ``nsim(max_delay_s=...)`` of its two files: the degraded file moved by ONE delay of whole samples (positive: it is late)
         and cut or zero-filled to the clean file's length.  A pair whose clean file is under 80 ms gets NaN.  The NSIM is this
-        project's (``nsim``) and the delay search is not ViSQOL's either: neither has been checked against that binary."""
+        project's (``nsim``) and the delay search is not ViSQOL's either: neither has been checked against that binary.  With
+        ``patch_s`` the NSIM is the patch-wise one (``nsim_patches`` after the same alignment) and the table gains ``patches_kept``,
+        ``offset_min_frames`` and ``offset_max_frames``: the kept patches of the pair, and the smallest and largest distance, in
+        frames of 20 ms, of a patch's found place from its own start (NaN where no patch is kept); without it the file is what it was."""
+        patches = check_patch_params(patch_s, search_s, vad_db, min_active) if patch_s is not None else None
         if clean is None:
             ref_paths, deg_paths = pairs_from_csv(degraded)
         else:
@@ -1880,18 +1946,23 @@ class Nomad:
         eng = self.engine
         paths = [p for pair in zip(ref_paths, deg_paths) for p in pair]      # file 2 k is pair k's clean file, 2 k + 1 its degraded one
         delays, scores = np.zeros(len(ref_paths), dtype=np.int64), np.full(len(ref_paths), np.nan)
+        kept, off_lo, off_hi = np.zeros(len(ref_paths), dtype=np.int64), np.full(len(ref_paths), np.nan), np.full(len(ref_paths), np.nan)
         held, fetches = {}, []
 
         def run(ks):
             cbuf, clens = eng._pack([held[2 * k] for k in ks])
             rows, delay, _ = eng.align((cbuf, clens), eng._pack([held[2 * k + 1] for k in ks]), 1, max_delay)
             ok = [i for i, n in enumerate(clens) if Engine.gammatone_frames(n) >= 1]
-            sims = None
+            sims = offs = None
             if ok:
                 pick = torch.as_tensor(ok, device=eng.device)
                 lens_ok = [clens[i] for i in ok]
-                sims = eng.nsim((cbuf[pick], lens_ok), (rows[0][pick], lens_ok), 1, want_bands=False)[0].reshape(-1)
-            fetches.append((ks, ok, eng.fetch_async(delay), eng.fetch_async(sims) if ok else None))
+                if patches is None:
+                    sims = eng.nsim((cbuf[pick], lens_ok), (rows[0][pick], lens_ok), 1, want_bands=False)[0].reshape(-1)
+                else:
+                    res = eng.nsim_patches((cbuf[pick], lens_ok), (rows[0][pick], lens_ok), 1, *patches, want_bands=False)
+                    sims, offs = res["nsim"].reshape(-1), eng.fetch_async(res["offsets"][:, 0, :].contiguous())
+            fetches.append((ks, ok, eng.fetch_async(delay), eng.fetch_async(sims) if ok else None, offs))
             for k in ks:
                 del held[2 * k], held[2 * k + 1]
 
@@ -1905,19 +1976,30 @@ class Nomad:
             ks = sorted(i // 2 for i in idxs if i % 2 and i - 1 in held)      # a pair is whole once its degraded file is here
             if ks:
                 run(ks)
-        for ks, ok, delay, sims in fetches:
+        for ks, ok, delay, sims, offs in fetches:
             delays[ks] = delay.result()
             if ok:
                 scores[[ks[i] for i in ok]] = sims.result()
+            if offs is not None:
+                table = np.asarray(offs.result())
+                rel = table - np.arange(table.shape[1])[None, :] * patches[0]      # from the patch's own start
+                for i, row in zip(ok, range(table.shape[0])):
+                    on = table[row] >= 0
+                    kept[ks[i]] = int(on.sum())
+                    if on.any():
+                        off_lo[ks[i]], off_hi[ks[i]] = rel[row][on].min(), rel[row][on].max()
         df = pd.DataFrame({"filepath_ref": ref_paths, "filepath_deg": deg_paths, "delay_samples": delays, "delay_s": delays / 16000.0,
                            "NSIM": scores})
+        if patches is not None:
+            df["patches_kept"], df["offset_min_frames"], df["offset_max_frames"] = kept, off_lo, off_hi
         if results_path is not None:
             os.makedirs(results_path, exist_ok=True)
             df.to_csv(os.path.join(results_path, "nsim_pairs.csv"), index=False)
         return df
 
     def mine_triplets(self, clean, noise=None, snr_db=None, clip_factor=None, reverberance=None, normalize=-23.0, lengths=None,
-                      N: int = 3, hard_sampling: bool = False, margin: float = 0.05, seed=0):
+                      N: int = 3, hard_sampling: bool = False, margin: float = 0.05, seed=0, patch_s=None, vad_db: float = 40.0,
+                      min_active: float = 1.0):
         """From clean clips to (Anchor, Positive, Negative) batches with nothing rendered to disk - the reference's data
         preparation (degrade, ``ffmpeg-normalize``, ViSQOL's NSIM, ``nsim_triplet_sampling.py``) on the GPU.  The clips are
         degraded at every given level (``snr_db`` with ``noise``, ``clip_factor``, ``reverberance``: the C conditions, in that
@@ -1929,8 +2011,13 @@ class Nomad:
         -> (anchor, positive, negative, info): each branch a ``(rows (K, stride) fp32 on the GPU, lengths)`` pair as
         ``forward_triplet`` / ``embed_ragged(packed=...)`` take them, K <= B N; ``info`` = {"nsim": the (B, C) float64 table,
         "conditions": [(kind, level)] per column, "triplets": ``create_triplets``' index table (member C is the clean clip),
-        "dropped": its count of draws that gave no row}.  The NSIM is this project's (``nsim``), not ViSQOL's.  No gradient."""
+        "dropped": its count of draws that gave no row}.  The NSIM is this project's (``nsim``), not ViSQOL's.  No gradient.
+        With ``patch_s`` the table is the patch-wise measure (``nsim_patches`` with ``vad_db`` and ``min_active``; the rows are
+        sample-aligned by construction, so a patch is searched for within one patch length of its place): silence then does not
+        count.  Clips one of whose rows has no kept patch (too short, nothing active enough) are left out of the sampling and
+        listed in ``info["no_patches"]``; ``info["triplets"]["clip"]`` keeps the clips' own indices."""
         from .triplets import create_triplets
+        patches = check_patch_params(patch_s, patch_s, vad_db, min_active) if patch_s is not None else None
         x, lens = self._rows_for_normalize(clean, lengths, "mine_triplets")
         if snr_db is not None and noise is None:
             raise ValueError("snr_db needs a noise signal: pass noise=")
@@ -1957,7 +2044,11 @@ class Nomad:
             if normalize is not None:
                 eng.degrade_normalize(packed=(out, lens_rep), target=normalize, inplace=True)
             spec_deg, _ = eng.gammatone(packed=(out, lens_rep))
-            scores.append(eng.nsim_of_spectrograms(spec_ref, spec_deg, frames, len(levels), want_bands=False)[0])
+            if patches is None:
+                scores.append(eng.nsim_of_spectrograms(spec_ref, spec_deg, frames, len(levels), want_bands=False)[0])
+            else:
+                scores.append(eng.nsim_patches_of_spectrograms(spec_ref, spec_deg, frames, [f for f in frames for _ in levels], len(levels),
+                                                               *patches, want_bands=False)["nsim"])
             members.append(out.view(B, len(levels), stride))
         if normalize is not None:
             clean_member = eng.degrade_normalize(packed=(buf, lens), target=normalize)[0]
@@ -1967,7 +2058,17 @@ class Nomad:
                 clean_member[b, n:] = 0.0
         members.append(clean_member.view(B, 1, stride))
         table = torch.cat(scores, dim=1).cpu().numpy()        # the one round trip
-        triplets, dropped = create_triplets(table, N=N, hard_sampling=hard_sampling, margin=margin, rng=seed)
+        no_patches = []
+        if patches is None:
+            triplets, dropped = create_triplets(table, N=N, hard_sampling=hard_sampling, margin=margin, rng=seed)
+        else:                     # a row without a kept patch has NaN: its clip is not sampled from
+            no_patches = [int(b) for b in np.nonzero(np.isnan(table).any(axis=1))[0]]
+            sampled = np.asarray([b for b in range(B) if b not in no_patches], dtype=np.int64)
+            if sampled.size == 0:
+                raise ValueError("mine_triplets: no clip has a kept patch in all of its rows (patch_s too long, or nothing active)")
+            triplets, dropped = create_triplets(table[sampled], N=N, hard_sampling=hard_sampling, margin=margin, rng=seed)
+            triplets = dict(triplets)
+            triplets["clip"] = sampled[triplets["clip"]]
         bank = torch.cat(members, dim=1)
         C1 = bank.shape[1]
         bank = bank.view(B * C1, stride)
@@ -1977,6 +2078,8 @@ class Nomad:
             idx = torch.from_numpy(triplets["clip"] * C1 + triplets[key]).to(eng.device)
             branches.append((bank.index_select(0, idx), list(branch_lens)))
         info = {"nsim": table, "conditions": [(kind, v) for kind, levels in sweeps for v in levels], "triplets": triplets, "dropped": dropped}
+        if patches is not None:
+            info["no_patches"] = no_patches
         return branches[0], branches[1], branches[2], info
 
     def _clean_batches(self, clean, lengths, budget: int):

@@ -38,7 +38,8 @@ Differences, on purpose:
   with, and no time spent on padded frames.  ``freeze_convnet: False`` is refused with it (the conv extractor's parameter
   gradients need equal-length batches).
 * ``triplets_on_device`` (not a reference key): ``{clean: <dir|csv>, valid_clean: <dir|csv>, noise: <wav>, snr_db: [...], clip:
-  [...], reverb: [...], normalize: -23, N: 3, hard_sampling: false, sampling_margin: 0.05}``.  With it ``train_df`` / ``valid_df``
+  [...], reverb: [...], normalize: -23, N: 3, hard_sampling: false, sampling_margin: 0.05, patch_s: null, vad_db: 40, min_active: 1.0}``
+  (``patch_s``: the table comes from the patch-wise NSIM, ``Nomad.nsim_patches``, so that silence does not count).  With it ``train_df`` / ``valid_df``
   are not read: a step takes ``train_bs // N`` clean clips, degrades them on the GPU at every listed level, takes each degraded
   row's NSIM with its clean clip, samples up to ``train_bs`` triplets by the reference's rule (``Nomad.mine_triplets``: the
   reference's offline ffmpeg / sox / ViSQOL / pandas preparation with nothing rendered to disk; the NSIM is this project's
@@ -79,7 +80,7 @@ def check_pad_mode(config) -> str:
     return mode
 
 MINING_DEFAULTS = dict(clean=None, valid_clean=None, noise=None, snr_db=None, clip=None, reverb=None, normalize=-23.0, N=3,
-                       hard_sampling=False, sampling_margin=0.05)
+                       hard_sampling=False, sampling_margin=0.05, patch_s=None, vad_db=40.0, min_active=1.0)
 
 
 def check_triplets_on_device(config, pad_mode: str) -> Optional[dict]:
@@ -102,6 +103,9 @@ def check_triplets_on_device(config, pad_mode: str) -> Optional[dict]:
         raise ValueError("triplets_on_device needs at least one of snr_db, clip and reverb (lists of levels)")
     if m["snr_db"] is not None and not m["noise"]:
         raise ValueError("triplets_on_device: snr_db needs noise: <wav>")
+    if m["patch_s"] is not None:
+        from .nomad import check_patch_params
+        check_patch_params(m["patch_s"], m["patch_s"], m["vad_db"], m["min_active"])
     m["N"] = int(m["N"])
     if m["N"] < 1 or int(config.get("train_bs", m["N"])) < m["N"] or int(config.get("val_bs", m["N"])) < m["N"]:
         raise ValueError(f"triplets_on_device: N = {m['N']} must be at least 1 and at most train_bs and val_bs")
@@ -138,7 +142,9 @@ class MinedTriplets:
         m = self.mining
         return self.nomad.mine_triplets(rows, noise=self.noise, snr_db=m["snr_db"], clip_factor=m["clip"], reverberance=m["reverb"],
                                         normalize=m["normalize"], lengths=lens, N=m["N"], hard_sampling=bool(m["hard_sampling"]),
-                                        margin=float(m["sampling_margin"]), seed=seed)
+                                        margin=float(m["sampling_margin"]), seed=seed,
+                                        **({} if m.get("patch_s") is None else
+                                           {"patch_s": m["patch_s"], "vad_db": m["vad_db"], "min_active": m["min_active"]}))
 
     def __iter__(self):
         order = self._rng.permutation(len(self.files)) if self.shuffle else np.arange(len(self.files))
