@@ -1147,6 +1147,14 @@ int nomad_profile_read(nomad_ctx* ctx, double ms[NOMAD_K_COUNT], long long launc
 int nomad_diag_gemm(nomad_ctx* ctx, const float* A_dev, const float* W_dev, const float* bias_dev,
                     const float* R_dev, float* C_dev, int M, int N, int K, int gelu, int tile,
                     nomad_stream_t stream);
+/* The fp32 positional convolution alone, in the frequency domain (512-point transforms, one 48 x 48 complex product per bin and
+ * group), on the caller's operands.  x: the padded group-major input [16][sum_c (T_c + 128)][48] (zero frames 0..63 and
+ * T_c + 64.. of every clip); v: weights [16][64][6144] ([out][tap * 48 + in], rows 48..63 unused); bias: [768] or null;
+ * y = x + gelu(u), u (nullable) = pos_conv(x) + bias: [sum_c T_c][768].  lens_host: the clips' frame counts T_c.  ragged = 0:
+ * the uniform launch (every T_c equal), 1: the ragged one.  Synchronous.  (libnomad_diag.so has the same hook for the direct and
+ * nested F(2,2) forms under another name.) */
+int nomad_diag_posconv_fft(nomad_ctx* ctx, const float* x_dev, const float* v_dev, const float* bias_dev, float* y_dev,
+                           float* u_dev, int B, const int* lens_host, int ragged, nomad_stream_t stream);
 /* The bf16 GEMM: A [M][K], W [N][K], R, C [M][N] are bf16; bias fp32.  tile (libnomad_hip.so): 1 = 128x128,
  * 2 = 128x64, 3 = 256x256, 4 = 64x64 (all BK = 64), 16 = 256x256 deep-pipelined; others: libnomad_diag.so. */
 int nomad_diag_gemm_bf16(nomad_ctx* ctx, const void* A_dev, const void* W_dev, const float* bias_dev,

@@ -71,6 +71,7 @@ struct Tuning {
     bool splitk_ln_fuse = true;    // NOMAD_SPLITK_LN: a split-K out_proj / fc2 normalises its rows in its own epilogue (splitk_epilogue_ln_kernel)
     bool f32_conv_wino = true;     // NOMAD_F32_CONV_WINO: conv1 .. conv4 of every fp32-product forward in polyphase Winograd form (conv_s2_f32.hip.h; 0: the implicit GEMM)
     bool f32_posconv_wino = true;  // NOMAD_F32_POSCONV_WINO: the pos-conv of every fp32-product forward in nested F(2,2) form (posconv_wino_f32.hip.h; 0: the direct 128-tap GEMM)
+    bool f32_posconv_fft = true;   // NOMAD_F32_POSCONV_FFT: the pos-conv of every fp32-product forward in the frequency domain (posconv_fft_f32.hip.h; 0: as NOMAD_F32_POSCONV_WINO says)
     int bf16_attn_tail = 0;        // NOMAD_BF16_ATTN_TAIL (diag): a last round of 256-query workgroups that is at most this many eighths full runs
                                    // as 128-query workgroups in a second launch (0: never; run_attention_bf16 - measured slower, A/B only)
     int bf16_ln_rows = 4;          // NOMAD_BF16_LN_ROWS: rows per wave of the bf16 forward's LayerNorm (4: one gamma / beta fetch per 4 rows; 1: A/B)
@@ -93,6 +94,7 @@ static void tuning_from_env(Tuning& t) {
     t.splitk_lnb_fuse = getb("NOMAD_SPLITK_LNB", t.splitk_lnb_fuse);
     t.f32_conv_wino = getb("NOMAD_F32_CONV_WINO", t.f32_conv_wino);
     t.f32_posconv_wino = getb("NOMAD_F32_POSCONV_WINO", t.f32_posconv_wino);
+    t.f32_posconv_fft = getb("NOMAD_F32_POSCONV_FFT", t.f32_posconv_fft);
     t.bf16_attn_tail = geti("NOMAD_BF16_ATTN_TAIL", t.bf16_attn_tail);
     t.bf16_ln_rows = geti("NOMAD_BF16_LN_ROWS", t.bf16_ln_rows);
     t.p9_short = geti("NOMAD_BF16_P9_SHORT", t.p9_short);
@@ -115,6 +117,9 @@ struct nomad_ctx {
     float *proj_w = nullptr, *proj_b = nullptr;
     float *pos_w = nullptr, *pos_b = nullptr;  // [16][64][6144] (rows 48..63 zero), k = tap*48 + cin
     float* pos_wt = nullptr;                   // pos_w in nested F(2,2) form [16 * kPwOps][64][kPwK] (posconv_wino_f32.hip.h): rebuilt wherever pos_w is
+    float* pos_wf = nullptr;                   // pos_w in the frequency domain [16][257][96][96] (posconv_fft_f32.hip.h): rebuilt wherever pos_w is
+    double* pos_tw64 = nullptr;                // exp(-2 pi i m / 512), m = 0 .. 511, (re, im) pairs: float64 for the weight transform ...
+    float* pos_tw32 = nullptr;                 // ... and rounded to fp32 for the transforms of the forward
     float *eln_w = nullptr, *eln_b = nullptr;
     LayerDev layers[NOMAD_NUM_LAYERS] = {};
     float *emb_w = nullptr, *emb_b = nullptr;

@@ -43,6 +43,7 @@
 #endif
 #include "pairwise.hip.h"
 #include "posconv_wino_f32.hip.h"
+#include "posconv_fft_f32.hip.h"
 #include "rowops.hip.h"
 #include "train.hip.h"
 #include "wav_reader.h"
@@ -87,6 +88,12 @@ void launch_wav_stats(const float* wav, int ld, int L0, int max_l0, int B, doubl
 size_t pos_wino_q_bytes(long long q_frames) { return sizeof(float) * 16 * kPwOps * 48 * (size_t)q_frames; }
 size_t pos_wino_s_bytes(long long q_rows) { return sizeof(float) * 16 * kPwOps * 48 * (size_t)q_rows; }
 
+// The form an fp32 forward of this context runs its pos-conv in, and so which buffers its workspace holds for it: the direct
+// 128-tap GEMM (none), the nested F(2,2) form (operands and products) or the frequency domain (the two spectra,
+// posconv_fft_f32.hip.h).  A forward runs one form, so the layouts hold one form's buffers.
+enum PosForm { kPosDirect = 0, kPosWino = 1, kPosFft = 2 };
+PosForm pos_form(const nomad_ctx* c) { return c->tune.f32_posconv_fft ? kPosFft : c->tune.f32_posconv_wino ? kPosWino : kPosDirect; }
+
 // floats in the split-K block of a small layer-output forward (Layout::splitk), 0 where that forward does not split: S x M x N
 // for the largest transformer problem splitk_applies / posconv_splitk_applies let through at M = s.M frames (S x N <= 6144: fc1
 // 2 x 3072, qkv 2 x 2304, fc2 / pos-conv 4 x 768), never more than the fixed cap those checks use.  The conv GEMMs of one clip
@@ -96,10 +103,10 @@ size_t layers_splitk_floats(const Shapes& s) {
 }
 
 struct Layout {
-    size_t stats, scale, shift, conv[7], featln, xpad, x, x2, y, qkv, ctxb, h, splitk, pwq, pws, total;
+    size_t stats, scale, shift, conv[7], featln, xpad, x, x2, y, qkv, ctxb, h, splitk, pwq, pws, pfx, pfy, total;
 };
 
-Layout make_layout(const Shapes& s, bool keep, bool pos_wino) {
+Layout make_layout(const Shapes& s, bool keep, PosForm pos) {
     Layout l{};
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -131,10 +138,13 @@ Layout make_layout(const Shapes& s, bool keep, bool pos_wino) {
     // whether such a forward splits depends on its shape alone - not on which streams other calls are running on
     const size_t sk = layers_splitk_floats(s);
     l.splitk = sk ? take(sk * sizeof(float)) : 0;
-    if (pos_wino) {   // operands and products of the pos-conv in nested F(2,2) form
+    if (pos == kPosWino) {   // operands and products of the pos-conv in nested F(2,2) form
         const size_t q = (size_t)(s.T + kPwRate - 1) / kPwRate;
         l.pwq = take(pos_wino_q_bytes((long long)s.B * (q + kPwTaps - 1)));
         l.pws = take(pos_wino_s_bytes((long long)s.B * q));
+    } else if (pos == kPosFft) {   // the spectra on either side of the bin products
+        l.pfx = take(pos_fft_spec_bytes((long long)s.B * pos_fft_blocks(s.T)));
+        l.pfy = take(pos_fft_spec_bytes((long long)s.B * pos_fft_blocks(s.T)));
     }
     l.total = off;
     return l;
@@ -155,6 +165,7 @@ struct RaggedShapes {
     long long pairs[5] = {};  // total output pairs of conv1 .. conv4 (Winograd form), sum ceil(L_i / 2)
     long long q_rows = 0, q_frames = 0;    // pos-conv in nested F(2,2) form: total operand rows, sum ceil(T_c / kPwRate), and frames, + kPwTaps - 1 each
                                            // (their prefix sums are formed on the device, in the call's workspace: posconv_wino_prefix_kernel)
+    long long units = 0;                   // pos-conv in the frequency domain: total units, sum ceil(T_c / kPfBlk) (prefix sums: posconv_fft_prefix_kernel)
     long long even[4] = {}, odd[4] = {};   // backward: total even / odd frames of conv levels 0 .. 3, sum ceil(L_i / 2) / sum floor(L_i / 2)
     // [lens(B) | pref_0 (B+1) | ... | pref_6 (B+1) | ppref (B+1) | bpref (B+1) | pairpref_1 .. pairpref_4 (B+1) |
     //  upref_0 .. upref_6 | epref_0 .. epref_3 | opref_0 .. opref_3 (B+1 each)]: the last three groups are the backward's -
@@ -200,6 +211,7 @@ bool make_ragged(int B, const int* lens, RaggedShapes* r) {
         const int q = (sh.T + kPwRate - 1) / kPwRate;
         r->q_rows += q;
         r->q_frames += q + kPwTaps - 1;
+        r->units += pos_fft_blocks(sh.T);
         const int nb = (sh.T + kPosBlk - 1) / kPosBlk;
         r->meta[r->off_bpref() + c + 1] = r->meta[r->off_bpref() + c] + nb;
         r->blocks += nb;
@@ -234,6 +246,7 @@ struct BatchGeom {
     long long pos_blocks = 0;
     RowMap blk_amap{}, blk_cmap{}, blk_rmap{};
     PosWinoGeom pos_wino{};        // the fp32 pos-conv in nested F(2,2) form (posconv_wino_f32.hip.h)
+    PosFftGeom pos_fft{};          // ... and in the frequency domain (posconv_fft_f32.hip.h)
     double attn_flops = 0.0;
     // the backward's: padded dU rows, even / odd frames of conv levels 0 .. 3 and their prefix sums (ragged), and the HOST copy of
     // the encoder's frame prefix sums (ragged; LayerDrop branches are clip ranges) - valid as long as the RaggedShapes it came from
@@ -272,6 +285,7 @@ BatchGeom geom_uniform(const Shapes& sh) {
     g.attn_flops = 4.0 * sh.B * 12.0 * (double)sh.T * sh.T * 64;
     const int q = (sh.T + kPwRate - 1) / kPwRate;
     g.pos_wino = PosWinoGeom{sh.B, sh.T, nullptr, nullptr, nullptr, nullptr, g.pad_rows, (long long)sh.B * q, (long long)sh.B * (q + kPwTaps - 1), q};
+    g.pos_fft = PosFftGeom{sh.B, sh.T, nullptr, nullptr, nullptr, g.pad_rows, sh.B * pos_fft_blocks(sh.T), pos_fft_blocks(sh.T)};
     for (int i = 0; i < 4; ++i) {
         g.even[i] = (long long)sh.B * ((sh.L[i] + 1) / 2);
         g.odd[i] = (long long)sh.B * (sh.L[i] / 2);
@@ -316,6 +330,7 @@ BatchGeom geom_ragged(const RaggedShapes& rs, int stride, const int* meta) {
     }
     g.pos_wino = PosWinoGeom{rs.B, 0, g.pref[6], g.ppref, nullptr, nullptr, rs.P, rs.q_rows, rs.q_frames,
                              (rs.max_t + kPwRate - 1) / kPwRate};
+    g.pos_fft = PosFftGeom{rs.B, 0, g.pref[6], g.ppref, nullptr, rs.P, (int)rs.units, pos_fft_blocks(rs.max_t)};
     g.host_tpref = rs.meta.data() + rs.off_pref(6);
     for (int i = 0; i < rs.B; ++i) {
         const double t = rs.meta[rs.off_pref(6) + i + 1] - rs.meta[rs.off_pref(6) + i];
@@ -327,13 +342,13 @@ BatchGeom geom_ragged(const RaggedShapes& rs, int stride, const int* meta) {
 // Workspace of every forward except the fp32 equal-length one (Layout): the ragged metadata, the front end's statistics, two
 // ping-pong conv buffers and the activations, elem_bytes per element (bf16: 2; fp32 or two bf16 planes: 4).
 struct ActLayout {
-    size_t meta, stats, scale, shift, conva, convb, xpad, x, x2, y, qkv, ctxb, h, pwq, pws, pwmeta, total;
+    size_t meta, stats, scale, shift, conva, convb, xpad, x, x2, y, qkv, ctxb, h, pwq, pws, pwmeta, pfx, pfy, pfmeta, total;
     long long capa, capb;  // elements per plane of the two conv ping-pong buffers
     long long xpad_plane;  // elements per plane of the padded pos-conv buffer, + xpad_slack zeroed elements (bf16x3)
 };
 
-// pos_wino: the fp32 forward with its pos-conv in nested F(2,2) form - the operand and product buffers of that form.
-ActLayout make_act_layout(const BatchGeom& g, size_t elem_bytes, size_t xpad_slack, bool pos_wino = false) {
+// pos: the fp32 forward with its pos-conv in nested F(2,2) form or in the frequency domain - the buffers of that form.
+ActLayout make_act_layout(const BatchGeom& g, size_t elem_bytes, size_t xpad_slack, PosForm pos = kPosDirect) {
     ActLayout l{};
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -358,10 +373,14 @@ ActLayout make_act_layout(const BatchGeom& g, size_t elem_bytes, size_t xpad_sla
     l.qkv = take(e * 2304 * M);
     l.ctxb = take(e * 768 * M);
     l.h = take(e * 3072 * M);
-    if (pos_wino) {
+    if (pos == kPosWino) {
         l.pwq = take(pos_wino_q_bytes(g.pos_wino.q_frames));
         l.pws = take(pos_wino_s_bytes(g.pos_wino.q_rows));
         l.pwmeta = take(sizeof(int) * 2 * (size_t)(g.B + 1));   // ragged: operand row / frame prefix sums
+    } else if (pos == kPosFft) {
+        l.pfx = take(pos_fft_spec_bytes(g.pos_fft.units));
+        l.pfy = take(pos_fft_spec_bytes(g.pos_fft.units));
+        l.pfmeta = take(sizeof(int) * (size_t)(g.B + 1));       // ragged: unit prefix sums
     }
     l.total = off;
     return l;
@@ -417,10 +436,10 @@ int span_upload(nomad_ctx* c, const SpanStage& st, hipStream_t s) {
 // The scoring forwards' prologue: the three steps over the ActLayout.  c == nullptr: nomad_workspace_bytes_ragged*, sizing only.
 int ragged_prologue(const char* who, nomad_ctx* c, bool ok, int B, int stride, const int* lens_host, size_t elem_bytes,
                     size_t xpad_slack, RaggedBatch* r, void* workspace = nullptr, size_t workspace_bytes = 0, hipStream_t s = nullptr,
-                    bool pos_wino = false) {
+                    PosForm pos = kPosDirect) {
     if (int rc = ragged_shapes(who, ok, B, c ? stride : -1, lens_host, &r->rs)) return rc;
     r->g = geom_ragged(r->rs, stride, nullptr);
-    r->lay = make_act_layout(r->g, elem_bytes, xpad_slack, pos_wino);
+    r->lay = make_act_layout(r->g, elem_bytes, xpad_slack, pos);
     if (!c) return 0;
     if (workspace_bytes < r->lay.total)
         return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, r->lay.total);
@@ -882,6 +901,59 @@ int run_posconv_wino(nomad_ctx* c, const float* xpad, const float* wt, const flo
     return 0;
 }
 
+// The pos-conv of an fp32-product forward runs in the frequency domain (posconv_fft_f32.hip.h): fp32 products only;
+// NOMAD_F32_POSCONV_FFT, ahead of NOMAD_F32_POSCONV_WINO.  Asked by forward_run alone, like posconv_wino.
+bool posconv_fft(const nomad_ctx* c) { return c->tune.f32_posconv_fft && !c->gemm_x3; }
+
+// the twiddle tables of that form, once per context
+int build_posconv_fft_tables(nomad_ctx* c, hipStream_t s) {
+    if (int rc = dev_alloc(c, "pos-conv twiddles", (size_t)2 * kPfN, &c->pos_tw64)) return rc;
+    if (int rc = dev_alloc(c, "pos-conv twiddles", (size_t)2 * kPfN, &c->pos_tw32)) return rc;
+    hipLaunchKernelGGL(posconv_fft_twiddle_kernel, dim3(kPfN / 256), dim3(256), 0, s, reinterpret_cast<double2*>(c->pos_tw64),
+                       reinterpret_cast<float2*>(c->pos_tw32));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// v (as pos_w) -> wf, queued on s; for the context's own weights behind everything that writes pos_w, like the nested form's.
+int launch_posconv_fft_weights(nomad_ctx* c, const float* v, float* wf, hipStream_t s) {
+    hipLaunchKernelGGL(posconv_fft_weight_kernel, dim3(kPfBins, 16), dim3(256), 0, s, v, reinterpret_cast<const double2*>(c->pos_tw64), wf);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// x + gelu(pos_conv(x) + bias) in the frequency domain.  xpad: the padded group-major input; wf: the transformed weights
+// [16][257][96][96]; y / upre (nullable): [sum T][768]; sx / sy: the two spectra (pos_fft_spec_bytes of geo.units each); umeta:
+// B + 1 ints for a ragged batch's unit prefix sums, formed here.  The same three kernels for every batch.
+int run_posconv_fft(nomad_ctx* c, const float* xpad, const float* wf, const float* bias, float* y, float* upre,
+                    const PosFftGeom& geo_in, float* sx, float* sy, int* umeta, hipStream_t s) {
+    PosFftGeom geo = geo_in;
+    if (!c->pos_tw32) return fail(NOMAD_ERR_INVALID, "pos-conv: no twiddle tables");
+    if (geo.units <= 0 || geo.units >= (1 << 30) / kPfCols || 16LL * geo.B > 65535)
+        return fail(NOMAD_ERR_INVALID, "pos-conv: %d units of %d clips", geo.units, geo.B);
+    if (geo.tpref && !umeta) return fail(NOMAD_ERR_INVALID, "pos-conv: a ragged batch without its unit prefix sums");
+    const float2* tw = reinterpret_cast<const float2*>(c->pos_tw32);
+    const dim3 grid(3 * geo.max_blocks, 16 * geo.B);
+    {
+        Scope sc(c, s, NOMAD_K_ROW, 0.0);
+        if (geo.tpref) {
+            hipLaunchKernelGGL(posconv_fft_prefix_kernel, dim3(1), dim3(64), 0, s, geo.tpref, geo.B, umeta);
+            geo.upref = umeta;
+        }
+        hipLaunchKernelGGL(posconv_fft_forward_kernel, grid, dim3(256), 0, s, xpad, tw, sx, geo);
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        Scope sc(c, s, NOMAD_K_GEMM, 2.0 * 16 * kPfBins * kPfCols * kPfCols * (double)geo.units);
+        hipLaunchKernelGGL(posconv_fft_bins_kernel, dim3(kPfBins, 16), dim3(256), 0, s, sx, wf, sy, geo.units);
+        HIP_TRY(hipGetLastError());
+    }
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(posconv_fft_inverse_kernel, grid, dim3(256), 0, s, sy, tw, bias, xpad, y, upre, geo);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 
 int run_layernorm(nomad_ctx* c, const float* in, const float* g, const float* b, float* out, float* out2, int M, int N,
                   hipStream_t s) {
@@ -1164,6 +1236,12 @@ int nomad_create(nomad_ctx** out, int device, const nomad_weights* w) {
             if (rc == 0) rc = rebuild_posconv_wino_weights(c, nullptr);
             if (rc == 0 && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_create: pos-conv weights: kernel");
         }
+        if (rc == 0) rc = build_posconv_fft_tables(c, nullptr);   // (every context: nomad_diag_posconv_fft runs the form whatever the switch says)
+        if (rc == 0 && c->tune.f32_posconv_fft) {
+            rc = dev_alloc(c, "nomad_create: pos-conv weights", kPfWeightFloats, &c->pos_wf);
+            if (rc == 0) rc = launch_posconv_fft_weights(c, c->pos_w, c->pos_wf, nullptr);
+        }
+        if (rc == 0 && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_create: pos-conv spectrum: kernel");
     }
     for (int l = 0; l < NOMAD_NUM_LAYERS && rc == 0; ++l) {
         const nomad_layer_weights& lw = w->layers[l];
@@ -1212,7 +1290,7 @@ int nomad_workspace_bytes(const nomad_ctx* c, int B, int n_samples, size_t* byte
     Shapes s;
     if (!c || !bytes || B <= 0 || !make_shapes(B, n_samples, &s))
         return fail(NOMAD_ERR_INVALID, "nomad_workspace_bytes: bad shape B=%d N=%d", B, n_samples);
-    *bytes = make_layout(s, c->keep, c->tune.f32_posconv_wino).total;
+    *bytes = make_layout(s, c->keep, pos_form(c)).total;
     return 0;
 }
 
@@ -1221,7 +1299,7 @@ int nomad_diag_workspace_region(const nomad_ctx* c, int B, int n_samples, const 
     Shapes s;
     if (!c || !name || !offset || !bytes || !make_shapes(B, n_samples, &s))
         return fail(NOMAD_ERR_INVALID, "nomad_diag_workspace_region: bad argument");
-    const Layout l = make_layout(s, c->keep, c->tune.f32_posconv_wino);
+    const Layout l = make_layout(s, c->keep, pos_form(c));
     if (strncmp(name, "conv", 4) == 0 && name[4] >= '0' && name[4] <= '6' && name[5] == 0) {
         const int i = name[4] - '0';
         *offset = l.conv[i];
@@ -1250,6 +1328,8 @@ struct F32Bufs {
     float *scale, *shift, *conv[7], *featln, *xpad, *x, *x2, *y, *qkv, *ctxb, *h;
     float *pwq = nullptr, *pws = nullptr;   // operands / products of the pos-conv in nested F(2,2) form (nullptr: the layout has none)
     int* pwmeta = nullptr;                  // ... and, for a ragged batch, the operands' 2 (B + 1) prefix sums
+    float *pfx = nullptr, *pfy = nullptr;   // the spectra of the pos-conv in the frequency domain (nullptr: the layout has none)
+    int* pfmeta = nullptr;                  // ... and, for a ragged batch, the units' B + 1 prefix sums
 };
 
 // The fp32 forward, over an equal-length or a ragged batch.  sv == nullptr: scoring mode (intermediates alias inside the
@@ -1354,7 +1434,11 @@ static int forward_run(nomad_ctx* c, const float* wav, const BatchGeom& g, const
         hipLaunchKernelGGL(dropout_groups_kernel, dim3(M), dim3(192), 0, s, xpad, T, g.grp_stride, d_in, kSiteInput, g.pref[6], g.ppref, B);
     }
     // ---- pos-conv: 16 groups x (M x 48 x 6144), x + gelu(conv + bias) -------------------------
-    if (posconv_wino(c)) {   // 9 / 16 of the products (posconv_wino_f32.hip.h)
+    if (posconv_fft(c)) {   // one 48 x 48 complex product per bin instead of 128 taps (posconv_fft_f32.hip.h)
+        if (!bf.pfx || !bf.pfy || !c->pos_wf) return fail(NOMAD_ERR_INVALID, "fp32 forward: no workspace for the pos-conv spectra");
+        if ((rc = run_posconv_fft(c, xpad, c->pos_wf, c->pos_b, sv ? sv->y0 : bf.y, sv ? sv->upc : nullptr, g.pos_fft, bf.pfx, bf.pfy, bf.pfmeta, s)))
+            return rc;
+    } else if (posconv_wino(c)) {   // 9 / 16 of the products (posconv_wino_f32.hip.h)
         if (!bf.pwq || !bf.pws) return fail(NOMAD_ERR_INVALID, "fp32 forward: no workspace for the pos-conv operands");
         if ((rc = run_posconv_wino(c, xpad, c->pos_wt, c->pos_b, sv ? sv->y0 : bf.y, sv ? sv->upc : nullptr, g.pos_wino, bf.pwq, bf.pws, bf.pwmeta, s)))
             return rc;
@@ -1475,14 +1559,15 @@ static int forward_impl(nomad_ctx* c, const float* wav, int B, int n_samples, co
     Shapes sh;
     if (!c || !wav || !emb || !workspace || B <= 0 || !make_shapes(B, n_samples, &sh))
         return fail(NOMAD_ERR_INVALID, "%s: bad argument (B=%d, n_samples=%d)", who, B, n_samples);
-    const Layout lay = make_layout(sh, c->keep, c->tune.f32_posconv_wino);
+    const Layout lay = make_layout(sh, c->keep, pos_form(c));
     if (workspace_bytes < lay.total)
         return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, lay.total);
     char* ws = static_cast<char*>(workspace);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.featln), F(lay.xpad), F(lay.x),
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
-    if (c->tune.f32_posconv_wino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws);
+    if (pos_form(c) == kPosWino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws);
+    if (pos_form(c) == kPosFft) bf.pfx = F(lay.pfx), bf.pfy = F(lay.pfy);
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(lay.conv[i]);
     const SplitKPlan ws_splitk = lay.splitk != 0 ? SplitKPlan{F(lay.splitk), layers_splitk_floats(sh)} : SplitKPlan{};
     return forward_run(c, wav, geom_uniform(sh), bf, head_w, head_b, emb, layers_out, ws_splitk, static_cast<hipStream_t>(stream), sv, mode);
@@ -1497,7 +1582,7 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
     RaggedBatch r;
     if (int rc = ragged_shapes(who, c && wav && emb && workspace, B, stride, lens_host, &r.rs)) return rc;
     r.g = geom_ragged(r.rs, stride, nullptr);
-    r.lay = make_act_layout(r.g, sizeof(float), 0, c->tune.f32_posconv_wino);
+    r.lay = make_act_layout(r.g, sizeof(float), 0, pos_form(c));
     if (workspace_bytes < r.lay.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who, workspace_bytes, r.lay.total);
     Saved sv{};
     if (saved) {   // every check before the first byte is queued
@@ -1513,7 +1598,8 @@ static int forward_ragged(nomad_ctx* c, const float* wav, int B, int stride, con
     const ActLayout& lay = r.lay;
     F32Bufs bf{reinterpret_cast<double*>(ws + lay.stats), F(lay.scale), F(lay.shift), {}, F(lay.convb), F(lay.xpad), F(lay.x),
                F(lay.x2), F(lay.y), F(lay.qkv), F(lay.ctxb), F(lay.h)};
-    if (c->tune.f32_posconv_wino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws), bf.pwmeta = reinterpret_cast<int*>(ws + lay.pwmeta);
+    if (pos_form(c) == kPosWino) bf.pwq = F(lay.pwq), bf.pws = F(lay.pws), bf.pwmeta = reinterpret_cast<int*>(ws + lay.pwmeta);
+    if (pos_form(c) == kPosFft) bf.pfx = F(lay.pfx), bf.pfy = F(lay.pfy), bf.pfmeta = reinterpret_cast<int*>(ws + lay.pfmeta);
     for (int i = 0; i < 7; ++i) bf.conv[i] = F(i % 2 ? lay.convb : lay.conva);   // conv6 lands in conva, LN(512) writes to convb
     return forward_run(c, wav, r.g, bf, head_w, head_b, emb, layers_out, SplitKPlan{}, s, saved ? &sv : nullptr, mode);
 }
@@ -2295,8 +2381,9 @@ int nomad_diag_timeline(unsigned long long* out_host, int n) {
     return 0;
 }
 
-/* Test hook: the fp32 pos-conv alone on the caller's operands, in the form this context's forwards run it in - nested F(2,2)
- * (posconv_wino_f32.hip.h) or, with NOMAD_F32_POSCONV_WINO=0 or bf16x3 products, the direct 128-tap GEMM.  x: the padded
+/* Test hook: the fp32 pos-conv alone on the caller's operands, in the form NOMAD_F32_POSCONV_WINO selects - nested F(2,2)
+ * (posconv_wino_f32.hip.h) or, with NOMAD_F32_POSCONV_WINO=0 or bf16x3 products, the direct 128-tap GEMM - whether or not this
+ * context's forwards run the frequency domain instead (nomad_diag_posconv_fft is that form's hook).  x: the padded
  * group-major input [16][sum_c (T_c + 128)][48] (zero frames 0..63 and T_c + 64.. of every clip); v: weights as pos_w,
  * [16][64][6144]; bias: [768] or null; y = x + gelu(u), u (nullable) = pos_conv(x) + bias: [sum_c T_c][768].  lens_host: the
  * clips' frame counts T_c.  ragged = 0: the uniform launch (every T_c equal), 1: the ragged one.  Synchronous. */
@@ -2367,6 +2454,46 @@ int nomad_diag_posconv(nomad_ctx* c, const float* x, const float* v, const float
 }
 #endif
 
+/* Test hook: the fp32 pos-conv alone on the caller's operands in the frequency domain (posconv_fft_f32.hip.h), whatever form this
+ * context's forwards run.  Arguments as nomad_diag_posconv.  Synchronous. */
+int nomad_diag_posconv_fft(nomad_ctx* c, const float* x, const float* v, const float* bias, float* y, float* u, int B,
+                           const int* lens_host, int ragged, nomad_stream_t stream) {
+    if (!c || !x || !v || !y || !lens_host || B <= 0) return fail(NOMAD_ERR_INVALID, "nomad_diag_posconv_fft: bad argument");
+    std::vector<int> meta(3 * (size_t)(B + 1), 0);   // frame / padded frame prefix sums; room for the units' (run_posconv_fft)
+    int max_t = 0;
+    long long units = 0;
+    for (int b = 0; b < B; ++b) {
+        const int T = lens_host[b];
+        if (T <= 0 || (!ragged && T != lens_host[0])) return fail(NOMAD_ERR_INVALID, "nomad_diag_posconv_fft: clip %d of %d frames", b, T);
+        meta[b + 1] = meta[b] + T;
+        meta[(B + 1) + b + 1] = meta[(B + 1) + b] + T + 128;
+        units += pos_fft_blocks(T);
+        max_t = std::max(max_t, T);
+    }
+    if (units >= (1 << 30) / kPfCols) return fail(NOMAD_ERR_INVALID, "nomad_diag_posconv_fft: %lld units", units);
+    PosFftGeom geo{B, ragged ? 0 : lens_host[0], nullptr, nullptr, nullptr, meta[(B + 1) + B], (int)units, pos_fft_blocks(max_t)};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t meta_bytes = (sizeof(int) * meta.size() + 255) & ~size_t(255), wf_bytes = sizeof(float) * kPfWeightFloats;
+    const size_t spec_bytes = (pos_fft_spec_bytes(units) + 255) & ~size_t(255);
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), meta_bytes + wf_bytes + 2 * spec_bytes));
+    int* dm = reinterpret_cast<int*>(d);
+    float* wf = reinterpret_cast<float*>(d + meta_bytes);
+    float* sx = reinterpret_cast<float*>(d + meta_bytes + wf_bytes);
+    float* sy = reinterpret_cast<float*>(d + meta_bytes + wf_bytes + spec_bytes);
+    int rc = 0;
+    if (hipMemcpy(dm, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_diag_posconv_fft: copy");
+    if (ragged) {
+        geo.tpref = dm;
+        geo.ppref = dm + (B + 1);
+    }
+    if (rc == 0) rc = launch_posconv_fft_weights(c, v, wf, s);
+    if (rc == 0) rc = run_posconv_fft(c, x, wf, bias, y, u, geo, sx, sy, dm + 2 * (B + 1), s);
+    if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(NOMAD_ERR_HIP, "nomad_diag_posconv_fft: kernel");
+    (void)hipFree(d);
+    return rc;
+}
+
 int nomad_diag_gemm_bf16(nomad_ctx* c, const void* A, const void* W, const float* bias, const void* R, void* C, int M,
                          int N, int K, int gelu, int tile, nomad_stream_t stream) {
     static const int kBN[] = {128, 128, 64, 256, 64, 128, 128, 128, 128, 256, 256, 128, 128, 128, 128, 256, 256, 256, 256, 256};
@@ -2395,7 +2522,7 @@ int nomad_embed(nomad_ctx* c, const float* wav, int B, int n_samples, const floa
 int nomad_workspace_bytes_ragged(const nomad_ctx* c, int B, const int* lengths_host, size_t* bytes) {
     RaggedBatch r;
     if (int rc = ragged_prologue("nomad_workspace_bytes_ragged", nullptr, c && bytes, B, 0, lengths_host, sizeof(float), 0, &r, nullptr, 0, nullptr,
-                                 c && c->tune.f32_posconv_wino))
+                                 c ? pos_form(c) : kPosDirect))
         return rc;
     *bytes = r.lay.total;
     return 0;
@@ -3151,6 +3278,8 @@ int refresh_weights(nomad_ctx* c, hipStream_t s) {
                        c->pos_nrm2, c->pos_w);
     if (c->pos_wt)
         if (int rc = rebuild_posconv_wino_weights(c, s)) return rc;
+    if (c->pos_wf)
+        if (int rc = launch_posconv_fft_weights(c, c->pos_w, c->pos_wf, s)) return rc;
     for (int i = 1; i < 7; ++i) {  // conv feature extractor: kernel layout [co][tap * 512 + ci]
         const long long n = 512LL * 512 * kConvK[i];
         hipLaunchKernelGGL(conv_repack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->theta + po.conv_w[i], c->conv_w[i],
