@@ -872,7 +872,8 @@ int nomad_degrade_reverb(nomad_ctx* ctx, const float* x_dev, int B, int stride, 
  * The rows the degradations make are, by construction; rows with ONE constant delay of whole samples (a codec round trip, a model
  * with latency) are brought there by nomad_align_delay / nomad_align_shift below.  Delays that change inside a file (clock drift, dropped
  * packets) are followed in steps of whole frames by nomad_nsim_patches.  Still outside what is claimed: sub-sample delays, and
- * agreement with ViSQOL's own aligner, which has not been measured.  No gradient, no MOS mapping.
+ * agreement with ViSQOL's own aligner, which has not been measured.  No MOS mapping.  The gradient of these two calls with respect
+ * to the degraded rows is nomad_nsim_backward / nomad_gammatone_backward ("NSIM as a loss" below).
  *
  * Rows are fp32, mono, at fs = sample_rate samples per second, fs in 16000 .. 48000 and a multiple of 50.  Everything below is float64.
  * Bank: N = 21 bands.  With EarQ = 9.26449, minBW = 24.7, lo = 50, hi = 8000:
@@ -929,6 +930,73 @@ size_t nomad_nsim_scratch_bytes(int B, int G, long long total_frames);
 int nomad_nsim(nomad_ctx* ctx, const double* spec_ref_dev, const double* spec_deg_dev, int B, int G, const int* frames_host /* [B] */,
                double intensity_range, double* nsim_out_dev /* [B G] */, double* bands_out_dev /* [B G][21] or NULL */, void* ws_dev,
                size_t ws_bytes, nomad_stream_t stream);
+
+/* ---- NSIM as a loss: the gradient of nomad_nsim and nomad_gammatone with respect to the degraded (estimated) rows --------------
+ * The whole-clip measure above, differentiated: d nsim[j] / d spec_deg (nomad_nsim_backward) and from there down to the samples of
+ * the degraded rows (nomad_gammatone_backward).  The clean rows get no gradient.  The patch search, the alignment and everything
+ * else in this header that says so stay without one.  The measure is this project's: its agreement with ViSQOL is not measured,
+ * and neither is that of its gradient with any differentiable ViSQOL.  All quantities are float64; the samples' gradient is rounded
+ * to fp32 once.
+ *
+ * The measure has maxima, a minimum, a clamp and square roots; these conventions make its gradient finite (digital silence
+ * included) and are the definition.  tests/nsim_grad_ref.py restates them.
+ *   Square roots: S = sqrt(acc / W) has gradient 0 where acc == 0; sigma = sqrt(var) has gradient 0 where var <= 0 (clamped or
+ *     exactly zero).
+ *   Floors: every max(value, floor) passes its gradient to value only where value > floor strictly; otherwise it goes to the
+ *     floor.  The constants eps and -45 take nothing; the per-frame floor p_t - 45 hands it to p_t.
+ *   Peak: p_t passes its gradient to the FIRST cell that attains it in the forward's own order: clean bands ascending, then
+ *     degraded bands ascending (a later cell replaces an earlier one only where it is strictly greater).  If that cell is a clean
+ *     one the gradient ends there.  Clean cells on p_t - 45 do hand their gradient to a degraded peak: the clean plane's
+ *     derivative is carried up to this step.  p_t's gradient is the sum over the clean cells on the frame's floor in ascending
+ *     bands, then the degraded ones in ascending bands.
+ *   Least: the smallest value left in either plane receives -sum(dR + dD) over all cells of both planes: thread i mod 256 of 256
+ *     adds dR[i] + dD[i] over its cells in ascending i, and the 256 sums are folded by halves (k += k + 128, k + 64, ..); the order
+ *     depends on F alone.  It passes that to the attaining cell with the lowest flat index t 21 + b, clean before degraded at the
+ *     same index; from there it goes on through that cell's floors as above.
+ *   Map: with g the call's upstream value for the row, every map cell receives gm = g / (21 F).  Per cell, with l and s the map's
+ *     two factors, Dl = mu_R^2 + mu_D^2 + C1, Ds = sigma_R sigma_D + C3: d cov = gm l / Ds; d (sigma_R sigma_D) = -(gm l s) / Ds;
+ *     d var_R = d (sigma_R sigma_D) sigma_D / (2 sigma_R) where var_R > 0, else 0 (var_D alike); d mu_R = gm s (2 mu_D - 2 l mu_R) /
+ *     Dl - d cov mu_D - 2 d var_R mu_R (mu_D alike); d w*R^2 = d var_R, d w*D^2 = d var_D, d w*(R D) = d cov.
+ *   Window: the 3 x 3 window's adjoint honours the replicated edges: cell (t, b) receives w[dt][db] (d mu + 2 X d w*X^2 + Y d w*(XY))
+ *     of every map cell (t', b') and window offset (dt, db) whose clamped index (clamp(t' + dt), clamp(b' + db)) lands on it - nine
+ *     terms for every cell, several of them from the same map cell at an edge - added in the order t' ascending, dt ascending
+ *     inside, b' ascending inside that, db ascending innermost.  X is the plane's own value at (t, b), Y the other plane's.
+ *   dB: d S = d X (10 / ln 10) / S where S > eps and 10 log10 S > -45, else 0.
+ *   Gammatone: with y the cascade's W outputs of frame t and band b, q[n] = c y[n] with c = dS / (S W) (0 where acc == 0).  Each
+ *     section from the zero state is a lower-triangular Toeplitz map whose transpose is the same section run over the time-reversed
+ *     sequence, so the frame's gradient is rev(sec0(sec1(sec2(sec3(rev(q)))))) in that section order, each section in the forward's
+ *     arithmetic (y = b0 x + z1; z1 = b1 x - a1 y + z2; z2 = -a2 y) from the zero state.  A sample's value: for every frame that
+ *     covers it, in ascending frame order, the frame's 21 band values are added in ascending band order, and the frames' sums are
+ *     added in that order; the result is rounded to fp32 once.
+ *   NaN: a row whose NSIM is NaN gets NaN in every cell of its dspec, and from there NaN over the samples of its whole frames,
+ *     [0, (F - 1) H + W); a NaN in dspec makes the samples of its frame NaN (silent frames included).  No other row changes a bit.
+ *     Samples of a trailing partial frame, and everything from the length to the stride, are written as 0.
+ *
+ *   nomad_nsim_backward       spec_ref_dev, spec_deg_dev, B, G, frames_host, intensity_range as nomad_nsim took them; grad_nsim_dev
+ *                             [B G] float64 -> dspec_deg_out_dev [G sum F_b][21] float64, packed as spec_deg_dev.  One workgroup
+ *                             per degraded row; it rebuilds the floored planes by the forward's own steps, so every comparison
+ *                             sees the forward's bits.  A row has the bits of its own B = 1, G = 1 call.
+ *   nomad_gammatone_backward  x_dev, R, stride, lens_host, sample_rate as nomad_gammatone took them (4-byte alignment is all the rows
+ *                             need, nothing behind a length is read); dspec_dev [sum F_r][21] float64 -> dx_out_dev [R][stride]
+ *                             fp32, every element written.  A row has the bits of its own R = 1 call whatever the batch, the
+ *                             stride and the base address.  The cascade's outputs are stored, not recomputed: the workspace holds
+ *                             W 21 doubles per frame (csrc/nsim_bwd.hip.h).
+ * Contract as the forward calls: asynchronous on the caller's stream, no allocation, deterministic, no atomics; the host tables are
+ * copied into the workspace ahead of the kernels; argument errors return before anything is queued, with the forward calls' codes
+ * for the same causes (NOMAD_ERR_INVALID also for a NULL grad_nsim_dev, dspec_dev or output; NOMAD_ERR_WORKSPACE).  Workspace:
+ *   nomad_nsim_backward_scratch_bytes(B, G, total_frames) = nomad_nsim's two tables + 9 x 8 x 21 G total_frames bytes;
+ *   nomad_gammatone_backward_scratch_bytes(R, stride, sample_rate) = nomad_gammatone's three tables + 8 x 21 W R F(stride) bytes,
+ *   F(stride) = nomad_gammatone_frames(stride, sample_rate) (0 for arguments the call would refuse, a stride below one frame
+ *   among them); both are written before they are read.
+ */
+size_t nomad_nsim_backward_scratch_bytes(int B, int G, long long total_frames);
+int nomad_nsim_backward(nomad_ctx* ctx, const double* spec_ref_dev, const double* spec_deg_dev, int B, int G, const int* frames_host /* [B] */,
+                        double intensity_range, const double* grad_nsim_dev /* [B G] */, double* dspec_deg_out_dev /* [G sum F_b][21] */,
+                        void* ws_dev, size_t ws_bytes, nomad_stream_t stream);
+size_t nomad_gammatone_backward_scratch_bytes(int R, int stride, int sample_rate);
+int nomad_gammatone_backward(nomad_ctx* ctx, const float* x_dev, int R, int stride, const int* lens_host, int sample_rate,
+                             const double* dspec_dev /* [sum F_r][21] */, float* dx_out_dev /* [R][stride] */, void* ws_dev, size_t ws_bytes,
+                             nomad_stream_t stream);
 
 /* ---- time alignment: the delay of every degraded row against its clean clip, and the rows moved by it ----------------------
  * A codec round trip (the reference's MP3, Opus and Vorbis conditions), a model with latency or a recording through a device shifts

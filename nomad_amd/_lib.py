@@ -81,6 +81,10 @@ SIGNATURES = {
     "nomad_gammatone": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "nomad_nsim_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_longlong]),
     "nomad_nsim": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_nsim_backward_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_longlong]),
+    "nomad_nsim_backward": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nomad_gammatone_backward_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nomad_gammatone_backward": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
     "nomad_nsim_patch_count": (C.c_int, [C.c_int, C.c_int]),
     "nomad_nsim_patches_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
     # (the second host table - the degraded rows' frame counts - goes in as an address, as nomad_align_delay's does)

@@ -30,6 +30,7 @@
 #include "reverb.hip.h"
 #include "loudness.hip.h"
 #include "nsim.hip.h"
+#include "nsim_bwd.hip.h"
 #include "nsim_patches.hip.h"
 #include "align.hip.h"
 #include "frontend.hip.h"
@@ -4421,6 +4422,116 @@ int nomad_nsim(nomad_ctx* c, const double* spec_ref, const double* spec_deg, int
     Scope sc(c, s, NOMAD_K_ROW, 0.0);
     hipLaunchKernelGGL(nsim_kernel, dim3((unsigned)(B * G)), dim3(256), 0, s, spec_ref, spec_deg, G, reinterpret_cast<const int*>(w),
                        reinterpret_cast<const long long*>(w + l.fpref), total, C1, C3, reinterpret_cast<double*>(w + l.planes), nsim_out, bands_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- NSIM as a loss (nsim_bwd.hip.h) ----
+// Scratch: nomad_gammatone's three tables, then y: [R F(stride)][W][21] float64, F(stride) the whole frames of a row as long as
+// the stride (the helper does not know the lengths; the call uses the rows' own frame counts, packed).
+static size_t gammatone_backward_y_bytes(long long frames, int W) { return sizeof(double) * (size_t)frames * (size_t)W * kGammatoneBands; }
+
+size_t nomad_gammatone_backward_scratch_bytes(int R, int stride, int sample_rate) {
+    const int W = gammatone_rate_ok(sample_rate) ? sample_rate / 50 * 4 : 0;
+    if (R < 1 || R > 65535 || stride < 4 || stride % 4 || !W || stride < W) {
+        (void)fail(NOMAD_ERR_INVALID,
+                   "nomad_gammatone_backward_scratch_bytes: bad argument (R=%d: 1 .. 65535, stride=%d: a positive multiple of 4 and at least one "
+                   "frame, sample_rate=%d: a multiple of 50 in %d .. %d)", R, stride, sample_rate, kGammatoneMinRate, kGammatoneMaxRate);
+        return 0;
+    }
+    return gammatone_layout(R).total + gammatone_backward_y_bytes((long long)R * nomad_gammatone_frames(stride, sample_rate), W);
+}
+
+int nomad_gammatone_backward(nomad_ctx* c, const float* x, int R, int stride, const int* lens, int sample_rate, const double* dspec, float* dx,
+                             void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_gammatone_backward";
+    if (!c || !x || !lens || !dspec || !dx || !ws)
+        return fail(NOMAD_ERR_INVALID, "%s: a NULL context, input, lengths, spectrogram gradient, output or workspace", who);
+    if (R < 1 || R > 65535) return fail(NOMAD_ERR_INVALID, "%s: R=%d rows, 1 .. 65535 are supported", who, R);
+    if (stride < 4 || stride % 4) return fail(NOMAD_ERR_INVALID, "%s: stride=%d is not a positive multiple of 4", who, stride);
+    if (!gammatone_rate_ok(sample_rate))
+        return fail(NOMAD_ERR_INVALID, "%s: sample_rate=%d, a multiple of 50 in %d .. %d is supported", who, sample_rate, kGammatoneMinRate,
+                    kGammatoneMaxRate);
+    const int H = sample_rate / 50, W = 4 * H;
+    int max_f = 0;
+    for (int r = 0; r < R; ++r) {
+        if (lens[r] < W || lens[r] > stride)
+            return fail(NOMAD_ERR_INVALID, "%s: row %d has length %d, one frame of %d samples .. stride=%d are supported", who, r, lens[r], W, stride);
+        const int f = (lens[r] - W) / H + 1;
+        max_f = f > max_f ? f : max_f;
+    }
+    const GammatoneLayout l = gammatone_layout(R);
+    const size_t need = l.total + gammatone_backward_y_bytes((long long)R * nomad_gammatone_frames(stride, sample_rate), W);
+    if (ws_bytes < need) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(l.total, 0);
+    memcpy(staged.data(), lens, sizeof(int) * (size_t)R);
+    long long* fp = reinterpret_cast<long long*>(staged.data() + l.fpref);
+    for (int r = 0; r < R; ++r) fp[r + 1] = fp[r] + ((lens[r] - W) / H + 1);
+    const double frames = (double)fp[R];
+    gammatone_bank(sample_rate, reinterpret_cast<double*>(staged.data() + l.coef), nullptr);
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), l.total, hipMemcpyHostToDevice, s));
+    Scope sc(c, s, NOMAD_K_ROW, 2.0 * 2.0 * 16.0 * frames * kGammatoneBands * W);
+    const size_t lds = sizeof(float) * (size_t)(kGammatoneBlockFrames + 3) * (size_t)(H + 1);   // the forward's: at most 57 660 bytes (48 kHz)
+    const int* lens_dev = reinterpret_cast<const int*>(w);
+    const long long* fpref_dev = reinterpret_cast<const long long*>(w + l.fpref);
+    double* y = reinterpret_cast<double*>(w + l.total);
+    hipLaunchKernelGGL(gammatone_adjoint_kernel, dim3((unsigned)((max_f + kGammatoneBlockFrames - 1) / kGammatoneBlockFrames), (unsigned)R),
+                       dim3(256), lds, s, x, stride, lens_dev, fpref_dev, reinterpret_cast<const double*>(w + l.coef), H, dspec, y);
+    hipLaunchKernelGGL(gammatone_gather_kernel, dim3((unsigned)((stride + 255) / 256), (unsigned)R), dim3(256), 0, s,
+                       static_cast<const double*>(y), stride, lens_dev, fpref_dev, H, dx);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Scratch: nomad_nsim's two tables, then planes [9][G total_frames][21] float64.
+static NsimLayout nsim_backward_layout(int B, int G, long long total_frames) {
+    NsimLayout l = nsim_layout(B, G, total_frames);
+    l.total = l.planes + kNsimBwdPlanes * sizeof(double) * (size_t)G * (size_t)total_frames * kGammatoneBands;
+    return l;
+}
+
+size_t nomad_nsim_backward_scratch_bytes(int B, int G, long long total_frames) {
+    if (B < 1 || B > 65535 || G < 1 || G > 64 || total_frames < B || total_frames > (1ll << 31)) {
+        (void)fail(NOMAD_ERR_INVALID, "nomad_nsim_backward_scratch_bytes: bad argument (B=%d: 1 .. 65535, G=%d: 1 .. 64, total_frames=%lld: B .. 2^31)",
+                   B, G, total_frames);
+        return 0;
+    }
+    return nsim_backward_layout(B, G, total_frames).total;
+}
+
+int nomad_nsim_backward(nomad_ctx* c, const double* spec_ref, const double* spec_deg, int B, int G, const int* frames, double intensity_range,
+                        const double* grad_nsim, double* dspec_deg_out, void* ws, size_t ws_bytes, nomad_stream_t stream) {
+    const char* who = "nomad_nsim_backward";
+    if (!c || !spec_ref || !spec_deg || !frames || !grad_nsim || !dspec_deg_out || !ws)
+        return fail(NOMAD_ERR_INVALID, "%s: a NULL context, spectrogram, frame counts, gradient, output or workspace", who);
+    if (B < 1 || B > 65535) return fail(NOMAD_ERR_INVALID, "%s: B=%d clips, 1 .. 65535 are supported", who, B);
+    if (G < 1 || G > 64) return fail(NOMAD_ERR_INVALID, "%s: G=%d rows per clip, 1 .. 64 are supported", who, G);
+    if (!std::isfinite(intensity_range) || !(intensity_range > 0.0))
+        return fail(NOMAD_ERR_INVALID, "%s: the intensity range must be finite and positive, got %g", who, intensity_range);
+    long long total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (frames[b] < 1) return fail(NOMAD_ERR_INVALID, "%s: clip %d has %d frames, at least 1 is needed", who, b, frames[b]);
+        total += frames[b];
+    }
+    if (total > (1ll << 31)) return fail(NOMAD_ERR_INVALID, "%s: %lld frames in all, at most 2^31 are supported", who, total);
+    const NsimLayout l = nsim_backward_layout(B, G, total);
+    if (ws_bytes < l.total) return fail(NOMAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    std::vector<char>& staged = c->degrade_meta_ring[c->degrade_seq++ % 16];
+    staged.assign(l.planes, 0);
+    memcpy(staged.data(), frames, sizeof(int) * (size_t)B);
+    long long* fp = reinterpret_cast<long long*>(staged.data() + l.fpref);
+    for (int b = 0; b < B; ++b) fp[b + 1] = fp[b] + frames[b];
+    HIP_TRY(hipMemcpyAsync(w, staged.data(), l.planes, hipMemcpyHostToDevice, s));
+    const double C1 = (0.01 * intensity_range) * (0.01 * intensity_range), C3 = (0.03 * intensity_range) * (0.03 * intensity_range) / 2.0;
+    Scope sc(c, s, NOMAD_K_ROW, 0.0);
+    hipLaunchKernelGGL(nsim_backward_kernel, dim3((unsigned)(B * G)), dim3(256), 0, s, spec_ref, spec_deg, G, reinterpret_cast<const int*>(w),
+                       reinterpret_cast<const long long*>(w + l.fpref), total, C1, C3, grad_nsim, reinterpret_cast<double*>(w + l.planes),
+                       dspec_deg_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -16,6 +16,8 @@ from .weights import check_state_dict, num_frames, num_windows
 
 P = "ssl_model."
 _SUFFIX = {"fp32": "", "bf16": "_bf16", "bf16x3": "_bf16x3"}   # of the C ABI's per-precision entry points
+# the largest workspace ``gammatone_backward`` / ``nsim_backward`` ask for in one call: rows beyond it go into further calls
+NSIM_BACKWARD_WORKSPACE_BYTES = 1 << 30
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -843,6 +845,79 @@ class Engine:
         spec_ref, frames = self.gammatone(packed=(cbuf, clens), sample_rate=sample_rate)
         spec_deg, _ = self.gammatone(packed=(dbuf, dlens), sample_rate=sample_rate)
         return self.nsim_of_spectrograms(spec_ref, spec_deg, frames, G, intensity_range, want_bands)
+
+    @staticmethod
+    def _groups(costs, fixed, what: str):
+        """Consecutive groups [lo, hi) of items whose workspace ``fixed(count) + sum(costs)`` stays within
+        ``NSIM_BACKWARD_WORKSPACE_BYTES``; an item that alone exceeds it raises."""
+        cap, out, lo, acc = int(NSIM_BACKWARD_WORKSPACE_BYTES), [], 0, 0
+        for i, c in enumerate(costs):
+            if fixed(1) + c > cap:
+                raise ValueError(f"{what} {i} alone needs a workspace of {fixed(1) + c} bytes, more than NSIM_BACKWARD_WORKSPACE_BYTES = {cap}")
+            if i > lo and fixed(i - lo + 1) + acc + c > cap:
+                out.append((lo, i))
+                lo, acc = i, 0
+            acc += c
+        out.append((lo, len(costs)))
+        return out
+
+    def gammatone_backward(self, dspec: torch.Tensor, waves=None, lengths=None, packed: Optional[Tuple[torch.Tensor, list]] = None,
+                           sample_rate: int = 16000):
+        """The gradient of ``gammatone`` with respect to the samples: dspec (sum F_r, 21) float64, the gradient with respect to the
+        spectrogram ``gammatone`` makes of these rows -> (R, stride) fp32 on the device, 0 behind every row's whole frames
+        (``nomad_gammatone_backward``; include/nomad_hip.h, "NSIM as a loss", states the conventions).  The rows are processed in
+        groups whose workspace - 168 W bytes per frame of a row as long as the stride - stays within
+        ``NSIM_BACKWARD_WORKSPACE_BYTES``; rows are independent, so the grouping changes no bit."""
+        sample_rate = self.check_gammatone(sample_rate)
+        buf, lens = self._rows(waves, lengths, packed)
+        self._check_dev(buf, "the rows")
+        R, stride = buf.shape
+        frames = [self.gammatone_frames(n, sample_rate) for n in lens]
+        if min(frames) < 1:
+            raise ValueError(f"a row of {min(lens)} samples is shorter than one frame of {sample_rate // 50 * 4}")
+        if not (torch.is_tensor(dspec) and dspec.is_cuda and dspec.dtype == torch.float64 and dspec.is_contiguous()
+                and tuple(dspec.shape) == (sum(frames), self.NSIM_BANDS)):
+            raise ValueError(f"dspec must be a contiguous float64 tensor of shape ({sum(frames)}, {self.NSIM_BANDS}) on {self.device}")
+        size = lambda k: self._scratch_size(self.lib.nomad_gammatone_backward_scratch_bytes, "nomad_gammatone_backward_scratch_bytes", k,
+                                            stride, sample_rate)
+        per_row = size(2) - size(1)
+        dx = torch.empty(R, stride, dtype=torch.float32, device=self.device)
+        at = 0
+        for lo, hi in self._groups([per_row] * R, lambda k: size(k) - k * per_row, "row"):
+            n = hi - lo
+            ws = self._workspace(size(n))
+            _lib.check(self.lib.nomad_gammatone_backward(self.ctx, buf[lo:hi].data_ptr(), n, stride, (C.c_int * n)(*lens[lo:hi]), sample_rate,
+                                                         dspec[at:].data_ptr(), dx[lo:hi].data_ptr(), ws.data_ptr(), ws.numel(),
+                                                         self._stream()), "nomad_gammatone_backward")
+            at += sum(frames[lo:hi])
+        return dx
+
+    def nsim_backward(self, spec_ref: torch.Tensor, spec_deg: torch.Tensor, frames, G: int, grad_nsim: torch.Tensor,
+                      intensity_range: float = 1.0):
+        """The gradient of ``nsim_of_spectrograms`` with respect to spec_deg: grad_nsim (B, G) float64, the gradient with respect to
+        the scores -> (G sum F_b, 21) float64, packed as spec_deg (``nomad_nsim_backward``; a row whose NSIM is NaN gets NaN).  The
+        clips are processed in groups as ``gammatone_backward`` processes rows."""
+        frames = [int(f) for f in frames]
+        B, G, total = len(frames), int(G), sum(frames)
+        intensity_range = float(intensity_range)
+        if not (math.isfinite(intensity_range) and intensity_range > 0.0):
+            raise ValueError(f"intensity_range must be finite and positive, got {intensity_range}")
+        for t, shape, name in ((spec_ref, (total, self.NSIM_BANDS), "spec_ref"), (spec_deg, (G * total, self.NSIM_BANDS), "spec_deg"),
+                               (grad_nsim, (B, G), "grad_nsim")):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {self.device}")
+        size = lambda k, f: self._scratch_size(self.lib.nomad_nsim_backward_scratch_bytes, "nomad_nsim_backward_scratch_bytes", k, G, f)
+        per_frame = size(1, 2) - size(1, 1)
+        out = torch.empty(G * total, self.NSIM_BANDS, dtype=torch.float64, device=self.device)
+        at = 0
+        for lo, hi in self._groups([per_frame * f for f in frames], lambda k: size(k, k) - k * per_frame, "clip"):
+            n, f = hi - lo, sum(frames[lo:hi])
+            ws = self._workspace(size(n, f))
+            _lib.check(self.lib.nomad_nsim_backward(self.ctx, spec_ref[at:].data_ptr(), spec_deg[G * at:].data_ptr(), n, G,
+                                                    (C.c_int * n)(*frames[lo:hi]), intensity_range, grad_nsim[lo:hi].data_ptr(),
+                                                    out[G * at:].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "nomad_nsim_backward")
+            at += f
+        return out
 
     NSIM_PATCH_MAX, NSIM_SEARCH_MAX = 64, 128
 

@@ -157,6 +157,9 @@ def loss_selection(L, layer_weights=None):
     return weights, depth
 
 
+NSIM_FRAME_SAMPLES = 1280   # one 80 ms gammatone frame at 16 kHz
+
+
 def check_reduction(reduction) -> str:
     if reduction not in ("mean", "none"):
         raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
@@ -765,6 +768,40 @@ class _ScoreFn(torch.autograd.Function):
         if dref is not None:
             dref = dref.to(ref_device, ref_dtype)
         return dwav, dref, None, None, None, None
+
+
+class _NsimLossFn(torch.autograd.Function):
+    """loss[b] = 1 - NSIM(estimate_b, clean_b): ``Engine.gammatone`` twice and ``nsim_of_spectrograms`` forward, ``Engine.nsim_backward``
+    and ``gammatone_backward`` backward, both float64 down to the fp32 samples.  ``clean`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, estimate, clean, nomad, lens, intensity_range):
+        eng = nomad.engine
+        est, _ = eng._rows(_loss_rows(estimate, eng), lens, None)
+        cln, _ = eng._rows(_loss_rows(clean, eng), lens, None)
+        spec_ref, frames = eng.gammatone(packed=(cln, lens))
+        spec_deg, _ = eng.gammatone(packed=(est, lens))
+        score, _ = eng.nsim_of_spectrograms(spec_ref, spec_deg, frames, 1, intensity_range, want_bands=False)
+        ctx.nomad, ctx.lens, ctx.frames, ctx.intensity_range, ctx.meta = nomad, lens, frames, intensity_range, (estimate.shape, estimate.shape[-1])
+        ctx.save_for_backward(est, spec_ref, spec_deg)
+        return 1.0 - score.view(-1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        est, spec_ref, spec_deg = ctx.saved_tensors
+        eng = ctx.nomad.engine
+        shape, width = ctx.meta
+        g = (-grad_out.to(eng.device, torch.float64)).reshape(len(ctx.lens), 1).contiguous()
+        dspec = eng.nsim_backward(spec_ref, spec_deg, ctx.frames, 1, g, ctx.intensity_range)
+        dx = eng.gammatone_backward(dspec, packed=(est, ctx.lens))
+        return dx[:, :width].reshape(shape), None, None, None, None
+
+
+def _loss_rows(wav, eng):
+    x = wav.detach().to(eng.device, torch.float32)
+    return (x.squeeze(1) if x.dim() == 3 else x).contiguous()
 
 
 class GraphedLoss:
@@ -1883,7 +1920,7 @@ class Nomad:
         delay against its clip (``align``: one whole-sample delay per row); the degraded rows may then have any lengths - a tensor
         of another width takes ``degraded_lengths`` - and the (B, G) int32 delays are returned as one more, last result.
         Modelled on ViSQOL's speech mode from memory and NOT checked against the ViSQOL binary, neither the measure nor the
-        delays; include/nomad_hip.h states both.  No gradient.  With ``patch_s`` (seconds; ``search_s``, ``vad_db``, ``min_active``
+        delays; include/nomad_hip.h states both.  No gradient (``nsim_loss`` is the whole-clip measure's differentiable form).  With ``patch_s`` (seconds; ``search_s``, ``vad_db``, ``min_active``
         as ``nsim_patches`` takes them) the score and the band values are the patch-wise ones of ``nsim_patches``, in the same
         tuple; ``patch_s=None`` is every call as it was."""
         if patch_s is not None:
@@ -1918,6 +1955,35 @@ class Nomad:
             G = 1
         score, per_band = eng.nsim((cbuf, clens), (dbuf, dlens), G, intensity_range=intensity_range, want_bands=bands)
         return (score, per_band) if bands else score
+
+    def nsim_loss(self, estimate, clean, lengths=None, reduction: str = "mean", intensity_range: float = 1.0):
+        """The gammatone-spectrogram NSIM as a loss: ``1 - nsim(estimate, clean)`` per clip in float64, the number ``nsim`` reports,
+        with a gradient down to ``estimate`` computed on the GPU in the same float64 arithmetic (``nomad_nsim_backward``,
+        ``nomad_gammatone_backward``).  estimate and clean (B,1,N) or (B,N) of one shape, fp32; lengths: the clips' exact lengths as
+        in ``forward`` (every clip at least 80 ms); -> (B,) float64, or with reduction="mean" their mean.  The gradient has
+        estimate's shape and dtype and is 0 behind every clip's whole frames; ``clean`` gets none and must not require one.  A
+        full-reference spectral term to add to the feature loss: ``nomad.forward(est, clean) + lam * nomad.nsim_loss(est, clean)``.
+        The whole-clip measure only (no alignment, no patch search), and this project's measure, not ViSQOL's: neither the number
+        nor the gradient has been checked against ViSQOL or any differentiable form of it.  include/nomad_hip.h ("NSIM as a
+        loss") states the conventions that keep the gradient finite on silence."""
+        check_reduction(reduction)
+        for t, name in ((estimate, "estimate"), (clean, "clean")):
+            if not torch.is_tensor(t) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[1] != 1):
+                raise ValueError(f"{name} must be (B,1,N) or (B,N), got {tuple(getattr(t, 'shape', ()))}")
+        if tuple(clean.shape) != tuple(estimate.shape):
+            raise ValueError(f"clean must have estimate's shape {tuple(estimate.shape)}, got {tuple(clean.shape)}")
+        if clean.requires_grad:
+            raise ValueError("nsim_loss differentiates with respect to estimate only: clean must not require a gradient")
+        intensity_range = float(intensity_range)
+        if not (math.isfinite(intensity_range) and intensity_range > 0.0):
+            raise ValueError(f"intensity_range must be finite and positive, got {intensity_range}")
+        lens = check_lengths(estimate, lengths) if lengths is not None else [int(estimate.shape[-1])] * estimate.shape[0]
+        if not lens:
+            raise ValueError("nsim_loss needs at least one clip")
+        if min(lens) < NSIM_FRAME_SAMPLES:
+            raise ValueError(f"a clip of {min(lens)} samples is shorter than one frame of {NSIM_FRAME_SAMPLES}")
+        loss = _NsimLossFn.apply(estimate, clean, self, lens, intensity_range)
+        return loss.mean() if reduction == "mean" else loss
 
     def nsim_files(self, degraded, clean=None, max_delay_s: float = 0.25, results_path=None, max_batch_samples: int = 64 * 160000,
                    patch_s=None, search_s: float = 1.2, vad_db: float = 40.0, min_active: float = 1.0):
